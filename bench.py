@@ -8,8 +8,13 @@ child processes (rendezvous on 127.0.0.1), relays rank 0's JSON line and exits w
 A "step" = one launch of the solve kernel over one batch of B independent MPC problem instances per GPU
 (synthetic initial states; inputs already resident in HBM). Weak scaling: B per GPU is fixed, instances are
 sharded one batch per GPU with no data-path collective; rank 0 broadcasts the shared model blob once over RCCL
-at start-up. Rank 0 prints ONE JSON line. The timed launch's outputs of sampled instances are compared bit for
-bit with the CPU oracle solving the same instances (verified_instances / verified_bit_exact in the line).
+at start-up. Rank 0 prints ONE JSON line. With --full, the timed launch's outputs of sampled instances are compared bit
+for bit with the CPU oracle solving the same instances (verified_instances / verified_bit_exact in the line).
+
+A plain run sets up, warms up, times --steps launches and prints the headline (metric, value, unit, higher_is_better, dtype, ms_per_step)
+and nothing else. --full adds everything else the line has always carried, after the timed leg: the check of the timed launch against the
+CPU oracle, single-solve latency, roofline, power, the other configurations and math modes, the float64 referee and the CPU baseline.
+--dump-outputs DIR writes the arrays the timed launches returned in their last step (uopt, xevol, info of rank 0's batch) as DIR/<name>.npy.
 
 This file: argument parsing, the timed leg, the JSON line. The pieces live in benchlib/ (counts, verify, power, ranks, legs).
 """
@@ -136,6 +141,27 @@ def corrupted_for_test(blob, rank):
     return blob
 
 
+DUMP_CAP_BYTES = 64 * 10**6
+
+
+def write_outputs(d, arrays, cap=DUMP_CAP_BYTES, seed=0):
+    """--dump-outputs: arrays whose rows are the instances of the batch, as d/<name>.npy in float32. When they hold more than `cap` bytes in all,
+    the same rows of every array for a fixed, seeded sample of the instances are written instead, and the sample's indices as d/instance_index.npy
+    (float64). Returns the indices written (None: every instance)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(a, np.float32) for k, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_instance = sum(a[0].nbytes for a in arrays.values())
+    idx = None
+    if per_instance * n > cap:
+        k = max(1, (cap - 4096) // (per_instance + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+        np.save(os.path.join(d, "instance_index.npy"), idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a if idx is None else a[idx]))
+    return idx
+
+
 def all_ranks_verified(V, rank, world, device=None, force=False):
     """Every rank has checked instances of ITS OWN launches (V: its verifier, drained). Returns ([(checked ok, asked) per rank], words differing in
     the whole job) on every rank: SUM of the bad words, all-gather of the per-rank counts — a wrong device binding or corrupted weights on rank 5
@@ -149,6 +175,24 @@ def all_ranks_verified(V, rank, world, device=None, force=False):
     return [tuple(r) for r in rows], total
 
 
+def headline(args, cfg, B, world, elapsed, c2_run):
+    """what every run's line holds: the timed launches' rate and what they ran (a --full run adds its other legs to it)"""
+    H, P, m = cfg.horizon, cfg.num_particles, cfg.num_motors
+    return {
+        "metric": (f"MPC solves/sec, Iris H=50 P=128, arithmetic {args.mlp_dtype}/{args.math_mode} (p50 solve latency in p50_solve_latency_ms: arithmetic f32/{args.math_mode}; "
+                   "same-arithmetic pairs in by_arithmetic; every arithmetic against float64 in vs_float64)" if c2_run else f"MPC solves/sec, {os.path.basename(args.config)}, arithmetic {args.mlp_dtype}/{args.math_mode}"),
+        "value": world * B * args.steps / elapsed, "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": DTYPE_NOTE[args.mlp_dtype] + "; " + MATH_NOTE[args.math_mode], "mlp_dtype": args.mlp_dtype, "math_mode": args.math_mode, "data": "synthetic",
+        "config": {"workload": f"{os.path.basename(args.config)}: H={H} P={P} m={m}, {B} independent MPC instances per GPU per step, "
+                               f"cold-start solves from the hover guess, max_iter={cfg.max_iter} maxls={cfg.ls_maxls}",
+                   "instances_per_gpu": B, "noise": "threefry2x32 keys (seed 10 split per instance), normal draws generated on the device",
+                   "parallelism": f"instances sharded over {world} GPU(s), no data-path collective"},
+        "library_build": lib_hash(),
+        "full": bool(args.full),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -157,24 +201,29 @@ def main():
     ap.add_argument("--batch", type=int, default=12288, help="MPC problem instances per GPU per step (eight rounds of the 1,536 instances an MI355X holds "
                     "at once: 256 CUs x 3 workgroups x 2 instances; from three rounds on the persistent launch hands instances out by ticket)")
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "c2_iris_traj_h50_p128.yaml"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--latency-reps", type=int, default=1000)
-    ap.add_argument("--latency-warmup", type=int, default=20)
     ap.add_argument("--mlp-dtype", default=DEFAULT_MLP, choices=["f32", "f16", "f32x3"],
                     help="f32x3 (default, the reported metric): f32 arithmetic with the layer-2 contractions as three-limb bf16 splits on the matrix pipe "
                          "(SPEC.md 9b), bit-identical to the oracle; f32: every contraction an f32 fma chain; f16: fp16-operand MLP contractions (SPEC.md 9)")
     ap.add_argument("--math-mode", default=DEFAULT_MATH, choices=["exact", "fast"],
                     help="fast (default): hardware transcendentals (SPEC.md 10), checked bit for bit through the oracle's instruction model (10a); exact: the software forms of SPEC.md 3")
     ap.add_argument("--max-iter", type=int, default=0, help="override the YAML's apg_mpc.max_iter (0: keep; profiling runs of the long-horizon config)")
-    ap.add_argument("--no-other-math-mode", "--no-tolerance-modes", dest="no_other_math_mode", action="store_true", help="skip the extra launches in the other math mode (exact <-> fast)")
-    ap.add_argument("--verify-budget-s", type=float, default=90.0, help="wall seconds the bit-exact checks of the timed launch may take on this host's cores: sets how many "
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed launches, write what the last one returned (uopt, xevol, info of rank 0's batch; float32) as DIR/<name>.npy; over "
+                         f"{DUMP_CAP_BYTES // 10**6} MB in all, a fixed seeded sample of the instances (indices in DIR/instance_index.npy)")
+    ap.add_argument("--full", action="store_true", help="after the timed leg, every other leg of the line (the options below); a plain run prints the headline only")
+    fl = ap.add_argument_group("legs of a --full run")
+    fl.add_argument("--no-cpu-baseline", action="store_true")
+    fl.add_argument("--cpu-threads", type=int, default=0)
+    fl.add_argument("--latency-reps", type=int, default=1000)
+    fl.add_argument("--latency-warmup", type=int, default=20)
+    fl.add_argument("--no-other-math-mode", "--no-tolerance-modes", dest="no_other_math_mode", action="store_true", help="skip the extra launches in the other math mode (exact <-> fast)")
+    fl.add_argument("--verify-budget-s", type=float, default=90.0, help="wall seconds the bit-exact checks of the timed launch may take on this host's cores: sets how many "
                     "instances are checked (at least 6, at most 24; a three-iteration solve calibrates the checker's speed)")
-    ap.add_argument("--referee", type=int, default=16, help="instances of the timed batch solved by the float64 build of the oracle for the vs_float64 table (0: none)")
-    ap.add_argument("--c4-reps", type=int, default=100, help="N > 1: barrier-aligned ticks of the one-instance-per-GPU leg (BASELINE config 4); 0 skips it")
-    ap.add_argument("--no-power", action="store_true", help="do not sample package power / shader clock beside the timed launches")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the secondary legs (C2 f32 chain, C3, C5 f32 / f16)")
-    ap.add_argument("--verify", type=int, default=-1, help="instances of the timed launch checked bit for bit against the CPU oracle "
+    fl.add_argument("--referee", type=int, default=16, help="instances of the timed batch solved by the float64 build of the oracle for the vs_float64 table (0: none)")
+    fl.add_argument("--c4-reps", type=int, default=100, help="N > 1: barrier-aligned ticks of the one-instance-per-GPU leg (BASELINE config 4); 0 skips it")
+    fl.add_argument("--no-power", action="store_true", help="do not sample package power / shader clock beside the timed launches")
+    fl.add_argument("--no-other-configs", action="store_true", help="skip the secondary legs (C2 f32 chain, C3, C5 f32 / f16)")
+    fl.add_argument("--verify", type=int, default=-1, help="instances of the timed launch checked bit for bit against the CPU oracle "
                     "(-1: a sample across the batch incl. ticket-drawn instances; 0: none)")
     args = ap.parse_args()
 
@@ -225,15 +274,15 @@ def main():
     cfg = cfg_of(args.config, args.mlp_dtype)
     if args.max_iter:
         cfg = cfg.replace(max_iter=args.max_iter, max_no_improvement_iter=args.max_iter)
-    H, P, m, B = cfg.horizon, cfg.num_particles, cfg.num_motors, args.batch
+    m, B = cfg.num_motors, args.batch
     c2_run = os.path.basename(args.config).startswith("c2_")
     # shared model: rank 0 builds it, RCCL broadcast over xGMI (read-only weights are the only shared data)
     from sde4mbrl_px4_amd.dist import broadcast_blob, max_over_ranks
     blob = (synthetic_iris() if m == 4 else synthetic_hexa()).to_blob() if rank == 0 else b""
     blob = corrupted_for_test(broadcast_blob(blob, src=0, device=dev, force=force_dist), rank)
-    if use_dist:        # every rank holds the same weights and runs the same build of the library, or the run stops here naming the rank that does not
+    if use_dist and args.full:        # every rank holds the same weights and runs the same build of the library, or the run stops here naming the rank that does not
         require_same_on_every_rank({"model blob": blob, "library build": lib_hash()}, device=dev, force=force_dist)
-    if args.math_mode == "fast" and args.verify != 0:
+    if args.full and args.math_mode == "fast" and args.verify != 0:
         instruction_model_check(ROOT, rank, progress)
 
     L = Leg(cfg, blob, B, dev_ord, rank, world, pos="posctrl" in os.path.basename(args.config))
@@ -245,7 +294,7 @@ def main():
         torch.cuda.synchronize()
 
     sampler = None
-    if not args.no_power and rank == 0:        # rank 0 samples every GPU of the job (sysfs; no child process, no collective)
+    if args.full and not args.no_power and rank == 0:        # rank 0 samples every GPU of the job (sysfs; no child process, no collective)
         ords = [int(os.environ["SDEMPC_BENCH_DEVICE"])] * world if "SDEMPC_BENCH_DEVICE" in os.environ else list(range(world))
         pci = {}
         for o in set(ords):
@@ -272,6 +321,20 @@ def main():
     if rank == 0:
         progress(f"timed leg done: {t1 - t0:.1f} s" + (f"; package {power['package_power_w_median']} W of {power['power_cap_w']}, sclk {power['sclk_mhz_median']} MHz" if power else ""))
     elapsed = max_over_ranks(t1 - t0, device=dev, force=force_dist)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dict(zip(("uopt", "xevol", "info"), L.host_outputs())))
+    head = headline(args, cfg, B, world, elapsed, c2_run) if rank == 0 else None
+    if not args.full:
+        if rank == 0:
+            head["bench_wall_s"] = time.perf_counter() - _T0
+            progress(f"done: {head['bench_wall_s']:.0f} s in all")
+            emit(head)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        L.close()
+        return 0
+    # ---- --full: every other leg of the line ---------------------------------------------------------------------------------------------------
     # per-launch kernel duration from HIP events, measured live on the launch stream (separate launches)
     ev_ms, n_grad, n_fwd = L.timed_events(min(args.steps, 3))
     kernel_name = L.solver.last_kernel_name()       # the instantiation the timed launches ran, as rocprofv3 names it
@@ -287,8 +350,6 @@ def main():
 
     out, lat_done = None, None
     if rank == 0:
-        solves = world * B * args.steps
-        value = solves / elapsed
         k_ms = float(np.mean(ev_ms))
         ach_tf, ach_gbs, bytes_solve, b_grad, b_ls = roofline_of(cfg, B, k_ms, n_grad, n_fwd)
         # HBM bytes per launch and the vector-issue figures from the PMC counters: they need rocprofv3 around the process (separate --pmc passes,
@@ -297,7 +358,7 @@ def main():
         # another build than the one the counters were taken on
         traffic, traffic_src, traffic_build, valu_issue = None, None, None, None
         pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        build = lib_hash()
+        build = head["library_build"]
         if os.path.exists(pmc):
             try:
                 rec = json.load(open(pmc)).get(f"{os.path.basename(args.config)}:B{B}:{args.mlp_dtype}:{args.math_mode}", {})
@@ -325,15 +386,9 @@ def main():
             lat_same, same_kernel, _ = latency_of(L, L.solver, min(args.latency_reps, 30), min(args.latency_warmup, 2))
         pw = (power or {}).get("package_power_w_median")
         energy = (pw * (elapsed / args.steps) / B) if isinstance(pw, (int, float)) else None       # per GPU: this GPU's watts x its launch time / its instances
-        out = {
-            "metric": (f"MPC solves/sec, Iris H=50 P=128, arithmetic {args.mlp_dtype}/{args.math_mode} (p50 solve latency in p50_solve_latency_ms: arithmetic f32/{args.math_mode}; "
-                       "same-arithmetic pairs in by_arithmetic; every arithmetic against float64 in vs_float64)" if c2_run else f"MPC solves/sec, {os.path.basename(args.config)}, arithmetic {args.mlp_dtype}/{args.math_mode}"),
-            "value": value, "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": DTYPE_NOTE[args.mlp_dtype] + "; " + MATH_NOTE[args.math_mode], "mlp_dtype": args.mlp_dtype, "math_mode": args.math_mode, "data": "synthetic",
-            "config": {"workload": f"{os.path.basename(args.config)}: H={H} P={P} m={m}, {B} independent MPC instances per GPU per step, "
-                                   f"cold-start solves from the hover guess, max_iter={cfg.max_iter} maxls={cfg.ls_maxls}",
-                       "instances_per_gpu": B, "noise": "threefry2x32 keys (seed 10 split per instance), normal draws generated on the device", "N_it_mean": n_it, "N_ls_mean": n_ls, "N_grad_evaluated_mean": n_grad, "N_forward_rollouts_mean": n_fwd, "parallelism": f"instances sharded over {world} GPU(s), no data-path collective"},
+        out = head
+        out["config"].update({"N_it_mean": n_it, "N_ls_mean": n_ls, "N_grad_evaluated_mean": n_grad, "N_forward_rollouts_mean": n_fwd})
+        out.update({
             "p50_solve_latency_ms": float(np.median(lat)) if lat else None,
             "p95_solve_latency_ms": float(np.percentile(lat, 95)) if lat else None,
             "latency_reps": len(lat), "latency_layout_fallbacks": fallbacks, "latency_kernel": single_kernel, "latency_mlp_dtype": "f32", "latency_math_mode": args.math_mode,
@@ -344,7 +399,6 @@ def main():
                                       "have no matrix instructions, so they exist for the f32 fma-chain arithmetic only; a single instance in the f32x3 arithmetic runs in the tile layout on one "
                                       "workgroup (the second figure). Both arithmetics are bit-identical to the oracle in their mode and agree with each other to 1e-6 on the controls",
             "p50_batch_latency_ms": float(np.median(ev_ms)),
-            "library_build": build,
             "power": power,
             "energy_per_solve_J": energy,
             "energy_per_solve_note": "median package power of this GPU over the timed launches x ms_per_step / instances per GPU: at the power cap this, not the clock, is what a faster kernel must lower",
@@ -370,7 +424,7 @@ def main():
                              "traffic": traffic, "bytes_per_solve": bytes_solve, "B_grad": b_grad, "B_ls": b_ls,
                              "checkpoint_bytes_per_solve": checkpoint_bytes(cfg, n_grad),
                              "note": "achieved = SURVEY 8d algorithmic bytes / kernel time; measured traffic additionally contains the activation-checkpoint stream"},
-        }
+        })
         if world > 1:
             out["cpu_baseline"] = "skipped (n_gpus > 1): reported by the single-GPU run"
     if use_dist:

@@ -4,7 +4,7 @@ import os
 import numpy as np
 import pytest
 
-from cases import CDIR
+from cases import CDIR, GOLDEN_DIR
 from sde4mbrl_px4_amd import jax_shim
 from sde4mbrl_px4_amd import synthetic_iris
 from sde4mbrl_px4_amd.sde_mpc_design import OptState, load_mpc_from_cfgfile
@@ -141,13 +141,8 @@ def test_unavailable_model_or_trajectory_is_an_error_not_a_silent_stand_in(tmp_p
     path that cannot be honoured raises; the synthetic vehicle / analytic lemniscate replace it only on request, with a warning."""
     import shutil
     monkeypatch.delenv("SDEMPC_ALLOW_SYNTHETIC", raising=False)
-    ref_yaml = "/root/reference/launch/iris_sitl_traj_mpc.yaml"
     y = tmp_path / "traj_mpc.yaml"
-    if os.path.exists(ref_yaml):
-        shutil.copy(ref_yaml, y)
-    else:   # GPU box: no reference tree; same two keys on top of this repo's C2 file
-        y.write_text("learned_model_params: ~/nowhere/iris_sitl_sde.pkl\ntrajectory_path: ~/nowhere/fast2_lemn.csv\n"
-                     + open(os.path.join(CDIR, "c2_iris_traj_h50_p128.yaml")).read())
+    shutil.copy(os.path.join(GOLDEN_DIR, "reference_mpc_yaml", "iris_sitl_traj_mpc.yaml"), y)      # the reference's file, verbatim
     with pytest.raises(FileNotFoundError, match="trajectory_path|learned_model_params"):
         load_mpc_from_cfgfile(str(y))
     with pytest.raises(FileNotFoundError, match="learned_model_params"):

@@ -11,7 +11,7 @@ from cases import CDIR, ROOT
 from sde4mbrl_px4_amd import MPCConfig, load_mpc_config, synthetic_hexa, synthetic_iris
 from sde4mbrl_px4_amd import _abi
 
-REF_LAUNCH = "/root/reference/launch"
+REF_LAUNCH = os.path.join(ROOT, "tests", "golden", "reference_mpc_yaml")      # the reference's shipped MPC YAML files (launch/*_mpc.yaml), verbatim
 
 
 def test_benchmark_configs_parse():
@@ -28,7 +28,6 @@ def test_benchmark_configs_parse():
     assert (c5.horizon, c5.num_particles) == (200, 1024)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_LAUNCH), reason="reference tree not present (GPU box)")
 def test_reference_yaml_files_parse_verbatim():
     """Every shipped MPC YAML of the reference parses; shipped sizes are H=20, P=1."""
     files = sorted(glob.glob(os.path.join(REF_LAUNCH, "*_mpc.yaml")))

@@ -102,6 +102,31 @@ def _bench_env(**kw):
     return env
 
 
+def test_bench_dump_outputs_every_instance_or_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: the arrays of the batch as DIR/<name>.npy in float32; over the size cap, the same rows of every array for a seeded
+    sample of the instances (the same sample on every run), whose indices are written beside them."""
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"uopt": rng.random((50, 6, 4), dtype=np.float32), "xevol": rng.random((50, 7, 13), dtype=np.float32), "info": rng.random((50, 8), dtype=np.float32)}
+    assert bench.write_outputs(str(tmp_path / "all"), arrays) is None
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "all" / f"{k}.npy")
+        assert b.dtype == np.float32 and b.tobytes() == a.tobytes()
+    assert not (tmp_path / "all" / "instance_index.npy").exists()
+    per = 4 * (6 * 4 + 7 * 13 + 8)
+    cap = 4096 + 20 * (per + 8)
+    idx = bench.write_outputs(str(tmp_path / "s1"), arrays, cap=cap)
+    assert len(idx) == 20 and list(idx) == sorted(set(idx.tolist())) and 0 <= idx[0] and idx[-1] < 50
+    assert np.array_equal(np.load(tmp_path / "s1" / "instance_index.npy"), idx.astype(np.float64))
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= cap
+    for k, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), a[idx])
+    assert np.array_equal(bench.write_outputs(str(tmp_path / "s2"), arrays, cap=cap), idx)
+    # a plain run and a --full run take the same options; the dump and --full are on the command line
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--dump-outputs DIR" in r.stdout and "--full" in r.stdout
+
+
 def test_bench_four_ranks_dry_run_over_gloo():
     """The rank plumbing of `bench.py --gpus 4` on the CPU (SDEMPC_BENCH_DRY=1: self-start, rendezvous on 127.0.0.1, blob broadcast, all-reduce MAX
     incl. a dropped tick, barriers, destroy) — what the first real multi-GPU run exercises before any kernel is launched. One JSON line, exit 0."""

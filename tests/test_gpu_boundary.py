@@ -136,7 +136,7 @@ def test_bench_two_ranks_self_started_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "64", "--max-iter", "12",
-                          "--latency-reps", "2", "--latency-warmup", "1", "--no-cpu-baseline", "--verify", "2", "--c4-reps", "6"],
+                          "--full", "--latency-reps", "2", "--latency-warmup", "1", "--no-cpu-baseline", "--verify", "2", "--c4-reps", "6"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -170,7 +170,7 @@ def test_bench_rccl_branch_on_one_gpu():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.pop("SDEMPC_BENCH_BACKEND", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--batch", "64", "--max-iter", "12",
-                          "--latency-reps", "2", "--latency-warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--no-tolerance-modes", "--verify", "2"],
+                          "--full", "--latency-reps", "2", "--latency-warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--no-tolerance-modes", "--verify", "2"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -184,6 +184,44 @@ def test_bench_rccl_branch_on_one_gpu():
                          env=env, capture_output=True, text=True, timeout=300)
     last = chk.stdout.strip().splitlines()[-1].split()                     # (RCCL prints its own banner lines before ours)
     assert chk.returncode == 0 and last[0] == "nccl" and float(last[1]) == 4.0, (chk.stdout[-500:], chk.stderr[-2000:])
+
+
+def test_bench_plain_run_dumps_what_its_timed_launches_returned(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline alone, and --dump-outputs writes what its last timed launch returned: every
+    instance's uopt / xevol / info in float32, instances of it bit for bit equal to the CPU oracle solving the problems the timed leg was given."""
+    import json
+    import subprocess
+    import sys
+    from cases import ROOT
+    from sde4mbrl_px4_amd import load_mpc_config, prng, synthetic_iris
+    from sde4mbrl_px4_amd.solver import SdeMpcSolver
+    B, it = 64, 12
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", str(B), "--max-iter", str(it),
+                          "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["full"] is False and rec["unit"] == "solves/s" and rec["higher_is_better"] is True
+    assert rec["value"] > 0 and abs(rec["value"] * rec["ms_per_step"] * 1e-3 - B) < 1e-6 * B          # B instances per timed step of ms_per_step
+    assert rec["metric"].startswith("MPC solves/sec") and rec["dtype"].startswith("f32")
+    assert not {"verified_instances", "roofline", "p50_solve_latency_ms", "power", "cpu_baseline", "other_configs"} & set(rec)
+    cfg = load_mpc_config(os.path.join(CDIR, "c2_iris_traj_h50_p128.yaml")).replace(mlp_dtype="f32x3", math_mode="fast", max_iter=it, max_no_improvement_iter=it)
+    got = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in ("uopt", "xevol", "info")}
+    assert got["uopt"].shape == (B, cfg.horizon, 4) and got["xevol"].shape == (B, cfg.horizon + 1, 13) and got["info"].shape == (B, 8)
+    assert all(a.dtype == np.float32 for a in got.values()) and not (tmp_path / "out" / "instance_index.npy").exists()
+    # the problems of bench.py's timed leg (benchlib/legs.py: Leg), solved by the oracle
+    blob = synthetic_iris().to_blob()
+    S = SdeMpcSolver(cfg, blob, max_batch=1)
+    yk, info0 = S.reset()
+    S.close()
+    x0, keys = W.random_initial_states(B, 0), prng.split(prng.PRNGKey(10), B)
+    O = orc.Oracle(cfg, blob)
+    for b in (0, B - 1):
+        xref = W.reference_window(0.05 * (b % 160), cfg.time_steps)
+        uo, xe, io, _ = O.solve(x0[b], xref, orc.noise_from_key(keys[b], cfg.num_particles, cfg.horizon), yk, float(info0["stepsize"]))
+        assert (bits_differ(got["uopt"][b], uo), bits_differ(got["xevol"][b], xe), bits_differ(got["info"][b], io)) == (0, 0, 0), b
 
 
 def test_hold_mode_tracks_the_current_state_in_the_right_frame():

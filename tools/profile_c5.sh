@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/$tag; rm -rf $out; mkdir -p $out
 rocprofv3 --list-avail 2>/dev/null | grep -o "SQ_[A-Z0-9_]*MFMA[A-Z0-9_]*" | sort -u > $out/mfma_counters.txt
 for dt in f32 f16; do
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $out/trace_$dt --output-format csv -- python3 bench.py --config configs/c5_iris_traj_h200_p1024.yaml --mlp-dtype $dt \
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $out/trace_$dt --output-format csv -- python3 bench.py --full --config configs/c5_iris_traj_h200_p1024.yaml --mlp-dtype $dt \
       --batch $B --max-iter $IT --steps 2 --warmup 1 --no-cpu-baseline --latency-reps 0 --verify 0 > $out/bench_$dt.log 2>&1 || echo "trace $dt failed"
   i=0
   for c in "FETCH_SIZE" "WRITE_SIZE" \
