@@ -254,6 +254,32 @@ int sdempc_solve_batch_keys(sdempc_handle* h, int32_t B, const float* x0, const 
                             const float* u_init /*[B][H][m]*/, const float* stepsize_in /*[B]*/,
                             float* uopt /*[B][H][m]*/, float* xevol /*[B][H+1][13]*/, sdempc_info* info /*[B]*/);
 
+/* ---- batched closed loop (SPEC.md §11) ---------------------------------------------------------
+ * B independent episodes of T control ticks, entirely on the device: per tick, the solve of sdempc_solve_batch_keys on the episode's
+ * state, then one Euler–Maruyama step of the handle's own model (step 0 of a rollout: dt = time_steps[0], sigma sqrt(dt), the handle's
+ * mlp_dtype and math_mode) under the first control of the solution and its own noise draw. No reference counterpart: the reference closes
+ * the loop only through PX4 SITL + Gazebo, one trajectory in real time. Episode b, solver frame, for tick k = 0 .. T-1:
+ *   (r', s) = split(r_k); solve with noise normal(s, (P, H, 6)), warm start y_k, step size s_k, reference xref[k or 0][b or 0];
+ *   (r_{k+1}, p) = split(r'); x_{k+1} = step(x_k, uopt_k[0], normal(p, (6,)));
+ *   y_{k+1} = [uopt_k[1:], uopt_k[H-1]]; s_{k+1} = info_k.stepsize.
+ * Host pointers:
+ *   x0 [B][13]; xref [xref_ticks][xref_batch][H+1][13] with xref_ticks 1 (one window on every tick) or T, xref_batch 1 (shared by
+ *   every episode) or B; keys u32[B][2] (r_0); u_init [B][H][m] and stepsize_in [B], or NULL for what sdempc_reset gives (uref tiled;
+ *   ls_init_stepsize if ls_maxls > 0, else stepsize).
+ *   Outputs: xs [B][T+1][13] (xs[b][0] = x0[b]), us [B][T][m] (the applied uopt_k[0]), info [B][T]; optionally (else NULL), to continue
+ *   the episodes: u_next [B][H][m] = y_T, stepsize_next [B] = s_T, keys_next u32[B][2] = r_T.
+ * Each tick's solve goes through sdempc_solve_batch_dev, so the layout choice is that of a solve of B instances and never changes a
+ * bit. The ticks are enqueued without a host synchronisation; outputs are copied back in chunks of ticks (at most 256 MiB of device
+ * buffers per chunk), so T is not bounded by device memory. A cooperative-layout barrier that gave up, or a ticket count that is off,
+ * is detected at the end of a chunk, and the whole batch then runs once more from the inputs in the one-workgroup-per-instance layouts.
+ * Non-finite states are not special-cased: they flow into the next solve as any state does (SPEC.md §3.7, §8). */
+int sdempc_closed_loop_batch(sdempc_handle* h, int32_t B, int32_t T, const float* x0,
+                             const float* xref, int32_t xref_ticks, int32_t xref_batch,
+                             const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                             float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][T]*/,
+                             float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                             uint32_t* keys_next /*[B][2] or NULL*/);
+
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so
  * repeating the call runs in the one-workgroup-per-instance layout. Also SDEMPC_EDEVICE when a large throughput launch that hands its

@@ -73,6 +73,9 @@ struct sdempc_handle {
     DevBuf d_part, d_act, d_traj, d_x0, d_u, d_xref, d_noise, d_step, d_cost, d_grad, d_xmean, d_uopt, d_info;
     // canonical-layout staging of the host-pointer entry points (allocated on their first use)
     DevBuf d_noise_canon, d_traj_canon, d_keys;
+    // closed loop (sdempc_closed_loop_batch, allocated on its first use): d_loop = keys u32[max_batch][2], solve keys u32[max_batch][2], plant noise
+    // f32[max_batch][6], one flag word; d_loop_chunk = the per-tick outputs of one chunk of ticks and the reference windows it reads (grown, never shrunk)
+    DevBuf d_loop, d_loop_chunk;
     DevBuf d_work;            // u64[4] work counters (KArgs::work)
     // cooperative latency path of the solve (allocated on its first use, sized for coop_cap instances)
     DevBuf d_coop_bar, d_coop_pp, d_coop_ck;
@@ -366,6 +369,17 @@ int timed_launch(sdempc_handle* h, hipStream_t st, F&& f) {
 
 
 int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_info* info);
+struct LoopIo {
+    int B, T, xref_ticks, xref_batch;
+    const float *x0, *xref;
+    const uint32_t* keys;
+    const float *u_init, *stepsize_in;
+    float *xs, *us;
+    sdempc_info* info;
+    float *u_next, *stepsize_next;
+    uint32_t* keys_next;
+};
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, bool* again);
 }  // namespace
 
 extern "C" {
@@ -537,7 +551,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -881,6 +895,27 @@ int sdempc_solve_batch_keys(sdempc_handle* h, int32_t B, const float* x0, const 
     });
 }
 
+int sdempc_closed_loop_batch(sdempc_handle* h, int32_t B, int32_t T, const float* x0, const float* xref, int32_t xref_ticks, int32_t xref_batch,
+                             const uint32_t* keys, const float* u_init, const float* stepsize_in, float* xs, float* us, sdempc_info* info,
+                             float* u_next, float* stepsize_next, uint32_t* keys_next) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if (T < 1) return fail(h, SDEMPC_EINVAL, "closed loop: T must be >= 1%s");
+    if (xref_ticks != 1 && xref_ticks != T) return fail(h, SDEMPC_EINVAL, "closed loop: xref_ticks must be 1 or T%s");
+    if (xref_batch != 1 && xref_batch != B) return fail(h, SDEMPC_EINVAL, "closed loop: xref_batch must be 1 or B%s");
+    if (!x0 || !xref || !keys || !xs || !us || !info) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    if ((rc = ensure_device(h))) return rc;
+    const LoopIo io{B, T, xref_ticks, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    for (int attempt = 0;; ++attempt) {
+        bool again = false;
+        if ((rc = closed_loop_run(h, io, &again))) return rc;
+        if (!again) return SDEMPC_OK;
+        if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
+    }
+    });
+}
+
 int sdempc_solve_status(sdempc_handle* h) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -929,5 +964,117 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (!to) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
+}
+// Device memory the per-tick buffers of one chunk of closed-loop ticks may take (sdempc_closed_loop_batch): the outputs (x_{k+1}, u_k, info_k)
+// of every episode and, when the reference moves per tick, the chunk's reference windows. T itself is unbounded: outputs are copied back and
+// references staged once per chunk (one host synchronisation per chunk, none per tick).
+constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
+
+// SPEC.md §11. Stages the host inputs, enqueues every tick of a chunk on the handle's stream (key schedule, noise, solve, plant step), copies
+// the chunk's outputs back and checks, once per chunk, whether a grid barrier of a cooperative-layout solve gave up or the ticket count of the
+// persistent launches is off: *again = true then, and the caller runs the whole batch once more from the host inputs (the handle has left
+// the cooperative layouts; results are the same in every layout).
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, bool* again) {
+    *again = false;
+    const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
+    const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)NX + m + 8;       // floats per reference window / per episode-tick of output
+    const bool xref_moves = io.xref_ticks > 1;
+    const size_t per_tick = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0);
+    const size_t fixed = xref_moves ? 0 : (size_t)Bx * XR, cap = LOOP_CHUNK_BYTES / sizeof(float);
+    const size_t fit = cap > fixed ? (cap - fixed) / per_tick : 0;
+    const int Tc = (int)(fit < 1 ? 1 : (fit < (size_t)T ? fit : (size_t)T));
+    const size_t chunk_floats = (size_t)Tc * per_tick + fixed;
+    int rc;
+    if (!h->d_loop.p && (rc = dev_alloc(h, h->d_loop, sizeof(uint32_t) * (size_t)h->max_batch * 10 + 16))) return rc;
+    if (h->d_loop_chunk.bytes < sizeof(float) * chunk_floats) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        dev_free(h->d_loop_chunk);
+        if ((rc = dev_alloc(h, h->d_loop_chunk, sizeof(float) * chunk_floats))) return rc;
+    }
+    uint32_t* d_keys = (uint32_t*)h->d_loop.p;                      // r_k, advanced in place
+    uint32_t* d_sub = d_keys + 2 * (size_t)h->max_batch;             // the solve's noise keys of the tick
+    float* d_xi = (float*)(d_sub + 2 * (size_t)h->max_batch);        // plant noise of the tick
+    unsigned* d_gave_up = (unsigned*)(d_xi + 6 * (size_t)h->max_batch);
+    float* c_xs = (float*)h->d_loop_chunk.p;                         // [Tc][B][13]
+    float* c_us = c_xs + (size_t)Tc * B * NX;                        // [Tc][B][m]
+    float* c_info = c_us + (size_t)Tc * B * m;                       // [Tc][B][8]
+    float* c_xref = c_info + (size_t)Tc * B * 8;                     // [Tc or 1][Bx][H+1][13]
+    float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place
+    hipStream_t st = h->stream;
+    // inputs (host vectors live until the synchronisation at the end of the first chunk)
+    std::vector<float> u0, s0;
+    const float* u_in = io.u_init;
+    const float* s_in = io.stepsize_in;
+    if (!u_in) {               // sdempc_reset: uref tiled
+        u0.resize((size_t)B * H * m);
+        for (size_t e = 0; e < u0.size(); ++e) u0[e] = h->cfg.uref[e % m];
+        u_in = u0.data();
+    }
+    if (!s_in) {
+        s0.assign(B, h->cfg.ls_maxls > 0 ? h->cfg.ls_init_stepsize : h->cfg.stepsize);
+        s_in = s0.data();
+    }
+    HIPCHK(h, hipMemcpyAsync(d_x, io.x0, sizeof(float) * B * NX, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(d_keys, io.keys, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->d_u.p, u_in, sizeof(float) * (size_t)B * H * m, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->d_step.p, s_in, sizeof(float) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemsetAsync(d_gave_up, 0, sizeof(unsigned), st));
+    if (!xref_moves) {
+        HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
+        if (Bx != B) HIPCHK(h, launch_broadcast_rows(c_xref, (float*)h->d_xref.p, (int)XR, B, st));
+    }
+    for (int b = 0; b < B; ++b) memcpy(io.xs + (size_t)b * (T + 1) * NX, io.x0 + (size_t)b * NX, sizeof(float) * NX);
+    std::vector<float> hx, hu, hi;
+    for (int k0 = 0; k0 < T; k0 += Tc) {
+        const int nk = T - k0 < Tc ? T - k0 : Tc;
+        if (xref_moves) HIPCHK(h, hipMemcpyAsync(c_xref, io.xref + (size_t)k0 * Bx * XR, sizeof(float) * nk * Bx * XR, hipMemcpyHostToDevice, st));
+        for (int kc = 0; kc < nk; ++kc) {
+            HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st));
+            HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));
+            const float* win = c_xref + (xref_moves ? (size_t)kc * Bx * XR : 0);
+            const float* xr = win;
+            if (Bx != B) {
+                if (xref_moves) HIPCHK(h, launch_broadcast_rows(win, (float*)h->d_xref.p, (int)XR, B, st));
+                xr = (const float*)h->d_xref.p;
+            }
+            float* info_k = c_info + (size_t)kc * B * 8;
+            if ((rc = sdempc_solve_batch_dev(h, B, d_x, xr, h->d_noise.p, h->d_u.p, h->d_step.p, h->d_uopt.p, h->d_xmean.p, info_k, st))) return rc;
+            LoopAdvance L;
+            L.uopt = (const float*)h->d_uopt.p; L.info = info_k; L.xi = d_xi;
+            L.coop_bar = h->last_coop_B > 0 ? (const unsigned*)h->d_coop_bar.p : nullptr;
+            L.x = d_x; L.u = (float*)h->d_u.p; L.step = (float*)h->d_step.p;
+            L.xs = c_xs + (size_t)kc * B * NX; L.us = c_us + (size_t)kc * B * m; L.gave_up = d_gave_up;
+            L.B = B; L.H = H;
+            HIPCHK(h, h->base.fast ? launch_loop_advance_fast(h->base, L, st) : launch_loop_advance(h->base, L, st));
+        }
+        hx.resize((size_t)nk * B * NX); hu.resize((size_t)nk * B * m); hi.resize((size_t)nk * B * 8);
+        unsigned gave_up = 0;
+        HIPCHK(h, hipMemcpyAsync(hx.data(), c_xs, sizeof(float) * hx.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(hu.data(), c_us, sizeof(float) * hu.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(hi.data(), c_info, sizeof(float) * hi.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(&gave_up, d_gave_up, sizeof gave_up, hipMemcpyDeviceToHost, st));
+        if (k0 + nk == T) {
+            if (io.u_next) HIPCHK(h, hipMemcpyAsync(io.u_next, h->d_u.p, sizeof(float) * (size_t)B * H * m, hipMemcpyDeviceToHost, st));
+            if (io.stepsize_next) HIPCHK(h, hipMemcpyAsync(io.stepsize_next, h->d_step.p, sizeof(float) * B, hipMemcpyDeviceToHost, st));
+            if (io.keys_next) HIPCHK(h, hipMemcpyAsync(io.keys_next, d_keys, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(h, hipStreamSynchronize(st));
+        if (gave_up) {             // the workgroups of a cooperative layout were not all resident: no second try on this handle
+            h->coop_off = true;
+            h->layout_fallbacks += 1;
+            h->last_coop_B = 0;
+            *again = true;
+            return 0;
+        }
+        if (tickets_consistent(h) != 0) { *again = true; return 0; }     // (the mirror is re-synchronised)
+        for (int kc = 0; kc < nk; ++kc)
+            for (int b = 0; b < B; ++b) {
+                const size_t r = (size_t)kc * B + b, k = (size_t)k0 + kc;
+                memcpy(io.xs + ((size_t)b * (T + 1) + k + 1) * NX, &hx[r * NX], sizeof(float) * NX);
+                memcpy(io.us + ((size_t)b * T + k) * m, &hu[r * m], sizeof(float) * m);
+                memcpy((float*)io.info + ((size_t)b * T + k) * 8, &hi[r * 8], sizeof(float) * 8);
+            }
+    }
+    return 0;
 }
 }  // namespace

@@ -144,6 +144,26 @@ hipError_t launch_grad_fast(const KArgs& a, int B, hipStream_t st);
 hipError_t launch_solve_fast(const KArgs& a, int B, hipStream_t st);
 hipError_t launch_solve_coop_fast(const KArgs& a, int B, hipStream_t st);      // the cooperative latency layouts in math_mode fast (same grid rules)
 hipError_t launch_solve_spec_fast(const KArgs& a, int B, hipStream_t st);
+// SPEC.md §11, the batched closed loop: per-tick plant step and hand-over to the next solve (sdempc_loop.inc.h, translation unit SDEMPC_TU = 4)
+struct LoopAdvance {
+    const float* uopt;          // [B][H][m] this tick's solutions
+    const float* info;          // [B][8] this tick's telemetry (step size at [1])
+    const float* xi;            // [B][6] plant noise of this tick
+    const unsigned* coop_bar;   // [B][COOP_BAR_WORDS] of this tick's cooperative-layout solve, or null
+    float* x;                   // [B][13] x_k in, x_{k+1} out (the next solve's initial states)
+    float* u;                   // [B][H][m] warm start of the next solve
+    float* step;                // [B] step size of the next solve
+    float* xs;                  // [B][13] x_{k+1} (output row of this tick)
+    float* us;                  // [B][m] applied control uopt_k[0] (output row of this tick)
+    unsigned* gave_up;          // one word, sticky: a grid barrier of a cooperative-layout solve of this loop gave up
+    int B, H;
+};
+hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
+hipError_t launch_loop_advance_fast(const KArgs& a, const LoopAdvance& L, hipStream_t st);
+// the tick's key schedule (sdempc_prng.hip): keys r_k -> r_{k+1} in place, the solve's noise keys into sub_dev u32[B][2], the plant noise into xi_dev f32[B][6]
+hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st);
+// rows_dev[b][0..n) = row_dev[0..n) for b < B
+hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st);
 // canonical [B][P][C] <-> device [B][G][C][32] (to_dev: zero-pads particles >= P)
 hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int P, int G, int C, hipStream_t st);
 // SPEC.md §7: noise of B instances from their threefry keys (device u32[B][2]) straight into the device layout [B][G][H][6][32]

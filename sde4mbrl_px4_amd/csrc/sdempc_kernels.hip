@@ -45,6 +45,7 @@
 // unit; the solve kernel has ~90 instantiations of ~25k instructions each): SDEMPC_TU = 0 — every kernel except the duo solve
 // kernels, and all launchers; 1 — the duo solve kernels of the two-wave teams (TeamPair, TeamBlock2); 2 — those of the four-wave
 // team (TeamBlock); 3 — those of the six-team workgroup (TeamHex). Units 1 to 3 hold nothing but explicit instantiations (list macros below), unit 0 declares them `extern template`.
+// 4 — the plant step of the batched closed loop and its launcher (sdempc_loop.inc.h, SPEC.md §11).
 #ifndef SDEMPC_TU
 #define SDEMPC_TU 0
 #endif
@@ -1108,6 +1109,15 @@ SDEMPC_DUO_TEAM(SDEMPC_DUO_DEF, TeamBlock)
 #elif SDEMPC_TU == 3
 SDEMPC_DUO_HEX(SDEMPC_DUO_DEF)
 }  // namespace exact / fastm
+#elif SDEMPC_TU == 4
+#include "sdempc_loop.inc.h"
+#if SDEMPC_FAST
+}  // namespace fastm
+hipError_t launch_loop_advance_fast(const KArgs& a, const LoopAdvance& L, hipStream_t st) { return fastm::launch_loop_advance(a, L, st); }
+#else
+}  // namespace exact
+hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st) { return exact::launch_loop_advance(a, L, st); }
+#endif
 #else
 SDEMPC_DUO_PAIR(SDEMPC_DUO_DECL)
 SDEMPC_DUO_HEX(SDEMPC_DUO_DECL)

@@ -143,4 +143,52 @@ hipError_t launch_noise_from_keys(const uint32_t* keys_dev, float* out, int B, i
     return hipGetLastError();
 }
 
+// ---- closed loop (SPEC.md §11): the key schedule of one tick, on device-resident keys ----
+// split(r, 2) = random_bits(r, 4): counters (0, 2) and (1, 3) give the words [y0(0), y0(1), y1(0), y1(1)]; the first key is
+// {y0(0), y0(1)}, the second {y1(0), y1(1)}.
+DI void split2(uint32_t k0, uint32_t k1, uint32_t* first, uint32_t* second) {
+    uint32_t a0 = 0u, a1 = 2u, c0 = 1u, c1 = 3u;
+    threefry2x32(k0, k1, a0, a1);
+    threefry2x32(k0, k1, c0, c1);
+    first[0] = a0; first[1] = c0;
+    second[0] = a1; second[1] = c1;
+}
+// one thread per episode: (r', s) = split(r_k), (r_{k+1}, p) = split(r'), xi_k = normal(p, (6,)) (random_bits(p, 6) pairs counter i with
+// i + 3). keys: r_k in, r_{k+1} out; sub: s (the solve's noise key); xi: [B][6]
+__global__ void __launch_bounds__(256) sdempc_loop_keys_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    uint32_t r1[2], s[2], r2[2], p[2];
+    split2(keys[2 * b], keys[2 * b + 1], r1, s);
+    split2(r1[0], r1[1], r2, p);
+    sub[2 * b] = s[0]; sub[2 * b + 1] = s[1];
+    keys[2 * b] = r2[0]; keys[2 * b + 1] = r2[1];
+#pragma unroll
+    for (uint32_t i = 0; i < 3; ++i) {
+        uint32_t x0 = i, x1 = i + 3u;
+        threefry2x32(p[0], p[1], x0, x1);
+        xi[6 * b + i] = bits_to_normal(x0);
+        xi[6 * b + 3 + i] = bits_to_normal(x1);
+    }
+}
+
+hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st) {
+    if (B < 1) return hipErrorInvalidValue;
+    sdempc_loop_keys_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B);
+    return hipGetLastError();
+}
+
+// rows[b] = row for b < B (one reference window shared by every episode of a closed-loop batch), n floats per row
+__global__ void __launch_bounds__(256) sdempc_broadcast_rows_kernel(const float* __restrict__ row, float* __restrict__ rows, int n, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) rows[i] = row[i % n];
+}
+
+hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st) {
+    if (B < 1 || n < 1) return hipErrorInvalidValue;
+    const long long total = (long long)n * B;
+    sdempc_broadcast_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(row_dev, rows_dev, n, total);
+    return hipGetLastError();
+}
+
 }  // namespace sdempc

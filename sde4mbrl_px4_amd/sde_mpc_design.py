@@ -137,6 +137,38 @@ class MpcProblem:
         return _arr(uo), st, new_rng, _arr(xevol[0])
 
 
+    def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None):
+        """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
+        Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
+        T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
+        and the states back once (not per tick). Tick k tracks self.xref(curr_t + k * dt_0, xdes) when a trajectory is loaded, else xdes
+        (default: the initial state). opt_state None starts from m_reset. Returns (xs f32[T+1][13] with xs[0] = x, us f32[T][m],
+        info f32[T][8], the OptState after the last tick, the key after the last tick)."""
+        if not self.shift_warm_start:
+            raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
+        T = int(T)
+        x = np.asarray(x, np.float32).reshape(13)
+        xs0 = enu2ned(x, np) if self.convert_to_enu else x
+        xdes = xs0 if xdes is None else np.asarray(xdes, np.float32).reshape(13)
+        if self.state_from_traj is not None:
+            dt0 = float(self.cfg.time_steps[0])
+            xref = np.stack([self.xref(float(curr_t) + k * dt0, xdes) for k in range(T)])[:, None]
+        else:
+            xref = self.xref(float(curr_t), xdes)[None, None]
+        rng = np.asarray(rng, dtype=np.uint32).reshape(1, 2)
+        u0 = s0 = None
+        if opt_state is not None:
+            u0 = np.asarray(opt_state.yk, np.float32)[None]
+            s0 = np.array([opt_state.stepsize], np.float32)
+        xs, us, info, u_next, s_next, k_next = self.solver().closed_loop(xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0)
+        xs = xs[0]
+        if self.convert_to_enu:
+            xs = np.concatenate([x[None], enu2ned(xs[1:], np)], axis=0)
+        i = info[0, -1]
+        st = OptState(_arr(u_next[0]), np.float32(i[0]), np.float32(s_next[0]), np.float32(i[2]), np.float32(i[3]), np.float32(i[4]),
+                      np.float32(i[5]), np.float32(i[6]), np.float32(i[7]))
+        return _arr(xs), _arr(us[0]), _arr(info[0]), st, k_next[0].copy()
+
 def _allow_synthetic(flag) -> bool:
     return bool(flag) if flag is not None else os.environ.get("SDEMPC_ALLOW_SYNTHETIC") == "1"
 

@@ -150,6 +150,41 @@ class SdeMpcSolver:
                                                      _fp(u_init), _fp(stepsize_in), _fp(uopt), _fp(xevol), info))
         return uopt, xevol, np.frombuffer(info, dtype=np.float32).reshape(B, 8).copy()
 
+    def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None):
+        """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
+        model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
+        with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
+        f32[H+1][13]; u_init [B][H][m] / stepsize_in [B] default to what reset() gives. Returns
+        (xs [B][T+1][13], us [B][T][m], info [B][T][8], u_next [B][H][m], stepsize_next [B], keys_next uint32[B][2])."""
+        x0 = _f32(x0)
+        B, T = x0.shape[0], int(T)
+        x0 = _f32(x0, (B, 13))
+        keys = self._keys(keys, B)
+        xref = _f32(xref)
+        if xref.ndim == 2:
+            xref = xref[None, None]
+        if xref.ndim != 4 or xref.shape[2:] != (self.H + 1, 13):
+            raise ValueError(f"xref must be f32[Tx][Bx][{self.H + 1}][13] or f32[{self.H + 1}][13], got {xref.shape}")
+        xref = np.ascontiguousarray(xref)
+        u_p = s_p = None
+        if u_init is not None:
+            u_init = _f32(u_init, (B, self.H, self.m))
+            u_p = _fp(u_init)
+        if stepsize_in is not None:
+            stepsize_in = _f32(stepsize_in, (B,))
+            s_p = _fp(stepsize_in)
+        xs = np.zeros((B, max(T, 0) + 1, 13), np.float32)
+        us = np.zeros((B, max(T, 0), self.m), np.float32)
+        info = np.zeros((B, max(T, 0), 8), np.float32)
+        u_next = np.zeros((B, self.H, self.m), np.float32)
+        s_next = np.zeros(B, np.float32)
+        k_next = np.zeros((B, 2), np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self.lib.sdempc_closed_loop_batch(
+            self._h, B, T, _fp(x0), _fp(xref), int(xref.shape[0]), int(xref.shape[1]), keys.ctypes.data_as(u32p), u_p, s_p,
+            _fp(xs), _fp(us), info.ctypes.data_as(C.POINTER(SdempcInfo)), _fp(u_next), _fp(s_next), k_next.ctypes.data_as(u32p)))
+        return xs, us, info, u_next, s_next, k_next
+
     def noise_from_keys(self, keys):
         """The canonical noise tensors f32[B][P][H][6] the device draws from keys (inspection / parity tests)."""
         keys = self._keys(keys)

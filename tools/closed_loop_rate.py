@@ -1,0 +1,78 @@
+"""Rate of the batched closed loop (SPEC.md §11, sdempc_closed_loop_batch) against the same ticks driven from Python.
+
+  1. Per-tick wall time at B = 1 (shipped P = 1 YAML, C1): MpcProblem.simulate over T ticks against a Python loop of m_mpc whose host step
+     takes the solver's own one-step prediction xevol[1] as the next state (plus the host-side key split of the plant noise). That host step
+     costs next to nothing (no model evaluation on the host: the package has none, and the CPU oracle is test infrastructure), so the
+     ratio is a lower bound on what the device loop saves. The two follow different trajectories from the same start, so iteration counts
+     and kernel times differ a little; the kernel trace below splits the closed loop's own tick.
+  2. Episode-ticks per second at C2 (arithmetic of bench.py: f32x3 / fast) with B = 12,288, against one batch solve of the same B.
+usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2]
+Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
+(solve kernel against key schedule, noise, plant step)."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+from sde4mbrl_px4_amd import load_mpc_config, prng, synthetic_iris
+from sde4mbrl_px4_amd import workload as W
+from sde4mbrl_px4_amd.sde_mpc_design import MpcProblem
+from sde4mbrl_px4_amd.solver import SdeMpcSolver
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--ticks", type=int, default=40)
+ap.add_argument("--c2-ticks", type=int, default=3)
+ap.add_argument("--skip-c2", action="store_true")
+ap.add_argument("--loop-only", action="store_true", help="B = 1 closed loops only (no Python-driven comparison): for a kernel trace")
+a = ap.parse_args()
+model = synthetic_iris()
+
+for name in ("iris_traj_shipped_h20_p1", "c1_iris_posctrl_h20_p32"):
+    cfg = load_mpc_config(os.path.join(ROOT, "configs", name + ".yaml"))
+    prob = MpcProblem(cfg=cfg, model=model, state_from_traj=W.lemniscate_state if cfg.trajectory_path else None)
+    x = W.random_initial_states(1, 4)[0]
+    rng = prng.PRNGKey(10)
+    prob.simulate(x, rng, 3)                                 # warm-up: device buffers, workspaces
+    t = time.perf_counter()
+    xs, us, info, st, _ = prob.simulate(x, rng, a.ticks)
+    dev = (time.perf_counter() - t) * 1e3 / a.ticks
+    if a.loop_only:
+        print(f"{name:26s} B=1: closed_loop {dev:7.3f} ms/tick over {a.ticks} ticks", flush=True)
+        continue
+    # the same ticks from Python: m_mpc, the key split of the plant noise, and the predicted state after one step as the next state
+    st = prob.m_reset(x=x, rng=rng)
+    r = rng.copy()
+    xk = x.copy()
+    t = time.perf_counter()
+    for k in range(a.ticks):
+        uo, st, r1, xevol = prob.m_mpc(xk, r, st, curr_t=k * float(cfg.time_steps[0]))
+        r, p = prng.split(r1, 2)
+        xk = np.asarray(xevol)[1].astype(np.float32)         # (in the frame of x, as m_mpc returns it)
+    host = (time.perf_counter() - t) * 1e3 / a.ticks
+    print(f"{name:26s} B=1: closed_loop {dev:7.3f} ms/tick; m_mpc loop {host:7.3f} ms/tick (x{host / dev:.2f})", flush=True)
+
+if not a.skip_c2:
+    cfg = load_mpc_config(os.path.join(ROOT, "configs", "c2_iris_traj_h50_p128.yaml")).replace(mlp_dtype="f32x3", math_mode="fast")
+    B, T = 12288, a.c2_ticks
+    x0 = W.random_initial_states(B, 3)
+    xref = np.stack([np.stack([W.reference_window(0.05 * (b % 160) + k * float(cfg.time_steps[0]), cfg.time_steps) for b in range(B)])
+                     for k in range(T)])                    # a moving window per episode: the largest staging the loop does
+    keys = prng.split(prng.PRNGKey(10), B)
+    S = SdeMpcSolver(cfg, model, max_batch=B)
+    yk, i0 = S.reset()
+    u0 = np.tile(yk[None], (B, 1, 1))
+    s0 = np.full(B, i0["stepsize"], np.float32)
+    S.solve_keys(x0, xref[0], keys, u0, s0)                 # warm-up
+    t = time.perf_counter()
+    S.solve_keys(x0, xref[0], keys, u0, s0)
+    one = time.perf_counter() - t
+    t = time.perf_counter()
+    S.closed_loop(x0, xref, keys, T, u_init=u0, stepsize_in=s0)
+    loop = time.perf_counter() - t
+    print(f"C2 f32x3/fast B={B}: closed_loop {B * T / loop:8.1f} episode-ticks/s ({loop / T:.3f} s/tick, T = {T}); one batch solve_keys "
+          f"{B / one:8.1f} solves/s ({one:.3f} s); ratio {(B * T / loop) / (B / one):.3f}", flush=True)
+    S.close()
