@@ -695,7 +695,7 @@ int sdempc_rollout_batch_dev(sdempc_handle* h, int32_t B, const void* x0_dev, co
     a.cost = (float*)cost_dev; a.xmean = (float*)xmean_dev; a.store_traj = store_traj;
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     h->traj_batch = 0;
-    rc = timed_launch(h, st, [&] { return a.fast ? launch_rollout_fast(a, B, st) : launch_rollout(a, B, st); });
+    rc = timed_launch(h, st, [&] { return launch_rollout(a, B, st); });
     if (rc == SDEMPC_OK && store_traj) h->traj_batch = B;
     return rc;
     });
@@ -714,7 +714,7 @@ int sdempc_grad_batch_dev(sdempc_handle* h, int32_t B, const void* x0_dev, const
     a.cost = (float*)cost_dev; a.grad = (float*)grad_dev;
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     h->traj_batch = 0;       // (the gradient's forward sweep streams x_t through the trajectory workspace)
-    return timed_launch(h, st, [&] { return a.fast ? launch_grad_fast(a, B, st) : launch_grad(a, B, st); });
+    return timed_launch(h, st, [&] { return launch_grad(a, B, st); });
     });
 }
 
@@ -728,7 +728,7 @@ int sdempc_solve_batch_dev(sdempc_handle* h, int32_t B, const void* x0_dev, cons
     if ((rc = ensure_device(h))) return rc;
     {   // workspace rows of this launch: the batch, or the team slots of a persistent throughput launch
         KArgs probe = h->base; probe.B = B;
-        if ((rc = ensure_workspace(h, probe.fast ? solve_workspace_rows_fast(probe, B) : solve_workspace_rows(probe, B)))) return rc;
+        if ((rc = ensure_workspace(h, solve_workspace_rows(probe, B)))) return rc;
     }
     h->traj_batch = 0;       // (a solve's gradient evaluations stream through the trajectory workspace, indexed by team slot)
     KArgs a = h->base;
@@ -758,15 +758,15 @@ int sdempc_solve_batch_dev(sdempc_handle* h, int32_t B, const void* x0_dev, cons
                 // the speculative kernel's outputs are tagged words {value, tag} that readers poll (streamed hand-off, sdempc_spec.inc.h): no tag of an
                 // earlier launch may survive (12 MB per C2 instance, a few microseconds of the 20 ms the launch takes)
                 HIPCHK(h, hipMemsetAsync(h->d_coop_pp.p, 0, sizeof(float) * coop_pp_floats(h->H, h->G) * (size_t)B, st));
-                return timed_launch(h, st, [&] { return a.fast ? launch_solve_spec_fast(a, B, st) : launch_solve_spec(a, B, st); });
+                return timed_launch(h, st, [&] { return launch_solve_spec(a, B, st); });
             }
-            if (B <= coop_max_instances(h->P, h->H, h->m, a.opt)) return timed_launch(h, st, [&] { return a.fast ? launch_solve_coop_fast(a, B, st) : launch_solve_coop(a, B, st); });
+            if (B <= coop_max_instances(h->P, h->H, h->m, a.opt)) return timed_launch(h, st, [&] { return launch_solve_coop(a, B, st); });
             h->last_coop_B = 0;
         }
     }
     h->last_coop_B = 0;
     const unsigned tickets_before = h->ticket_total;
-    rc = timed_launch(h, st, [&] { return a.fast ? launch_solve_fast(a, B, st) : launch_solve(a, B, st); });
+    rc = timed_launch(h, st, [&] { return launch_solve(a, B, st); });
     h->last_ticketed = rc == SDEMPC_OK && h->ticket_total != tickets_before;
     return rc;
     });
@@ -1045,7 +1045,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, bool* again) {
             L.x = d_x; L.u = (float*)h->d_u.p; L.step = (float*)h->d_step.p;
             L.xs = c_xs + (size_t)kc * B * NX; L.us = c_us + (size_t)kc * B * m; L.gave_up = d_gave_up;
             L.B = B; L.H = H;
-            HIPCHK(h, h->base.fast ? launch_loop_advance_fast(h->base, L, st) : launch_loop_advance(h->base, L, st));
+            HIPCHK(h, launch_loop_advance(h->base, L, st));
         }
         hx.resize((size_t)nk * B * NX); hu.resize((size_t)nk * B * m); hi.resize((size_t)nk * B * 8);
         unsigned gave_up = 0;

@@ -62,22 +62,15 @@ DI void duo_reform_rotation(const float* x, float* Rm) {
     rot_from_q(xq, Rm);
 }
 
-// TIMING-ONLY diagnostic (tools/build_variant.sh ckl2 "-DSDEMPC_VAR_CKPT_CACHED=1"; results are WRONG): every step's layer-2 activation rows alias the rows of
-// step 0, so the checkpoint stream of the gradient evaluations stays in the caches instead of crossing HBM twice — the upper bound of what removing the
-// stream (recomputing layer 2 in the adjoint) could buy at the power cap, before the recompute is paid for (profiles/r4_ab.txt).
-#ifndef SDEMPC_VAR_CKPT_CACHED
-#define SDEMPC_VAR_CKPT_CACHED 0
-#endif
-#if SDEMPC_VAR_CKPT_CACHED
-#define CKPT_T(t) 0
-#else
-#define CKPT_T(t) (t)
-#endif
+// The layer-2 checkpoint stream of the gradient evaluations crosses HBM twice. A timing-only build whose rows of every step aliased those of step 0 (the
+// stream stayed in the caches; wrong results) bounds what removing it, i.e. recomputing layer 2 in the adjoint, could buy at the power cap: + 3.5 %, before
+// the recompute is paid for (profiles/r4_ab.txt).
 // One Euler-Maruyama step for the wave's 64 particles. CKPT: stream the second hidden layer of both passes to the groups' checkpoint
 // rows (acA / acB: this step's rows of group A / group B).
 // Issue priority, rotated among the waves of a SIMD. The arbiter serves the higher s_setprio first and, among equals, the OLDER wave slot:
 // left alone, identical work takes 382 / 438 / 765 ms in wave slots 0 / 1 / 2 (tools/phase_clock.py), and a launch that gives every team the
-// same number of instances waits for the teams in slot 2. Every step each wave sets its priority to (time slice + its wave slot) mod 3: the
+// same number of instances waits for the teams in slot 2. With the rotation it takes the same time in every slot (profiles/r2_phase_clock.txt,
+// a striped launch of 3,072: 370 / 421 / 517 ms by slot without, 475 / 479 / 477 ms with). Every step each wave sets its priority to (time slice + its wave slot) mod 3: the
 // three waves of a SIMD read the same clock, so at any moment they hold three different priorities and each is the favoured one for a third of
 // the time (slices of 0.66 ms; 0.08 ... 42 ms measured alike, 10 us slices recover only half). Striped launches: C2 at 3,072 instances
 // 2,905 -> 3,150 solves/s, C3 at 1,536 1,486 -> 1,583, C5 at 768 (one round) 884 -> 959; ticketed launches unchanged (3,150). Only the
@@ -86,9 +79,6 @@ DI void duo_reform_rotation(const float* x, float* Rm) {
 // (the stall-prone adjoint sweep first, or last) were measured too: -0.4 % / -2.2 %.
 constexpr int PRIO_SLICE_LOG2 = 16;               // 2^16 ticks of the 100 MHz s_memrealtime clock
 DI void duo_rotate_priority() {
-#if SDEMPC_VAR_NO_ROTATE      // diagnostic builds: the arbiter's own order (profiles/r2_phase_clock.txt)
-    return;
-#endif
     const unsigned slot = __builtin_amdgcn_s_getreg(63492) & 15u;                              // HW_REG_HW_ID[3:0]: wave slot on its SIMD
     const unsigned r = ((unsigned)(__builtin_amdgcn_s_memrealtime() >> PRIO_SLICE_LOG2) + slot) % 3u;
     if (r == 0) __builtin_amdgcn_s_setprio(0);
@@ -336,7 +326,7 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
                     for (int i = 0; i < NN; ++i) xin[i] = nzb[nzo + (unsigned)(((t + 1) * NN + i) * 32)];
                 }
             }
-            duo_step_fwd<F16, true, NZS>(a, sm, ww, t, h, lane, pr.hasB, x, xi, xn, A, acA + (size_t)CKPT_T(t) * ACT_STRIDE, acB + (size_t)CKPT_T(t) * ACT_STRIDE);
+            duo_step_fwd<F16, true, NZS>(a, sm, ww, t, h, lane, pr.hasB, x, xi, xn, A, acA + (size_t)t * ACT_STRIDE, acB + (size_t)t * ACT_STRIDE);
             if constexpr (NZS) { if (t + 1 < H) duo_noise_request(nzb, nzo, t + 1, sm.nzs); }   // before this step's scalar / trajectory stores: older than they are
             if (pr.own) {
                 const unsigned so = aso + (unsigned)(t * ACT_STRIDE);
@@ -373,8 +363,8 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
             // (the 25 loads below are requested at the top of their own step. A register prefetch a step ahead spills; the LDS staging rows
             // have room for 6 of the 24 dwords. A timing-only build that redirected these loads to cache-resident rows bounds what a perfect
             // prefetch could buy: 12 % of the adjoint sweep, 4 % of the launch.)
-            const float* apA = acA + (size_t)CKPT_T(t) * ACT_STRIDE;
-            const float* apB = acB + (size_t)CKPT_T(t) * ACT_STRIDE;
+            const float* apA = acA + (size_t)t * ACT_STRIDE;
+            const float* apB = acB + (size_t)t * ACT_STRIDE;
             float4 hA[4], hB[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) hA[q] = *reinterpret_cast<const float4*>(apA + (q * 64 + lane) * 4);

@@ -112,15 +112,14 @@ struct KArgs {
 // last element; multiple of 4
 __host__ __device__ inline int part_stride(int H) { const int a = H * 12, b = (H + 1) * 13; return ((a > b ? a : b) + 1 + 3) & ~3; }
 // Activation checkpoint of the gradient's forward sweep, floats per (instance, group, step): h2 tile (4 chunks x 64 lanes x 4) + step
-// scalars (32 x 8) [+ SDEMPC_CKPT1 further layer-1 tiles of 1024 floats: 1 = drift h1, 2 = drift and density h1 (build-time experiment)]
-#ifndef SDEMPC_CKPT1
-#define SDEMPC_CKPT1 0
-#endif
-constexpr int ACT_STRIDE = 1280 + 1024 * SDEMPC_CKPT1;
+// scalars (32 x 8). Checkpointing layer-1 tiles too was measured slower (HBM).
+constexpr int ACT_STRIDE = 1280;
 size_t smem_bytes(int H, int m, int ipb);   // ipb: instances (teams) per workgroup
 // host function pointer of the kernel the calling thread launched last through the launch_* functions below (for sdempc_last_kernel_name)
 void note_kernel(const void* host_fn);
 const void* last_launched_kernel();
+// The launchers and solve_workspace_rows serve both math modes: each picks sdempc::exact or sdempc::fastm (SPEC.md §10: the same source built with
+// hardware transcendentals) from KArgs::fast.
 // Cooperative latency path of the solve (exact f32, P >= 2): workgroups per instance, workspace sizes, launcher.
 // coop_max_instances: how many instances fit one workgroup per CU on the current device (0 = path unavailable for this shape)
 int coop_nwg(int P);
@@ -137,13 +136,6 @@ hipError_t launch_grad(const KArgs& a, int B, hipStream_t st);
 hipError_t launch_solve(const KArgs& a, int B, hipStream_t st);
 // rows of KArgs::traj / act / part / ustg a solve launch of B instances indexes (B, or the team slots of a persistent launch)
 int solve_workspace_rows(const KArgs& a, int B);
-int solve_workspace_rows_fast(const KArgs& a, int B);
-// math_mode fast (SPEC.md §10): the same kernels built with hardware transcendentals (second translation unit)
-hipError_t launch_rollout_fast(const KArgs& a, int B, hipStream_t st);
-hipError_t launch_grad_fast(const KArgs& a, int B, hipStream_t st);
-hipError_t launch_solve_fast(const KArgs& a, int B, hipStream_t st);
-hipError_t launch_solve_coop_fast(const KArgs& a, int B, hipStream_t st);      // the cooperative latency layouts in math_mode fast (same grid rules)
-hipError_t launch_solve_spec_fast(const KArgs& a, int B, hipStream_t st);
 // SPEC.md §11, the batched closed loop: per-tick plant step and hand-over to the next solve (sdempc_loop.inc.h, translation unit SDEMPC_TU = 4)
 struct LoopAdvance {
     const float* uopt;          // [B][H][m] this tick's solutions
@@ -159,7 +151,6 @@ struct LoopAdvance {
     int B, H;
 };
 hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
-hipError_t launch_loop_advance_fast(const KArgs& a, const LoopAdvance& L, hipStream_t st);
 // the tick's key schedule (sdempc_prng.hip): keys r_k -> r_{k+1} in place, the solve's noise keys into sub_dev u32[B][2], the plant noise into xi_dev f32[B][6]
 hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st);
 // rows_dev[b][0..n) = row_dev[0..n) for b < B

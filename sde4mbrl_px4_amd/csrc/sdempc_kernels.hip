@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "sdempc_kernels.h"
 
 // This file is compiled twice (Makefile): SDEMPC_FAST=0 -> namespace sdempc::exact, the bit-reproducible arithmetic of SPEC.md
@@ -67,15 +68,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define FMA(a, b, c) __builtin_fmaf((a), (b), (c))
 #define DI __device__ __forceinline__
-// phase fences for the instruction scheduler (SDEMPC_SB=0 lets hipcc interleave freely)
-#ifndef SDEMPC_SB
-#define SDEMPC_SB 1
-#endif
-#if SDEMPC_SB
+// phase fences for the instruction scheduler: hipcc moves no instruction across one
 #define SCHED_PHASE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define SCHED_PHASE() ((void)0)
-#endif
 
 constexpr int NX = 13, NN = 6, HID = 32;
 
@@ -187,8 +181,8 @@ constexpr int UST = 36;
 constexpr int REC = 64, NZL = 8;                       // cooperative layouts: floats per step record / per noise row in LDS (sdempc_lane2.inc.h)
 constexpr int COOP_ROW = 172;                          // floats per (particle, step) checkpoint row of the cooperative layouts (sdempc_lane2.inc.h)
 // per-instance output workspace of the cooperative layouts (KArgs::coop_pp): 2 x SPEC_SLOTS slots of [part_stride(H)][Ppad] per-particle outputs — 64-bit
-// tagged words {value, tag} in the speculative kernel (zeroed by the host before each of its launches: coop_pp_tagged_bytes), floats in the first two slots'
-// worth of the region in the plain cooperative kernel — then [2][part_stride(H)] 64-bit tagged totals
+// tagged words {value, tag} in the speculative kernel (zeroed by the host before each of its launches: hipMemsetAsync of d_coop_pp in sdempc_solve_batch_dev),
+// floats in the first two slots' worth of the region in the plain cooperative kernel — then [2][part_stride(H)] 64-bit tagged totals
 constexpr int SPEC_SLOTS = 9;
 __host__ __device__ inline size_t coop_gtot_offset(int H, int Ppad) { return (size_t)2 * 2 * SPEC_SLOTS * part_stride(H) * Ppad; }
 __host__ __device__ inline size_t coop_pp_stride(int H, int Ppad) { return coop_gtot_offset(H, Ppad) + 4 * (size_t)part_stride(H); }
@@ -662,16 +656,6 @@ DI float block_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const 
                     *reinterpret_cast<float4*>(ap + 1024 + j * 8) = make_float4(A.eta, A.Fb[0], A.Fb[1], A.Fb[2]);
                     ap[1024 + j * 8 + 4] = A.rn;
                 }
-#if SDEMPC_CKPT1 >= 1
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    *reinterpret_cast<float4*>(ap + 1280 + (q * 64 + lane) * 4) = make_float4(A.h1d[4 * q], A.h1d[4 * q + 1], A.h1d[4 * q + 2], A.h1d[4 * q + 3]);
-#endif
-#if SDEMPC_CKPT1 >= 2
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    *reinterpret_cast<float4*>(ap + 2304 + (q * 64 + lane) * 4) = make_float4(A.h1n[4 * q], A.h1n[4 * q + 1], A.h1n[4 * q + 2], A.h1n[4 * q + 3]);
-#endif
             }
             float l = stage_cost<false>(a, xn, sm.xref + (t + 1) * NX, nullptr);
             l = FMA(a.C.res_mult * A.eta, A.eta, l);
@@ -695,25 +679,11 @@ DI float block_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const 
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         // software pipeline: the loads of step t-1 are issued while step t is being processed
         float4 nh[4], ns4;
-#if SDEMPC_CKPT1 >= 1
-        float4 nh1[4];
-#endif
-#if SDEMPC_CKPT1 >= 2
-        float4 nh1n[4];
-#endif
         float nrn, nxt[NX], nxi[NN];
         auto issue_loads = [&](int t) {
             const float* ap = ac + (size_t)t * ACT_STRIDE;
 #pragma unroll
             for (int q = 0; q < 4; ++q) nh[q] = *reinterpret_cast<const float4*>(ap + (q * 64 + lane) * 4);
-#if SDEMPC_CKPT1 >= 1
-#pragma unroll
-            for (int q = 0; q < 4; ++q) nh1[q] = *reinterpret_cast<const float4*>(ap + 1280 + (q * 64 + lane) * 4);
-#endif
-#if SDEMPC_CKPT1 >= 2
-#pragma unroll
-            for (int q = 0; q < 4; ++q) nh1n[q] = *reinterpret_cast<const float4*>(ap + 2304 + (q * 64 + lane) * 4);
-#endif
             ns4 = *reinterpret_cast<const float4*>(ap + 1024 + j * 8);
             nrn = ap[1024 + j * 8 + 4];
             const float* tp = tj + (size_t)t * NX * 32;
@@ -729,16 +699,6 @@ DI float block_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const 
             f32x16 h2l;
 #pragma unroll
             for (int q = 0; q < 4; ++q) { h2l[4 * q] = nh[q].x; h2l[4 * q + 1] = nh[q].y; h2l[4 * q + 2] = nh[q].z; h2l[4 * q + 3] = nh[q].w; }
-#if SDEMPC_CKPT1 >= 1
-            f32x16 h1dl;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { h1dl[4 * q] = nh1[q].x; h1dl[4 * q + 1] = nh1[q].y; h1dl[4 * q + 2] = nh1[q].z; h1dl[4 * q + 3] = nh1[q].w; }
-#endif
-#if SDEMPC_CKPT1 >= 2
-            f32x16 h1nl;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { h1nl[4 * q] = nh1n[q].x; h1nl[4 * q + 1] = nh1n[q].y; h1nl[4 * q + 2] = nh1n[q].z; h1nl[4 * q + 3] = nh1n[q].w; }
-#endif
             const float eta_l = ns4.x, fb0 = ns4.y, fb1 = ns4.z, fb2 = ns4.w, rn_l = nrn;
 #pragma unroll
             for (int i = 0; i < NX; ++i) xt[i] = nxt[i];
@@ -758,12 +718,6 @@ DI float block_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const 
             // recompute layer 1 only (R, v_body, 6 MFMAs, 32 tanh); everything downstream of it comes from the checkpoint
             // (the unused remainder of step_fwd is dead code and is removed by the compiler)
             step_fwd<F16, PK>(a, sm, ww, t, h, lane, xt, xi, xn, A);
-#if SDEMPC_CKPT1 >= 1
-            A.h1d = h1dl;      // checkpointed: the drift tile's MFMAs and tanh in step_fwd above become dead code
-#endif
-#if SDEMPC_CKPT1 >= 2
-            A.h1n = h1nl;
-#endif
             A.h2 = h2l; A.eta = eta_l; A.Fb[0] = fb0; A.Fb[1] = fb1; A.Fb[2] = fb2; A.rn = rn_l;
 #pragma unroll
             for (int i = 0; i < 3; ++i) A.Jom[i] = a.M.J[i] * xt[10 + i];
@@ -1078,6 +1032,29 @@ __global__ void __launch_bounds__(Team::BNT, (MODE == 2 && PK ? 1 : (MODE == 1 |
     solve_instance<Team, M, F16, PK, MODE>(a, sm, ww, LW, CC, b, tid);
 }
 
+// ------------------------------------------------------------------------------------------------
+// host-side dispatch of run-time shapes to instantiations
+// ------------------------------------------------------------------------------------------------
+// f(std::integral_constant<int, M>{}) for the instantiation that serves m motors: M = 4 or 6 (the reference's vehicles), else the generic
+// 8-slot one (any m <= 8, zero-padded). LIMITED: a layout whose generic instantiation exists only in an all-variants build; other builds
+// refuse other motor counts there, and the <8> branch is never instantiated.
+template <bool LIMITED = false, class F>
+static hipError_t with_m(int m, F&& f) {
+    if (m == 4) return f(std::integral_constant<int, 4>{});
+    if (m == 6) return f(std::integral_constant<int, 6>{});
+    if constexpr (!LIMITED || SDEMPC_ALL_VARIANTS) return f(std::integral_constant<int, 8>{});
+    else return hipErrorInvalidValue;
+}
+// motor counts whose instantiations exist in every layout (the LIMITED ones included): the reference's two vehicles; any m in an all-variants
+// build (other motor counts otherwise run one group per wave: same bits)
+static constexpr bool every_layout_built(int m) { return m == 4 || m == 6 || SDEMPC_ALL_VARIANTS != 0; }
+// f(std::integral_constant<int, F16>{}) for KArgs::f16 (mlp_dtype): 0 f32, 1 fp16 operands, 2 three-limb bf16 splits
+template <class F>
+static hipError_t with_f16(int f16, F&& f) {
+    if (f16 == 2) return f(std::integral_constant<int, 2>{});
+    return f16 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+}
+
 // duo solve kernels (MODE 3: noise staging rows, control table in LDS or global memory; MODE 4: neither in LDS), by team shape
 #define SDEMPC_DUO_M(X, TEAM, M)                                                                                   \
     X(TEAM, M, 0, 3, false) X(TEAM, M, 1, 3, false) X(TEAM, M, 2, 3, false) X(TEAM, M, 0, 3, true) X(TEAM, M, 1, 3, true) X(TEAM, M, 2, 3, true)  \
@@ -1111,13 +1088,7 @@ SDEMPC_DUO_HEX(SDEMPC_DUO_DEF)
 }  // namespace exact / fastm
 #elif SDEMPC_TU == 4
 #include "sdempc_loop.inc.h"
-#if SDEMPC_FAST
-}  // namespace fastm
-hipError_t launch_loop_advance_fast(const KArgs& a, const LoopAdvance& L, hipStream_t st) { return fastm::launch_loop_advance(a, L, st); }
-#else
-}  // namespace exact
-hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st) { return exact::launch_loop_advance(a, L, st); }
-#endif
+}  // namespace exact / fastm
 #else
 SDEMPC_DUO_PAIR(SDEMPC_DUO_DECL)
 SDEMPC_DUO_HEX(SDEMPC_DUO_DECL)
@@ -1163,14 +1134,11 @@ static hipError_t launch_k(Kern k, const KArgs& a, hipStream_t st, int ipb, int 
 }
 template <class Team>
 static hipError_t launch_rollout_team(const KArgs& a, hipStream_t st) {
-    if (a.f16 == 2) return launch_k(sdempc_rollout_kernel<Team, 2>, a, st, Team::IPB);
-    return a.f16 ? launch_k(sdempc_rollout_kernel<Team, 1>, a, st, Team::IPB) : launch_k(sdempc_rollout_kernel<Team, 0>, a, st, Team::IPB);
+    return with_f16(a.f16, [&](auto F16) { return launch_k(sdempc_rollout_kernel<Team, F16>, a, st, Team::IPB); });
 }
 template <class Team, int F16>
 static hipError_t launch_grad_team(const KArgs& a, hipStream_t st) {
-    if (a.m == 4) return launch_k(sdempc_grad_kernel<Team, 4, F16>, a, st, Team::IPB);
-    if (a.m == 6) return launch_k(sdempc_grad_kernel<Team, 6, F16>, a, st, Team::IPB);
-    return launch_k(sdempc_grad_kernel<Team, 8, F16>, a, st, Team::IPB);
+    return with_m(a.m, [&](auto M) { return launch_k(sdempc_grad_kernel<Team, M, F16>, a, st, Team::IPB); });
 }
 // LaunchOpts::cus = compute units of the handle's device (set by the C ABI when the device is bound): a grid of at most that many
 // workgroups leaves one wave per SIMD. Every dispatch decision below comes from the handle's LaunchOpts (sdempc_set_option); no
@@ -1203,9 +1171,6 @@ static hipError_t launch_persistent(Kern k, const KArgs& a, hipStream_t st, int 
     if (a.ws_rows > 0 && grid * (size_t)ipb > (size_t)a.ws_rows) return hipErrorInvalidValue;      // team slots beyond the workspace rows: never launch (sdempc_api.cpp sizes them from solve_workspace_rows)
     KArgs ka = a;
     ka.tickets = a.work != nullptr && a.ticket_host != nullptr && (size_t)a.B >= 3 * grid * (size_t)ipb;
-#if SDEMPC_VAR_STATIC       // diagnostic builds: striped assignment at every batch size (tools/phase_clock.py)
-    ka.tickets = 0;
-#endif
     if (ka.tickets) ka.ticket_base = *a.ticket_host;       // the teams' initial instances are 0 .. grid * ipb - 1; the draws hand out the rest
     note_kernel((const void*)k);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(bnt), sb, st, ka);
@@ -1242,27 +1207,9 @@ static hipError_t launch_duo_small(const KArgs& a, hipStream_t st) {
         return launch_persistent(sdempc_solve_kernel<TeamPair, M, F16, false, 3, false>, a, st, 4, TeamPair::BNT, true, 2);
     return launch_duo_m<TeamBlock2, M, F16>(a, st);
 }
-// motor counts whose instantiations exist in every layout: the reference's two vehicles; the generic 8-slot instantiation of the duo / six-team /
-// cooperative / speculative layouts only in an all-variants build (other motor counts otherwise run one group per wave: same bits)
-static bool every_layout_built(int m) { return m == 4 || m == 6 || SDEMPC_ALL_VARIANTS != 0; }
 template <int F16>
 static hipError_t launch_duo(const KArgs& a, hipStream_t st) {
-    if (a.G <= 4) {
-        if (a.m == 4) return launch_duo_small<4, F16>(a, st);
-        if (a.m == 6) return launch_duo_small<6, F16>(a, st);
-#if SDEMPC_ALL_VARIANTS
-        return launch_duo_small<8, F16>(a, st);
-#else
-        return hipErrorInvalidValue;      // (not reached: launch_solve_team asks every_layout_built)
-#endif
-    }
-    if (a.m == 4) return launch_duo_m<TeamBlock, 4, F16>(a, st);
-    if (a.m == 6) return launch_duo_m<TeamBlock, 6, F16>(a, st);
-#if SDEMPC_ALL_VARIANTS
-    return launch_duo_m<TeamBlock, 8, F16>(a, st);
-#else
-    return hipErrorInvalidValue;
-#endif
+    return with_m<true>(a.m, [&](auto M) { return a.G <= 4 ? launch_duo_small<M, F16>(a, st) : launch_duo_m<TeamBlock, M, F16>(a, st); });
 }
 // duo = auto, up to four groups: does a batch of B fit resident with one group per wave (launch_solve_team, solve_workspace_rows)?
 static bool one_group_per_wave_batch(const KArgs& a, int B) {
@@ -1273,46 +1220,41 @@ static bool one_group_per_wave_batch(const KArgs& a, int B) {
     if (per_cu > 3) per_cu = 3;
     return (size_t)B <= per_cu * (size_t)(a.opt.cus > 0 ? a.opt.cus : 256);
 }
+// The tile layouts' solve launch of B instances (launch_solve_team; solve_workspace_rows sizes the workspaces from the same two predicates).
+// Packed-f32 tanh (exact f32, all-variants build only): small-batch (latency) launches of one workgroup per CU at most leave a lone wave per
+// SIMD, which is issue-bound. SDEMPC_OPT_PK forces either instantiation (A/B, tests).
+static bool takes_pk(const KArgs& a, int B) {
+    if (!SDEMPC_ALL_VARIANTS || a.f16 != 0 || FAST) return false;
+    const int ipb = team_ipb(a.G, a.H, a.m), wgs = (B + ipb - 1) / ipb;
+    return a.opt.pk >= 0 ? a.opt.pk == 1 : wgs <= a.opt.cus;
+}
+// Duo layout, persistent: every multi-group instance (measured, same box: C2 +1.3 %, C3 +4.4 %, C5 +7.5 % over one group per wave)
+// except batches that one 32-particle group per wave holds resident at once (three four-wave workgroups per CU: B <= 3 x CUs at C2). Those run
+// one group per wave: four waves per instance instead of the duo layout's two, i.e. the shorter chain per instance and twice the waves per CU
+// (same box, C2 f32x3: B = 1..256 149 against 245 ms per launch, 512 189 / 260, 768 273 / 306; from 1,024 on the duo layout's 1,536 resident
+// instances win: 383 / 343)
+static bool takes_duo(const KArgs& a, int B) {
+    return a.G >= 2 && a.opt.duo != 0 && every_layout_built(a.m) && !one_group_per_wave_batch(a, B);
+}
 template <class Team, int F16>
 static hipError_t launch_solve_team(const KArgs& a, hipStream_t st) {
 #if SDEMPC_ALL_VARIANTS
     if constexpr (F16 == 0 && !FAST) {
-        // small-batch (latency) launches: one workgroup per CU at most -> a lone wave per SIMD is issue-bound -> packed tanh
-        const int wgs = (a.B + Team::IPB - 1) / Team::IPB;
-        const bool pk = a.opt.pk >= 0 ? a.opt.pk == 1 : wgs <= a.opt.cus;     // SDEMPC_OPT_PK forces either instantiation (A/B, tests)
-        if (pk) {
-            if constexpr (Team::IPB == 1) {
-                if (a.G > 4) {   // more particle groups than the four waves of a workgroup: eight waves halve the sequential depth
-                    if (a.m == 4) return launch_k(sdempc_solve_kernel<TeamBlock8, 4, 0, true>, a, st, 1, TeamBlock8::BNT);
-                    if (a.m == 6) return launch_k(sdempc_solve_kernel<TeamBlock8, 6, 0, true>, a, st, 1, TeamBlock8::BNT);
-                    return launch_k(sdempc_solve_kernel<TeamBlock8, 8, 0, true>, a, st, 1, TeamBlock8::BNT);
-                }
-            }
-            if (a.m == 4) return launch_k(sdempc_solve_kernel<Team, 4, 0, true>, a, st, Team::IPB);
-            if (a.m == 6) return launch_k(sdempc_solve_kernel<Team, 6, 0, true>, a, st, Team::IPB);
-            return launch_k(sdempc_solve_kernel<Team, 8, 0, true>, a, st, Team::IPB);
+        if (takes_pk(a, a.B)) {
+            if (a.G > 4)   // more particle groups than the four waves of a workgroup: eight waves halve the sequential depth
+                return with_m(a.m, [&](auto M) { return launch_k(sdempc_solve_kernel<TeamBlock8, M, 0, true>, a, st, 1, TeamBlock8::BNT); });
+            return with_m(a.m, [&](auto M) { return launch_k(sdempc_solve_kernel<Team, M, 0, true>, a, st, Team::IPB); });
         }
     }
 #endif
     if constexpr (Team::IPB == 1) {
-        // auto: every multi-group instance (measured, same box: C2 +1.3 %, C3 +4.4 %, C5 +7.5 % over one group per wave)
-        // Batches that one 32-particle group per wave holds resident at once (three four-wave workgroups per CU: B <= 3 x CUs at C2) run
-        // that way: four waves per instance instead of the duo layout's two, i.e. the shorter chain per instance and twice the waves per
-        // CU (same box, C2 f32x3: B = 1..256 149 against 245 ms per launch, 512 189 / 260, 768 273 / 306; from 1,024 on the duo layout's
-        // 1,536 resident instances win: 383 / 343)
-        if (a.G >= 2 && a.opt.duo != 0 && every_layout_built(a.m) && !one_group_per_wave_batch(a, a.B)) return launch_duo<F16>(a, st);
-        // long horizons: with the control table in LDS only two workgroups fit a CU; without it three do (the kernel is built for three)
-        if (use_global_ust(a.H, a.m, a.opt) && a.ustg) {
-            if (a.m == 4) return launch_k(sdempc_solve_kernel<Team, 4, F16, false, 0, true>, a, st, 1, Team::BNT, false);
-            if (a.m == 6) return launch_k(sdempc_solve_kernel<Team, 6, F16, false, 0, true>, a, st, 1, Team::BNT, false);
-#if SDEMPC_ALL_VARIANTS
-            return launch_k(sdempc_solve_kernel<Team, 8, F16, false, 0, true>, a, st, 1, Team::BNT, false);
-#endif
-        }
+        if (takes_duo(a, a.B)) return launch_duo<F16>(a, st);
+        // long horizons: with the control table in LDS only two workgroups fit a CU; without it three do (the kernel is built for three).
+        // (A motor count without that instantiation takes the LDS table below.)
+        if (use_global_ust(a.H, a.m, a.opt) && a.ustg && every_layout_built(a.m))
+            return with_m<true>(a.m, [&](auto M) { return launch_k(sdempc_solve_kernel<Team, M, F16, false, 0, true>, a, st, 1, Team::BNT, false); });
     }
-    if (a.m == 4) return launch_k(sdempc_solve_kernel<Team, 4, F16>, a, st, Team::IPB);
-    if (a.m == 6) return launch_k(sdempc_solve_kernel<Team, 6, F16>, a, st, Team::IPB);
-    return launch_k(sdempc_solve_kernel<Team, 8, F16>, a, st, Team::IPB);
+    return with_m(a.m, [&](auto M) { return launch_k(sdempc_solve_kernel<Team, M, F16>, a, st, Team::IPB); });
 }
 // Single-particle lane layout: f32 contractions only, one wave per instance (SDEMPC_OPT_LANE = 0 forces the tile layout: A/B, tests)
 static bool use_lane(const KArgs& k) {
@@ -1326,9 +1268,7 @@ static hipError_t launch_lane(int what, const KArgs& k, hipStream_t st) {
     return launch_k(sdempc_solve_kernel<TeamWave, M, false, false, 1>, k, st, TeamWave::IPB);
 }
 static hipError_t launch_lane_m(int what, const KArgs& k, hipStream_t st) {
-    if (k.m == 4) return launch_lane<4>(what, k, st);
-    if (k.m == 6) return launch_lane<6>(what, k, st);
-    return launch_lane<8>(what, k, st);
+    return with_m(k.m, [&](auto M) { return launch_lane<M>(what, k, st); });
 }
 // ---- cooperative latency path (f32 contractions; both math modes) ----
 int coop_nwg(int P) { return (P + 3) / 4; }
@@ -1383,13 +1323,7 @@ hipError_t launch_solve_spec(const KArgs& a, int B, hipStream_t st) {
     if (B < 1 || B > (spec_max_instances)(k.P, k.H, k.m, k.opt) || !k.coop_bar || !k.coop_pp || !k.coop_ck) return hipErrorInvalidValue;
     k.coop_ngrp = k.opt.cus / (B * k.coop_nwg);
     if (k.coop_ngrp > SPEC_GROUPS) k.coop_ngrp = SPEC_GROUPS;
-    if (k.m == 4) return launch_spec_m<4>(k, st);
-    if (k.m == 6) return launch_spec_m<6>(k, st);
-#if SDEMPC_ALL_VARIANTS
-    return launch_spec_m<8>(k, st);
-#else
-    return hipErrorInvalidValue;
-#endif
+    return with_m<true>(k.m, [&](auto M) { return launch_spec_m<M>(k, st); });
 }
 template <int M>
 static hipError_t launch_coop_m(const KArgs& k, hipStream_t st) {
@@ -1408,32 +1342,17 @@ static hipError_t launch_coop_m(const KArgs& k, hipStream_t st) {
 hipError_t launch_solve_coop(const KArgs& a, int B, hipStream_t st) {
     KArgs k = a; k.B = B; k.coop_nwg = coop_nwg(k.P);
     if (B < 1 || B > (coop_max_instances)(k.P, k.H, k.m, k.opt) || !k.coop_bar || !k.coop_pp || !k.coop_ck) return hipErrorInvalidValue;
-    if (k.m == 4) return launch_coop_m<4>(k, st);
-    if (k.m == 6) return launch_coop_m<6>(k, st);
-#if SDEMPC_ALL_VARIANTS
-    return launch_coop_m<8>(k, st);
-#else
-    return hipErrorInvalidValue;
-#endif
+    return with_m<true>(k.m, [&](auto M) { return launch_coop_m<M>(k, st); });
 }
 
 // Rows of the per-instance / per-slot workspaces (KArgs::traj, act, part, ustg) a solve launch of B instances touches: B for the
 // layouts that run one workgroup (or wave) per instance, the number of team slots for the persistent duo launches (at most six teams
-// per CU: 128-thread workgroups six per CU, or three four-wave workgroups of two teams). Mirrors the dispatch of launch_solve_team.
+// per CU: 128-thread workgroups six per CU, or three four-wave workgroups of two teams). Decided as in launch_solve_team.
 int solve_workspace_rows(const KArgs& k, int B) {
-    if (use_lane(k) || use_wave_team(k.G, k.H, k.m)) return B;
-#if SDEMPC_ALL_VARIANTS
-    if (k.f16 == 0 && !FAST) {
-        const bool pk = k.opt.pk >= 0 ? k.opt.pk == 1 : B <= k.opt.cus;
-        if (pk) return B;
-    }
-#endif
-    if (one_group_per_wave_batch(k, B)) return B;      // (launch_solve_team: batches that fit resident with one group per wave)
-    if (k.G >= 2 && k.opt.duo != 0 && every_layout_built(k.m)) {       // (team slots come in workgroups of up to two teams: an odd batch leaves the last slot idle but counted; six-team workgroups only run full)
-        const int slots = 6 * (k.opt.cus > 0 ? k.opt.cus : 256), even = (B + 1) & ~1;
-        return even < slots ? even : slots;
-    }
-    return B;
+    if (use_wave_team(k.G, k.H, k.m) || takes_pk(k, B) || !takes_duo(k, B)) return B;
+    // team slots come in workgroups of up to two teams: an odd batch leaves the last slot idle but counted; six-team workgroups only run full
+    const int slots = 6 * (k.opt.cus > 0 ? k.opt.cus : 256), even = (B + 1) & ~1;
+    return even < slots ? even : slots;
 }
 hipError_t launch_rollout(const KArgs& a, int B, hipStream_t st) {
     KArgs k = a; k.B = B;
@@ -1443,14 +1362,14 @@ hipError_t launch_rollout(const KArgs& a, int B, hipStream_t st) {
 hipError_t launch_grad(const KArgs& a, int B, hipStream_t st) {
     KArgs k = a; k.B = B;
     if (use_lane(k)) return launch_lane_m(1, k, st);
-    if (use_wave_team(k.G, k.H, k.m)) return k.f16 == 2 ? launch_grad_team<TeamWave, 2>(k, st) : k.f16 ? launch_grad_team<TeamWave, 1>(k, st) : launch_grad_team<TeamWave, 0>(k, st);
-    return k.f16 == 2 ? launch_grad_team<TeamBlock, 2>(k, st) : k.f16 ? launch_grad_team<TeamBlock, 1>(k, st) : launch_grad_team<TeamBlock, 0>(k, st);
+    const bool wave = use_wave_team(k.G, k.H, k.m);
+    return with_f16(k.f16, [&](auto F16) { return wave ? launch_grad_team<TeamWave, F16>(k, st) : launch_grad_team<TeamBlock, F16>(k, st); });
 }
 hipError_t launch_solve(const KArgs& a, int B, hipStream_t st) {
     KArgs k = a; k.B = B;
     if (use_lane(k)) return launch_lane_m(2, k, st);
-    if (use_wave_team(k.G, k.H, k.m)) return k.f16 == 2 ? launch_solve_team<TeamWave, 2>(k, st) : k.f16 ? launch_solve_team<TeamWave, 1>(k, st) : launch_solve_team<TeamWave, 0>(k, st);
-    return k.f16 == 2 ? launch_solve_team<TeamBlock, 2>(k, st) : k.f16 ? launch_solve_team<TeamBlock, 1>(k, st) : launch_solve_team<TeamBlock, 0>(k, st);
+    const bool wave = use_wave_team(k.G, k.H, k.m);
+    return with_f16(k.f16, [&](auto F16) { return wave ? launch_solve_team<TeamWave, F16>(k, st) : launch_solve_team<TeamBlock, F16>(k, st); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1500,30 +1419,41 @@ hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int 
 
 #if SDEMPC_FAST
 }  // namespace fastm
-hipError_t launch_rollout_fast(const KArgs& a, int B, hipStream_t st) { return fastm::launch_rollout(a, B, st); }
-hipError_t launch_grad_fast(const KArgs& a, int B, hipStream_t st) { return fastm::launch_grad(a, B, st); }
-hipError_t launch_solve_fast(const KArgs& a, int B, hipStream_t st) { return fastm::launch_solve(a, B, st); }
-int solve_workspace_rows_fast(const KArgs& a, int B) { return fastm::solve_workspace_rows(a, B); }
-hipError_t launch_solve_coop_fast(const KArgs& a, int B, hipStream_t st) { return fastm::launch_solve_coop(a, B, st); }
-hipError_t launch_solve_spec_fast(const KArgs& a, int B, hipStream_t st) { return fastm::launch_solve_spec(a, B, st); }
 #else
 }  // namespace exact
+// The entry points of sdempc_kernels.h. Those that depend on the math mode take it from KArgs::fast here, and only here: fastm is this unit
+// built with SDEMPC_FAST=1, launch_loop_advance lives in the loop unit of either mode (SDEMPC_TU = 4).
+namespace exact {
+hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
+}
+namespace fastm {
+hipError_t launch_rollout(const KArgs& a, int B, hipStream_t st);
+hipError_t launch_grad(const KArgs& a, int B, hipStream_t st);
+hipError_t launch_solve(const KArgs& a, int B, hipStream_t st);
+int solve_workspace_rows(const KArgs& a, int B);
+hipError_t launch_solve_coop(const KArgs& a, int B, hipStream_t st);
+hipError_t launch_solve_spec(const KArgs& a, int B, hipStream_t st);
+hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
+}
 static thread_local const void* g_last_kernel_fn = nullptr;
 void note_kernel(const void* host_fn) { g_last_kernel_fn = host_fn; }
 const void* last_launched_kernel() { return g_last_kernel_fn; }
 size_t smem_bytes(int H, int m, int ipb) { return exact::smem_bytes(H, m, ipb); }
 int team_ipb(int G, int H, int m) { return exact::team_ipb(G, H, m); }
-hipError_t launch_rollout(const KArgs& a, int B, hipStream_t st) { return exact::launch_rollout(a, B, st); }
-hipError_t launch_grad(const KArgs& a, int B, hipStream_t st) { return exact::launch_grad(a, B, st); }
-hipError_t launch_solve(const KArgs& a, int B, hipStream_t st) { return exact::launch_solve(a, B, st); }
-int solve_workspace_rows(const KArgs& a, int B) { return exact::solve_workspace_rows(a, B); }
+hipError_t launch_rollout(const KArgs& a, int B, hipStream_t st) { return a.fast ? fastm::launch_rollout(a, B, st) : exact::launch_rollout(a, B, st); }
+hipError_t launch_grad(const KArgs& a, int B, hipStream_t st) { return a.fast ? fastm::launch_grad(a, B, st) : exact::launch_grad(a, B, st); }
+hipError_t launch_solve(const KArgs& a, int B, hipStream_t st) { return a.fast ? fastm::launch_solve(a, B, st) : exact::launch_solve(a, B, st); }
+int solve_workspace_rows(const KArgs& a, int B) { return a.fast ? fastm::solve_workspace_rows(a, B) : exact::solve_workspace_rows(a, B); }
 int coop_nwg(int P) { return exact::coop_nwg(P); }
 int coop_max_instances(int P, int H, int m, const LaunchOpts& o) { return exact::coop_max_instances(P, H, m, o); }
 size_t coop_pp_floats(int H, int G) { return exact::coop_pp_floats(H, G); }
 size_t coop_ck_floats(int H, int P) { return exact::coop_ck_floats(H, P); }
-hipError_t launch_solve_coop(const KArgs& a, int B, hipStream_t st) { return exact::launch_solve_coop(a, B, st); }
+hipError_t launch_solve_coop(const KArgs& a, int B, hipStream_t st) { return a.fast ? fastm::launch_solve_coop(a, B, st) : exact::launch_solve_coop(a, B, st); }
 int spec_max_instances(int P, int H, int m, const LaunchOpts& o) { return exact::spec_max_instances(P, H, m, o); }
-hipError_t launch_solve_spec(const KArgs& a, int B, hipStream_t st) { return exact::launch_solve_spec(a, B, st); }
+hipError_t launch_solve_spec(const KArgs& a, int B, hipStream_t st) { return a.fast ? fastm::launch_solve_spec(a, B, st) : exact::launch_solve_spec(a, B, st); }
+hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st) {
+    return a.fast ? fastm::launch_loop_advance(a, L, st) : exact::launch_loop_advance(a, L, st);
+}
 hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int P, int G, int C, hipStream_t st) {
     return exact::launch_relayout(to_dev, in, out, B, P, G, C, st);
 }

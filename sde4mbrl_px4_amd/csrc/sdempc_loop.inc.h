@@ -49,8 +49,8 @@ hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t
     k.H = 1;
     const size_t sb = smem_bytes(1, k.m, TeamWave::IPB);
     const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
-    if (k.f16 == 1) sdempc_loop_advance_kernel<1><<<grid, TeamWave::BNT, sb, st>>>(k, L);
-    else if (k.f16 == 2) sdempc_loop_advance_kernel<2><<<grid, TeamWave::BNT, sb, st>>>(k, L);
-    else sdempc_loop_advance_kernel<0><<<grid, TeamWave::BNT, sb, st>>>(k, L);
-    return hipGetLastError();
+    return with_f16(k.f16, [&](auto F16) {
+        sdempc_loop_advance_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L);
+        return hipGetLastError();
+    });
 }
