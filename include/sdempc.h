@@ -38,8 +38,9 @@ extern "C" {
 #endif
 
 /* Version of this header's struct layouts and entry points; sdempc_abi_version() returns the one the library was built with. A binding
- * compares the two before it passes a struct (2: sdempc_cfg grew the state_constr fields, handle options, work counters). */
-#define SDEMPC_ABI_VERSION 2
+ * compares the two before it passes a struct (2: sdempc_cfg grew the state_constr fields, handle options, work counters; 3: sdempc_plant_cfg and
+ * sdempc_closed_loop_batch_plant). */
+#define SDEMPC_ABI_VERSION 3
 
 #define SDEMPC_NX 13          /* state dims */
 #define SDEMPC_NNOISE 6       /* noisy state dims: v(3), omega(3) */
@@ -279,6 +280,38 @@ int sdempc_closed_loop_batch(sdempc_handle* h, int32_t B, int32_t T, const float
                              float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][T]*/,
                              float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
                              uint32_t* keys_next /*[B][2] or NULL*/);
+
+/* ---- batched closed loop against a separate plant (SPEC.md §11a) -------------------------------
+ * sdempc_closed_loop_batch with the vehicle NOT the controller's model: episode b is stepped by plant_blobs[plant_of[b]] (model blobs of SPEC.md §2
+ * with the handle's motor count), `substeps` Euler–Maruyama steps of length `dt` per control tick with the applied control uopt_k[0] held, in the
+ * plant's own mlp_dtype / math_mode — each blob prepared for that arithmetic exactly as sdempc_create prepares the handle's. No reference counterpart
+ * (the reference's plant is PX4 SITL + Gazebo). Tick k of episode b is that of sdempc_closed_loop_batch except
+ *   (r_{k+1}, p) = split(r'); Xi = normal(p, (substeps, 6)), ONE draw of 6 * substeps values (SPEC.md §7.1: counter i pairs with i + 3 * substeps);
+ *   z_0 = x_k; z_{j+1} = step_plant(z_j, uopt_k[0], Xi[j]); x_{k+1} = z_substeps.
+ * With num_plants = 1, the handle's own blob, substeps = 1, dt = 0 and both arithmetic fields -1 the results are bit-identical to
+ * sdempc_closed_loop_batch. Results depend only on plant_blobs[plant_of[b]], never on B, on the order or multiplicity of the blobs or on the layout
+ * of the solves. The plants are prepared on the host and staged to the device once per call. Every argument is checked before the first HIP call:
+ * SDEMPC_EINVAL for struct_size, num_plants outside 1 .. B, substeps outside 1 .. SDEMPC_PLANT_MAX_SUBSTEPS, dt negative or not finite, an arithmetic
+ * field outside its values, plant_of NULL with 1 < num_plants < B, an index outside [0, num_plants), a motor count that differs from the handle's;
+ * SDEMPC_EBLOB for a short blob or a bad header. All other arguments, outputs, chunking and the re-run are those of sdempc_closed_loop_batch. */
+#define SDEMPC_PLANT_MAX_SUBSTEPS 64
+typedef struct sdempc_plant_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_plant_cfg) */
+    int32_t num_plants;    /* Np: 1 .. B */
+    int32_t substeps;      /* n: plant steps per control tick, 1 .. SDEMPC_PLANT_MAX_SUBSTEPS */
+    float dt;              /* plant step length; 0: (float)time_steps[0] / (float)n, one float32 division */
+    int32_t mlp_dtype;     /* arithmetic of the plant step: 0 f32, 1 f16, 2 f32x3; -1: the handle's */
+    int32_t math_mode;     /* 0 exact, 1 fast; -1: the handle's */
+} sdempc_plant_cfg;
+int sdempc_closed_loop_batch_plant(sdempc_handle* h, const sdempc_plant_cfg* pc,
+                                   const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                   const int32_t* plant_of /*[B]; NULL: all 0 if num_plants == 1, identity if num_plants == B*/,
+                                   int32_t B, int32_t T, const float* x0,
+                                   const float* xref, int32_t xref_ticks, int32_t xref_batch,
+                                   const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                   float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][T]*/,
+                                   float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                   uint32_t* keys_next /*[B][2] or NULL*/);
 
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so

@@ -56,12 +56,20 @@ class SdempcInfo(C.Structure):
         "num_ls_trials")]
 
 
+class SdempcPlantCfg(C.Structure):
+    """sdempc_plant_cfg (SPEC.md §11a): the plant set of sdempc_closed_loop_batch_plant."""
+    _fields_ = [("struct_size", C.c_int32), ("num_plants", C.c_int32), ("substeps", C.c_int32), ("dt", C.c_float),
+                ("mlp_dtype", C.c_int32), ("math_mode", C.c_int32)]
+
+
+PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
+
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
 
 # execution options of a handle (include/sdempc.h, SDEMPC_OPT_*)
 OPTIONS = {"lane": 1, "coop": 2, "spec": 3, "pk": 4, "ustg": 5, "coop_launch": 6, "coop_fence": 7, "coop_spin_us": 8, "device_cus": 9, "duo": 10, "hex": 11, "test_absent_wg": 12}
 
-ABI_VERSION = 2          # include/sdempc.h: SDEMPC_ABI_VERSION (the layout of SdempcCfg / SdempcInfo below)
+ABI_VERSION = 3          # include/sdempc.h: SDEMPC_ABI_VERSION (the layout of SdempcCfg / SdempcInfo below)
 
 _LIB = None
 
@@ -124,6 +132,8 @@ def load_library():
     lib.sdempc_noise_from_keys.argtypes = [vp, i32, u32p, fp]
     lib.sdempc_solve_batch_keys.argtypes = [vp, i32, fp, fp, u32p, fp, fp, fp, fp, C.POINTER(SdempcInfo)]
     lib.sdempc_closed_loop_batch.argtypes = [vp, i32, i32, fp, fp, i32, i32, u32p, fp, fp, fp, fp, C.POINTER(SdempcInfo), fp, fp, u32p]
+    lib.sdempc_closed_loop_batch_plant.argtypes = [vp, C.POINTER(SdempcPlantCfg), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i32)] + \
+        lib.sdempc_closed_loop_batch.argtypes[1:]
     lib.sdempc_solve_status.argtypes = [vp]
     lib.sdempc_solve_status.restype = C.c_int
     lib.sdempc_layout_fallbacks.argtypes = [vp]
@@ -137,7 +147,8 @@ def load_library():
     for name in ("sdempc_set_device", "sdempc_reset", "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch",
                  "sdempc_noise_to_device_layout", "sdempc_solve_batch_dev", "sdempc_rollout_batch_dev",
                  "sdempc_grad_batch_dev", "sdempc_noise_to_device_layout_dev", "sdempc_traj_to_canonical_dev",
-                 "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch"):
+                 "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
+                 "sdempc_closed_loop_batch_plant"):
         getattr(lib, name).restype = C.c_int
     _LIB = lib
     return lib
@@ -149,4 +160,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_traj_dev_floats", "sdempc_noise_to_device_layout", "sdempc_solve_batch_dev", "sdempc_rollout_batch_dev",
     "sdempc_grad_batch_dev", "sdempc_last_kernel_ms", "sdempc_last_kernel_name", "sdempc_work_counters", "sdempc_solve_status", "sdempc_layout_fallbacks", "sdempc_noise_to_device_layout_dev", "sdempc_traj_to_canonical_dev",
     "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
+    "sdempc_closed_loop_batch_plant",
 ]

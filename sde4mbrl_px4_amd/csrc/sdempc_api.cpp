@@ -48,6 +48,103 @@ struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
 };
+
+// What a model blob becomes for one arithmetic and one time grid — the one statement of it, for the handle's own model (sdempc_create) and for the plants of
+// sdempc_closed_loop_batch_plant: the device payload (mlp_dtype f16: the fp16 rounding of SPEC.md §9; math_mode fast: the forward block and the block of
+// the vector-Jacobian products of §10b), the kernels' model constants (ModelK, with the scale offset of §10e) and sigma_i * sqrt(dt_t) (SPEC.md §5: float32).
+// f: the blob's float payload (SDEMPC_BLOB_FLOATS); mlp_dtype / math_mode already validated.
+struct PreparedModel {
+    std::vector<float> blob_f;   // one block, or two in math_mode fast
+    std::vector<float> sdt;      // [nsteps][6]
+    ModelK M;
+};
+void prepare_model(const float* f, int mlp_dtype, int math_mode, const float* time_steps, int nsteps, PreparedModel& out) {
+    std::vector<float>& B = out.blob_f;
+    B.assign(f, f + SDEMPC_BLOB_FLOATS);
+    if (mlp_dtype == 1) {   // layer-1 state-input weights and layer-2 weights live in fp16 (forward and adjoint alike)
+        for (int i = 0; i < 64 * 6; ++i) B[blob::W1Z + i] = f16_rtz_host(B[blob::W1Z + i]);
+        for (int i = 0; i < 32 * 32; ++i) B[blob::W2 + i] = f16_rtz_host(B[blob::W2 + i]);
+    }
+    if (math_mode == 1) {
+        // SPEC.md §10b: the hardware tanh is evaluated as r = rcp(1 + exp2(a')), a' = (2 log2 e) a, tanh(a) = 1 - 2 r. The pre-scale goes into the weights
+        // and biases that feed a tanh (one rounding each), the affine map 1 - 2 r into the weights and biases that consume one (exact factors, biases by
+        // sequential sums), and the derivative 1 - tanh^2 = 4 (r - r^2) leaves its factor 4 in the transposed weights (exact). The device blob becomes
+        // two blocks of the same layout: [forward weights][weights of the vector-Jacobian products]; float32 host arithmetic, no contraction.
+        const float c = 2.885390043258667f;
+        const std::vector<float> o = B;
+        std::vector<float> F = o, V = o;
+        for (int i = 0; i < 64 * 6; ++i) { float w = c * o[blob::W1Z + i]; F[blob::W1Z + i] = mlp_dtype == 1 ? f16_rtz_host(w) : w; }
+        for (int i = 0; i < 64; ++i) F[blob::B1 + i] = c * o[blob::B1 + i];
+        for (int i = 0; i < 32 * 8; ++i) F[blob::W1U + i] = c * o[blob::W1U + i];
+        for (int j = 0; j < 32; ++j) {
+            float sum = c * o[blob::B2 + j];
+            for (int k = 0; k < 32; ++k) {
+                float w = c * o[blob::W2 + j * 32 + k];
+                if (mlp_dtype == 1) w = f16_rtz_host(w);
+                sum = sum + w;
+                F[blob::W2 + j * 32 + k] = -2.0f * w;
+            }
+            F[blob::B2 + j] = sum;
+        }
+        for (int i = 0; i < 6; ++i) {
+            float sum = o[blob::B3 + i];
+            for (int k = 0; k < 32; ++k) { sum = sum + o[blob::W3 + i * 32 + k]; F[blob::W3 + i * 32 + k] = -2.0f * o[blob::W3 + i * 32 + k]; }
+            F[blob::B3 + i] = sum;
+        }
+        {
+            float sum = o[blob::B3N];
+            for (int k = 0; k < 32; ++k) { sum = sum + o[blob::W3N + k]; F[blob::W3N + k] = -2.0f * o[blob::W3N + k]; }
+            F[blob::B3N] = sum;
+        }
+        for (int i = 0; i < 32 * 32; ++i) V[blob::W2 + i] = 4.0f * o[blob::W2 + i];
+        for (int i = 0; i < 6 * 32; ++i) V[blob::W3 + i] = 4.0f * o[blob::W3 + i];
+        for (int k = 0; k < 32; ++k) V[blob::W3N + k] = 4.0f * o[blob::W3N + k];
+        if (mlp_dtype == 1) {
+            // mlp_dtype f16 quantises c * w once more (toward zero), so the forward pass evaluates the weights F / c, not the Wq the blob held:
+            // the vector-Jacobian products differentiate what was evaluated (SPEC.md §10b, last item of "Adjoint")
+            for (int i = 0; i < 64 * 6; ++i) V[blob::W1Z + i] = F[blob::W1Z + i] / c;
+            for (int i = 0; i < 32 * 32; ++i) V[blob::W2 + i] = (-2.0f * F[blob::W2 + i]) / c;
+        }
+        B = F;
+        B.insert(B.end(), V.begin(), V.end());
+    }
+    out.sdt.resize((size_t)nsteps * SDEMPC_NNOISE);
+    const float* sigma = f + blob::SIGMA;
+    for (int t = 0; t < nsteps; ++t) {
+        float sq = sqrtf(time_steps[t]);
+        for (int i = 0; i < SDEMPC_NNOISE; ++i) out.sdt[(size_t)t * SDEMPC_NNOISE + i] = sigma[i] * sq;
+    }
+    ModelK& M = out.M;
+    memset(&M, 0, sizeof M);
+    M.inv_mass = f[0]; M.grav = f[1];
+    for (int i = 0; i < 3; ++i) { M.J[i] = f[2 + i]; M.iJ[i] = f[5 + i]; }
+    M.ct2 = f[8]; M.ct1 = f[9]; M.ct0 = f[10]; M.cm2 = f[11]; M.cm1 = f[12];
+    for (int j = 0; j < 8; ++j) { M.rx[j] = f[16 + j]; M.ry[j] = f[24 + j]; M.dir[j] = f[32 + j]; }
+    for (int i = 0; i < 3; ++i) { M.sF[i] = f[40 + i]; M.sT[i] = f[43 + i]; }
+    for (int i = 0; i < 6; ++i) M.b3[i] = B[blob::B3 + i];      // (math_mode fast: the forward block's, SPEC.md §10b)
+    M.b3n = B[blob::B3N];
+    M.adj_s0 = -2.0f; M.adj_i0 = 1.0f;
+    if (math_mode == 1 && mlp_dtype != 0) {
+        // SPEC.md §10e: the scale offset of the adjoint's binary16 contractions. With the largest output adjoint of a particle scaled into [2^eoff, 2^(eoff+1)),
+        // |abar2| < 2^(eoff+1) B3/4, |abar1n| < 2^(eoff+1) Bn/4, |abar1d| < 2^(eoff+1) C2 B3/16 (|r - r^2| <= 1/4; B3, Bn: absolute column sums of the forward
+        // output weights, C2: of 4 W2): eoff = min(10, 14 - e) with 2^e > the largest of the three bounds keeps all of them below 2^15 (binary16 ends at 65504).
+        // float32 host arithmetic, sums in ascending index order; the oracle derives the same number by the same statements.
+        const float* F = B.data();
+        const float* V = F + SDEMPC_BLOB_FLOATS;
+        float B3 = 0.0f, Bn = 0.0f, C2 = 0.0f;
+        for (int k = 0; k < 32; ++k) {
+            float s3 = 0.0f, s2 = 0.0f;
+            for (int i = 0; i < 6; ++i) s3 = s3 + fabsf(F[blob::W3 + i * 32 + k]);
+            for (int j = 0; j < 32; ++j) s2 = s2 + fabsf(V[blob::W2 + j * 32 + k]);
+            B3 = fmaxf(B3, s3); C2 = fmaxf(C2, s2); Bn = fmaxf(Bn, fabsf(F[blob::W3N + k]));
+        }
+        const float bound = fmaxf(fmaxf(B3 * 0.25f, Bn * 0.25f), (C2 * (B3 * 0.25f)) * 0.25f);
+        int e = 0, eoff = 10;
+        if (bound > 0.0f && bound < INFINITY) { (void)frexpf(bound, &e); if (14 - e < eoff) eoff = 14 - e; }
+        if (eoff < -40) eoff = -40;
+        M.adj_s0 = ldexpf(-2.0f, eoff); M.adj_i0 = ldexpf(1.0f, -eoff);
+    }
+}
 }  // namespace
 
 struct sdempc_handle {
@@ -76,6 +173,10 @@ struct sdempc_handle {
     // closed loop (sdempc_closed_loop_batch, allocated on its first use): d_loop = keys u32[max_batch][2], solve keys u32[max_batch][2], plant noise
     // f32[max_batch][6], one flag word; d_loop_chunk = the per-tick outputs of one chunk of ticks and the reference windows it reads (grown, never shrunk)
     DevBuf d_loop, d_loop_chunk;
+    // closed loop against a separate plant (sdempc_closed_loop_batch_plant): the prepared plants of the current call (model constants, payloads, sigma sqrt(dt),
+    // step length, plant_of) and the plant noise of a tick, one allocation (grown, never shrunk); plant_stage: its host image, alive until the call returns
+    DevBuf d_plant;
+    std::vector<char> plant_stage;
     DevBuf d_work;            // u64[4] work counters (KArgs::work)
     // cooperative latency path of the solve (allocated on its first use, sized for coop_cap instances)
     DevBuf d_coop_bar, d_coop_pp, d_coop_ck;
@@ -105,6 +206,15 @@ int fail(sdempc_handle* h, int code, const char* fmt, const char* detail = "") {
 // SDEMPC_ENOMEM and anything else into SDEMPC_EINVAL. The handlers themselves allocate nothing that can throw past them.
 void set_error_nothrow(const sdempc_handle* h, const char* msg) noexcept {
     try { if (h) h->err = msg; else g_create_error = msg; } catch (...) { /* no room even for the message: the code still reports it */ }
+}
+// size and header of a model blob (SPEC.md §2); its motor count is header word 2
+int check_blob(sdempc_handle* h, const void* model_blob, size_t blob_bytes) {
+    if (!model_blob || blob_bytes < sizeof(int32_t) * SDEMPC_BLOB_HEADER_INTS + sizeof(float) * SDEMPC_BLOB_FLOATS)
+        return fail(h, SDEMPC_EBLOB, "model blob too small%s");
+    const int32_t* hd = (const int32_t*)model_blob;
+    if (hd[0] != SDEMPC_BLOB_MAGIC || hd[1] != 1 || hd[3] != SDEMPC_HID || hd[4] != 6 || hd[5] != SDEMPC_NNOISE)
+        return fail(h, SDEMPC_EBLOB, "model blob header mismatch%s");
+    return 0;
 }
 template <class F>
 int guarded(const sdempc_handle* h, F&& f) noexcept {
@@ -379,7 +489,16 @@ struct LoopIo {
     float *u_next, *stepsize_next;
     uint32_t* keys_next;
 };
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, bool* again);
+// SPEC.md §11a: the plant set of one sdempc_closed_loop_batch_plant call, staged on the device (stage_plants)
+struct PlantRun {
+    KArgs k;        // argument block of launch_loop_plant: the handle's with the plant's arithmetic and step length (one shared plant: its M / wts / sdt too)
+    LoopPlant Q;
+    float* xi;      // [B][substeps][6] plant noise of a tick
+};
+int check_loop_args(sdempc_handle* h, const LoopIo& io);
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant);
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, bool* again);
+int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out);
 }  // namespace
 
 extern "C" {
@@ -394,11 +513,8 @@ int sdempc_create(const sdempc_cfg* cfg, const void* model_blob, size_t blob_byt
     if (!out) return fail(nullptr, SDEMPC_EINVAL, "out is NULL%s");
     *out = nullptr;
     if (!cfg || cfg->struct_size != (int32_t)sizeof(sdempc_cfg)) return fail(nullptr, SDEMPC_EINVAL, "cfg NULL or struct_size mismatch%s");
-    if (!model_blob || blob_bytes < sizeof(int32_t) * SDEMPC_BLOB_HEADER_INTS + sizeof(float) * SDEMPC_BLOB_FLOATS)
-        return fail(nullptr, SDEMPC_EBLOB, "model blob too small%s");
+    if (int rc = check_blob(nullptr, model_blob, blob_bytes)) return rc;
     const int32_t* hd = (const int32_t*)model_blob;
-    if (hd[0] != SDEMPC_BLOB_MAGIC || hd[1] != 1 || hd[3] != SDEMPC_HID || hd[4] != 6 || hd[5] != SDEMPC_NNOISE)
-        return fail(nullptr, SDEMPC_EBLOB, "model blob header mismatch%s");
     const int m = hd[2];
     if (m < 1 || m > SDEMPC_MAX_MOTORS || m != cfg->num_motors) return fail(nullptr, SDEMPC_EINVAL, "num_motors of cfg and model blob differ or out of range%s");
     if (cfg->horizon < 1 || cfg->horizon > 4096 || cfg->num_particles < 1 || !cfg->time_steps || max_batch < 1)
@@ -420,63 +536,13 @@ int sdempc_create(const sdempc_cfg* cfg, const void* model_blob, size_t blob_byt
     h->time_steps.assign(cfg->time_steps, cfg->time_steps + h->H);
     h->cfg.time_steps = h->time_steps.data();
     const float* f = (const float*)(hd + SDEMPC_BLOB_HEADER_INTS);
-    h->blob_f.assign(f, f + SDEMPC_BLOB_FLOATS);
     if (cfg->mlp_dtype < 0 || cfg->mlp_dtype > 2) return fail(nullptr, SDEMPC_EINVAL, "mlp_dtype must be 0 (f32), 1 (f16) or 2 (f32x3)%s");
     if (cfg->math_mode != 0 && cfg->math_mode != 1) return fail(nullptr, SDEMPC_EINVAL, "math_mode must be 0 (exact) or 1 (fast)%s");
-    if (cfg->mlp_dtype == 1) {   // layer-1 state-input weights and layer-2 weights live in fp16 (forward and adjoint alike)
-        for (int i = 0; i < 64 * 6; ++i) h->blob_f[blob::W1Z + i] = f16_rtz_host(h->blob_f[blob::W1Z + i]);
-        for (int i = 0; i < 32 * 32; ++i) h->blob_f[blob::W2 + i] = f16_rtz_host(h->blob_f[blob::W2 + i]);
-    }
-    if (cfg->math_mode == 1) {
-        // SPEC.md §10b: the hardware tanh is evaluated as r = rcp(1 + exp2(a')), a' = (2 log2 e) a, tanh(a) = 1 - 2 r. The pre-scale goes into the weights
-        // and biases that feed a tanh (one rounding each), the affine map 1 - 2 r into the weights and biases that consume one (exact factors, biases by
-        // sequential sums), and the derivative 1 - tanh^2 = 4 (r - r^2) leaves its factor 4 in the transposed weights (exact). The device blob becomes
-        // two blocks of the same layout: [forward weights][weights of the vector-Jacobian products]; float32 host arithmetic, no contraction.
-        const float c = 2.885390043258667f;
-        const std::vector<float> o = h->blob_f;
-        std::vector<float> F = o, V = o;
-        for (int i = 0; i < 64 * 6; ++i) { float w = c * o[blob::W1Z + i]; F[blob::W1Z + i] = cfg->mlp_dtype == 1 ? f16_rtz_host(w) : w; }
-        for (int i = 0; i < 64; ++i) F[blob::B1 + i] = c * o[blob::B1 + i];
-        for (int i = 0; i < 32 * 8; ++i) F[blob::W1U + i] = c * o[blob::W1U + i];
-        for (int j = 0; j < 32; ++j) {
-            float sum = c * o[blob::B2 + j];
-            for (int k = 0; k < 32; ++k) {
-                float w = c * o[blob::W2 + j * 32 + k];
-                if (cfg->mlp_dtype == 1) w = f16_rtz_host(w);
-                sum = sum + w;
-                F[blob::W2 + j * 32 + k] = -2.0f * w;
-            }
-            F[blob::B2 + j] = sum;
-        }
-        for (int i = 0; i < 6; ++i) {
-            float sum = o[blob::B3 + i];
-            for (int k = 0; k < 32; ++k) { sum = sum + o[blob::W3 + i * 32 + k]; F[blob::W3 + i * 32 + k] = -2.0f * o[blob::W3 + i * 32 + k]; }
-            F[blob::B3 + i] = sum;
-        }
-        {
-            float sum = o[blob::B3N];
-            for (int k = 0; k < 32; ++k) { sum = sum + o[blob::W3N + k]; F[blob::W3N + k] = -2.0f * o[blob::W3N + k]; }
-            F[blob::B3N] = sum;
-        }
-        for (int i = 0; i < 32 * 32; ++i) V[blob::W2 + i] = 4.0f * o[blob::W2 + i];
-        for (int i = 0; i < 6 * 32; ++i) V[blob::W3 + i] = 4.0f * o[blob::W3 + i];
-        for (int k = 0; k < 32; ++k) V[blob::W3N + k] = 4.0f * o[blob::W3N + k];
-        if (cfg->mlp_dtype == 1) {
-            // mlp_dtype f16 quantises c * w once more (toward zero), so the forward pass evaluates the weights F / c, not the Wq the blob held:
-            // the vector-Jacobian products differentiate what was evaluated (SPEC.md §10b, last item of "Adjoint")
-            for (int i = 0; i < 64 * 6; ++i) V[blob::W1Z + i] = F[blob::W1Z + i] / c;
-            for (int i = 0; i < 32 * 32; ++i) V[blob::W2 + i] = (-2.0f * F[blob::W2 + i]) / c;
-        }
-        h->blob_f = F;
-        h->blob_f.insert(h->blob_f.end(), V.begin(), V.end());
-    }
+    PreparedModel pm;
+    prepare_model(f, cfg->mlp_dtype, cfg->math_mode, h->time_steps.data(), h->H, pm);
+    h->blob_f = std::move(pm.blob_f);
     // tables (SPEC.md §5: float32 host arithmetic)
-    const float* sigma = f + blob::SIGMA;
-    h->h_sdt.resize((size_t)h->H * SDEMPC_NNOISE);
-    for (int t = 0; t < h->H; ++t) {
-        float sq = sqrtf(h->time_steps[t]);
-        for (int i = 0; i < SDEMPC_NNOISE; ++i) h->h_sdt[(size_t)t * SDEMPC_NNOISE + i] = sigma[i] * sq;
-    }
+    h->h_sdt = std::move(pm.sdt);
     h->h_disc.resize(h->H + 1);
     float d = 1.0f / (float)h->H;
     for (int t = 0; t <= h->H; ++t) { h->h_disc[t] = d; d = d * cfg->discount; }
@@ -493,34 +559,7 @@ int sdempc_create(const sdempc_cfg* cfg, const void* model_blob, size_t blob_byt
     a.invP = 1.0f / (float)h->P;
     a.f16 = cfg->mlp_dtype;              // 0 f32, 1 fp16 operands (SPEC.md §9), 2 three-limb bf16 split of the layer-2 contractions (§9b)
     a.fast = cfg->math_mode == 1;
-    a.M.inv_mass = f[0]; a.M.grav = f[1];
-    for (int i = 0; i < 3; ++i) { a.M.J[i] = f[2 + i]; a.M.iJ[i] = f[5 + i]; }
-    a.M.ct2 = f[8]; a.M.ct1 = f[9]; a.M.ct0 = f[10]; a.M.cm2 = f[11]; a.M.cm1 = f[12];
-    for (int j = 0; j < 8; ++j) { a.M.rx[j] = f[16 + j]; a.M.ry[j] = f[24 + j]; a.M.dir[j] = f[32 + j]; }
-    for (int i = 0; i < 3; ++i) { a.M.sF[i] = f[40 + i]; a.M.sT[i] = f[43 + i]; }
-    for (int i = 0; i < 6; ++i) a.M.b3[i] = h->blob_f[blob::B3 + i];      // (math_mode fast: the forward block's, SPEC.md §10b)
-    a.M.b3n = h->blob_f[blob::B3N];
-    a.M.adj_s0 = -2.0f; a.M.adj_i0 = 1.0f;
-    if (cfg->math_mode == 1 && cfg->mlp_dtype != 0) {
-        // SPEC.md §10e: the scale offset of the adjoint's binary16 contractions. With the largest output adjoint of a particle scaled into [2^eoff, 2^(eoff+1)),
-        // |abar2| < 2^(eoff+1) B3/4, |abar1n| < 2^(eoff+1) Bn/4, |abar1d| < 2^(eoff+1) C2 B3/16 (|r - r^2| <= 1/4; B3, Bn: absolute column sums of the forward
-        // output weights, C2: of 4 W2): eoff = min(10, 14 - e) with 2^e > the largest of the three bounds keeps all of them below 2^15 (binary16 ends at 65504).
-        // float32 host arithmetic, sums in ascending index order; the oracle derives the same number by the same statements.
-        const float* F = h->blob_f.data();
-        const float* V = F + SDEMPC_BLOB_FLOATS;
-        float B3 = 0.0f, Bn = 0.0f, C2 = 0.0f;
-        for (int k = 0; k < 32; ++k) {
-            float s3 = 0.0f, s2 = 0.0f;
-            for (int i = 0; i < 6; ++i) s3 = s3 + fabsf(F[blob::W3 + i * 32 + k]);
-            for (int j = 0; j < 32; ++j) s2 = s2 + fabsf(V[blob::W2 + j * 32 + k]);
-            B3 = fmaxf(B3, s3); C2 = fmaxf(C2, s2); Bn = fmaxf(Bn, fabsf(F[blob::W3N + k]));
-        }
-        const float bound = fmaxf(fmaxf(B3 * 0.25f, Bn * 0.25f), (C2 * (B3 * 0.25f)) * 0.25f);
-        int e = 0, eoff = 10;
-        if (bound > 0.0f && bound < INFINITY) { (void)frexpf(bound, &e); if (14 - e < eoff) eoff = 14 - e; }
-        if (eoff < -40) eoff = -40;
-        a.M.adj_s0 = ldexpf(-2.0f, eoff); a.M.adj_i0 = ldexpf(1.0f, -eoff);
-    }
+    a.M = pm.M;
     for (int i = 0; i < 3; ++i) { a.C.perr[i] = cfg->perr[i]; a.C.verr[i] = cfg->verr[i]; a.C.qerr[i] = cfg->qerr[i]; a.C.werr[i] = cfg->werr[i]; }
     a.C.res_mult = cfg->res_mult; a.C.uerr = cfg->uerr; a.C.slew = cfg->u_slew_coeff; a.C.slew_cc = cfg->u_slew_constr_coeff;
     a.C.has_sc = cfg->has_slew_constr;
@@ -551,7 +590,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -899,20 +938,43 @@ int sdempc_closed_loop_batch(sdempc_handle* h, int32_t B, int32_t T, const float
                              const uint32_t* keys, const float* u_init, const float* stepsize_in, float* xs, float* us, sdempc_info* info,
                              float* u_next, float* stepsize_next, uint32_t* keys_next) {
     return guarded(h, [&]() -> int {
-    int rc = check_batch(h, B);
-    if (rc) return rc;
-    if (T < 1) return fail(h, SDEMPC_EINVAL, "closed loop: T must be >= 1%s");
-    if (xref_ticks != 1 && xref_ticks != T) return fail(h, SDEMPC_EINVAL, "closed loop: xref_ticks must be 1 or T%s");
-    if (xref_batch != 1 && xref_batch != B) return fail(h, SDEMPC_EINVAL, "closed loop: xref_batch must be 1 or B%s");
-    if (!x0 || !xref || !keys || !xs || !us || !info) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
-    if ((rc = ensure_device(h))) return rc;
     const LoopIo io{B, T, xref_ticks, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
-    for (int attempt = 0;; ++attempt) {
-        bool again = false;
-        if ((rc = closed_loop_run(h, io, &again))) return rc;
-        if (!again) return SDEMPC_OK;
-        if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
+    int rc = check_loop_args(h, io);
+    if (rc) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    return closed_loop_attempts(h, io, nullptr);       // no plant set: the handle's own model, one step of time_steps[0] per tick (SPEC.md §11)
+    });
+}
+
+int sdempc_closed_loop_batch_plant(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes,
+                                   const int32_t* plant_of, int32_t B, int32_t T, const float* x0, const float* xref, int32_t xref_ticks,
+                                   int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in, float* xs, float* us,
+                                   sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next) {
+    return guarded(h, [&]() -> int {
+    const LoopIo io{B, T, xref_ticks, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    int rc = check_loop_args(h, io);
+    if (rc) return rc;
+    // every check of the plant set happens here, before the first HIP call
+    if (!pc || pc->struct_size != (int32_t)sizeof(sdempc_plant_cfg)) return fail(h, SDEMPC_EINVAL, "plant: cfg NULL or struct_size mismatch%s");
+    if (pc->num_plants < 1 || pc->num_plants > B) return fail(h, SDEMPC_EINVAL, "plant: num_plants must be between 1 and B%s");
+    if (pc->substeps < 1 || pc->substeps > SDEMPC_PLANT_MAX_SUBSTEPS) return fail(h, SDEMPC_EINVAL, "plant: substeps must be between 1 and SDEMPC_PLANT_MAX_SUBSTEPS (64)%s");
+    if (!(pc->dt >= 0.0f) || !(pc->dt < INFINITY)) return fail(h, SDEMPC_EINVAL, "plant: dt must be finite and >= 0 (0: time_steps[0] / substeps)%s");
+    if (pc->mlp_dtype < -1 || pc->mlp_dtype > 2) return fail(h, SDEMPC_EINVAL, "plant: mlp_dtype must be -1 (the handle's), 0 (f32), 1 (f16) or 2 (f32x3)%s");
+    if (pc->math_mode < -1 || pc->math_mode > 1) return fail(h, SDEMPC_EINVAL, "plant: math_mode must be -1 (the handle's), 0 (exact) or 1 (fast)%s");
+    if (!plant_blobs || !plant_blob_bytes) return fail(h, SDEMPC_EINVAL, "plant: NULL blob table%s");
+    const int Np = pc->num_plants;
+    if (!plant_of && Np != 1 && Np != B) return fail(h, SDEMPC_EINVAL, "plant: plant_of may be NULL only when num_plants is 1 or B%s");
+    if (plant_of)
+        for (int b = 0; b < B; ++b)
+            if (plant_of[b] < 0 || plant_of[b] >= Np) return fail(h, SDEMPC_EINVAL, "plant: plant_of holds an index outside [0, num_plants)%s");
+    for (int p = 0; p < Np; ++p) {
+        if ((rc = check_blob(h, plant_blobs[p], plant_blob_bytes[p]))) return rc;
+        if (((const int32_t*)plant_blobs[p])[2] != h->m) return fail(h, SDEMPC_EINVAL, "plant: num_motors of a plant blob differs from the handle's%s");
     }
+    if ((rc = ensure_device(h))) return rc;
+    PlantRun run;
+    if ((rc = stage_plants(h, *pc, plant_blobs, plant_of, B, &run))) return rc;
+    return closed_loop_attempts(h, io, &run);
     });
 }
 
@@ -965,6 +1027,71 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
 }
+// argument checks shared by the two closed-loop entry points; no HIP call
+int check_loop_args(sdempc_handle* h, const LoopIo& io) {
+    int rc = check_batch(h, io.B);
+    if (rc) return rc;
+    if (io.T < 1) return fail(h, SDEMPC_EINVAL, "closed loop: T must be >= 1%s");
+    if (io.xref_ticks != 1 && io.xref_ticks != io.T) return fail(h, SDEMPC_EINVAL, "closed loop: xref_ticks must be 1 or T%s");
+    if (io.xref_batch != 1 && io.xref_batch != io.B) return fail(h, SDEMPC_EINVAL, "closed loop: xref_batch must be 1 or B%s");
+    if (!io.x0 || !io.xref || !io.keys || !io.xs || !io.us || !io.info) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    return 0;
+}
+// the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant) {
+    for (int attempt = 0;; ++attempt) {
+        bool again = false;
+        int rc = closed_loop_run(h, io, plant, &again);
+        if (rc) return rc;
+        if (!again) return SDEMPC_OK;
+        if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
+    }
+}
+// SPEC.md §11a. Prepares every plant blob for the plant's arithmetic and step length exactly as sdempc_create prepares the handle's (prepare_model) and
+// stages the set on the device ONCE per call, in one allocation and one copy on the handle's stream: [ModelK x Np][payload x Np][sigma sqrt(dt) x Np][dt]
+// [plant_of x B], then room for the plant noise of a tick. The arguments were checked by the caller.
+int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out) {
+    const int Np = pc.num_plants, n = pc.substeps;
+    const int dtype = pc.mlp_dtype < 0 ? h->cfg.mlp_dtype : pc.mlp_dtype, mode = pc.math_mode < 0 ? h->cfg.math_mode : pc.math_mode;
+    const float dt = pc.dt == 0.0f ? h->time_steps[0] / (float)n : pc.dt;
+    const size_t stride = (size_t)SDEMPC_BLOB_FLOATS * (mode == 1 ? 2 : 1);
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_model = 0, o_wts = up16(sizeof(ModelK) * Np), o_sdt = o_wts + up16(sizeof(float) * stride * Np);
+    const size_t o_dt = o_sdt + up16(sizeof(float) * SDEMPC_NNOISE * Np), o_of = o_dt + 16, o_xi = o_of + up16(sizeof(int32_t) * (plant_of ? B : 0));
+    const size_t total = o_xi + sizeof(float) * (size_t)B * n * SDEMPC_NNOISE;
+    std::vector<char>& stg = h->plant_stage;
+    stg.assign(o_xi, 0);
+    PreparedModel pm;
+    for (int p = 0; p < Np; ++p) {
+        prepare_model((const float*)((const int32_t*)blobs[p] + SDEMPC_BLOB_HEADER_INTS), dtype, mode, &dt, 1, pm);
+        memcpy(&stg[o_model + sizeof(ModelK) * p], &pm.M, sizeof(ModelK));
+        memcpy(&stg[o_wts + sizeof(float) * stride * p], pm.blob_f.data(), sizeof(float) * stride);
+        memcpy(&stg[o_sdt + sizeof(float) * SDEMPC_NNOISE * p], pm.sdt.data(), sizeof(float) * SDEMPC_NNOISE);
+        if (p == 0) out->k.M = pm.M;
+    }
+    memcpy(&stg[o_dt], &dt, sizeof dt);
+    if (plant_of) memcpy(&stg[o_of], plant_of, sizeof(int32_t) * B);
+    int rc;
+    if (h->d_plant.bytes < total) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        dev_free(h->d_plant);
+        if ((rc = dev_alloc(h, h->d_plant, total))) return rc;
+    }
+    char* d = (char*)h->d_plant.p;
+    HIPCHK(h, hipMemcpyAsync(d, stg.data(), o_xi, hipMemcpyHostToDevice, h->stream));
+    const ModelK M0 = out->k.M;
+    out->k = h->base;
+    out->k.f16 = dtype; out->k.fast = mode == 1;
+    out->k.M = M0;                                      // (read by the kernel only when every episode shares plant 0)
+    out->k.wts = (const float*)(d + o_wts); out->k.sdt = (const float*)(d + o_sdt); out->k.dt = (const float*)(d + o_dt);
+    const bool shared = Np == 1;
+    out->Q.models = shared ? nullptr : (const ModelK*)(d + o_model);
+    out->Q.wts = out->k.wts; out->Q.sdt = out->k.sdt;
+    out->Q.plant_of = plant_of && !shared ? (const int*)(d + o_of) : nullptr;
+    out->Q.wts_stride = (int)stride; out->Q.substeps = n;
+    out->xi = (float*)(d + o_xi);
+    return 0;
+}
 // Device memory the per-tick buffers of one chunk of closed-loop ticks may take (sdempc_closed_loop_batch): the outputs (x_{k+1}, u_k, info_k)
 // of every episode and, when the reference moves per tick, the chunk's reference windows. T itself is unbounded: outputs are copied back and
 // references staged once per chunk (one host synchronisation per chunk, none per tick).
@@ -974,7 +1101,7 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // the chunk's outputs back and checks, once per chunk, whether a grid barrier of a cooperative-layout solve gave up or the ticket count of the
 // persistent launches is off: *again = true then, and the caller runs the whole batch once more from the host inputs (the handle has left
 // the cooperative layouts; results are the same in every layout).
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, bool* again) {
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)NX + m + 8;       // floats per reference window / per episode-tick of output
@@ -993,8 +1120,9 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, bool* again) {
     }
     uint32_t* d_keys = (uint32_t*)h->d_loop.p;                      // r_k, advanced in place
     uint32_t* d_sub = d_keys + 2 * (size_t)h->max_batch;             // the solve's noise keys of the tick
-    float* d_xi = (float*)(d_sub + 2 * (size_t)h->max_batch);        // plant noise of the tick
-    unsigned* d_gave_up = (unsigned*)(d_xi + 6 * (size_t)h->max_batch);
+    float* d_xi6 = (float*)(d_sub + 2 * (size_t)h->max_batch);       // plant noise of the tick (SPEC.md §11: six values per episode)
+    unsigned* d_gave_up = (unsigned*)(d_xi6 + 6 * (size_t)h->max_batch);
+    float* d_xi = plant ? plant->xi : d_xi6;                         // (SPEC.md §11a: 6 * substeps values per episode, beside the staged plants)
     float* c_xs = (float*)h->d_loop_chunk.p;                         // [Tc][B][13]
     float* c_us = c_xs + (size_t)Tc * B * NX;                        // [Tc][B][m]
     float* c_info = c_us + (size_t)Tc * B * m;                       // [Tc][B][8]
@@ -1029,7 +1157,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, bool* again) {
         const int nk = T - k0 < Tc ? T - k0 : Tc;
         if (xref_moves) HIPCHK(h, hipMemcpyAsync(c_xref, io.xref + (size_t)k0 * Bx * XR, sizeof(float) * nk * Bx * XR, hipMemcpyHostToDevice, st));
         for (int kc = 0; kc < nk; ++kc) {
-            HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st));
+            if (plant) HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st, plant->Q.substeps));
+            else HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st));
             HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));
             const float* win = c_xref + (xref_moves ? (size_t)kc * Bx * XR : 0);
             const float* xr = win;
@@ -1045,7 +1174,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, bool* again) {
             L.x = d_x; L.u = (float*)h->d_u.p; L.step = (float*)h->d_step.p;
             L.xs = c_xs + (size_t)kc * B * NX; L.us = c_us + (size_t)kc * B * m; L.gave_up = d_gave_up;
             L.B = B; L.H = H;
-            HIPCHK(h, launch_loop_advance(h->base, L, st));
+            if (plant) HIPCHK(h, launch_loop_plant(plant->k, L, plant->Q, st));
+            else HIPCHK(h, launch_loop_advance(h->base, L, st));
         }
         hx.resize((size_t)nk * B * NX); hu.resize((size_t)nk * B * m); hi.resize((size_t)nk * B * 8);
         unsigned gave_up = 0;

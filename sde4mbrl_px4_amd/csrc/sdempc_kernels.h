@@ -151,8 +151,22 @@ struct LoopAdvance {
     int B, H;
 };
 hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
-// the tick's key schedule (sdempc_prng.hip): keys r_k -> r_{k+1} in place, the solve's noise keys into sub_dev u32[B][2], the plant noise into xi_dev f32[B][6]
-hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st);
+// SPEC.md §11a, the closed loop against a separate plant: which model steps episode b, and how often per tick. LoopAdvance::xi is [B][substeps][6] here.
+// models == null: ONE plant for every episode — the launch's KArgs carry it (M, wts, sdt) and the four episodes of a workgroup share its LDS images,
+// as in launch_loop_advance. Otherwise episode b is stepped by plant p = plant_of ? plant_of[b] : b, and every wave stages its own images.
+struct LoopPlant {
+    const ModelK* models;       // [Np] physics prior and output-layer constants of each prepared plant, or null
+    const float* wts;           // [Np][wts_stride] prepared blob payloads (math_mode fast: forward block, then the block of the vector-Jacobian products)
+    const float* sdt;           // [Np][6] sigma_i * sqrt(dt) of each plant
+    const int* plant_of;        // [B] plant index of each episode, or null (identity)
+    int wts_stride;             // floats between two plants' payloads
+    int substeps;               // Euler–Maruyama steps per tick, the applied control held (>= 1)
+};
+// `a`: the handle's argument block with the PLANT's arithmetic (f16, fast), dt -> one float (the plant's step length) and, for one shared plant, its M / wts / sdt
+hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st);
+// the tick's key schedule (sdempc_prng.hip): keys r_k -> r_{k+1} in place, the solve's noise keys into sub_dev u32[B][2], the plant noise into
+// xi_dev f32[B][substeps][6]: ONE draw normal(p, 6 * substeps) per episode (SPEC.md §7.1: counter i pairs with i + 3 * substeps), row j for substep j
+hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st, int substeps = 1);
 // rows_dev[b][0..n) = row_dev[0..n) for b < B
 hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st);
 // canonical [B][P][C] <-> device [B][G][C][32] (to_dev: zero-pads particles >= P)

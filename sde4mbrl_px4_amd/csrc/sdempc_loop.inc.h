@@ -43,6 +43,86 @@ __global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_advance_kernel(KArg
     }
 }
 
+// SPEC.md §11a: the same hand-over behind a SEPARATE plant — episode b is stepped by the model Q names for it, Q.substeps times at the plant's own step
+// length and in the plant's own arithmetic (this kernel's namespace and F16 are the plant's, independent of the solve's), the applied control held.
+// The argument block arrives as for the kernel above (H = 1; dt -> the plant's step length) and the wave works on a copy `a`: with per-episode plants (Q.models) the wave
+// replaces a.M, a.wts and a.sdt by its plant's, read through a readfirstlane'd index (wave-uniform addresses, before the kernel's first store: scalar
+// loads, so the model constants stay in SGPRs as the kernel arguments they replace do), and stages its OWN LDS images — the workgroup's LDS holds four
+// carves of one team each instead of one carve of four teams (16 KB per episode, 64 KB per workgroup: two workgroups per CU). With one shared plant the
+// four episodes share one carve, as above. block_prepass indexes the rotor tables of a.M by a run-time motor index, which a kernel argument serves by a
+// scalar load at a computed offset but a modified copy could only serve from scratch: the per-episode path hands it the wave's argument block in LDS
+// (plant_kargs_floats() floats per wave behind the carves) and keeps the register copy for step_fwd, whose indices are all static.
+// The prepass runs once per tick (control table row 0 from uopt_k[0] with the plant's polynomials and W1u); every substep is step_fwd at t = 0, xn fed back.
+__host__ __device__ constexpr int plant_kargs_floats() { return (int)((sizeof(KArgs) + 15) / 16 * 4); }
+template <int F16>
+__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_plant_kernel(KArgs a0, LoopAdvance L, LoopPlant Q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    KArgs a = a0;                   // (a0 stays the untouched kernel argument: the shared-plant prepass indexes it at run time)
+    const int H = L.H, m = a.m;
+    const int tid = TeamWave::tid();
+    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
+    const bool per = Q.models != nullptr, live = b < L.B;      // (both wave-uniform)
+    if (per && live) {
+        const int p = __builtin_amdgcn_readfirstlane(Q.plant_of ? Q.plant_of[b] : b);
+        a.M = Q.models[p];
+        a.wts = Q.wts + (size_t)p * Q.wts_stride;
+        a.sdt = Q.sdt + (size_t)p * NN;
+    }
+    Smem sm = per ? carve(smem + (size_t)TeamWave::team() * smem_floats(1, m, 1), 1, m, 0) : carve(smem, 1, m, TeamWave::team());
+    WaveW ww;
+    load_weights(a, sm, ww, per ? tid : (int)threadIdx.x, per ? TeamWave::NT : TeamWave::BNT);
+    KArgs* const lk = reinterpret_cast<KArgs*>(smem + TeamWave::IPB * smem_floats(1, m, 1) + (size_t)TeamWave::team() * plant_kargs_floats());
+    if (per && tid == 0) { lk->H = 1; lk->m = m; lk->M = a.M; }        // (what block_prepass reads)
+    __syncthreads();
+    if (!live) return;              // (wave-uniform; no workgroup-wide barrier below)
+    const int lane = tid & 63, h = lane >> 5;
+    const float* uo = L.uopt + (size_t)b * H * m;
+    if (per) block_prepass<TeamWave>(*lk, sm, uo, tid);
+    else block_prepass<TeamWave>(a0, sm, uo, tid);
+    float x[NX], xn[NX], xi[NN];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
+    TeamWave::sync();
+    const float* xrow = L.xi + (size_t)b * Q.substeps * NN;
+#pragma nounroll
+    for (int j = 0; j < Q.substeps; ++j) {
+#pragma unroll
+        for (int i = 0; i < NN; ++i) xi[i] = xrow[j * NN + i];
+        StepAux A;
+        step_fwd<F16, false>(a, sm, ww, 0, h, lane, x, xi, xn, A);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) x[i] = xn[i];
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) { L.x[(size_t)b * NX + i] = x[i]; L.xs[(size_t)b * NX + i] = x[i]; }
+        L.step[b] = L.info[(size_t)b * 8 + 1];
+        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
+    }
+    if (lane < m) L.us[(size_t)b * m + lane] = uo[lane];
+    float* un = L.u + (size_t)b * H * m;
+    for (int e = tid; e < H * m; e += TeamWave::NT) {   // y_{k+1} = [uopt_k[1:], uopt_k[H-1]]
+        const int t = e / m;
+        un[e] = uo[(t + 1 < H ? t + 1 : t) * m + (e - t * m)];
+    }
+}
+
+hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st) {
+    if (L.B < 1 || L.H != a.H || Q.substeps < 1 || (Q.models && (!Q.wts || !Q.sdt || Q.wts_stride < BLOB_FLOATS + VJP_BASE))) return hipErrorInvalidValue;
+    KArgs k = a;
+    k.H = 1;
+    const size_t sb = Q.models ? TeamWave::IPB * (smem_bytes(1, k.m, 1) + sizeof(float) * plant_kargs_floats()) : smem_bytes(1, k.m, TeamWave::IPB);
+    const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
+    return with_f16(k.f16, [&](auto F16) {
+        if (sb > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)sdempc_loop_plant_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
+            if (e != hipSuccess) return e;
+        }
+        sdempc_loop_plant_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q);
+        return hipGetLastError();
+    });
+}
+
 hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st) {
     if (L.B < 1 || L.H != a.H) return hipErrorInvalidValue;
     KArgs k = a;

@@ -172,9 +172,30 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_kernel(uint32_t* __restr
     }
 }
 
-hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st) {
-    if (B < 1) return hipErrorInvalidValue;
-    sdempc_loop_keys_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B);
+// SPEC.md §11a: the same schedule with n plant substeps per tick — xi_k = normal(p, (n, 6)), ONE draw of 6 n values (random_bits(p, 6 n) pairs
+// counter i with i + 3 n: element i of the flat draw is the first word of block i, element 3 n + i the second). xi: [B][n][6]; n = 1 is the kernel above.
+__global__ void __launch_bounds__(256) sdempc_loop_keys_sub_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int n) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    uint32_t r1[2], s[2], r2[2], p[2];
+    split2(keys[2 * b], keys[2 * b + 1], r1, s);
+    split2(r1[0], r1[1], r2, p);
+    sub[2 * b] = s[0]; sub[2 * b + 1] = s[1];
+    keys[2 * b] = r2[0]; keys[2 * b + 1] = r2[1];
+    const uint32_t half = 3u * (uint32_t)n;
+    float* row = xi + (size_t)b * 2u * half;
+    for (uint32_t i = 0; i < half; ++i) {
+        uint32_t x0 = i, x1 = i + half;
+        threefry2x32(p[0], p[1], x0, x1);
+        row[i] = bits_to_normal(x0);
+        row[half + i] = bits_to_normal(x1);
+    }
+}
+
+hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st, int substeps) {
+    if (B < 1 || substeps < 1) return hipErrorInvalidValue;
+    if (substeps == 1) sdempc_loop_keys_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B);
+    else sdempc_loop_keys_sub_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, substeps);
     return hipGetLastError();
 }
 

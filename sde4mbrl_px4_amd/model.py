@@ -62,6 +62,33 @@ class RotorSDEModel:
             kw[k] = a
         return cls(num_motors=m, mass=float(d["mass"]), grav=float(d["grav"]), b3n=float(d["b3n"]), **kw)
 
+    def perturbed(self, rng, *, mass=0.0, inertia=0.0, thrust=0.0, moment=0.0, sigma=0.0, residual=0.0) -> "RotorSDEModel":
+        """A copy whose named parameter groups are scaled by independent uniform relative perturbations, element by element:
+        value * (1 + a * U(-1, 1)) in float32, a the keyword's amount — the domain-randomisation helper for the plants of
+        SdeMpcSolver.closed_loop(plant=...) (SPEC.md §11a). Deterministic in `rng` (a numpy.random.Generator): the draws are taken in the
+        fixed order below, for every group whatever its amount, so one keyword never changes another group's draw. `self` is untouched;
+        all amounts zero give a model with a byte-identical blob.
+          mass      -> mass                      inertia  -> inertia[3]
+          thrust    -> thrust_poly[3]            moment   -> moment_poly[2]
+          sigma     -> sigma[6]                  residual -> W2[32][32] (the hidden layer of the residual drift net)
+        Rotor geometry, the residual scales and the other MLP weights are copied as they are."""
+        import dataclasses
+        kw = {k: (np.array(v, dtype=np.float32, copy=True) if isinstance(v, np.ndarray) else v) for k, v in
+              ((f.name, getattr(self, f.name)) for f in dataclasses.fields(self))}
+
+        def scale(value, amount):
+            v = np.asarray(value, np.float32)
+            u = rng.uniform(-1.0, 1.0, size=v.shape).astype(np.float32)
+            return v * (np.float32(1.0) + np.float32(amount) * u)
+
+        kw["mass"] = float(scale(self.mass, mass))
+        kw["inertia"] = scale(self.inertia, inertia)
+        kw["thrust_poly"] = scale(self.thrust_poly, thrust)
+        kw["moment_poly"] = scale(self.moment_poly, moment)
+        kw["sigma"] = scale(self.sigma, sigma)
+        kw["W2"] = scale(self.W2, residual)
+        return RotorSDEModel(**kw)
+
     def to_blob(self) -> bytes:
         m = self.num_motors
         assert 1 <= m <= MAX_MOTORS

@@ -137,13 +137,16 @@ class MpcProblem:
         return _arr(uo), st, new_rng, _arr(xevol[0])
 
 
-    def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None):
+    def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
+                 plant_mlp_dtype=None, plant_math_mode=None):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
         and the states back once (not per tick). Tick k tracks self.xref(curr_t + k * dt_0, xdes) when a trajectory is loaded, else xdes
         (default: the initial state). opt_state None starts from m_reset. Returns (xs f32[T+1][13] with xs[0] = x, us f32[T][m],
-        info f32[T][8], the OptState after the last tick, the key after the last tick)."""
+        info f32[T][8], the OptState after the last tick, the key after the last tick).
+        plant / plant_*: fly another vehicle than the controller's model (a RotorSDEModel or a blob), stepped plant_substeps times per tick —
+        the arguments of SdeMpcSolver.closed_loop (SPEC.md §11a), passed through for this one episode."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -160,7 +163,9 @@ class MpcProblem:
         if opt_state is not None:
             u0 = np.asarray(opt_state.yk, np.float32)[None]
             s0 = np.array([opt_state.stepsize], np.float32)
-        xs, us, info, u_next, s_next, k_next = self.solver().closed_loop(xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0)
+        xs, us, info, u_next, s_next, k_next = self.solver().closed_loop(
+            xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
+            plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode)
         xs = xs[0]
         if self.convert_to_enu:
             xs = np.concatenate([x[None], enu2ned(xs[1:], np)], axis=0)

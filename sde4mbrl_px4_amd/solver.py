@@ -28,6 +28,19 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+MLP_DTYPES = {"f32": 0, "f16": 1, "f32x3": 2}      # sdempc_cfg::mlp_dtype / sdempc_plant_cfg::mlp_dtype (as MPCConfig.to_cfg)
+MATH_MODES = {"exact": 0, "fast": 1}
+
+
+def _abi_enum(table, value, what):
+    """'f32x3' -> 2; integers pass through."""
+    if isinstance(value, str):
+        if value not in table:
+            raise ValueError(f"{what}: unknown value {value!r} (one of {sorted(table)})")
+        return table[value]
+    return int(value)
+
+
 class SdeMpcSolver:
     """One solver handle = one (MPC config, model). Single-threaded, like the reference's solver
     objects (one blocking call at a time, sde_control.py:420)."""
@@ -150,12 +163,20 @@ class SdeMpcSolver:
                                                      _fp(u_init), _fp(stepsize_in), _fp(uopt), _fp(xevol), info))
         return uopt, xevol, np.frombuffer(info, dtype=np.float32).reshape(B, 8).copy()
 
-    def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None):
+    def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
+                    plant_mlp_dtype=None, plant_math_mode=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
         f32[H+1][13]; u_init [B][H][m] / stepsize_in [B] default to what reset() gives. Returns
-        (xs [B][T+1][13], us [B][T][m], info [B][T][8], u_next [B][H][m], stepsize_next [B], keys_next uint32[B][2])."""
+        (xs [B][T+1][13], us [B][T][m], info [B][T][8], u_next [B][H][m], stepsize_next [B], keys_next uint32[B][2]).
+
+        plant (SPEC.md §11a, sdempc_closed_loop_batch_plant): the vehicle the controller flies when it is NOT the controller's model — a
+        RotorSDEModel or a blob (one plant for every episode), or a sequence of Np of them with plant_of int[B] naming each episode's plant
+        (optional when Np is 1 or B: all 0 / identity). plant_substeps Euler–Maruyama steps per tick with the applied control held;
+        plant_dt their length (None: float32(time_steps[0]) / float32(plant_substeps)); plant_mlp_dtype / plant_math_mode the arithmetic
+        of the plant step (None: the handle's) — pin them to compare two controller arithmetics on one and the same vehicle. With
+        plant=None every plant_* argument must keep its default and the call is sdempc_closed_loop_batch, unchanged."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -180,9 +201,28 @@ class SdeMpcSolver:
         s_next = np.zeros(B, np.float32)
         k_next = np.zeros((B, 2), np.uint32)
         u32p = C.POINTER(C.c_uint32)
-        self._check(self.lib.sdempc_closed_loop_batch(
-            self._h, B, T, _fp(x0), _fp(xref), int(xref.shape[0]), int(xref.shape[1]), keys.ctypes.data_as(u32p), u_p, s_p,
-            _fp(xs), _fp(us), info.ctypes.data_as(C.POINTER(SdempcInfo)), _fp(u_next), _fp(s_next), k_next.ctypes.data_as(u32p)))
+        tail = (B, T, _fp(x0), _fp(xref), int(xref.shape[0]), int(xref.shape[1]), keys.ctypes.data_as(u32p), u_p, s_p,
+                _fp(xs), _fp(us), info.ctypes.data_as(C.POINTER(SdempcInfo)), _fp(u_next), _fp(s_next), k_next.ctypes.data_as(u32p))
+        if plant is None:
+            if plant_of is not None or plant_substeps != 1 or plant_dt is not None or plant_mlp_dtype is not None or plant_math_mode is not None:
+                raise ValueError("closed_loop: plant_of / plant_substeps / plant_dt / plant_mlp_dtype / plant_math_mode need plant=...")
+            self._check(self.lib.sdempc_closed_loop_batch(self._h, *tail))
+            return xs, us, info, u_next, s_next, k_next
+        plants = [plant] if hasattr(plant, "to_blob") or isinstance(plant, (bytes, bytearray, memoryview)) else list(plant)
+        blobs = [p.to_blob() if hasattr(p, "to_blob") else bytes(p) for p in plants]
+        Np = len(blobs)
+        bufs = (C.c_char_p * max(Np, 1))(*blobs)
+        sizes = (C.c_size_t * max(Np, 1))(*[len(b) for b in blobs])
+        of_p = None
+        if plant_of is not None:
+            plant_of = np.ascontiguousarray(plant_of, dtype=np.int32)
+            if plant_of.shape != (B,):
+                raise ValueError(f"plant_of must be int[{B}], got {plant_of.shape}")
+            of_p = plant_of.ctypes.data_as(C.POINTER(C.c_int32))
+        pc = _abi.SdempcPlantCfg(C.sizeof(_abi.SdempcPlantCfg), Np, int(plant_substeps), 0.0 if plant_dt is None else float(np.float32(plant_dt)),
+                                 -1 if plant_mlp_dtype is None else _abi_enum(MLP_DTYPES, plant_mlp_dtype, "plant_mlp_dtype"),
+                                 -1 if plant_math_mode is None else _abi_enum(MATH_MODES, plant_math_mode, "plant_math_mode"))
+        self._check(self.lib.sdempc_closed_loop_batch_plant(self._h, C.byref(pc), C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *tail))
         return xs, us, info, u_next, s_next, k_next
 
     def noise_from_keys(self, keys):

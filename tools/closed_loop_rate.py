@@ -6,7 +6,11 @@
      ratio is a lower bound on what the device loop saves. The two follow different trajectories from the same start, so iteration counts
      and kernel times differ a little; the kernel trace below splits the closed loop's own tick.
   2. Episode-ticks per second at C2 (arithmetic of bench.py: f32x3 / fast) with B = 12,288, against one batch solve of the same B.
-usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2]
+  3. --plant one | per-episode [--substeps N]: the same two measurements against a separate plant (SPEC.md §11a) — one perturbed vehicle for every
+     episode, or one per episode (domain randomisation); `own` (default) is the plain loop, the handle's model as the plant. The plants' blobs
+     are made before the clock starts (RotorSDEModel.perturbed + to_blob is host work of the caller, not of the loop).
+     --repeats R times the C2 loop R times on one handle (run-to-run spread of one session).
+usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|one|per-episode] [--substeps N] [--repeats R]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -28,20 +32,42 @@ ap.add_argument("--ticks", type=int, default=40)
 ap.add_argument("--c2-ticks", type=int, default=3)
 ap.add_argument("--skip-c2", action="store_true")
 ap.add_argument("--loop-only", action="store_true", help="B = 1 closed loops only (no Python-driven comparison): for a kernel trace")
+ap.add_argument("--skip-b1", action="store_true", help="skip the B = 1 part")
+ap.add_argument("--plant", choices=("own", "one", "per-episode"), default="own")
+ap.add_argument("--substeps", type=int, default=1)
+ap.add_argument("--repeats", type=int, default=1)
 a = ap.parse_args()
 model = synthetic_iris()
+if a.plant == "own" and a.substeps != 1:
+    ap.error("--substeps needs --plant one or per-episode")
 
-for name in ("iris_traj_shipped_h20_p1", "c1_iris_posctrl_h20_p32"):
+
+def plant_kw(B):
+    """keyword arguments of closed_loop / simulate for --plant: blobs of vehicles perturbed by +-20 % in mass, inertia, thrust curve and W2"""
+    if a.plant == "own":
+        return {}
+    rng = np.random.default_rng(1)
+    n = 1 if a.plant == "one" else B
+    blobs = [model.perturbed(rng, mass=0.2, inertia=0.2, thrust=0.2, residual=0.2).to_blob() for _ in range(n)]
+    return {"plant": blobs[0] if a.plant == "one" else blobs, "plant_substeps": a.substeps}
+
+
+tag = "" if a.plant == "own" else f" plant={a.plant} substeps={a.substeps}"
+
+for name in (() if a.skip_b1 else ("iris_traj_shipped_h20_p1", "c1_iris_posctrl_h20_p32")):
     cfg = load_mpc_config(os.path.join(ROOT, "configs", name + ".yaml"))
     prob = MpcProblem(cfg=cfg, model=model, state_from_traj=W.lemniscate_state if cfg.trajectory_path else None)
     x = W.random_initial_states(1, 4)[0]
     rng = prng.PRNGKey(10)
-    prob.simulate(x, rng, 3)                                 # warm-up: device buffers, workspaces
+    pk = plant_kw(1)
+    if pk:
+        pk["plant"] = pk["plant"] if a.plant == "one" else pk["plant"][0]
+    prob.simulate(x, rng, 3, **pk)                           # warm-up: device buffers, workspaces
     t = time.perf_counter()
-    xs, us, info, st, _ = prob.simulate(x, rng, a.ticks)
+    xs, us, info, st, _ = prob.simulate(x, rng, a.ticks, **pk)
     dev = (time.perf_counter() - t) * 1e3 / a.ticks
     if a.loop_only:
-        print(f"{name:26s} B=1: closed_loop {dev:7.3f} ms/tick over {a.ticks} ticks", flush=True)
+        print(f"{name:26s} B=1{tag}: closed_loop {dev:7.3f} ms/tick over {a.ticks} ticks", flush=True)
         continue
     # the same ticks from Python: m_mpc, the key split of the plant noise, and the predicted state after one step as the next state
     st = prob.m_reset(x=x, rng=rng)
@@ -70,9 +96,11 @@ if not a.skip_c2:
     t = time.perf_counter()
     S.solve_keys(x0, xref[0], keys, u0, s0)
     one = time.perf_counter() - t
-    t = time.perf_counter()
-    S.closed_loop(x0, xref, keys, T, u_init=u0, stepsize_in=s0)
-    loop = time.perf_counter() - t
-    print(f"C2 f32x3/fast B={B}: closed_loop {B * T / loop:8.1f} episode-ticks/s ({loop / T:.3f} s/tick, T = {T}); one batch solve_keys "
-          f"{B / one:8.1f} solves/s ({one:.3f} s); ratio {(B * T / loop) / (B / one):.3f}", flush=True)
+    pk = plant_kw(B)
+    for rep in range(a.repeats):
+        t = time.perf_counter()
+        S.closed_loop(x0, xref, keys, T, u_init=u0, stepsize_in=s0, **pk)
+        loop = time.perf_counter() - t
+        print(f"C2 f32x3/fast B={B}{tag}: closed_loop {B * T / loop:8.1f} episode-ticks/s ({loop / T:.3f} s/tick, T = {T}); one batch solve_keys "
+              f"{B / one:8.1f} solves/s ({one:.3f} s); ratio {(B * T / loop) / (B / one):.3f}", flush=True)
     S.close()
