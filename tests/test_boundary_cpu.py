@@ -231,7 +231,7 @@ def test_shared_block_layouts_and_command_selection():
 
 
 # ---- N3: importer for pickled parameter trees (layout supplied by the caller; nothing about the external format is guessed) ----
-def test_param_tree_importer_round_trip(tmp_path):
+def test_param_tree_importer_round_trip(tmp_path, ref=None):
     import pickle
 
     import yaml
@@ -239,7 +239,7 @@ def test_param_tree_importer_round_trip(tmp_path):
     from sde4mbrl_px4_amd import synthetic_hexa
     from sde4mbrl_px4_amd.importer import import_sde_pickle, load_param_tree
 
-    ref = synthetic_hexa()
+    ref = ref or synthetic_hexa()
     m = ref.num_motors
     W1 = np.concatenate([ref.W1z[:32], ref.W1u], axis=1)            # [32, 6+m]
     tree = {   # Haiku-style: module -> {w [in, out], b}; arrays are plain numpy (jax.device_get before pickling)
@@ -280,3 +280,11 @@ def test_param_tree_importer_round_trip(tmp_path):
             return (os.system, ("echo pwned",))
     with pytest.raises(pickle.UnpicklingError, match="refusing"):
         load_param_tree(pickle.dumps({"w": Evil()}))
+
+
+@pytest.mark.parametrize("m", [4, 5])
+def test_param_tree_importer_round_trip_of_an_asymmetric_vehicle(tmp_path, m):
+    """The same round trip with a vehicle that has none of the synthetic ones' zeros and equal pairs (tests/cases.py: b3, b3n, ct0 != 0, three distinct
+    inertias, six distinct scales and sigma, non-unit rotor_dir): a field the importer dropped or swapped would change the blob."""
+    from cases import asymmetric_model
+    test_param_tree_importer_round_trip(tmp_path, asymmetric_model(m))

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import orc
-from cases import ROOT, bits_differ
+from cases import ROOT, asymmetric_cfg, asymmetric_model, asymmetric_problem, bits_differ
 from sde4mbrl_px4_amd import MPCConfig, synthetic_hexa, synthetic_iris, synthetic_multirotor
 from sde4mbrl_px4_amd import workload as W
 
@@ -16,7 +16,17 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import sde_mpc_numpy as R2  # noqa: E402
 
 
+def _asymmetric(m, **kw):
+    """The asymmetric fixtures (tests/cases.py): instance 1 of 2 carries the 150 degree attitude AND the negated quaternion."""
+    cfg = asymmetric_cfg(m, **kw)
+    x0, xref, noise, u = asymmetric_problem(cfg, 2, 17)
+    return cfg, asymmetric_model(m), x0[1], xref[1], noise[1], u[1]
+
+
 def _case(name):
+    if name.startswith("asymmetric"):       # no symmetry, no zero term, per-motor-distinct settings; m = 4 / 6 / generic (8-slot tables)
+        m = {"asymmetric": 4, "asymmetric_hexa": 6, "asymmetric_m5": 5}[name]
+        return _asymmetric(m, horizon=8, num_short_dt=5, long_step_dt=0.1, num_particles=40 if m == 4 else 9, max_iter=7, max_no_improvement_iter=7)
     if name == "iris":
         cfg = MPCConfig(horizon=8, num_short_dt=5, long_step_dt=0.1, num_particles=40, u_slew_coeff=1.0, max_iter=7, max_no_improvement_iter=7)
         model = synthetic_iris()
@@ -40,6 +50,10 @@ def _case(name):
     noise = W.make_noise(1, P, H, 5)[0]
     u = np.clip(np.asarray(cfg.uref, np.float32) + 0.1 * np.random.default_rng(2).standard_normal((H, m)), 1e-4, 1).astype(np.float32)
     return cfg, model, x0, xref, noise, u
+
+
+CASES = ["iris", "hexa_slew_constr", "single_particle", "state_constr", "asymmetric"]
+MORE_ASYMMETRIC = ["asymmetric_hexa", "asymmetric_m5"]
 
 
 def test_software_fma_is_exact():
@@ -71,7 +85,7 @@ def test_elementary_functions_match_the_c_oracle_bit_for_bit():
     assert bits_differ(R2.sigmoid(x * 4), np.array([L.orc_sigmoid(float(v)) for v in x * 4], np.float32)) == 0
 
 
-@pytest.mark.parametrize("name", ["iris", "hexa_slew_constr", "single_particle", "state_constr"])
+@pytest.mark.parametrize("name", CASES + MORE_ASYMMETRIC)
 def test_forward_rollout_bit_identical_to_the_c_oracle(name):
     cfg, model, x0, xref, noise, u = _case(name)
     O, N = orc.Oracle(cfg, model), R2.Restatement(cfg, model)
@@ -80,7 +94,7 @@ def test_forward_rollout_bit_identical_to_the_c_oracle(name):
     assert np.float32(c_o) == c_n and bits_differ(traj_n, traj_o) == 0 and bits_differ(mean_n, mean_o) == 0
 
 
-@pytest.mark.parametrize("name", ["iris", "hexa_slew_constr", "single_particle", "state_constr"])
+@pytest.mark.parametrize("name", CASES + MORE_ASYMMETRIC)
 def test_adjoint_sweep_bit_identical_to_the_c_oracle(name):
     """SPEC.md §5.4-§5.5 written a second time (all particles at once, NumPy float32 with the exact software fma): cost and gradient of the
     second restatement equal the C oracle's bit for bit — the hand-derived vector-Jacobian product is no longer a single point of failure."""
@@ -91,7 +105,7 @@ def test_adjoint_sweep_bit_identical_to_the_c_oracle(name):
     assert np.float32(c_o) == c_n and bits_differ(g_n, g_o.astype(np.float32)) == 0
 
 
-@pytest.mark.parametrize("name", ["iris", "hexa_slew_constr", "single_particle", "state_constr"])
+@pytest.mark.parametrize("name", CASES)
 def test_full_solve_of_the_second_restatement_bit_identical_to_the_c_oracle(name):
     """SPEC.md §8 on the second restatement's OWN cost and gradient (no oracle callback anywhere): same iterates, same line-search
     decisions, same telemetry as the C oracle's solve."""
@@ -103,7 +117,7 @@ def test_full_solve_of_the_second_restatement_bit_identical_to_the_c_oracle(name
     assert info_o[2] >= 3 and bits_differ(un, uo) == 0 and bits_differ(info_n, info_o) == 0
 
 
-@pytest.mark.parametrize("name", ["iris", "hexa_slew_constr", "single_particle", "state_constr"])
+@pytest.mark.parametrize("name", CASES)
 def test_adjoint_against_reverse_mode_autodiff(name):
     """The hand-derived vector-Jacobian product of the oracle (SPEC.md §5.4-§5.5) against torch.autograd on a float64 writing of the model
     that shares no code with it: float64 oracle build to 1e-6 (its tables — discount powers, sigma sqrt(dt) — are computed in float64, here
@@ -142,8 +156,8 @@ def test_second_model_of_the_matrix_instruction_reproduces_the_hardware(dtn):
     assert not bad, bad[:5]
 
 
-@pytest.mark.parametrize("mlp", ["f32x3", "f16"])
-def test_matrix_pipe_modes_bit_identical_to_the_c_oracle(mlp):
+@pytest.mark.parametrize("mlp,vehicle", [("f32x3", "iris"), ("f16", "iris"), ("f32x3", "asymmetric"), ("f16", "asymmetric")], ids=["f32x3", "f16", "f32x3-asymmetric", "f16-asymmetric"])
+def test_matrix_pipe_modes_bit_identical_to_the_c_oracle(mlp, vehicle):
     """Rollout, gradient and a short full solve of a tiny problem (2 particles, 3 steps) in the two matrix-pipe modes: the second restatement
     (limb split / fp16 rounding in NumPy, the instruction in Python integers) equals the C oracle bit for bit."""
     cfg = MPCConfig(horizon=3, num_short_dt=2, long_step_dt=0.1, num_particles=2, u_slew_coeff=1.0, max_iter=2, max_no_improvement_iter=2, mlp_dtype=mlp)
@@ -152,6 +166,8 @@ def test_matrix_pipe_modes_bit_identical_to_the_c_oracle(mlp):
     xref = W.reference_window(0.1, cfg.time_steps)
     noise = W.make_noise(1, 2, 3, 2)[0]
     u = np.clip(0.71 + 0.1 * np.random.default_rng(1).standard_normal((3, 4)), 1e-4, 1).astype(np.float32)
+    if vehicle == "asymmetric":
+        cfg, model, x0, xref, noise, u = _asymmetric(4, horizon=3, num_short_dt=2, long_step_dt=0.1, num_particles=2, max_iter=2, max_no_improvement_iter=2, mlp_dtype=mlp)
     O, N = orc.Oracle(cfg, model), R2.Restatement(cfg, model)
     c_o, traj_o, mean_o = O.rollout(x0, u, xref, noise, want_traj=True, want_mean=True)
     c_n, traj_n, mean_n = N.rollout(x0, u, xref, noise)
@@ -186,8 +202,9 @@ def test_second_model_of_the_transcendental_instructions_equals_the_c_model(func
     assert bits_differ(got, want) == 0
 
 
-@pytest.mark.parametrize("mlp", ["f32", "f32x3", "f16"])
-def test_fast_math_mode_bit_identical_to_the_c_oracle(mlp):
+@pytest.mark.parametrize("mlp,vehicle", [(d, v) for v in ("iris", "asymmetric") for d in ("f32", "f32x3", "f16")],
+                         ids=["f32", "f32x3", "f16", "f32-asymmetric", "f32x3-asymmetric", "f16-asymmetric"])
+def test_fast_math_mode_bit_identical_to_the_c_oracle(mlp, vehicle):
     """math_mode fast written a second time (SPEC.md §10b: the weight sets built in NumPy float32, the activation kept as r, the three instructions
     through the NumPy statement of §10a): rollout, gradient and a short full solve equal the C oracle bit for bit, in every contraction arithmetic."""
     big = mlp == "f32"
@@ -199,6 +216,9 @@ def test_fast_math_mode_bit_identical_to_the_c_oracle(mlp):
     xref = W.reference_window(0.1, cfg.time_steps)
     noise = W.make_noise(1, P, H, 2)[0]
     u = np.clip(0.71 + 0.1 * np.random.default_rng(1).standard_normal((H, 4)), 1e-4, 1).astype(np.float32)
+    if vehicle == "asymmetric":     # (b3, b3n != 0: the folded biases of SPEC.md §10b start from them)
+        cfg, model, x0, xref, noise, u = _asymmetric(4, horizon=H, num_short_dt=2, long_step_dt=0.1, num_particles=P, max_iter=3 if big else 2, max_no_improvement_iter=3,
+                                                     mlp_dtype=mlp, math_mode="fast")
     O, N = orc.Oracle(cfg, model), R2.Restatement(cfg, model, hw=_hw())
     c_o, traj_o, mean_o = O.rollout(x0, u, xref, noise, want_traj=True, want_mean=True)
     c_n, traj_n, mean_n = N.rollout(x0, u, xref, noise)
