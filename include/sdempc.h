@@ -168,6 +168,26 @@ int sdempc_device_ready(const sdempc_handle* h);
  *   SDEMPC_OPT_TEST_ABSENT_WG -1 none / >= 0 workgroup index -1       (none)               FAULT INJECTION for the tests of the bounded waits: that workgroup of a
  *                                                                                          cooperative-layout grid leaves at once, as a workgroup that never became
  *                                                                                          resident would; the launch then gives up within its spin budget
+ *   SDEMPC_OPT_TEST_WS_FILL   -1 none / 0..255 byte value    -1       (none)               POISON for the tests of handle state: every float-valued device buffer the handle
+ *                                                                                          allocates from then on (set it before the first device call to reach all of them)
+ *                                                                                          is filled with that byte right after its hipMalloc, complete before the call goes
+ *                                                                                          on to its launches; 255 makes every word a NaN pattern. Results do not change:
+ *                                                                                          no kernel may read a word of these buffers that the same call has not written.
+ *                                                                                          Filled: the workspaces (particle x horizon tensor, activation checkpoint,
+ *                                                                                          partial sums, control table), the cooperative layouts' per-particle outputs and
+ *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs,
+ *                                                                                          the closed loop's key / chunk / plant buffers. (The particle x horizon tensor is
+ *                                                                                          zeroed at allocation otherwise; nothing depends on that.) Keep their initial value:
+ *                                                                                          - the work counters and the ticket word: running totals, zero at creation by
+ *                                                                                            definition (sdempc_work_counters, sdempc_solve_status compare against them);
+ *                                                                                          - the grid-barrier words of the cooperative layouts: arrival counters and the
+ *                                                                                            give-up flag, integers zeroed on the stream ahead of every launch — a poisoned
+ *                                                                                            flag could not be told from a barrier that gave up;
+ *                                                                                          - the tags of the tagged hand-off words inside the per-particle outputs: the
+ *                                                                                            buffer is filled at allocation, but its per-launch clear (by the host for the
+ *                                                                                            speculative layout, by the kernel's first workgroup for the plain cooperative
+ *                                                                                            one) stays, and comes after the fill: a tag is a flag, not data;
+ *                                                                                          - tables and key buffers copied whole from the host before their first use.
  *   SDEMPC_OPT_DEVICE_CUS     read-only                                                    compute units of the handle's device (after the first device call)
  */
 #define SDEMPC_OPT_LANE 1
@@ -182,6 +202,7 @@ int sdempc_device_ready(const sdempc_handle* h);
 #define SDEMPC_OPT_DUO 10
 #define SDEMPC_OPT_HEX 11
 #define SDEMPC_OPT_TEST_ABSENT_WG 12
+#define SDEMPC_OPT_TEST_WS_FILL 13
 int sdempc_set_option(sdempc_handle* h, int32_t key, int32_t value);
 int sdempc_get_option(const sdempc_handle* h, int32_t key, int32_t* value);
 

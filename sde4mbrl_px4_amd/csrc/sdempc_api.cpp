@@ -190,6 +190,7 @@ struct sdempc_handle {
     int last_coop_B = 0;      // > 0: the last solve launch took the cooperative path with this many instances (error flags to check)
     bool coop_off = false;    // a grid barrier timed out once: this handle stays on the one-workgroup-per-instance layouts
     int layout_fallbacks = 0; // how often that happened (sdempc_layout_fallbacks)
+    int ws_fill = -1;         // SDEMPC_OPT_TEST_WS_FILL: 0..255 = byte every float-valued device buffer is filled with right after its hipMalloc (dev_alloc); -1: none
 };
 
 namespace {
@@ -273,10 +274,22 @@ unsigned coop_spin_ticks(const sdempc_handle* h) {
     return (unsigned)(ms * 1e5f);
 }
 
-int dev_alloc(sdempc_handle* h, DevBuf& b, size_t bytes) {
+// Work the host put on the null stream (hipMemset) is over before anything is enqueued behind it on another stream: the handle's own stream and
+// the streams callers pass are non-blocking, i.e. not ordered against the null stream by the runtime.
+int null_stream_done(sdempc_handle* h) {
+    HIPCHK(h, hipStreamSynchronize(nullptr));
+    return 0;
+}
+// fill: a float-valued buffer whose initial contents nothing may depend on — SDEMPC_OPT_TEST_WS_FILL writes its byte over it, complete before
+// the caller goes on to its launch path (include/sdempc.h lists the buffers that are exempt, and why)
+int dev_alloc(sdempc_handle* h, DevBuf& b, size_t bytes, bool fill = false) {
     if (bytes == 0) bytes = 16;
     HIPCHK(h, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
+    if (fill && h->ws_fill >= 0) {
+        HIPCHK(h, hipMemset(b.p, h->ws_fill, bytes));
+        return null_stream_done(h);
+    }
     return 0;
 }
 void dev_free(DevBuf& b) {
@@ -327,18 +340,19 @@ int ensure_device_impl(sdempc_handle* h) {
         h->base.C.sc_n = h->cfg.num_state_constr;
         h->base.C.sc_tab = (const CostK::StateBound*)h->d_sctab.p;
     }
-    if ((rc = dev_alloc(h, h->d_x0, sizeof(float) * B * SDEMPC_NX))) return rc;
-    if ((rc = dev_alloc(h, h->d_u, sizeof(float) * B * H * m))) return rc;
-    if ((rc = dev_alloc(h, h->d_xref, sizeof(float) * B * (H + 1) * SDEMPC_NX))) return rc;
-    if ((rc = dev_alloc(h, h->d_noise, sizeof(float) * noise_floats(h, B)))) return rc;
-    if ((rc = dev_alloc(h, h->d_step, sizeof(float) * B))) return rc;
-    if ((rc = dev_alloc(h, h->d_cost, sizeof(float) * B))) return rc;
-    if ((rc = dev_alloc(h, h->d_grad, sizeof(float) * B * H * m))) return rc;
-    if ((rc = dev_alloc(h, h->d_xmean, sizeof(float) * B * (H + 1) * SDEMPC_NX))) return rc;
-    if ((rc = dev_alloc(h, h->d_uopt, sizeof(float) * B * H * m))) return rc;
-    if ((rc = dev_alloc(h, h->d_info, sizeof(float) * B * 8))) return rc;
+    if ((rc = dev_alloc(h, h->d_x0, sizeof(float) * B * SDEMPC_NX, true))) return rc;
+    if ((rc = dev_alloc(h, h->d_u, sizeof(float) * B * H * m, true))) return rc;
+    if ((rc = dev_alloc(h, h->d_xref, sizeof(float) * B * (H + 1) * SDEMPC_NX, true))) return rc;
+    if ((rc = dev_alloc(h, h->d_noise, sizeof(float) * noise_floats(h, B), true))) return rc;
+    if ((rc = dev_alloc(h, h->d_step, sizeof(float) * B, true))) return rc;
+    if ((rc = dev_alloc(h, h->d_cost, sizeof(float) * B, true))) return rc;
+    if ((rc = dev_alloc(h, h->d_grad, sizeof(float) * B * H * m, true))) return rc;
+    if ((rc = dev_alloc(h, h->d_xmean, sizeof(float) * B * (H + 1) * SDEMPC_NX, true))) return rc;
+    if ((rc = dev_alloc(h, h->d_uopt, sizeof(float) * B * H * m, true))) return rc;
+    if ((rc = dev_alloc(h, h->d_info, sizeof(float) * B * 8, true))) return rc;
     if ((rc = dev_alloc(h, h->d_work, sizeof(unsigned long long) * 5))) return rc;      // 4 counters + the persistent launches' instance ticket
     HIPCHK(h, hipMemset(h->d_work.p, 0, h->d_work.bytes));
+    if ((rc = null_stream_done(h))) return rc;
     h->base.work = (unsigned long long*)h->d_work.p;
     h->base.ticket_host = &h->ticket_total;
     h->ticket_total = 0;                                   // matches the zeroed ticket word
@@ -363,11 +377,17 @@ int ensure_workspace(sdempc_handle* h, int rows) {
     h->base.traj = h->base.act = h->base.part = h->base.ustg = nullptr;
     const int H = h->H;
     int rc;
-    if ((rc = dev_alloc(h, h->d_traj, sizeof(float) * traj_floats(h, rows)))) return rc;
-    HIPCHK(h, hipMemset(h->d_traj.p, 0, h->d_traj.bytes));
-    if ((rc = dev_alloc(h, h->d_act, sizeof(float) * (size_t)rows * h->G * H * ACT_STRIDE))) return rc;
-    if ((rc = dev_alloc(h, h->d_part, sizeof(float) * (size_t)rows * h->G * part_stride(H)))) return rc;
-    if ((rc = dev_alloc(h, h->d_ustg, sizeof(float) * (size_t)rows * H * 36))) return rc;
+    if ((rc = dev_alloc(h, h->d_traj, sizeof(float) * traj_floats(h, rows), true))) return rc;
+    // Zeroed since the first version, as hygiene: no kernel reads a word of it that the same launch has not written (every lane of a group row is
+    // stored before the adjoint sweep loads it; sdempc_traj_to_canonical_dev is refused unless a store_traj rollout filled the rows, and skips the
+    // padded particles) — so SDEMPC_OPT_TEST_WS_FILL fills it like the others.
+    if (h->ws_fill < 0) {
+        HIPCHK(h, hipMemset(h->d_traj.p, 0, h->d_traj.bytes));
+        if ((rc = null_stream_done(h))) return rc;
+    }
+    if ((rc = dev_alloc(h, h->d_act, sizeof(float) * (size_t)rows * h->G * H * ACT_STRIDE, true))) return rc;
+    if ((rc = dev_alloc(h, h->d_part, sizeof(float) * (size_t)rows * h->G * part_stride(H), true))) return rc;
+    if ((rc = dev_alloc(h, h->d_ustg, sizeof(float) * (size_t)rows * H * 36, true))) return rc;
     h->base.traj = (float*)h->d_traj.p;
     h->base.act = (float*)h->d_act.p;
     h->base.part = (float*)h->d_part.p;
@@ -409,7 +429,7 @@ void noise_to_dev_layout(const sdempc_handle* h, int B, const float* in, float* 
 int stage_common(sdempc_handle* h, int B, const float* x0, const float* u, const float* xref, const float* noise) {
     const int H = h->H, m = h->m;
     int rc;
-    if (!h->d_noise_canon.p && (rc = dev_alloc(h, h->d_noise_canon, sizeof(float) * (size_t)h->max_batch * h->P * H * SDEMPC_NNOISE))) return rc;
+    if (!h->d_noise_canon.p && (rc = dev_alloc(h, h->d_noise_canon, sizeof(float) * (size_t)h->max_batch * h->P * H * SDEMPC_NNOISE, true))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_x0.p, x0, sizeof(float) * B * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_u.p, u, sizeof(float) * B * H * m, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_xref.p, xref, sizeof(float) * B * (H + 1) * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
@@ -638,6 +658,10 @@ int sdempc_set_option(sdempc_handle* h, int32_t key, int32_t value) {
             if (value < -1) return fail(h, SDEMPC_EINVAL, "absent workgroup must be -1 (none) or a workgroup index%s");
             o.absent_wg = value;
             return SDEMPC_OK;
+        case SDEMPC_OPT_TEST_WS_FILL:
+            if (value < -1 || value > 255) return fail(h, SDEMPC_EINVAL, "workspace fill must be -1 (none) or a byte value 0..255%s");
+            h->ws_fill = value;
+            return SDEMPC_OK;
         case SDEMPC_OPT_COOP_SPIN_US:
             if (value < -1) return fail(h, SDEMPC_EINVAL, "spin budget must be -1 (derived) or >= 0 microseconds%s");
             h->spin_us = value;
@@ -662,6 +686,7 @@ int sdempc_get_option(const sdempc_handle* h, int32_t key, int32_t* value) {
         case SDEMPC_OPT_COOP_FENCE: *value = o.coop_fence; break;
         case SDEMPC_OPT_HEX: *value = o.hex; break;
         case SDEMPC_OPT_TEST_ABSENT_WG: *value = o.absent_wg; break;
+        case SDEMPC_OPT_TEST_WS_FILL: *value = h->ws_fill; break;
         case SDEMPC_OPT_COOP_SPIN_US: *value = h->spin_us >= 0 ? h->spin_us : (int32_t)(coop_spin_ticks(h) / 100u); break;
         case SDEMPC_OPT_DEVICE_CUS: *value = o.cus; break;
         default: return SDEMPC_EINVAL;
@@ -784,8 +809,8 @@ int sdempc_solve_batch_dev(sdempc_handle* h, int32_t B, const void* x0_dev, cons
         if (!h->d_coop_bar.p) {
             const int cap = cmax < h->max_batch ? cmax : h->max_batch;
             if ((rc = dev_alloc(h, h->d_coop_bar, sizeof(unsigned) * COOP_BAR_WORDS * (size_t)cap))) return rc;
-            if ((rc = dev_alloc(h, h->d_coop_pp, sizeof(float) * coop_pp_floats(h->H, h->G) * cap))) return rc;
-            if ((rc = dev_alloc(h, h->d_coop_ck, sizeof(float) * coop_ck_floats(h->H, h->P) * cap))) return rc;
+            if ((rc = dev_alloc(h, h->d_coop_pp, sizeof(float) * coop_pp_floats(h->H, h->G) * cap, true))) return rc;
+            if ((rc = dev_alloc(h, h->d_coop_ck, sizeof(float) * coop_ck_floats(h->H, h->P) * cap, true))) return rc;
             h->coop_cap = cap;
         }
         if (B <= h->coop_cap) {
@@ -828,7 +853,7 @@ int sdempc_noise_from_keys(sdempc_handle* h, int32_t B, const uint32_t* keys, fl
     if (!keys || !noise) return fail(h, SDEMPC_EINVAL, "NULL pointer%s");
     if ((rc = ensure_device(h))) return rc;
     const size_t nf = (size_t)h->P * h->H * SDEMPC_NNOISE;
-    if (!h->d_noise_canon.p && (rc = dev_alloc(h, h->d_noise_canon, sizeof(float) * (size_t)h->max_batch * nf))) return rc;
+    if (!h->d_noise_canon.p && (rc = dev_alloc(h, h->d_noise_canon, sizeof(float) * (size_t)h->max_batch * nf, true))) return rc;
     if ((rc = noise_from_keys(h, B, keys, (float*)h->d_noise.p, h->stream))) return rc;
     HIPCHK(h, launch_relayout(false, (const float*)h->d_noise.p, (float*)h->d_noise_canon.p, B, h->P, h->G, h->H * SDEMPC_NNOISE, h->stream));
     HIPCHK(h, hipMemcpyAsync(noise, h->d_noise_canon.p, sizeof(float) * B * nf, hipMemcpyDeviceToHost, h->stream));
@@ -879,7 +904,7 @@ int sdempc_rollout_batch(sdempc_handle* h, int32_t B, const float* x0, const flo
     if (xmean) HIPCHK(h, hipMemcpyAsync(xmean, h->d_xmean.p, sizeof(float) * B * (H + 1) * SDEMPC_NX, hipMemcpyDeviceToHost, h->stream));
     if (traj) {
         const size_t nf = (size_t)P * (H + 1) * SDEMPC_NX;
-        if (!h->d_traj_canon.p && (rc = dev_alloc(h, h->d_traj_canon, sizeof(float) * h->max_batch * nf))) return rc;
+        if (!h->d_traj_canon.p && (rc = dev_alloc(h, h->d_traj_canon, sizeof(float) * h->max_batch * nf, true))) return rc;
         if ((rc = sdempc_traj_to_canonical_dev(h, B, h->d_traj_canon.p, h->stream))) return rc;
         HIPCHK(h, hipMemcpyAsync(traj, h->d_traj_canon.p, sizeof(float) * B * nf, hipMemcpyDeviceToHost, h->stream));
     }
@@ -1001,7 +1026,10 @@ int sdempc_work_counters(sdempc_handle* h, uint64_t out[4], int32_t reset) {
     unsigned long long v[4];
     HIPCHK(h, hipMemcpy(v, h->d_work.p, sizeof v, hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; ++i) out[i] = v[i];
-    if (reset) HIPCHK(h, hipMemset(h->d_work.p, 0, sizeof v));
+    if (reset) {
+        HIPCHK(h, hipMemset(h->d_work.p, 0, sizeof v));
+        return null_stream_done(h);     // (the next solve may be enqueued on a non-blocking stream)
+    }
     return SDEMPC_OK;
     });
 }
@@ -1075,7 +1103,7 @@ int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const
     if (h->d_plant.bytes < total) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         dev_free(h->d_plant);
-        if ((rc = dev_alloc(h, h->d_plant, total))) return rc;
+        if ((rc = dev_alloc(h, h->d_plant, total, true))) return rc;      // (tables and indices are copied in below, on the stream, before anything reads them)
     }
     char* d = (char*)h->d_plant.p;
     HIPCHK(h, hipMemcpyAsync(d, stg.data(), o_xi, hipMemcpyHostToDevice, h->stream));
@@ -1112,11 +1140,11 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, b
     const int Tc = (int)(fit < 1 ? 1 : (fit < (size_t)T ? fit : (size_t)T));
     const size_t chunk_floats = (size_t)Tc * per_tick + fixed;
     int rc;
-    if (!h->d_loop.p && (rc = dev_alloc(h, h->d_loop, sizeof(uint32_t) * (size_t)h->max_batch * 10 + 16))) return rc;
+    if (!h->d_loop.p && (rc = dev_alloc(h, h->d_loop, sizeof(uint32_t) * (size_t)h->max_batch * 10 + 16, true))) return rc;
     if (h->d_loop_chunk.bytes < sizeof(float) * chunk_floats) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         dev_free(h->d_loop_chunk);
-        if ((rc = dev_alloc(h, h->d_loop_chunk, sizeof(float) * chunk_floats))) return rc;
+        if ((rc = dev_alloc(h, h->d_loop_chunk, sizeof(float) * chunk_floats, true))) return rc;
     }
     uint32_t* d_keys = (uint32_t*)h->d_loop.p;                      // r_k, advanced in place
     uint32_t* d_sub = d_keys + 2 * (size_t)h->max_batch;             // the solve's noise keys of the tick

@@ -326,3 +326,28 @@ def test_state_constr_section_parses_in_penalty_form(tmp_path):
     from sde4mbrl_px4_amd.solver import SdeMpcSolver
     S = SdeMpcSolver(c, synthetic_iris(), max_batch=1)
     S.close()
+
+
+def test_test_ws_fill_option_round_trip():
+    """SDEMPC_OPT_TEST_WS_FILL (key 13): -1 by default and with no environment default, any byte value, validated; host-only."""
+    from sde4mbrl_px4_amd.solver import SdeMpcSolver, SdempcError
+    hdr = open(os.path.join(ROOT, "include", "sdempc.h")).read()
+    assert int(re.search(r"#define SDEMPC_OPT_TEST_WS_FILL (\d+)", hdr).group(1)) == _abi.OPTIONS["test_ws_fill"] == 13
+    assert {int(v) for v in re.findall(r"#define SDEMPC_OPT_[A-Z_]+ (\d+)", hdr)} == set(_abi.OPTIONS.values())
+    os.environ["SDEMPC_TEST_WS_FILL"] = "255"
+    try:
+        S = SdeMpcSolver(load_mpc_config(os.path.join(CDIR, "c1_iris_posctrl_h20_p32.yaml")), synthetic_iris(), max_batch=2)
+    finally:
+        os.environ.pop("SDEMPC_TEST_WS_FILL", None)
+    assert S.get_option("test_ws_fill") == -1
+    for v in (0, 255, 0x7F, -1):
+        S.set_option("test_ws_fill", v)
+        assert S.get_option("test_ws_fill") == v
+    for bad in (256, -2):
+        with pytest.raises(SdempcError, match="fill"):
+            S.set_option("test_ws_fill", bad)
+    assert S.get_option("test_ws_fill") == -1 and not S.device_ready()
+    S.close()
+    S = SdeMpcSolver(load_mpc_config(os.path.join(CDIR, "c1_iris_posctrl_h20_p32.yaml")), synthetic_iris(), max_batch=2, options={"test_ws_fill": 255})
+    assert S.get_option("test_ws_fill") == 255
+    S.close()
