@@ -334,6 +334,41 @@ int sdempc_closed_loop_batch_plant(sdempc_handle* h, const sdempc_plant_cfg* pc,
                                    float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
                                    uint32_t* keys_next /*[B][2] or NULL*/);
 
+/* ---- batched closed loop at the node's timing (SPEC.md §11b) ------------------------------------
+ * sdempc_closed_loop_batch_plant with a controller that is as late as the reference node's: its MPC worker solves asynchronously, one solve at a time
+ * (sde_control.py:365-450), and the state callback keeps flying the latest finished solution, indexed by the time since the state it was computed from
+ * (sde_control.py:283-306). Three parameters, uniform over the batch: a solve every `solve_period` = S control ticks (Ns = ceil(T / S) solves), whose
+ * solution arrives `solve_delay` = D plant substeps after the state it was computed from (0 <= D <= S * substeps: one solve at a time), and a first-order
+ * motor lag `lag_alpha` (0: off). Period j covers ticks k = j S + i, i = 0 .. min(S, T - j S) - 1; episode b carries (x, r, y, s, a), a the motor state [m]:
+ *   i = 0:  (r', sub) = split(r); solve j on x with noise normal(sub, (P, H, 6)), warm start y, step size s, reference xref[j or 0][b or 0]; (r, p) = split(r');
+ *   i > 0:  (r, p) = split(r);                                           (no solve)
+ *   Xi = normal(p, (substeps, 6)), one draw as in sdempc_closed_loop_batch_plant; for substep jj, q = i * substeps + jj:
+ *     c = (q >= D ? uopt_j : y)[min(i, H-1)];  a_l = fma(alpha, c_l - a_l, a_l) if alpha > 0, else a = c exactly;  x = step_plant(x, a, Xi[jj]);
+ *   xs[b][k+1] = x after the tick's last substep; us[b][k] = the a that substep 0 of tick k applied;
+ *   after the period's last tick: y = rows uopt_j[min(t + S, H-1)], s = info_j.stepsize.
+ * Until the first solution arrives the vehicle flies the initial warm start (u_init; NULL: uref, the hover command). A plant set is always given (the
+ * handle's own blob for the controller's model). u_act_in [B][m] is the initial motor state (NULL: u_init[b][0]). info is [B][Ns]; xref is
+ * [xref_solves][xref_batch][H+1][13] with xref_solves 1 or Ns. To continue: u_next, stepsize_next, keys_next and u_act_next [B][m] (each may be NULL); the
+ * continuation is bit-exact when T is a multiple of S. S = 1, D = 0, alpha = 0 is sdempc_closed_loop_batch_plant bit for bit. One kernel launch advances
+ * the plant by a whole period. Every argument is checked before the first HIP call: SDEMPC_EINVAL for struct_size, S < 1, D outside [0, S * substeps],
+ * alpha negative, above 1 or not finite, xref_solves not 1 or Ns, and for everything sdempc_closed_loop_batch_plant refuses. Outputs, chunking (by
+ * whole periods) and the re-run are those of sdempc_closed_loop_batch. No ABI version change: detect the entry point by its symbol. */
+typedef struct sdempc_timing_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_timing_cfg) */
+    int32_t solve_period;  /* S: control ticks per solve, >= 1 */
+    int32_t solve_delay;   /* D: plant substeps until a solution is applied, 0 .. S * substeps */
+    float lag_alpha;       /* motor lag per plant substep: 0 off, else 0 < alpha <= 1 */
+} sdempc_timing_cfg;
+int sdempc_closed_loop_batch_timed(sdempc_handle* h, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                   const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                   const int32_t* plant_of /*[B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                   const float* xref, int32_t xref_solves, int32_t xref_batch,
+                                   const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                   const float* u_act_in /*[B][m] or NULL*/,
+                                   float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][Ns]*/,
+                                   float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                   uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/);
+
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so
  * repeating the call runs in the one-workgroup-per-instance layout. Also SDEMPC_EDEVICE when a large throughput launch that hands its

@@ -62,6 +62,11 @@ class SdempcPlantCfg(C.Structure):
                 ("mlp_dtype", C.c_int32), ("math_mode", C.c_int32)]
 
 
+class SdempcTimingCfg(C.Structure):
+    """sdempc_timing_cfg (SPEC.md §11b): solve period, solve delay and motor lag of sdempc_closed_loop_batch_timed."""
+    _fields_ = [("struct_size", C.c_int32), ("solve_period", C.c_int32), ("solve_delay", C.c_int32), ("lag_alpha", C.c_float)]
+
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -134,6 +139,7 @@ def load_library():
     lib.sdempc_closed_loop_batch.argtypes = [vp, i32, i32, fp, fp, i32, i32, u32p, fp, fp, fp, fp, C.POINTER(SdempcInfo), fp, fp, u32p]
     lib.sdempc_closed_loop_batch_plant.argtypes = [vp, C.POINTER(SdempcPlantCfg), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i32)] + \
         lib.sdempc_closed_loop_batch.argtypes[1:]
+    # (sdempc_closed_loop_batch_timed is not part of ABI version 3's first builds: timed_entry() resolves it by symbol on first use)
     lib.sdempc_solve_status.argtypes = [vp]
     lib.sdempc_solve_status.restype = C.c_int
     lib.sdempc_layout_fallbacks.argtypes = [vp]
@@ -154,11 +160,26 @@ def load_library():
     return lib
 
 
+def timed_entry(lib):
+    """sdempc_closed_loop_batch_timed (SPEC.md §11b) with its prototype set. The ABI version did not change with it, so a library built from an
+    older tree of the same version may lack it: detected here, by symbol, and only when a call needs it."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_timed
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_timed (SPEC.md §11b): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(lib.sdempc_closed_loop_batch_plant.argtypes)        # h, plant cfg, blobs, sizes, plant_of, B, T, x0, xref, n, n, keys, u_init, stepsize_in, xs, us, info, 3 x next
+        fp = C.POINTER(C.c_float)
+        fn.argtypes = [a[0], C.POINTER(SdempcTimingCfg)] + a[1:14] + [fp] + a[14:] + [fp]
+        fn.restype = C.c_int
+    return fn
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
     "sdempc_traj_dev_floats", "sdempc_noise_to_device_layout", "sdempc_solve_batch_dev", "sdempc_rollout_batch_dev",
     "sdempc_grad_batch_dev", "sdempc_last_kernel_ms", "sdempc_last_kernel_name", "sdempc_work_counters", "sdempc_solve_status", "sdempc_layout_fallbacks", "sdempc_noise_to_device_layout_dev", "sdempc_traj_to_canonical_dev",
     "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
-    "sdempc_closed_loop_batch_plant",
+    "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed",
 ]

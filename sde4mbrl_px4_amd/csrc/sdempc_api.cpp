@@ -515,10 +515,19 @@ struct PlantRun {
     LoopPlant Q;
     float* xi;      // [B][substeps][6] plant noise of a tick
 };
-int check_loop_args(sdempc_handle* h, const LoopIo& io);
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant);
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, bool* again);
-int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out);
+// SPEC.md §11b: the timing of one sdempc_closed_loop_batch_timed call. With it LoopIo::xref_ticks counts SOLVES (1 or Ns) and LoopIo::info is [B][Ns].
+struct TimedRun {
+    int S, D;                   // solve period in ticks, solve delay in plant substeps
+    float alpha;                // motor lag (0: off)
+    const float* u_act_in;      // [B][m] or null (u_init[b][0])
+    float* u_act_next;          // [B][m] or null
+};
+inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
+int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves);
+int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B);
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed = nullptr);
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, bool* again);
+int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
 extern "C" {
@@ -964,7 +973,7 @@ int sdempc_closed_loop_batch(sdempc_handle* h, int32_t B, int32_t T, const float
                              float* u_next, float* stepsize_next, uint32_t* keys_next) {
     return guarded(h, [&]() -> int {
     const LoopIo io{B, T, xref_ticks, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
-    int rc = check_loop_args(h, io);
+    int rc = check_loop_args(h, io, T);
     if (rc) return rc;
     if ((rc = ensure_device(h))) return rc;
     return closed_loop_attempts(h, io, nullptr);       // no plant set: the handle's own model, one step of time_steps[0] per tick (SPEC.md §11)
@@ -977,29 +986,38 @@ int sdempc_closed_loop_batch_plant(sdempc_handle* h, const sdempc_plant_cfg* pc,
                                    sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next) {
     return guarded(h, [&]() -> int {
     const LoopIo io{B, T, xref_ticks, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
-    int rc = check_loop_args(h, io);
+    int rc = check_loop_args(h, io, T);
     if (rc) return rc;
-    // every check of the plant set happens here, before the first HIP call
-    if (!pc || pc->struct_size != (int32_t)sizeof(sdempc_plant_cfg)) return fail(h, SDEMPC_EINVAL, "plant: cfg NULL or struct_size mismatch%s");
-    if (pc->num_plants < 1 || pc->num_plants > B) return fail(h, SDEMPC_EINVAL, "plant: num_plants must be between 1 and B%s");
-    if (pc->substeps < 1 || pc->substeps > SDEMPC_PLANT_MAX_SUBSTEPS) return fail(h, SDEMPC_EINVAL, "plant: substeps must be between 1 and SDEMPC_PLANT_MAX_SUBSTEPS (64)%s");
-    if (!(pc->dt >= 0.0f) || !(pc->dt < INFINITY)) return fail(h, SDEMPC_EINVAL, "plant: dt must be finite and >= 0 (0: time_steps[0] / substeps)%s");
-    if (pc->mlp_dtype < -1 || pc->mlp_dtype > 2) return fail(h, SDEMPC_EINVAL, "plant: mlp_dtype must be -1 (the handle's), 0 (f32), 1 (f16) or 2 (f32x3)%s");
-    if (pc->math_mode < -1 || pc->math_mode > 1) return fail(h, SDEMPC_EINVAL, "plant: math_mode must be -1 (the handle's), 0 (exact) or 1 (fast)%s");
-    if (!plant_blobs || !plant_blob_bytes) return fail(h, SDEMPC_EINVAL, "plant: NULL blob table%s");
-    const int Np = pc->num_plants;
-    if (!plant_of && Np != 1 && Np != B) return fail(h, SDEMPC_EINVAL, "plant: plant_of may be NULL only when num_plants is 1 or B%s");
-    if (plant_of)
-        for (int b = 0; b < B; ++b)
-            if (plant_of[b] < 0 || plant_of[b] >= Np) return fail(h, SDEMPC_EINVAL, "plant: plant_of holds an index outside [0, num_plants)%s");
-    for (int p = 0; p < Np; ++p) {
-        if ((rc = check_blob(h, plant_blobs[p], plant_blob_bytes[p]))) return rc;
-        if (((const int32_t*)plant_blobs[p])[2] != h->m) return fail(h, SDEMPC_EINVAL, "plant: num_motors of a plant blob differs from the handle's%s");
-    }
+    if ((rc = check_plant_args(h, pc, plant_blobs, plant_blob_bytes, plant_of, B))) return rc;      // (before the first HIP call)
     if ((rc = ensure_device(h))) return rc;
     PlantRun run;
     if ((rc = stage_plants(h, *pc, plant_blobs, plant_of, B, &run))) return rc;
     return closed_loop_attempts(h, io, &run);
+    });
+}
+
+int sdempc_closed_loop_batch_timed(sdempc_handle* h, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc, const void* const* plant_blobs,
+                                   const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T, const float* x0, const float* xref,
+                                   int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in,
+                                   const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next, float* stepsize_next,
+                                   uint32_t* keys_next, float* u_act_next) {
+    return guarded(h, [&]() -> int {
+    if (!h) return SDEMPC_EINVAL;
+    // every check happens here, before the first HIP call
+    if (!tc || tc->struct_size != (int32_t)sizeof(sdempc_timing_cfg)) return fail(h, SDEMPC_EINVAL, "timing: cfg NULL or struct_size mismatch%s");
+    if (tc->solve_period < 1) return fail(h, SDEMPC_EINVAL, "timing: solve_period must be >= 1%s");
+    if (!(tc->lag_alpha >= 0.0f) || !(tc->lag_alpha <= 1.0f)) return fail(h, SDEMPC_EINVAL, "timing: lag_alpha must be 0 (off) or in (0, 1]%s");
+    const LoopIo io{B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    int rc = check_loop_args(h, io, T >= 1 ? loop_solves(T, tc->solve_period) : 1);
+    if (rc) return rc;
+    if ((rc = check_plant_args(h, pc, plant_blobs, plant_blob_bytes, plant_of, B))) return rc;
+    if (tc->solve_delay < 0 || (long long)tc->solve_delay > (long long)tc->solve_period * pc->substeps)
+        return fail(h, SDEMPC_EINVAL, "timing: solve_delay must be between 0 and solve_period * substeps (one solve at a time)%s");
+    if ((rc = ensure_device(h))) return rc;
+    const TimedRun timed{tc->solve_period, tc->solve_delay, tc->lag_alpha, u_act_in, u_act_next};
+    PlantRun run;
+    if ((rc = stage_plants(h, *pc, plant_blobs, plant_of, B, &run, tc->solve_period < T ? tc->solve_period : T))) return rc;
+    return closed_loop_attempts(h, io, &run, &timed);
     });
 }
 
@@ -1056,20 +1074,42 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
     }
 }
 // argument checks shared by the two closed-loop entry points; no HIP call
-int check_loop_args(sdempc_handle* h, const LoopIo& io) {
+int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves) {
     int rc = check_batch(h, io.B);
     if (rc) return rc;
     if (io.T < 1) return fail(h, SDEMPC_EINVAL, "closed loop: T must be >= 1%s");
-    if (io.xref_ticks != 1 && io.xref_ticks != io.T) return fail(h, SDEMPC_EINVAL, "closed loop: xref_ticks must be 1 or T%s");
+    if (io.xref_ticks != 1 && io.xref_ticks != solves)
+        return fail(h, SDEMPC_EINVAL, solves == io.T ? "closed loop: xref_ticks must be 1 or T%s" : "closed loop: xref_solves must be 1 or ceil(T / solve_period)%s");
     if (io.xref_batch != 1 && io.xref_batch != io.B) return fail(h, SDEMPC_EINVAL, "closed loop: xref_batch must be 1 or B%s");
     if (!io.x0 || !io.xref || !io.keys || !io.xs || !io.us || !io.info) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
     return 0;
 }
+// every check of a plant set (SPEC.md §11a), shared by the two entry points that take one; no HIP call
+int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B) {
+    int rc;
+    if (!pc || pc->struct_size != (int32_t)sizeof(sdempc_plant_cfg)) return fail(h, SDEMPC_EINVAL, "plant: cfg NULL or struct_size mismatch%s");
+    if (pc->num_plants < 1 || pc->num_plants > B) return fail(h, SDEMPC_EINVAL, "plant: num_plants must be between 1 and B%s");
+    if (pc->substeps < 1 || pc->substeps > SDEMPC_PLANT_MAX_SUBSTEPS) return fail(h, SDEMPC_EINVAL, "plant: substeps must be between 1 and SDEMPC_PLANT_MAX_SUBSTEPS (64)%s");
+    if (!(pc->dt >= 0.0f) || !(pc->dt < INFINITY)) return fail(h, SDEMPC_EINVAL, "plant: dt must be finite and >= 0 (0: time_steps[0] / substeps)%s");
+    if (pc->mlp_dtype < -1 || pc->mlp_dtype > 2) return fail(h, SDEMPC_EINVAL, "plant: mlp_dtype must be -1 (the handle's), 0 (f32), 1 (f16) or 2 (f32x3)%s");
+    if (pc->math_mode < -1 || pc->math_mode > 1) return fail(h, SDEMPC_EINVAL, "plant: math_mode must be -1 (the handle's), 0 (exact) or 1 (fast)%s");
+    if (!plant_blobs || !plant_blob_bytes) return fail(h, SDEMPC_EINVAL, "plant: NULL blob table%s");
+    const int Np = pc->num_plants;
+    if (!plant_of && Np != 1 && Np != B) return fail(h, SDEMPC_EINVAL, "plant: plant_of may be NULL only when num_plants is 1 or B%s");
+    if (plant_of)
+        for (int b = 0; b < B; ++b)
+            if (plant_of[b] < 0 || plant_of[b] >= Np) return fail(h, SDEMPC_EINVAL, "plant: plant_of holds an index outside [0, num_plants)%s");
+    for (int p = 0; p < Np; ++p) {
+        if ((rc = check_blob(h, plant_blobs[p], plant_blob_bytes[p]))) return rc;
+        if (((const int32_t*)plant_blobs[p])[2] != h->m) return fail(h, SDEMPC_EINVAL, "plant: num_motors of a plant blob differs from the handle's%s");
+    }
+    return 0;
+}
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant) {
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, &again);
+        int rc = closed_loop_run(h, io, plant, timed, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -1077,8 +1117,8 @@ int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* pla
 }
 // SPEC.md §11a. Prepares every plant blob for the plant's arithmetic and step length exactly as sdempc_create prepares the handle's (prepare_model) and
 // stages the set on the device ONCE per call, in one allocation and one copy on the handle's stream: [ModelK x Np][payload x Np][sigma sqrt(dt) x Np][dt]
-// [plant_of x B], then room for the plant noise of a tick. The arguments were checked by the caller.
-int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out) {
+// [plant_of x B], then room for the plant noise of a tick (of xi_ticks ticks: a solve period of SPEC.md §11b). The arguments were checked by the caller.
+int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks) {
     const int Np = pc.num_plants, n = pc.substeps;
     const int dtype = pc.mlp_dtype < 0 ? h->cfg.mlp_dtype : pc.mlp_dtype, mode = pc.math_mode < 0 ? h->cfg.math_mode : pc.math_mode;
     const float dt = pc.dt == 0.0f ? h->time_steps[0] / (float)n : pc.dt;
@@ -1086,7 +1126,7 @@ int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_model = 0, o_wts = up16(sizeof(ModelK) * Np), o_sdt = o_wts + up16(sizeof(float) * stride * Np);
     const size_t o_dt = o_sdt + up16(sizeof(float) * SDEMPC_NNOISE * Np), o_of = o_dt + 16, o_xi = o_of + up16(sizeof(int32_t) * (plant_of ? B : 0));
-    const size_t total = o_xi + sizeof(float) * (size_t)B * n * SDEMPC_NNOISE;
+    const size_t total = o_xi + sizeof(float) * (size_t)B * n * SDEMPC_NNOISE * (size_t)xi_ticks;      // (§11b: the noise of a whole solve period)
     std::vector<char>& stg = h->plant_stage;
     stg.assign(o_xi, 0);
     PreparedModel pm;
@@ -1129,18 +1169,23 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // the chunk's outputs back and checks, once per chunk, whether a grid barrier of a cooperative-layout solve gave up or the ticket count of the
 // persistent launches is off: *again = true then, and the caller runs the whole batch once more from the host inputs (the handle has left
 // the cooperative layouts; results are the same in every layout).
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, bool* again) {
+// SPEC.md §11b (timed): the unit of work is a solve PERIOD of S ticks — one key schedule, one solve and one plant launch per period, chunks of whole
+// periods, info and moving references per solve. Without `timed` a period is one tick and every launch is the one it was (S = 1 below).
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
-    const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)NX + m + 8;       // floats per reference window / per episode-tick of output
+    const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
+    const int Ns = loop_solves(T, S);
+    const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m) + 8;       // floats per reference window / per episode-period of output
     const bool xref_moves = io.xref_ticks > 1;
-    const size_t per_tick = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0);
+    const size_t per_period = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0);
     const size_t fixed = xref_moves ? 0 : (size_t)Bx * XR, cap = LOOP_CHUNK_BYTES / sizeof(float);
-    const size_t fit = cap > fixed ? (cap - fixed) / per_tick : 0;
-    const int Tc = (int)(fit < 1 ? 1 : (fit < (size_t)T ? fit : (size_t)T));
-    const size_t chunk_floats = (size_t)Tc * per_tick + fixed;
+    const size_t fit = cap > fixed ? (cap - fixed) / per_period : 0;
+    const int Pc = (int)(fit < 1 ? 1 : (fit < (size_t)Ns ? fit : (size_t)Ns));      // periods per chunk
+    const size_t Tc = (size_t)Pc * S;                                               // tick rows per chunk
+    const size_t chunk_floats = (size_t)Pc * per_period + fixed;
     int rc;
-    if (!h->d_loop.p && (rc = dev_alloc(h, h->d_loop, sizeof(uint32_t) * (size_t)h->max_batch * 10 + 16, true))) return rc;
+    if (!h->d_loop.p && (rc = dev_alloc(h, h->d_loop, sizeof(uint32_t) * (size_t)h->max_batch * (10 + SDEMPC_MAX_MOTORS) + 16, true))) return rc;
     if (h->d_loop_chunk.bytes < sizeof(float) * chunk_floats) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         dev_free(h->d_loop_chunk);
@@ -1150,15 +1195,16 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, b
     uint32_t* d_sub = d_keys + 2 * (size_t)h->max_batch;             // the solve's noise keys of the tick
     float* d_xi6 = (float*)(d_sub + 2 * (size_t)h->max_batch);       // plant noise of the tick (SPEC.md §11: six values per episode)
     unsigned* d_gave_up = (unsigned*)(d_xi6 + 6 * (size_t)h->max_batch);
+    float* d_mot = (float*)(d_gave_up + 4);                          // motor state a [B][m] (SPEC.md §11b)
     float* d_xi = plant ? plant->xi : d_xi6;                         // (SPEC.md §11a: 6 * substeps values per episode, beside the staged plants)
     float* c_xs = (float*)h->d_loop_chunk.p;                         // [Tc][B][13]
-    float* c_us = c_xs + (size_t)Tc * B * NX;                        // [Tc][B][m]
-    float* c_info = c_us + (size_t)Tc * B * m;                       // [Tc][B][8]
-    float* c_xref = c_info + (size_t)Tc * B * 8;                     // [Tc or 1][Bx][H+1][13]
+    float* c_us = c_xs + Tc * B * NX;                                // [Tc][B][m]
+    float* c_info = c_us + Tc * B * m;                               // [Pc][B][8]
+    float* c_xref = c_info + (size_t)Pc * B * 8;                     // [Pc or 1][Bx][H+1][13]
     float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place
     hipStream_t st = h->stream;
     // inputs (host vectors live until the synchronisation at the end of the first chunk)
-    std::vector<float> u0, s0;
+    std::vector<float> u0, s0, a0;
     const float* u_in = io.u_init;
     const float* s_in = io.stepsize_in;
     if (!u_in) {               // sdempc_reset: uref tiled
@@ -1175,46 +1221,66 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, b
     HIPCHK(h, hipMemcpyAsync(h->d_u.p, u_in, sizeof(float) * (size_t)B * H * m, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(h->d_step.p, s_in, sizeof(float) * B, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemsetAsync(d_gave_up, 0, sizeof(unsigned), st));
+    if (timed) {               // the motor state starts as u_act_in, or as the first row of the warm start
+        const float* a_in = timed->u_act_in;
+        if (!a_in) {
+            a0.resize((size_t)B * m);
+            for (int b = 0; b < B; ++b) memcpy(&a0[(size_t)b * m], u_in + (size_t)b * H * m, sizeof(float) * m);
+            a_in = a0.data();
+        }
+        HIPCHK(h, hipMemcpyAsync(d_mot, a_in, sizeof(float) * (size_t)B * m, hipMemcpyHostToDevice, st));
+    }
     if (!xref_moves) {
         HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
         if (Bx != B) HIPCHK(h, launch_broadcast_rows(c_xref, (float*)h->d_xref.p, (int)XR, B, st));
     }
     for (int b = 0; b < B; ++b) memcpy(io.xs + (size_t)b * (T + 1) * NX, io.x0 + (size_t)b * NX, sizeof(float) * NX);
     std::vector<float> hx, hu, hi;
-    for (int k0 = 0; k0 < T; k0 += Tc) {
-        const int nk = T - k0 < Tc ? T - k0 : Tc;
-        if (xref_moves) HIPCHK(h, hipMemcpyAsync(c_xref, io.xref + (size_t)k0 * Bx * XR, sizeof(float) * nk * Bx * XR, hipMemcpyHostToDevice, st));
-        for (int kc = 0; kc < nk; ++kc) {
-            if (plant) HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st, plant->Q.substeps));
+    for (int j0 = 0; j0 < Ns; j0 += Pc) {
+        const int np = Ns - j0 < Pc ? Ns - j0 : Pc;                                  // periods of this chunk
+        const size_t k0 = (size_t)j0 * S;
+        const int nk = (int)((size_t)T - k0 < (size_t)np * S ? (size_t)T - k0 : (size_t)np * S);      // ticks of this chunk
+        if (xref_moves) HIPCHK(h, hipMemcpyAsync(c_xref, io.xref + (size_t)j0 * Bx * XR, sizeof(float) * np * Bx * XR, hipMemcpyHostToDevice, st));
+        for (int jc = 0; jc < np; ++jc) {
+            const int ticks = nk - jc * S < S ? nk - jc * S : S;                    // (the last period of the run may be partial)
+            if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st));
+            else if (plant) HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st, plant->Q.substeps));
             else HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st));
             HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));
-            const float* win = c_xref + (xref_moves ? (size_t)kc * Bx * XR : 0);
+            const float* win = c_xref + (xref_moves ? (size_t)jc * Bx * XR : 0);
             const float* xr = win;
             if (Bx != B) {
                 if (xref_moves) HIPCHK(h, launch_broadcast_rows(win, (float*)h->d_xref.p, (int)XR, B, st));
                 xr = (const float*)h->d_xref.p;
             }
-            float* info_k = c_info + (size_t)kc * B * 8;
-            if ((rc = sdempc_solve_batch_dev(h, B, d_x, xr, h->d_noise.p, h->d_u.p, h->d_step.p, h->d_uopt.p, h->d_xmean.p, info_k, st))) return rc;
+            float* info_j = c_info + (size_t)jc * B * 8;
+            if ((rc = sdempc_solve_batch_dev(h, B, d_x, xr, h->d_noise.p, h->d_u.p, h->d_step.p, h->d_uopt.p, h->d_xmean.p, info_j, st))) return rc;
             LoopAdvance L;
-            L.uopt = (const float*)h->d_uopt.p; L.info = info_k; L.xi = d_xi;
+            L.uopt = (const float*)h->d_uopt.p; L.info = info_j; L.xi = d_xi;
             L.coop_bar = h->last_coop_B > 0 ? (const unsigned*)h->d_coop_bar.p : nullptr;
             L.x = d_x; L.u = (float*)h->d_u.p; L.step = (float*)h->d_step.p;
-            L.xs = c_xs + (size_t)kc * B * NX; L.us = c_us + (size_t)kc * B * m; L.gave_up = d_gave_up;
+            L.xs = c_xs + (size_t)jc * S * B * NX; L.us = c_us + (size_t)jc * S * B * m; L.gave_up = d_gave_up;
             L.B = B; L.H = H;
-            if (plant) HIPCHK(h, launch_loop_plant(plant->k, L, plant->Q, st));
+            if (timed) {
+                LoopPeriod R;
+                R.act = d_mot; R.alpha = timed->alpha; R.ticks = ticks; R.xi_ticks = S; R.shift = timed->S < H ? timed->S : H;
+                const long long never = (long long)ticks * plant->Q.substeps;       // (a solution that arrives at the period's end is flown by the next period, as its tail)
+                R.arrive = (int)(timed->D < never ? timed->D : never);
+                HIPCHK(h, launch_loop_period(plant->k, L, plant->Q, R, st));
+            } else if (plant) HIPCHK(h, launch_loop_plant(plant->k, L, plant->Q, st));
             else HIPCHK(h, launch_loop_advance(h->base, L, st));
         }
-        hx.resize((size_t)nk * B * NX); hu.resize((size_t)nk * B * m); hi.resize((size_t)nk * B * 8);
+        hx.resize((size_t)nk * B * NX); hu.resize((size_t)nk * B * m); hi.resize((size_t)np * B * 8);
         unsigned gave_up = 0;
         HIPCHK(h, hipMemcpyAsync(hx.data(), c_xs, sizeof(float) * hx.size(), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipMemcpyAsync(hu.data(), c_us, sizeof(float) * hu.size(), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipMemcpyAsync(hi.data(), c_info, sizeof(float) * hi.size(), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipMemcpyAsync(&gave_up, d_gave_up, sizeof gave_up, hipMemcpyDeviceToHost, st));
-        if (k0 + nk == T) {
+        if (j0 + np == Ns) {
             if (io.u_next) HIPCHK(h, hipMemcpyAsync(io.u_next, h->d_u.p, sizeof(float) * (size_t)B * H * m, hipMemcpyDeviceToHost, st));
             if (io.stepsize_next) HIPCHK(h, hipMemcpyAsync(io.stepsize_next, h->d_step.p, sizeof(float) * B, hipMemcpyDeviceToHost, st));
             if (io.keys_next) HIPCHK(h, hipMemcpyAsync(io.keys_next, d_keys, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
+            if (timed && timed->u_act_next) HIPCHK(h, hipMemcpyAsync(timed->u_act_next, d_mot, sizeof(float) * (size_t)B * m, hipMemcpyDeviceToHost, st));
         }
         HIPCHK(h, hipStreamSynchronize(st));
         if (gave_up) {             // the workgroups of a cooperative layout were not all resident: no second try on this handle
@@ -1227,11 +1293,13 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, b
         if (tickets_consistent(h) != 0) { *again = true; return 0; }     // (the mirror is re-synchronised)
         for (int kc = 0; kc < nk; ++kc)
             for (int b = 0; b < B; ++b) {
-                const size_t r = (size_t)kc * B + b, k = (size_t)k0 + kc;
+                const size_t r = (size_t)kc * B + b, k = k0 + kc;
                 memcpy(io.xs + ((size_t)b * (T + 1) + k + 1) * NX, &hx[r * NX], sizeof(float) * NX);
                 memcpy(io.us + ((size_t)b * T + k) * m, &hu[r * m], sizeof(float) * m);
-                memcpy((float*)io.info + ((size_t)b * T + k) * 8, &hi[r * 8], sizeof(float) * 8);
             }
+        for (int jc = 0; jc < np; ++jc)
+            for (int b = 0; b < B; ++b)
+                memcpy((float*)io.info + ((size_t)b * Ns + j0 + jc) * 8, &hi[((size_t)jc * B + b) * 8], sizeof(float) * 8);
     }
     return 0;
 }

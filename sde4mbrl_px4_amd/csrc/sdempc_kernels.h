@@ -164,9 +164,25 @@ struct LoopPlant {
 };
 // `a`: the handle's argument block with the PLANT's arithmetic (f16, fast), dt -> one float (the plant's step length) and, for one shared plant, its M / wts / sdt
 hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st);
+// SPEC.md §11b, the closed loop at the node's timing: ONE launch advances a whole solve period — `ticks` control ticks of Q.substeps plant steps each —
+// flying the previous solution's tail (LoopAdvance::u, the warm start y_j) until plant substep `arrive` of the period and this period's solution
+// (LoopAdvance::uopt) from then on, through a first-order motor lag. Here LoopAdvance::xi is [B][xi_ticks][substeps][6], xs / us are [ticks][B][13] / [ticks][B][m]
+// (tick rows B episodes apart) and LoopAdvance::u is read for the commands, then rewritten shifted by `shift` rows.
+struct LoopPeriod {
+    float* act;                 // [B][m] motor state a: in, and out after the period's last substep
+    float alpha;                // motor lag: 0 off (a = c exactly), else a <- fma(alpha, c - a, a) before every substep
+    int ticks;                  // control ticks of this period: min(S, T - j S), >= 1
+    int xi_ticks;               // tick rows per episode in LoopAdvance::xi (>= ticks)
+    int shift;                  // rows the warm start moves up: min(S, H) (row t <- uopt[min(t + shift, H - 1)])
+    int arrive;                 // substep index inside the period at which the command source switches from y_j to uopt_j; >= ticks * substeps: never
+};
+hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st);
 // the tick's key schedule (sdempc_prng.hip): keys r_k -> r_{k+1} in place, the solve's noise keys into sub_dev u32[B][2], the plant noise into
 // xi_dev f32[B][substeps][6]: ONE draw normal(p, 6 * substeps) per episode (SPEC.md §7.1: counter i pairs with i + 3 * substeps), row j for substep j
 hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st, int substeps = 1);
+// SPEC.md §11b: the key schedule of one solve period — tick 0 is the schedule above, every later tick advances the key by ONE split (no solve, no solve
+// key) and draws its plant noise the same way. xi_dev f32[B][xi_ticks][substeps][6], rows 0 .. ticks-1 written.
+hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st);
 // rows_dev[b][0..n) = row_dev[0..n) for b < B
 hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st);
 // canonical [B][P][C] <-> device [B][G][C][32] (to_dev: zero-pads particles >= P)

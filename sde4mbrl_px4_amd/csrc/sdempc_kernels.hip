@@ -46,7 +46,7 @@
 // unit; the solve kernel has ~90 instantiations of ~25k instructions each): SDEMPC_TU = 0 — every kernel except the duo solve
 // kernels, and all launchers; 1 — the duo solve kernels of the two-wave teams (TeamPair, TeamBlock2); 2 — those of the four-wave
 // team (TeamBlock); 3 — those of the six-team workgroup (TeamHex). Units 1 to 3 hold nothing but explicit instantiations (list macros below), unit 0 declares them `extern template`.
-// 4 — the plant steps of the batched closed loop and their launchers (sdempc_loop.inc.h, SPEC.md §11, §11a).
+// 4 — the plant steps of the batched closed loop and their launchers (sdempc_loop.inc.h, SPEC.md §11, §11a, §11b).
 #ifndef SDEMPC_TU
 #define SDEMPC_TU 0
 #endif
@@ -1426,6 +1426,7 @@ hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int 
 namespace exact {
 hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
 hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st);
+hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st);
 }
 namespace fastm {
 hipError_t launch_rollout(const KArgs& a, int B, hipStream_t st);
@@ -1436,6 +1437,7 @@ hipError_t launch_solve_coop(const KArgs& a, int B, hipStream_t st);
 hipError_t launch_solve_spec(const KArgs& a, int B, hipStream_t st);
 hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
 hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st);
+hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st);
 }
 static thread_local const void* g_last_kernel_fn = nullptr;
 void note_kernel(const void* host_fn) { g_last_kernel_fn = host_fn; }
@@ -1458,6 +1460,9 @@ hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t
 }
 hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st) {      // (a.fast: the PLANT's math mode)
     return a.fast ? fastm::launch_loop_plant(a, L, Q, st) : exact::launch_loop_plant(a, L, Q, st);
+}
+hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st) {      // (a.fast: the PLANT's math mode)
+    return a.fast ? fastm::launch_loop_period(a, L, Q, R, st) : exact::launch_loop_period(a, L, Q, R, st);
 }
 hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int P, int G, int C, hipStream_t st) {
     return exact::launch_relayout(to_dev, in, out, B, P, G, C, st);

@@ -1,5 +1,5 @@
 // sdempc_loop.inc.h — the plant of the batched closed loop (SPEC.md §11): one Euler–Maruyama step of the handle's own model per episode and
-// tick, plus the hand-over to the next tick's solve (applied control, shifted warm start, step size).
+// tick, plus the hand-over to the next tick's solve (applied control, shifted warm start, step size); §11a: a separate plant; §11b: a whole solve period.
 // Fragment of sdempc_kernels.hip, translation unit SDEMPC_TU = 4: included inside namespace sdempc::{exact|fastm} (compiled once per math mode).
 //
 // The step is the rollout's own device code: step_fwd at t = 0 on a control table built by block_prepass, i.e. the arithmetic of step 0
@@ -119,6 +119,105 @@ hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPla
             if (e != hipSuccess) return e;
         }
         sdempc_loop_plant_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q);
+        return hipGetLastError();
+    });
+}
+
+// SPEC.md §11b: a whole solve period behind the same plant set — R.ticks control ticks of Q.substeps Euler–Maruyama steps each in ONE launch, so that a loop
+// whose ticks are millisecond-scale solves does not pay a launch per plant step. The prologue is the kernel's above (shared or per-episode LDS carves, the
+// wave's argument block in LDS for the per-episode prepass). Substep q = i * substeps + jj of the period flies row min(i, H - 1) of the previous solution's
+// tail (L.u: the warm start y_j) while q < R.arrive and of this period's solution (L.uopt) from then on; the arrival point is the same for every episode,
+// so the choice is wave-uniform. Lane l < m carries motor l's state: a_l <- fma(alpha, c_l - a_l, a_l) before every substep, or a_l = c_l with the lag off.
+// The applied control row lives in the team's sm.v[5] (an optimiser vector the step does not use) and block_prepass reruns whenever it can have changed:
+// every substep with the lag on, at tick starts and at the arrival substep otherwise (rerunning it on an unchanged row writes the same table).
+// Every read of the warm start precedes its rewrite: the commands are read inside the substep loop, the shifted rows are written after it, by the same wave.
+template <int F16>
+__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_period_kernel(KArgs a0, LoopAdvance L, LoopPlant Q, LoopPeriod R) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    KArgs a = a0;
+    const int H = L.H, m = a.m;
+    const int tid = TeamWave::tid();
+    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
+    const bool per = Q.models != nullptr, live = b < L.B;      // (both wave-uniform)
+    if (per && live) {
+        const int p = __builtin_amdgcn_readfirstlane(Q.plant_of ? Q.plant_of[b] : b);
+        a.M = Q.models[p];
+        a.wts = Q.wts + (size_t)p * Q.wts_stride;
+        a.sdt = Q.sdt + (size_t)p * NN;
+    }
+    Smem sm = per ? carve(smem + (size_t)TeamWave::team() * smem_floats(1, m, 1), 1, m, 0) : carve(smem, 1, m, TeamWave::team());
+    WaveW ww;
+    load_weights(a, sm, ww, per ? tid : (int)threadIdx.x, per ? TeamWave::NT : TeamWave::BNT);
+    KArgs* const lk = reinterpret_cast<KArgs*>(smem + TeamWave::IPB * smem_floats(1, m, 1) + (size_t)TeamWave::team() * plant_kargs_floats());
+    if (per && tid == 0) { lk->H = 1; lk->m = m; lk->M = a.M; }        // (what block_prepass reads)
+    __syncthreads();
+    if (!live) return;              // (wave-uniform; no workgroup-wide barrier below)
+    const int lane = tid & 63, h = lane >> 5, n = Q.substeps;
+    const bool lag = R.alpha > 0.0f, mine = lane < m;
+    const float* uo = L.uopt + (size_t)b * H * m;
+    float* yw = L.u + (size_t)b * H * m;
+    float* act = sm.v[5];           // [m] the applied control of the current substep
+    float am = mine ? R.act[(size_t)b * m + lane] : 0.0f;
+    float x[NX], xn[NX], xi[NN];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
+    const float* xrow = L.xi + (size_t)b * R.xi_ticks * n * NN;
+#pragma nounroll
+    for (int i = 0; i < R.ticks; ++i) {
+        const int row = (i < H - 1 ? i : H - 1) * m;
+#pragma nounroll
+        for (int jj = 0; jj < n; ++jj) {
+            const int q = i * n + jj;
+            if (lag || jj == 0 || q == R.arrive) {
+                if (mine) {
+                    const float c = (q >= R.arrive ? uo : yw)[row + lane];
+                    am = lag ? FMA(R.alpha, c - am, am) : c;
+                    act[lane] = am;
+                }
+                TeamWave::sync();       // (the row is written, the previous substep's reads of the control table are done)
+                if (per) block_prepass<TeamWave>(*lk, sm, act, tid);
+                else block_prepass<TeamWave>(a0, sm, act, tid);
+                TeamWave::sync();
+            }
+            if (jj == 0 && mine) L.us[((size_t)i * L.B + b) * m + lane] = am;
+#pragma unroll
+            for (int e = 0; e < NN; ++e) xi[e] = xrow[q * NN + e];
+            StepAux A;
+            step_fwd<F16, false>(a, sm, ww, 0, h, lane, x, xi, xn, A);
+#pragma unroll
+            for (int e = 0; e < NX; ++e) x[e] = xn[e];
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int e = 0; e < NX; ++e) L.xs[((size_t)i * L.B + b) * NX + e] = x[e];
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) L.x[(size_t)b * NX + i] = x[i];
+        L.step[b] = L.info[(size_t)b * 8 + 1];
+        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
+    }
+    if (mine) R.act[(size_t)b * m + lane] = am;
+    for (int e = tid; e < H * m; e += TeamWave::NT) {   // y_{j+1}: row t = uopt_j[min(t + S, H - 1)]
+        const int t = e / m, ts = t + R.shift < H ? t + R.shift : H - 1;
+        yw[e] = uo[ts * m + (e - t * m)];
+    }
+}
+
+hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st) {
+    if (L.B < 1 || L.H != a.H || Q.substeps < 1 || (Q.models && (!Q.wts || !Q.sdt || Q.wts_stride < BLOB_FLOATS + VJP_BASE))) return hipErrorInvalidValue;
+    if (!R.act || R.ticks < 1 || R.xi_ticks < R.ticks || R.shift < 1 || R.shift > a.H || R.arrive < 0 || !(R.alpha >= 0.0f && R.alpha <= 1.0f)) return hipErrorInvalidValue;
+    KArgs k = a;
+    k.H = 1;
+    const size_t sb = Q.models ? TeamWave::IPB * (smem_bytes(1, k.m, 1) + sizeof(float) * plant_kargs_floats()) : smem_bytes(1, k.m, TeamWave::IPB);
+    const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
+    return with_f16(k.f16, [&](auto F16) {
+        if (sb > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)sdempc_loop_period_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
+            if (e != hipSuccess) return e;
+        }
+        sdempc_loop_period_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q, R);
         return hipGetLastError();
     });
 }

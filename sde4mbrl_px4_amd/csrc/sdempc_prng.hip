@@ -199,6 +199,40 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
     return hipGetLastError();
 }
 
+// SPEC.md §11b: the schedule of one solve period of `ticks` control ticks. Tick 0 is the tick of the kernels above ((r', s) = split(r), (r, p) = split(r'));
+// every later tick has no solve: (r, p) = split(r). Each tick draws normal(p, (n, 6)) as above. xi: [B][xi_ticks][n][6], rows 0 .. ticks-1 written.
+__global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int ticks,
+                                                                      int xi_ticks, int n) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    uint32_t r[2] = {keys[2 * b], keys[2 * b + 1]};
+    const uint32_t half = 3u * (uint32_t)n;
+    for (int i = 0; i < ticks; ++i) {
+        uint32_t r2[2], p[2];
+        if (i == 0) {
+            uint32_t r1[2], s[2];
+            split2(r[0], r[1], r1, s);
+            sub[2 * b] = s[0]; sub[2 * b + 1] = s[1];
+            split2(r1[0], r1[1], r2, p);
+        } else split2(r[0], r[1], r2, p);
+        r[0] = r2[0]; r[1] = r2[1];
+        float* row = xi + ((size_t)b * xi_ticks + i) * 2u * half;
+        for (uint32_t e = 0; e < half; ++e) {
+            uint32_t x0 = e, x1 = e + half;
+            threefry2x32(p[0], p[1], x0, x1);
+            row[e] = bits_to_normal(x0);
+            row[half + e] = bits_to_normal(x1);
+        }
+    }
+    keys[2 * b] = r[0]; keys[2 * b + 1] = r[1];
+}
+
+hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st) {
+    if (B < 1 || substeps < 1 || ticks < 1 || xi_ticks < ticks) return hipErrorInvalidValue;
+    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps);
+    return hipGetLastError();
+}
+
 // rows[b] = row for b < B (one reference window shared by every episode of a closed-loop batch), n floats per row
 __global__ void __launch_bounds__(256) sdempc_broadcast_rows_kernel(const float* __restrict__ row, float* __restrict__ rows, int n, long long total) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;

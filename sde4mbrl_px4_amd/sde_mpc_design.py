@@ -138,7 +138,7 @@ class MpcProblem:
 
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
-                 plant_mlp_dtype=None, plant_math_mode=None):
+                 plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -146,7 +146,10 @@ class MpcProblem:
         (default: the initial state). opt_state None starts from m_reset. Returns (xs f32[T+1][13] with xs[0] = x, us f32[T][m],
         info f32[T][8], the OptState after the last tick, the key after the last tick).
         plant / plant_*: fly another vehicle than the controller's model (a RotorSDEModel or a blob), stepped plant_substeps times per tick —
-        the arguments of SdeMpcSolver.closed_loop (SPEC.md §11a), passed through for this one episode."""
+        the arguments of SdeMpcSolver.closed_loop (SPEC.md §11a), passed through for this one episode.
+        solve_period / solve_delay / motor_lag: the controller at the node's timing (SPEC.md §11b) — a solve every solve_period ticks, applied
+        solve_delay plant substeps late, through a first-order motor lag. Solve j then tracks self.xref(curr_t + j * solve_period * dt_0, xdes), info is
+        f32[Ns][8] with Ns = ceil(T / solve_period), and the motor state starts at the warm start's first row."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -155,7 +158,8 @@ class MpcProblem:
         xdes = xs0 if xdes is None else np.asarray(xdes, np.float32).reshape(13)
         if self.state_from_traj is not None:
             dt0 = float(self.cfg.time_steps[0])
-            xref = np.stack([self.xref(float(curr_t) + k * dt0, xdes) for k in range(T)])[:, None]
+            S = int(solve_period)
+            xref = np.stack([self.xref(float(curr_t) + j * S * dt0, xdes) for j in range(-(-T // max(S, 1)))])[:, None]
         else:
             xref = self.xref(float(curr_t), xdes)[None, None]
         rng = np.asarray(rng, dtype=np.uint32).reshape(1, 2)
@@ -165,7 +169,7 @@ class MpcProblem:
             s0 = np.array([opt_state.stepsize], np.float32)
         xs, us, info, u_next, s_next, k_next = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
-            plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode)
+            plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag)[:6]
         xs = xs[0]
         if self.convert_to_enu:
             xs = np.concatenate([x[None], enu2ned(xs[1:], np)], axis=0)

@@ -164,7 +164,7 @@ class SdeMpcSolver:
         return uopt, xevol, np.frombuffer(info, dtype=np.float32).reshape(B, 8).copy()
 
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
-                    plant_mlp_dtype=None, plant_math_mode=None):
+                    plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -176,7 +176,15 @@ class SdeMpcSolver:
         (optional when Np is 1 or B: all 0 / identity). plant_substeps Euler–Maruyama steps per tick with the applied control held;
         plant_dt their length (None: float32(time_steps[0]) / float32(plant_substeps)); plant_mlp_dtype / plant_math_mode the arithmetic
         of the plant step (None: the handle's) — pin them to compare two controller arithmetics on one and the same vehicle. With
-        plant=None every plant_* argument must keep its default and the call is sdempc_closed_loop_batch, unchanged."""
+        plant=None every plant_* argument must keep its default and the call is sdempc_closed_loop_batch, unchanged.
+
+        solve_period / solve_delay / motor_lag / u_act_in (SPEC.md §11b, sdempc_closed_loop_batch_timed): the controller at the node's timing — a solve
+        every solve_period ticks, whose solution is applied solve_delay plant substeps after the state it was computed from (0 .. solve_period *
+        plant_substeps; until then the vehicle flies the previous solution's tail, row by row), and a first-order motor lag a <- a + motor_lag (c - a)
+        per plant substep (0: off) from the motor state u_act_in [B][m] (None: u_init[:, 0]). With all four at their defaults the call is exactly the
+        one above. Otherwise xref is f32[Tx][Bx][H+1][13] with Tx in {1, Ns}, Ns = ceil(T / solve_period) (one window per SOLVE), info is [B][Ns][8], the
+        plant defaults to the handle's own model, and a 7-tuple comes back: the six above and u_act_next [B][m]. Carrying (xs[:, -1], u_next,
+        stepsize_next, keys_next, u_act_next) into the next call continues the episodes bit for bit when T is a multiple of solve_period."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -187,7 +195,26 @@ class SdeMpcSolver:
         if xref.ndim != 4 or xref.shape[2:] != (self.H + 1, 13):
             raise ValueError(f"xref must be f32[Tx][Bx][{self.H + 1}][13] or f32[{self.H + 1}][13], got {xref.shape}")
         xref = np.ascontiguousarray(xref)
-        u_p = s_p = None
+        timed = not (solve_period == 1 and solve_delay == 0 and motor_lag == 0.0 and u_act_in is None)
+        Ns = T
+        if timed:
+            S_, D_, alpha = int(solve_period), int(solve_delay), float(np.float32(motor_lag))
+            if S_ < 1:
+                raise ValueError("closed_loop: solve_period must be >= 1")
+            if D_ < 0 or D_ > S_ * int(plant_substeps):
+                raise ValueError(f"closed_loop: solve_delay must be between 0 and solve_period * plant_substeps = {S_ * int(plant_substeps)} plant substeps "
+                                 "(the worker runs one solve at a time)")
+            if not (0.0 <= alpha <= 1.0):
+                raise ValueError("closed_loop: motor_lag must be 0 (off) or in (0, 1]")
+            Ns = -(-max(T, 0) // S_)
+            if plant is None:       # the entry point always takes a plant set: the handle's own model, prepared as sdempc_create prepared it
+                if plant_of is not None or plant_dt is not None or plant_mlp_dtype is not None or plant_math_mode is not None:
+                    raise ValueError("closed_loop: plant_of / plant_dt / plant_mlp_dtype / plant_math_mode need plant=...")
+                plant = self._blob.raw
+        u_p = s_p = a_p = None
+        if u_act_in is not None:
+            u_act_in = _f32(u_act_in, (B, self.m))
+            a_p = _fp(u_act_in)
         if u_init is not None:
             u_init = _f32(u_init, (B, self.H, self.m))
             u_p = _fp(u_init)
@@ -196,7 +223,7 @@ class SdeMpcSolver:
             s_p = _fp(stepsize_in)
         xs = np.zeros((B, max(T, 0) + 1, 13), np.float32)
         us = np.zeros((B, max(T, 0), self.m), np.float32)
-        info = np.zeros((B, max(T, 0), 8), np.float32)
+        info = np.zeros((B, max(Ns, 0), 8), np.float32)
         u_next = np.zeros((B, self.H, self.m), np.float32)
         s_next = np.zeros(B, np.float32)
         k_next = np.zeros((B, 2), np.uint32)
@@ -222,6 +249,12 @@ class SdeMpcSolver:
         pc = _abi.SdempcPlantCfg(C.sizeof(_abi.SdempcPlantCfg), Np, int(plant_substeps), 0.0 if plant_dt is None else float(np.float32(plant_dt)),
                                  -1 if plant_mlp_dtype is None else _abi_enum(MLP_DTYPES, plant_mlp_dtype, "plant_mlp_dtype"),
                                  -1 if plant_math_mode is None else _abi_enum(MATH_MODES, plant_math_mode, "plant_math_mode"))
+        if timed:
+            tc = _abi.SdempcTimingCfg(C.sizeof(_abi.SdempcTimingCfg), S_, D_, alpha)
+            a_next = np.zeros((B, self.m), np.float32)
+            self._check(_abi.timed_entry(self.lib)(self._h, C.byref(tc), C.byref(pc), C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *tail[:9], a_p,
+                                                    *tail[9:], _fp(a_next)))
+            return xs, us, info, u_next, s_next, k_next, a_next
         self._check(self.lib.sdempc_closed_loop_batch_plant(self._h, C.byref(pc), C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *tail))
         return xs, us, info, u_next, s_next, k_next
 

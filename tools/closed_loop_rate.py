@@ -10,7 +10,13 @@
      episode, or one per episode (domain randomisation); `own` (default) is the plain loop, the handle's model as the plant. The plants' blobs
      are made before the clock starts (RotorSDEModel.perturbed + to_blob is host work of the caller, not of the loop).
      --repeats R times the C2 loop R times on one handle (run-to-run spread of one session).
-usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|one|per-episode] [--substeps N] [--repeats R]
+  4. --small-batch B: ticks per second of a SMALL loop (C1, B episodes, --ticks ticks, one hold window), where a tick is a millisecond-scale solve and
+     the launches around it are a visible share — the size at which one plant launch per solve period (SPEC.md §11b) matters. --plant self is the
+     handle's own model through sdempc_closed_loop_batch_plant; --timed sends the call through sdempc_closed_loop_batch_timed even at --period 1
+     --delay 0 --lag 0 (the same arithmetic, one period kernel per tick); --period S --delay D --lag ALPHA set the timing. Nothing else runs in this mode.
+     With SDEMPC_LIB naming a library of the parent commit the default keywords measure that commit's entry points from the same process setup.
+usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
+                                        [--small-batch B [--timed] [--period S] [--delay D] [--lag ALPHA]]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -33,9 +39,14 @@ ap.add_argument("--c2-ticks", type=int, default=3)
 ap.add_argument("--skip-c2", action="store_true")
 ap.add_argument("--loop-only", action="store_true", help="B = 1 closed loops only (no Python-driven comparison): for a kernel trace")
 ap.add_argument("--skip-b1", action="store_true", help="skip the B = 1 part")
-ap.add_argument("--plant", choices=("own", "one", "per-episode"), default="own")
+ap.add_argument("--plant", choices=("own", "self", "one", "per-episode"), default="own")
 ap.add_argument("--substeps", type=int, default=1)
 ap.add_argument("--repeats", type=int, default=1)
+ap.add_argument("--small-batch", type=int, default=0, help="C1 with this many episodes: ticks/s of a loop whose ticks are millisecond-scale solves")
+ap.add_argument("--timed", action="store_true", help="--small-batch: go through sdempc_closed_loop_batch_timed whatever the timing")
+ap.add_argument("--period", type=int, default=1)
+ap.add_argument("--delay", type=int, default=0)
+ap.add_argument("--lag", type=float, default=0.0)
 a = ap.parse_args()
 model = synthetic_iris()
 if a.plant == "own" and a.substeps != 1:
@@ -46,6 +57,8 @@ def plant_kw(B):
     """keyword arguments of closed_loop / simulate for --plant: blobs of vehicles perturbed by +-20 % in mass, inertia, thrust curve and W2"""
     if a.plant == "own":
         return {}
+    if a.plant == "self":
+        return {"plant": model.to_blob(), "plant_substeps": a.substeps}
     rng = np.random.default_rng(1)
     n = 1 if a.plant == "one" else B
     blobs = [model.perturbed(rng, mass=0.2, inertia=0.2, thrust=0.2, residual=0.2).to_blob() for _ in range(n)]
@@ -53,6 +66,26 @@ def plant_kw(B):
 
 
 tag = "" if a.plant == "own" else f" plant={a.plant} substeps={a.substeps}"
+
+if a.small_batch:
+    cfg = load_mpc_config(os.path.join(ROOT, "configs", "c1_iris_posctrl_h20_p32.yaml"))
+    B, T = a.small_batch, a.ticks
+    x0 = W.random_initial_states(B, 3)
+    hold = W.constant_reference(W.HOVER, cfg.horizon)
+    keys = prng.split(prng.PRNGKey(10), B)
+    S = SdeMpcSolver(cfg, model, max_batch=B)
+    kw = plant_kw(B)
+    if a.timed or a.period != 1 or a.delay or a.lag:
+        kw.update(solve_period=a.period, solve_delay=a.delay, motor_lag=a.lag, u_act_in=np.tile(np.asarray(cfg.uref, np.float32)[: cfg.num_motors], (B, 1)))
+        tag += f" timed S={a.period} D={a.delay} alpha={a.lag}"
+    S.closed_loop(x0, hold, keys, 2 * a.period, **kw)       # warm-up: device buffers, workspaces
+    for rep in range(a.repeats):
+        t = time.perf_counter()
+        S.closed_loop(x0, hold, keys, T, **kw)
+        dt = time.perf_counter() - t
+        print(f"C1 B={B} T={T}{tag}: {T / dt:8.1f} ticks/s ({B * T / dt:9.1f} episode-ticks/s, {dt * 1e3 / T:.3f} ms/tick)", flush=True)
+    S.close()
+    sys.exit(0)
 
 for name in (() if a.skip_b1 else ("iris_traj_shipped_h20_p1", "c1_iris_posctrl_h20_p32")):
     cfg = load_mpc_config(os.path.join(ROOT, "configs", name + ".yaml"))
