@@ -176,7 +176,8 @@ int sdempc_device_ready(const sdempc_handle* h);
  *                                                                                          Filled: the workspaces (particle x horizon tensor, activation checkpoint,
  *                                                                                          partial sums, control table), the cooperative layouts' per-particle outputs and
  *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs,
- *                                                                                          the closed loop's key / chunk / plant buffers. (The particle x horizon tensor is
+ *                                                                                          the closed loop's key / chunk / plant buffers (the chunk buffer includes the
+ *                                                                                          staged disturbance rows and plant-schedule rows of a scenario). (The particle x horizon tensor is
  *                                                                                          zeroed at allocation otherwise; nothing depends on that.) Keep their initial value:
  *                                                                                          - the work counters and the ticket word: running totals, zero at creation by
  *                                                                                            definition (sdempc_work_counters, sdempc_solve_status compare against them);
@@ -188,6 +189,9 @@ int sdempc_device_ready(const sdempc_handle* h);
  *                                                                                            speculative layout, by the kernel's first workgroup for the plain cooperative
  *                                                                                            one) stays, and comes after the fill: a tag is a flag, not data;
  *                                                                                          - tables and key buffers copied whole from the host before their first use.
+ *   SDEMPC_OPT_TEST_LOOP_CHUNK_BYTES -1 built-in / >= 0 bytes  -1     (none)               TEST AID for the chunk boundaries of the closed loop: device bytes the per-tick buffers
+ *                                                                                          of one chunk may take (-1: the built-in 256 MiB). A chunk always holds at least one
+ *                                                                                          solve period, so 0 or 1 cuts a run into one chunk per period. Results do not change.
  *   SDEMPC_OPT_DEVICE_CUS     read-only                                                    compute units of the handle's device (after the first device call)
  */
 #define SDEMPC_OPT_LANE 1
@@ -203,6 +207,7 @@ int sdempc_device_ready(const sdempc_handle* h);
 #define SDEMPC_OPT_HEX 11
 #define SDEMPC_OPT_TEST_ABSENT_WG 12
 #define SDEMPC_OPT_TEST_WS_FILL 13
+#define SDEMPC_OPT_TEST_LOOP_CHUNK_BYTES 14
 int sdempc_set_option(sdempc_handle* h, int32_t key, int32_t value);
 int sdempc_get_option(const sdempc_handle* h, int32_t key, int32_t* value);
 
@@ -368,6 +373,42 @@ int sdempc_closed_loop_batch_timed(sdempc_handle* h, const sdempc_timing_cfg* ti
                                    float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][Ns]*/,
                                    float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
                                    uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/);
+
+/* ---- batched closed loop with a scenario (SPEC.md §11c) -----------------------------------------
+ * sdempc_closed_loop_batch_timed with two optional per-tick schedules: things that HAPPEN to a vehicle during an episode. With dist NULL and plant_ticks 1
+ * the call is sdempc_closed_loop_batch_timed bit for bit.
+ *   Disturbance: dist f32[dist_ticks][dist_batch][6], dist_ticks 1 or T (per control TICK, not per solve), dist_batch 1 or B, tick-major like xref; an index
+ *   into a size-1 axis is 0. Row (k, b) = (w_v[3], w_om[3]): an external linear acceleration in the solver's world frame and an external angular acceleration
+ *   in the body frame, held over every substep of tick k. After each x = step_plant(x, a, Xi[jj]) of tick k:
+ *     v_i = fma(w_v[i], dt_p, v_i) (x[3 + i]); om_i = fma(w_om[i], dt_p, om_i) (x[10 + i]), i = 0..2, dt_p the plant's float32 step length (what step_plant
+ *   uses). Position and attitude are untouched. The six fmas are applied whenever dist is given, zero rows included (a zero row changes nothing but a -0
+ *   component, which becomes +0). xs[b][k+1] is the state after the last substep's fmas.
+ *   Plant schedule: plant_of is int32[plant_ticks][B], plant_ticks 1 (the plant_of of sdempc_closed_loop_batch_plant) or T: tick k of episode b is stepped by
+ *   plant_blobs[plant_of[k or 0][b]]. A switch happens at a tick start (also in the middle of a solve period) and changes the vehicle only: physics prior, W1u
+ *   (the control table is re-formed from the new blob) and sigma sqrt(dt_p); x, the motor state, keys, warm start and the plant set's dt and arithmetic carry
+ *   over. With plant_ticks = T num_plants may be up to B * T (one episode that drops a payload needs two blobs) and plant_of must be given.
+ * Results depend only on the blobs an episode names, never on B, on the order or multiplicity of the set or on the layout of the solves; the key schedule
+ * depends on S and T only; continuation from (xs[:, T], u_next, stepsize_next, keys_next, u_act_next) with the schedules sliced at T is bit-exact when T is a
+ * multiple of S. The chunk's disturbance and schedule rows are staged per chunk, like moving references. Every argument is checked before the first HIP call:
+ * SDEMPC_EINVAL for struct_size, dist_ticks not 1 or T, dist_batch not 1 or B, plant_ticks not 1 or T, a non-finite dist entry, a scheduled index outside
+ * [0, num_plants), num_plants outside 1 .. B * plant_ticks, plant_of NULL with plant_ticks > 1 (or where sdempc_closed_loop_batch_plant refuses it), and for
+ * everything sdempc_closed_loop_batch_timed refuses. No ABI version change: detect the entry point by its symbol. */
+typedef struct sdempc_scenario_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_scenario_cfg) */
+    const float* dist;     /* [dist_ticks][dist_batch][6] or NULL: no disturbance */
+    int32_t dist_ticks;    /* 1 or T (ignored when dist is NULL) */
+    int32_t dist_batch;    /* 1 or B (ignored when dist is NULL) */
+    int32_t plant_ticks;   /* Tp: 1 or T; plant_of is [plant_ticks][B] */
+} sdempc_scenario_cfg;
+int sdempc_closed_loop_batch_scenario(sdempc_handle* h, const sdempc_scenario_cfg* scenario, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                      const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                      const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                      const float* xref, int32_t xref_solves, int32_t xref_batch,
+                                      const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                      const float* u_act_in /*[B][m] or NULL*/,
+                                      float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][Ns]*/,
+                                      float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                      uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/);
 
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so

@@ -67,12 +67,19 @@ class SdempcTimingCfg(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("solve_period", C.c_int32), ("solve_delay", C.c_int32), ("lag_alpha", C.c_float)]
 
 
+class SdempcScenarioCfg(C.Structure):
+    """sdempc_scenario_cfg (SPEC.md §11c): the disturbance schedule and the rows of the plant schedule of sdempc_closed_loop_batch_scenario."""
+    _fields_ = [("struct_size", C.c_int32), ("dist", C.POINTER(C.c_float)), ("dist_ticks", C.c_int32), ("dist_batch", C.c_int32),
+                ("plant_ticks", C.c_int32)]
+
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
 
 # execution options of a handle (include/sdempc.h, SDEMPC_OPT_*)
-OPTIONS = {"lane": 1, "coop": 2, "spec": 3, "pk": 4, "ustg": 5, "coop_launch": 6, "coop_fence": 7, "coop_spin_us": 8, "device_cus": 9, "duo": 10, "hex": 11, "test_absent_wg": 12, "test_ws_fill": 13}
+OPTIONS = {"lane": 1, "coop": 2, "spec": 3, "pk": 4, "ustg": 5, "coop_launch": 6, "coop_fence": 7, "coop_spin_us": 8, "device_cus": 9, "duo": 10, "hex": 11, "test_absent_wg": 12, "test_ws_fill": 13,
+           "test_loop_chunk_bytes": 14}
 
 ABI_VERSION = 3          # include/sdempc.h: SDEMPC_ABI_VERSION (the layout of SdempcCfg / SdempcInfo below)
 
@@ -175,11 +182,25 @@ def timed_entry(lib):
     return fn
 
 
+def scenario_entry(lib):
+    """sdempc_closed_loop_batch_scenario (SPEC.md §11c) with its prototype set: the timed entry point's arguments behind a scenario cfg. Detected by
+    symbol and only when a call needs it, as timed_entry is (no ABI version change)."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_scenario
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_scenario (SPEC.md §11c): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(timed_entry(lib).argtypes)
+        fn.argtypes = [a[0], C.POINTER(SdempcScenarioCfg)] + a[1:]
+        fn.restype = C.c_int
+    return fn
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
     "sdempc_traj_dev_floats", "sdempc_noise_to_device_layout", "sdempc_solve_batch_dev", "sdempc_rollout_batch_dev",
     "sdempc_grad_batch_dev", "sdempc_last_kernel_ms", "sdempc_last_kernel_name", "sdempc_work_counters", "sdempc_solve_status", "sdempc_layout_fallbacks", "sdempc_noise_to_device_layout_dev", "sdempc_traj_to_canonical_dev",
     "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
-    "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed",
+    "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed", "sdempc_closed_loop_batch_scenario",
 ]

@@ -190,6 +190,7 @@ struct sdempc_handle {
     int last_coop_B = 0;      // > 0: the last solve launch took the cooperative path with this many instances (error flags to check)
     bool coop_off = false;    // a grid barrier timed out once: this handle stays on the one-workgroup-per-instance layouts
     int layout_fallbacks = 0; // how often that happened (sdempc_layout_fallbacks)
+    int loop_chunk_bytes = -1;   // SDEMPC_OPT_TEST_LOOP_CHUNK_BYTES: device bytes per chunk of closed-loop ticks; -1: the built-in LOOP_CHUNK_BYTES
     int ws_fill = -1;         // SDEMPC_OPT_TEST_WS_FILL: 0..255 = byte every float-valued device buffer is filled with right after its hipMalloc (dev_alloc); -1: none
 };
 
@@ -514,6 +515,7 @@ struct PlantRun {
     KArgs k;        // argument block of launch_loop_plant: the handle's with the plant's arithmetic and step length (one shared plant: its M / wts / sdt too)
     LoopPlant Q;
     float* xi;      // [B][substeps][6] plant noise of a tick
+    float dt;       // the plant's step length
 };
 // SPEC.md §11b: the timing of one sdempc_closed_loop_batch_timed call. With it LoopIo::xref_ticks counts SOLVES (1 or Ns) and LoopIo::info is [B][Ns].
 struct TimedRun {
@@ -522,11 +524,18 @@ struct TimedRun {
     const float* u_act_in;      // [B][m] or null (u_init[b][0])
     float* u_act_next;          // [B][m] or null
 };
+// SPEC.md §11c: the schedules of one sdempc_closed_loop_batch_scenario call (host pointers; staged per chunk by closed_loop_run)
+struct ScenarioRun {
+    const float* dist;          // [Td][Bd][6] or null
+    int Td, Bd;
+    const int32_t* plant_of;    // [Tp][B] or null (identity); read only when the plant set has more than one member
+    int Tp;
+};
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves);
-int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B);
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed = nullptr);
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, bool* again);
+int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows = 1);
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed = nullptr, const ScenarioRun* scen = nullptr);
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -675,6 +684,10 @@ int sdempc_set_option(sdempc_handle* h, int32_t key, int32_t value) {
             if (value < -1) return fail(h, SDEMPC_EINVAL, "spin budget must be -1 (derived) or >= 0 microseconds%s");
             h->spin_us = value;
             return SDEMPC_OK;
+        case SDEMPC_OPT_TEST_LOOP_CHUNK_BYTES:
+            if (value < -1) return fail(h, SDEMPC_EINVAL, "loop chunk bytes must be -1 (built-in) or >= 0%s");
+            h->loop_chunk_bytes = value;
+            return SDEMPC_OK;
         default: return fail(h, SDEMPC_EINVAL, "unknown option key%s");
     }
     });
@@ -696,6 +709,7 @@ int sdempc_get_option(const sdempc_handle* h, int32_t key, int32_t* value) {
         case SDEMPC_OPT_HEX: *value = o.hex; break;
         case SDEMPC_OPT_TEST_ABSENT_WG: *value = o.absent_wg; break;
         case SDEMPC_OPT_TEST_WS_FILL: *value = h->ws_fill; break;
+        case SDEMPC_OPT_TEST_LOOP_CHUNK_BYTES: *value = h->loop_chunk_bytes; break;
         case SDEMPC_OPT_COOP_SPIN_US: *value = h->spin_us >= 0 ? h->spin_us : (int32_t)(coop_spin_ticks(h) / 100u); break;
         case SDEMPC_OPT_DEVICE_CUS: *value = o.cus; break;
         default: return SDEMPC_EINVAL;
@@ -1021,6 +1035,43 @@ int sdempc_closed_loop_batch_timed(sdempc_handle* h, const sdempc_timing_cfg* tc
     });
 }
 
+int sdempc_closed_loop_batch_scenario(sdempc_handle* h, const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc,
+                                      const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T,
+                                      const float* x0, const float* xref, int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init,
+                                      const float* stepsize_in, const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next,
+                                      float* stepsize_next, uint32_t* keys_next, float* u_act_next) {
+    return guarded(h, [&]() -> int {
+    if (!h) return SDEMPC_EINVAL;
+    // every check happens here, before the first HIP call
+    if (!sc || sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg)) return fail(h, SDEMPC_EINVAL, "scenario: cfg NULL or struct_size mismatch%s");
+    if (!tc || tc->struct_size != (int32_t)sizeof(sdempc_timing_cfg)) return fail(h, SDEMPC_EINVAL, "timing: cfg NULL or struct_size mismatch%s");
+    if (tc->solve_period < 1) return fail(h, SDEMPC_EINVAL, "timing: solve_period must be >= 1%s");
+    if (!(tc->lag_alpha >= 0.0f) || !(tc->lag_alpha <= 1.0f)) return fail(h, SDEMPC_EINVAL, "timing: lag_alpha must be 0 (off) or in (0, 1]%s");
+    const LoopIo io{B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    int rc = check_loop_args(h, io, T >= 1 ? loop_solves(T, tc->solve_period) : 1);
+    if (rc) return rc;
+    if (sc->plant_ticks != 1 && sc->plant_ticks != T) return fail(h, SDEMPC_EINVAL, "scenario: plant_ticks must be 1 or T%s");
+    if (sc->plant_ticks > 1 && !plant_of) return fail(h, SDEMPC_EINVAL, "scenario: plant_of may not be NULL with plant_ticks > 1%s");
+    if ((rc = check_plant_args(h, pc, plant_blobs, plant_blob_bytes, plant_of, B, sc->plant_ticks))) return rc;
+    if (tc->solve_delay < 0 || (long long)tc->solve_delay > (long long)tc->solve_period * pc->substeps)
+        return fail(h, SDEMPC_EINVAL, "timing: solve_delay must be between 0 and solve_period * substeps (one solve at a time)%s");
+    if (sc->dist) {
+        if (sc->dist_ticks != 1 && sc->dist_ticks != T) return fail(h, SDEMPC_EINVAL, "scenario: dist_ticks must be 1 or T%s");
+        if (sc->dist_batch != 1 && sc->dist_batch != B) return fail(h, SDEMPC_EINVAL, "scenario: dist_batch must be 1 or B%s");
+        const size_t nd = (size_t)sc->dist_ticks * sc->dist_batch * SDEMPC_NNOISE;
+        for (size_t e = 0; e < nd; ++e)
+            if (!(fabsf(sc->dist[e]) < INFINITY)) return fail(h, SDEMPC_EINVAL, "scenario: dist holds a non-finite entry%s");
+    }
+    if ((rc = ensure_device(h))) return rc;
+    const TimedRun timed{tc->solve_period, tc->solve_delay, tc->lag_alpha, u_act_in, u_act_next};
+    const ScenarioRun scen{sc->dist, sc->dist ? sc->dist_ticks : 1, sc->dist ? sc->dist_batch : 1, plant_of, sc->plant_ticks};
+    PlantRun run;
+    // (a schedule is staged per chunk by the loop; stage_plants takes the set itself)
+    if ((rc = stage_plants(h, *pc, plant_blobs, nullptr, B, &run, tc->solve_period < T ? tc->solve_period : T))) return rc;
+    return closed_loop_attempts(h, io, &run, &timed, &scen);
+    });
+}
+
 int sdempc_solve_status(sdempc_handle* h) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1085,10 +1136,12 @@ int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves) {
     return 0;
 }
 // every check of a plant set (SPEC.md §11a), shared by the two entry points that take one; no HIP call
-int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B) {
+// sched_rows: rows of plant_of (SPEC.md §11c: a plant index per tick and episode; 1 everywhere else)
+int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows) {
     int rc;
     if (!pc || pc->struct_size != (int32_t)sizeof(sdempc_plant_cfg)) return fail(h, SDEMPC_EINVAL, "plant: cfg NULL or struct_size mismatch%s");
-    if (pc->num_plants < 1 || pc->num_plants > B) return fail(h, SDEMPC_EINVAL, "plant: num_plants must be between 1 and B%s");
+    if (pc->num_plants < 1 || (long long)pc->num_plants > (long long)B * sched_rows)
+        return fail(h, SDEMPC_EINVAL, sched_rows > 1 ? "plant: num_plants must be between 1 and B * plant_ticks%s" : "plant: num_plants must be between 1 and B%s");
     if (pc->substeps < 1 || pc->substeps > SDEMPC_PLANT_MAX_SUBSTEPS) return fail(h, SDEMPC_EINVAL, "plant: substeps must be between 1 and SDEMPC_PLANT_MAX_SUBSTEPS (64)%s");
     if (!(pc->dt >= 0.0f) || !(pc->dt < INFINITY)) return fail(h, SDEMPC_EINVAL, "plant: dt must be finite and >= 0 (0: time_steps[0] / substeps)%s");
     if (pc->mlp_dtype < -1 || pc->mlp_dtype > 2) return fail(h, SDEMPC_EINVAL, "plant: mlp_dtype must be -1 (the handle's), 0 (f32), 1 (f16) or 2 (f32x3)%s");
@@ -1097,7 +1150,7 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
     const int Np = pc->num_plants;
     if (!plant_of && Np != 1 && Np != B) return fail(h, SDEMPC_EINVAL, "plant: plant_of may be NULL only when num_plants is 1 or B%s");
     if (plant_of)
-        for (int b = 0; b < B; ++b)
+        for (size_t b = 0; b < (size_t)B * sched_rows; ++b)
             if (plant_of[b] < 0 || plant_of[b] >= Np) return fail(h, SDEMPC_EINVAL, "plant: plant_of holds an index outside [0, num_plants)%s");
     for (int p = 0; p < Np; ++p) {
         if ((rc = check_blob(h, plant_blobs[p], plant_blob_bytes[p]))) return rc;
@@ -1106,10 +1159,10 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
     return 0;
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed) {
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -1158,6 +1211,7 @@ int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const
     out->Q.plant_of = plant_of && !shared ? (const int*)(d + o_of) : nullptr;
     out->Q.wts_stride = (int)stride; out->Q.substeps = n;
     out->xi = (float*)(d + o_xi);
+    out->dt = dt;
     return 0;
 }
 // Device memory the per-tick buffers of one chunk of closed-loop ticks may take (sdempc_closed_loop_batch): the outputs (x_{k+1}, u_k, info_k)
@@ -1171,15 +1225,21 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // the cooperative layouts; results are the same in every layout).
 // SPEC.md §11b (timed): the unit of work is a solve PERIOD of S ticks — one key schedule, one solve and one plant launch per period, chunks of whole
 // periods, info and moving references per solve. Without `timed` a period is one tick and every launch is the one it was (S = 1 below).
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, bool* again) {
+// SPEC.md §11c (scen, with timed and plant): the chunk's disturbance rows and plant-schedule rows (one per TICK) are staged per chunk beside the moving
+// references and counted in the chunk's bytes; a schedule of one row is staged once. The plant step is then launch_loop_scenario.
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
     const int Ns = loop_solves(T, S);
     const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m) + 8;       // floats per reference window / per episode-period of output
     const bool xref_moves = io.xref_ticks > 1;
-    const size_t per_period = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0);
-    const size_t fixed = xref_moves ? 0 : (size_t)Bx * XR, cap = LOOP_CHUNK_BYTES / sizeof(float);
+    const bool gust = scen && scen->dist, sched = scen && plant && plant->Q.models;        // (one shared plant: nothing to schedule)
+    const bool dist_moves = gust && scen->Td > 1, sched_moves = sched && scen->Tp > 1;
+    const size_t DR = gust ? (size_t)scen->Bd * SDEMPC_NNOISE : 0, SR = sched ? (size_t)B : 0;       // floats per tick row of the disturbance / words of the schedule
+    const size_t per_period = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0);
+    const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR);
+    const size_t cap = (h->loop_chunk_bytes < 0 ? LOOP_CHUNK_BYTES : (size_t)h->loop_chunk_bytes) / sizeof(float);
     const size_t fit = cap > fixed ? (cap - fixed) / per_period : 0;
     const int Pc = (int)(fit < 1 ? 1 : (fit < (size_t)Ns ? fit : (size_t)Ns));      // periods per chunk
     const size_t Tc = (size_t)Pc * S;                                               // tick rows per chunk
@@ -1201,6 +1261,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* c_us = c_xs + Tc * B * NX;                                // [Tc][B][m]
     float* c_info = c_us + Tc * B * m;                               // [Pc][B][8]
     float* c_xref = c_info + (size_t)Pc * B * 8;                     // [Pc or 1][Bx][H+1][13]
+    float* c_dist = c_xref + (xref_moves ? (size_t)Pc : 1) * Bx * XR;         // [Tc or 1][Bd][6] (SPEC.md §11c)
+    int32_t* c_sched = (int32_t*)(c_dist + (dist_moves ? Tc : 1) * DR);       // [Tc or 1][B]
     float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place
     hipStream_t st = h->stream;
     // inputs (host vectors live until the synchronisation at the end of the first chunk)
@@ -1234,6 +1296,17 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
         if (Bx != B) HIPCHK(h, launch_broadcast_rows(c_xref, (float*)h->d_xref.p, (int)XR, B, st));
     }
+    std::vector<int32_t> ident;
+    if (gust && !dist_moves) HIPCHK(h, hipMemcpyAsync(c_dist, scen->dist, sizeof(float) * DR, hipMemcpyHostToDevice, st));
+    if (sched && !sched_moves) {
+        const int32_t* row = scen->plant_of;
+        if (!row) {                // (no plant_of: num_plants == B, the identity)
+            ident.resize(B);
+            for (int b = 0; b < B; ++b) ident[b] = b;
+            row = ident.data();
+        }
+        HIPCHK(h, hipMemcpyAsync(c_sched, row, sizeof(int32_t) * SR, hipMemcpyHostToDevice, st));
+    }
     for (int b = 0; b < B; ++b) memcpy(io.xs + (size_t)b * (T + 1) * NX, io.x0 + (size_t)b * NX, sizeof(float) * NX);
     std::vector<float> hx, hu, hi;
     for (int j0 = 0; j0 < Ns; j0 += Pc) {
@@ -1241,6 +1314,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         const size_t k0 = (size_t)j0 * S;
         const int nk = (int)((size_t)T - k0 < (size_t)np * S ? (size_t)T - k0 : (size_t)np * S);      // ticks of this chunk
         if (xref_moves) HIPCHK(h, hipMemcpyAsync(c_xref, io.xref + (size_t)j0 * Bx * XR, sizeof(float) * np * Bx * XR, hipMemcpyHostToDevice, st));
+        if (dist_moves) HIPCHK(h, hipMemcpyAsync(c_dist, scen->dist + k0 * DR, sizeof(float) * nk * DR, hipMemcpyHostToDevice, st));
+        if (sched_moves) HIPCHK(h, hipMemcpyAsync(c_sched, scen->plant_of + k0 * SR, sizeof(int32_t) * nk * SR, hipMemcpyHostToDevice, st));
         for (int jc = 0; jc < np; ++jc) {
             const int ticks = nk - jc * S < S ? nk - jc * S : S;                    // (the last period of the run may be partial)
             if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st));
@@ -1266,7 +1341,16 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 R.act = d_mot; R.alpha = timed->alpha; R.ticks = ticks; R.xi_ticks = S; R.shift = timed->S < H ? timed->S : H;
                 const long long never = (long long)ticks * plant->Q.substeps;       // (a solution that arrives at the period's end is flown by the next period, as its tail)
                 R.arrive = (int)(timed->D < never ? timed->D : never);
-                HIPCHK(h, launch_loop_period(plant->k, L, plant->Q, R, st));
+                if (scen) {
+                    const size_t t0 = (size_t)jc * S;                                // first tick row of this period inside the chunk
+                    LoopScenario C;
+                    C.dist = gust ? c_dist + (dist_moves ? t0 * DR : 0) : nullptr;
+                    C.dist_tick_stride = dist_moves ? (int)DR : 0; C.dist_ep_stride = gust && scen->Bd > 1 ? SDEMPC_NNOISE : 0;
+                    C.plant = sched ? c_sched + (sched_moves ? t0 * SR : 0) : nullptr;
+                    C.plant_tick_stride = sched_moves ? B : 0;
+                    C.dtp = plant->dt;
+                    HIPCHK(h, launch_loop_scenario(plant->k, L, plant->Q, R, C, st));
+                } else HIPCHK(h, launch_loop_period(plant->k, L, plant->Q, R, st));
             } else if (plant) HIPCHK(h, launch_loop_plant(plant->k, L, plant->Q, st));
             else HIPCHK(h, launch_loop_advance(h->base, L, st));
         }

@@ -177,6 +177,18 @@ struct LoopPeriod {
     int arrive;                 // substep index inside the period at which the command source switches from y_j to uopt_j; >= ticks * substeps: never
 };
 hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st);
+// SPEC.md §11c, the closed loop with a scenario: launch_loop_period plus a disturbance row per control tick and a plant index per control tick. Both
+// pointers address the PERIOD's first tick (the host steps them from period to period); tick i of the period reads row i, or row 0 when the stride is 0.
+struct LoopScenario {
+    const float* dist;          // (w_v[3], w_omega[3]) of tick i, episode b at dist[i * dist_tick_stride + b * dist_ep_stride + 0..5], or null: no disturbance
+    int dist_tick_stride;       // floats between two ticks' rows: Bd * 6, or 0 (one row for every tick)
+    int dist_ep_stride;         // floats between two episodes' rows: 6, or 0 (one row for every episode)
+    const int* plant;           // plant index of tick i, episode b at plant[i * plant_tick_stride + b]; required with per-episode plants (LoopPlant::models),
+                                // where it replaces LoopPlant::plant_of; ignored with one shared plant
+    int plant_tick_stride;      // B, or 0 (one row for every tick)
+    float dtp;                  // the plant's step length (what LoopAdvance's KArgs::dt points at)
+};
+hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st);
 // the tick's key schedule (sdempc_prng.hip): keys r_k -> r_{k+1} in place, the solve's noise keys into sub_dev u32[B][2], the plant noise into
 // xi_dev f32[B][substeps][6]: ONE draw normal(p, 6 * substeps) per episode (SPEC.md §7.1: counter i pairs with i + 3 * substeps), row j for substep j
 hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st, int substeps = 1);

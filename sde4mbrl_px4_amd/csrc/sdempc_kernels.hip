@@ -46,7 +46,7 @@
 // unit; the solve kernel has ~90 instantiations of ~25k instructions each): SDEMPC_TU = 0 — every kernel except the duo solve
 // kernels, and all launchers; 1 — the duo solve kernels of the two-wave teams (TeamPair, TeamBlock2); 2 — those of the four-wave
 // team (TeamBlock); 3 — those of the six-team workgroup (TeamHex). Units 1 to 3 hold nothing but explicit instantiations (list macros below), unit 0 declares them `extern template`.
-// 4 — the plant steps of the batched closed loop and their launchers (sdempc_loop.inc.h, SPEC.md §11, §11a, §11b).
+// 4 — the plant steps of the batched closed loop and their launchers (sdempc_loop.inc.h, SPEC.md §11, §11a, §11b, §11c).
 #ifndef SDEMPC_TU
 #define SDEMPC_TU 0
 #endif
@@ -1089,6 +1089,15 @@ SDEMPC_DUO_HEX(SDEMPC_DUO_DEF)
 #elif SDEMPC_TU == 4
 #include "sdempc_loop.inc.h"
 }  // namespace exact / fastm
+#if !SDEMPC_FAST
+// launch_loop_scenario (SPEC.md §11c) picks its math mode here, in the loop unit of the exact build (a.fast: the PLANT's math mode)
+namespace fastm {
+hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st);
+}
+hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st) {
+    return a.fast ? fastm::launch_loop_scenario(a, L, Q, R, C, st) : exact::launch_loop_scenario(a, L, Q, R, C, st);
+}
+#endif
 #else
 SDEMPC_DUO_PAIR(SDEMPC_DUO_DECL)
 SDEMPC_DUO_HEX(SDEMPC_DUO_DECL)

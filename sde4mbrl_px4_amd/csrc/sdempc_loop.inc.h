@@ -1,5 +1,5 @@
 // sdempc_loop.inc.h — the plant of the batched closed loop (SPEC.md §11): one Euler–Maruyama step of the handle's own model per episode and
-// tick, plus the hand-over to the next tick's solve (applied control, shifted warm start, step size); §11a: a separate plant; §11b: a whole solve period.
+// tick, plus the hand-over to the next tick's solve (applied control, shifted warm start, step size); §11a: a separate plant; §11b: a whole solve period; §11c: a period with a scenario.
 // Fragment of sdempc_kernels.hip, translation unit SDEMPC_TU = 4: included inside namespace sdempc::{exact|fastm} (compiled once per math mode).
 //
 // The step is the rollout's own device code: step_fwd at t = 0 on a control table built by block_prepass, i.e. the arithmetic of step 0
@@ -218,6 +218,135 @@ hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPl
             if (e != hipSuccess) return e;
         }
         sdempc_loop_period_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q, R);
+        return hipGetLastError();
+    });
+}
+
+// SPEC.md §11c: the period kernel with a SCENARIO — per control tick an external acceleration on the state (a disturbance row, held over the tick's substeps)
+// and the plant that flies the tick (a plant index per tick and episode). Body, hand-over and every argument of sdempc_loop_period_kernel; what differs:
+//  * the disturbance row of tick i is six floats at a wave-uniform address; after every step_fwd the register copy of x takes v_e <- fma(w_v[e], dtp, v_e)
+//    and omega_e <- fma(w_om[e], dtp, omega_e), dtp the plant's step length — six fmas, applied whenever a schedule is given (zero rows included);
+//  * the ticks of the period are walked in RUNS of ticks that name one plant. A run starts by staging that plant into the wave's own LDS carve (load_weights,
+//    WaveW, the wave's argument block for the prepass; TeamWave::sync on both sides), so inside a run the model constants are what they are in the period kernel:
+//    values defined before the tick loop, not loop-carried ones. The first run's staging is the period kernel's prologue. The state x, the motor state, the
+//    applied-control row and the noise rows carry over a switch untouched; sigma sqrt(dt) travels with the weights (sm.sdt), the rotor tables with lk->M.
+//    The wave's argument block goes from global memory to LDS lane by lane (no register copy indexed at run time, hence no scratch on its way).
+//  * one shared plant (Q.models == null): nothing to switch, the four episodes share one carve as before and C.plant is not read.
+template <int F16>
+__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_scenario_kernel(KArgs a0, LoopAdvance L, LoopPlant Q, LoopPeriod R, LoopScenario C) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int H = L.H, m = a0.m;
+    const int tid = TeamWave::tid();
+    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
+    const bool per = Q.models != nullptr, live = b < L.B;      // (both wave-uniform)
+    Smem sm = per ? carve(smem + (size_t)TeamWave::team() * smem_floats(1, m, 1), 1, m, 0) : carve(smem, 1, m, TeamWave::team());
+    WaveW ww;
+    KArgs* const lk = reinterpret_cast<KArgs*>(smem + TeamWave::IPB * smem_floats(1, m, 1) + (size_t)TeamWave::team() * plant_kargs_floats());
+    if (!per) {                     // (workgroup-uniform: a kernel argument)
+        load_weights(a0, sm, ww, threadIdx.x, TeamWave::BNT);
+        __syncthreads();
+    }
+    if (!live) return;              // (wave-uniform; no workgroup-wide barrier below)
+    const int lane = tid & 63, h = lane >> 5, n = Q.substeps;
+    const bool lag = R.alpha > 0.0f, mine = lane < m, gust = C.dist != nullptr;
+    const float* uo = L.uopt + (size_t)b * H * m;
+    float* yw = L.u + (size_t)b * H * m;
+    float* act = sm.v[5];           // [m] the applied control of the current substep
+    float am = mine ? R.act[(size_t)b * m + lane] : 0.0f;
+    float x[NX], xn[NX], xi[NN];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
+    const float* xrow = L.xi + (size_t)b * R.xi_ticks * n * NN;
+    const float* drow = gust ? C.dist + (size_t)b * C.dist_ep_stride : nullptr;
+    const int* prow = per ? C.plant + b : nullptr;
+    int i = 0;
+#pragma nounroll
+    while (i < R.ticks) {           // one run of ticks that name the same plant
+        KArgs a = a0;
+        int iend = R.ticks;
+        if (per) {
+            const int p = __builtin_amdgcn_readfirstlane(prow[(size_t)i * C.plant_tick_stride]);
+            iend = i + 1;
+#pragma nounroll
+            while (iend < R.ticks && __builtin_amdgcn_readfirstlane(prow[(size_t)iend * C.plant_tick_stride]) == p) ++iend;
+            a.M = Q.models[p];
+            a.wts = Q.wts + (size_t)p * Q.wts_stride;
+            a.sdt = Q.sdt + (size_t)p * NN;
+            TeamWave::sync();       // (the previous run's reads of the carve are done)
+            load_weights(a, sm, ww, tid, TeamWave::NT);
+            if (tid == 0) { lk->H = 1; lk->m = m; }
+            const float* msrc = reinterpret_cast<const float*>(Q.models + p);
+            float* mdst = reinterpret_cast<float*>(&lk->M);
+            for (int e = tid; e < (int)(sizeof(ModelK) / sizeof(float)); e += TeamWave::NT) mdst[e] = msrc[e];      // (what block_prepass reads)
+            TeamWave::sync();
+        }
+#pragma nounroll
+        for (; i < iend; ++i) {
+            const int row = (i < H - 1 ? i : H - 1) * m;
+            float w[NN];
+#pragma unroll
+            for (int e = 0; e < NN; ++e)
+                w[e] = gust ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, drow[(size_t)i * C.dist_tick_stride + e]))) : 0.0f;
+#pragma nounroll
+            for (int jj = 0; jj < n; ++jj) {
+                const int q = i * n + jj;
+                if (lag || jj == 0 || q == R.arrive) {
+                    if (mine) {
+                        const float c = (q >= R.arrive ? uo : yw)[row + lane];
+                        am = lag ? FMA(R.alpha, c - am, am) : c;
+                        act[lane] = am;
+                    }
+                    TeamWave::sync();       // (the row is written, the previous substep's reads of the control table are done)
+                    if (per) block_prepass<TeamWave>(*lk, sm, act, tid);
+                    else block_prepass<TeamWave>(a0, sm, act, tid);
+                    TeamWave::sync();
+                }
+                if (jj == 0 && mine) L.us[((size_t)i * L.B + b) * m + lane] = am;
+#pragma unroll
+                for (int e = 0; e < NN; ++e) xi[e] = xrow[q * NN + e];
+                StepAux A;
+                step_fwd<F16, false>(a, sm, ww, 0, h, lane, x, xi, xn, A);
+#pragma unroll
+                for (int e = 0; e < NX; ++e) x[e] = xn[e];
+                if (gust) {
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) { x[3 + e] = FMA(w[e], C.dtp, x[3 + e]); x[10 + e] = FMA(w[3 + e], C.dtp, x[10 + e]); }
+                }
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int e = 0; e < NX; ++e) L.xs[((size_t)i * L.B + b) * NX + e] = x[e];
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) L.x[(size_t)b * NX + i] = x[i];
+        L.step[b] = L.info[(size_t)b * 8 + 1];
+        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
+    }
+    if (mine) R.act[(size_t)b * m + lane] = am;
+    for (int e = tid; e < H * m; e += TeamWave::NT) {   // y_{j+1}: row t = uopt_j[min(t + S, H - 1)]
+        const int t = e / m, ts = t + R.shift < H ? t + R.shift : H - 1;
+        yw[e] = uo[ts * m + (e - t * m)];
+    }
+}
+
+hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st) {
+    if (L.B < 1 || L.H != a.H || Q.substeps < 1 || (Q.models && (!Q.wts || !Q.sdt || Q.wts_stride < BLOB_FLOATS + VJP_BASE))) return hipErrorInvalidValue;
+    if (!R.act || R.ticks < 1 || R.xi_ticks < R.ticks || R.shift < 1 || R.shift > a.H || R.arrive < 0 || !(R.alpha >= 0.0f && R.alpha <= 1.0f)) return hipErrorInvalidValue;
+    if ((Q.models && !C.plant) || (C.plant_tick_stride != 0 && C.plant_tick_stride != L.B)) return hipErrorInvalidValue;
+    if (C.dist_tick_stride < 0 || (C.dist_ep_stride != 0 && C.dist_ep_stride != NN) || !(C.dtp > 0.0f)) return hipErrorInvalidValue;
+    KArgs k = a;
+    k.H = 1;
+    const size_t sb = Q.models ? TeamWave::IPB * (smem_bytes(1, k.m, 1) + sizeof(float) * plant_kargs_floats()) : smem_bytes(1, k.m, TeamWave::IPB);
+    const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
+    return with_f16(k.f16, [&](auto F16) {
+        if (sb > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)sdempc_loop_scenario_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
+            if (e != hipSuccess) return e;
+        }
+        sdempc_loop_scenario_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q, R, C);
         return hipGetLastError();
     });
 }

@@ -138,7 +138,7 @@ class MpcProblem:
 
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
-                 plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0):
+                 plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -149,7 +149,11 @@ class MpcProblem:
         the arguments of SdeMpcSolver.closed_loop (SPEC.md §11a), passed through for this one episode.
         solve_period / solve_delay / motor_lag: the controller at the node's timing (SPEC.md §11b) — a solve every solve_period ticks, applied
         solve_delay plant substeps late, through a first-order motor lag. Solve j then tracks self.xref(curr_t + j * solve_period * dt_0, xdes), info is
-        f32[Ns][8] with Ns = ceil(T / solve_period), and the motor state starts at the warm start's first row."""
+        f32[Ns][8] with Ns = ceil(T / solve_period), and the motor state starts at the warm start's first row.
+        disturbance / plant_of: a scenario (SPEC.md §11c) — disturbance f32[T][6] or f32[6], an external linear (world) and angular (body) acceleration per
+        tick GIVEN IN THE FRAME OF x (under convert_to_enu the vector rules of enu2ned take it into the solver's frame, exactly: (x, y, z) -> (y, x, -z) and
+        (wx, wy, wz) -> (wx, -wy, -wz)); plant_of int[T] names, per tick, which member of the sequence `plant` flies the tick (a payload dropped at
+        tick k: plant=[loaded, empty], plant_of = [0] * k + [1] * (T - k)). Either one makes the call the timed one (info per solve)."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -167,9 +171,22 @@ class MpcProblem:
         if opt_state is not None:
             u0 = np.asarray(opt_state.yk, np.float32)[None]
             s0 = np.array([opt_state.stepsize], np.float32)
+        if disturbance is not None:
+            w = np.asarray(disturbance, np.float32)
+            if w.shape not in ((6,), (T, 6)):
+                raise ValueError(f"MpcProblem.simulate: disturbance must be f32[{T}][6] or f32[6], got {w.shape}")
+            if self.convert_to_enu:
+                w = np.stack([w[..., 1], w[..., 0], -w[..., 2], w[..., 3], -w[..., 4], -w[..., 5]], axis=-1)
+            disturbance = np.ascontiguousarray(w, np.float32)
+        if plant_of is not None:
+            plant_of = np.asarray(plant_of, np.int32)
+            if plant_of.shape != (T,):
+                raise ValueError(f"MpcProblem.simulate: plant_of must be int[{T}] (one episode: the plant of every tick), got {plant_of.shape}")
+            plant_of = plant_of[:, None]
         xs, us, info, u_next, s_next, k_next = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
-            plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag)[:6]
+            plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag,
+            disturbance=disturbance, plant_of=plant_of)[:6]
         xs = xs[0]
         if self.convert_to_enu:
             xs = np.concatenate([x[None], enu2ned(xs[1:], np)], axis=0)

@@ -164,7 +164,7 @@ class SdeMpcSolver:
         return uopt, xevol, np.frombuffer(info, dtype=np.float32).reshape(B, 8).copy()
 
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
-                    plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None):
+                    plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -184,7 +184,15 @@ class SdeMpcSolver:
         per plant substep (0: off) from the motor state u_act_in [B][m] (None: u_init[:, 0]). With all four at their defaults the call is exactly the
         one above. Otherwise xref is f32[Tx][Bx][H+1][13] with Tx in {1, Ns}, Ns = ceil(T / solve_period) (one window per SOLVE), info is [B][Ns][8], the
         plant defaults to the handle's own model, and a 7-tuple comes back: the six above and u_act_next [B][m]. Carrying (xs[:, -1], u_next,
-        stepsize_next, keys_next, u_act_next) into the next call continues the episodes bit for bit when T is a multiple of solve_period."""
+        stepsize_next, keys_next, u_act_next) into the next call continues the episodes bit for bit when T is a multiple of solve_period.
+
+        disturbance / a 2-D plant_of (SPEC.md §11c, sdempc_closed_loop_batch_scenario): things that happen to a vehicle during an episode. disturbance is
+        f32[Td][Bd][6] with Td in {1, T} (per control TICK) and Bd in {1, B}, or [T][6] (shared by all episodes), or [6] (constant); row (k, b) is an external
+        linear acceleration in the solver's world frame and an external angular acceleration in the body frame, added to v and omega after every plant
+        substep of tick k: fma(w, dt_plant, .). A [B][6] array is not accepted (it cannot be told from [T][6]). plant_of int[T][B] names the plant of every
+        tick: a switch at a tick start changes the vehicle only (state, motor state, keys and warm start carry over), and the set may then hold up to B * T
+        plants. With disturbance=None and a 1-D plant_of the call takes the routes above, unchanged; otherwise it is the timed call (7-tuple, xref and info
+        per solve, the plant defaulting to the handle's own model) with the schedules applied."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -195,7 +203,27 @@ class SdeMpcSolver:
         if xref.ndim != 4 or xref.shape[2:] != (self.H + 1, 13):
             raise ValueError(f"xref must be f32[Tx][Bx][{self.H + 1}][13] or f32[{self.H + 1}][13], got {xref.shape}")
         xref = np.ascontiguousarray(xref)
-        timed = not (solve_period == 1 and solve_delay == 0 and motor_lag == 0.0 and u_act_in is None)
+        dist = sched = None
+        if disturbance is not None:
+            dist = _f32(disturbance)
+            if dist.ndim == 1 and dist.shape == (6,):
+                dist = dist[None, None]
+            elif dist.ndim == 2 and dist.shape == (T, 6):
+                dist = dist[:, None]
+            if dist.ndim != 3 or dist.shape[2] != 6 or dist.shape[0] not in (1, T) or dist.shape[1] not in (1, B):
+                raise ValueError(f"closed_loop: disturbance must be f32[Td][Bd][6] with Td in (1, {T}) and Bd in (1, {B}), f32[{T}][6] or f32[6], "
+                                 f"got {np.shape(disturbance)}")
+            if not np.isfinite(dist).all():
+                raise ValueError("closed_loop: disturbance holds a non-finite entry")
+            dist = np.ascontiguousarray(dist)
+        if plant_of is not None and np.ndim(plant_of) == 2:
+            sched = np.ascontiguousarray(plant_of, dtype=np.int32)
+            if sched.shape[0] not in (1, T) or sched.shape[1] != B:
+                raise ValueError(f"closed_loop: a 2-D plant_of must be int[Tp][{B}] with Tp in (1, {T}), got {sched.shape}")
+            if plant is None:
+                raise ValueError("closed_loop: plant_of needs plant=...")
+        scenario = dist is not None or sched is not None
+        timed = scenario or not (solve_period == 1 and solve_delay == 0 and motor_lag == 0.0 and u_act_in is None)
         Ns = T
         if timed:
             S_, D_, alpha = int(solve_period), int(solve_delay), float(np.float32(motor_lag))
@@ -241,7 +269,9 @@ class SdeMpcSolver:
         bufs = (C.c_char_p * max(Np, 1))(*blobs)
         sizes = (C.c_size_t * max(Np, 1))(*[len(b) for b in blobs])
         of_p = None
-        if plant_of is not None:
+        if sched is not None:
+            of_p = sched.ctypes.data_as(C.POINTER(C.c_int32))
+        elif plant_of is not None:
             plant_of = np.ascontiguousarray(plant_of, dtype=np.int32)
             if plant_of.shape != (B,):
                 raise ValueError(f"plant_of must be int[{B}], got {plant_of.shape}")
@@ -252,6 +282,12 @@ class SdeMpcSolver:
         if timed:
             tc = _abi.SdempcTimingCfg(C.sizeof(_abi.SdempcTimingCfg), S_, D_, alpha)
             a_next = np.zeros((B, self.m), np.float32)
+            if scenario:
+                sc = _abi.SdempcScenarioCfg(C.sizeof(_abi.SdempcScenarioCfg), None if dist is None else _fp(dist), 1 if dist is None else dist.shape[0],
+                                            1 if dist is None else dist.shape[1], 1 if sched is None else sched.shape[0])
+                self._check(_abi.scenario_entry(self.lib)(self._h, C.byref(sc), C.byref(tc), C.byref(pc), C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p,
+                                                          *tail[:9], a_p, *tail[9:], _fp(a_next)))
+                return xs, us, info, u_next, s_next, k_next, a_next
             self._check(_abi.timed_entry(self.lib)(self._h, C.byref(tc), C.byref(pc), C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *tail[:9], a_p,
                                                     *tail[9:], _fp(a_next)))
             return xs, us, info, u_next, s_next, k_next, a_next

@@ -15,8 +15,11 @@
      handle's own model through sdempc_closed_loop_batch_plant; --timed sends the call through sdempc_closed_loop_batch_timed even at --period 1
      --delay 0 --lag 0 (the same arithmetic, one period kernel per tick); --period S --delay D --lag ALPHA set the timing. Nothing else runs in this mode.
      With SDEMPC_LIB naming a library of the parent commit the default keywords measure that commit's entry points from the same process setup.
+  5. --disturbance / --plant-switch K: the same loops with a scenario (SPEC.md §11c, sdempc_closed_loop_batch_scenario) — a random disturbance row per tick
+     and episode, and / or every episode changing its plant at tick K (--plant self or one: to one perturbed vehicle; per-episode: to its neighbour's).
+     They apply to --small-batch and to the C2 loop, where --timed / --period / --delay / --lag now apply too (one reference window per solve).
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
-                                        [--small-batch B [--timed] [--period S] [--delay D] [--lag ALPHA]]
+                                        [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -47,6 +50,8 @@ ap.add_argument("--timed", action="store_true", help="--small-batch: go through 
 ap.add_argument("--period", type=int, default=1)
 ap.add_argument("--delay", type=int, default=0)
 ap.add_argument("--lag", type=float, default=0.0)
+ap.add_argument("--disturbance", action="store_true", help="a disturbance row per tick and episode (SPEC.md §11c)")
+ap.add_argument("--plant-switch", type=int, default=-1, metavar="K", help="every episode changes its plant at tick K (SPEC.md §11c; needs --plant self, one or per-episode)")
 a = ap.parse_args()
 model = synthetic_iris()
 if a.plant == "own" and a.substeps != 1:
@@ -65,7 +70,36 @@ def plant_kw(B):
     return {"plant": blobs[0] if a.plant == "one" else blobs, "plant_substeps": a.substeps}
 
 
+def scenario_kw(kw, B, T):
+    """kw plus the schedules of --disturbance / --plant-switch for a call of T ticks"""
+    kw = dict(kw)
+    if a.disturbance:
+        kw["disturbance"] = np.random.default_rng(2).uniform(-2.0, 2.0, (T, B, 6)).astype(np.float32)
+    if a.plant_switch >= 0:
+        if a.plant == "own":
+            ap.error("--plant-switch needs --plant self, one or per-episode")
+        if isinstance(kw["plant"], list):
+            before, after = np.arange(B), (np.arange(B) + 1) % B
+        else:
+            kw["plant"] = [kw["plant"], model.perturbed(np.random.default_rng(5), mass=0.2, inertia=0.2, thrust=0.2, residual=0.2).to_blob()]
+            before, after = np.zeros(B), np.ones(B)
+        kw["plant_of"] = np.stack([before if k < a.plant_switch else after for k in range(T)]).astype(np.int32)
+    return kw
+
+
+def timing_kw(cfg, B):
+    if not (a.timed or a.period != 1 or a.delay or a.lag):
+        return {}
+    return dict(solve_period=a.period, solve_delay=a.delay, motor_lag=a.lag, u_act_in=np.tile(np.asarray(cfg.uref, np.float32)[: cfg.num_motors], (B, 1)))
+
+
 tag = "" if a.plant == "own" else f" plant={a.plant} substeps={a.substeps}"
+if a.timed or a.period != 1 or a.delay or a.lag:
+    tag += f" timed S={a.period} D={a.delay} alpha={a.lag}"
+if a.disturbance:
+    tag += " disturbance"
+if a.plant_switch >= 0:
+    tag += f" plant-switch at {a.plant_switch}"
 
 if a.small_batch:
     cfg = load_mpc_config(os.path.join(ROOT, "configs", "c1_iris_posctrl_h20_p32.yaml"))
@@ -74,11 +108,9 @@ if a.small_batch:
     hold = W.constant_reference(W.HOVER, cfg.horizon)
     keys = prng.split(prng.PRNGKey(10), B)
     S = SdeMpcSolver(cfg, model, max_batch=B)
-    kw = plant_kw(B)
-    if a.timed or a.period != 1 or a.delay or a.lag:
-        kw.update(solve_period=a.period, solve_delay=a.delay, motor_lag=a.lag, u_act_in=np.tile(np.asarray(cfg.uref, np.float32)[: cfg.num_motors], (B, 1)))
-        tag += f" timed S={a.period} D={a.delay} alpha={a.lag}"
-    S.closed_loop(x0, hold, keys, 2 * a.period, **kw)       # warm-up: device buffers, workspaces
+    kw = {**plant_kw(B), **timing_kw(cfg, B)}
+    S.closed_loop(x0, hold, keys, 2 * a.period, **scenario_kw(kw, B, 2 * a.period))       # warm-up: device buffers, workspaces
+    kw = scenario_kw(kw, B, T)
     for rep in range(a.repeats):
         t = time.perf_counter()
         S.closed_loop(x0, hold, keys, T, **kw)
@@ -119,7 +151,7 @@ if not a.skip_c2:
     B, T = 12288, a.c2_ticks
     x0 = W.random_initial_states(B, 3)
     xref = np.stack([np.stack([W.reference_window(0.05 * (b % 160) + k * float(cfg.time_steps[0]), cfg.time_steps) for b in range(B)])
-                     for k in range(T)])                    # a moving window per episode: the largest staging the loop does
+                     for k in range(0, T, a.period)])       # a moving window per episode and solve: the largest staging the loop does
     keys = prng.split(prng.PRNGKey(10), B)
     S = SdeMpcSolver(cfg, model, max_batch=B)
     yk, i0 = S.reset()
@@ -129,7 +161,7 @@ if not a.skip_c2:
     t = time.perf_counter()
     S.solve_keys(x0, xref[0], keys, u0, s0)
     one = time.perf_counter() - t
-    pk = plant_kw(B)
+    pk = scenario_kw({**plant_kw(B), **timing_kw(cfg, B)}, B, T)
     for rep in range(a.repeats):
         t = time.perf_counter()
         S.closed_loop(x0, xref, keys, T, u_init=u0, stepsize_in=s0, **pk)
