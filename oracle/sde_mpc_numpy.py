@@ -914,7 +914,8 @@ class Restatement:
         return F(fma(tot, self.invP, self.control_cost(u))), traj, xmean
 
     # ---- §8: the optimiser, with cost / gradient supplied by callables (the tests pass the C oracle's) ----
-    def solve(self, cost_fn, grad_fn, u_init, stepsize_in):
+    def solve(self, cost_fn, grad_fn, u_init, stepsize_in, events=None):
+        """events: a list that receives one dict per iteration, the event record of oracle/sde_mpc_oracle.c (EV_*) under the same names."""
         C, H, m = self.cfg, self.H, self.m
         lo, hi = np.asarray([b[0] for b in C.input_bound], F), np.asarray([b[1] for b in C.input_bound], F)
         if not C.enforce_ubound:
@@ -934,14 +935,22 @@ class Restatement:
             c_y, g = grad_fn(yk)
             c_y, g = F(c_y), np.asarray(g, F)
             gsq = self.dot256(g, g)
+            ev = dict(c_y=c_y, plain=int(plain), kr=kr, gsq=gsq, noimp=noimp, cause=0)
+            if events is not None:
+                events.append(ev)
             if not (gsq < np.inf):
+                ev["cause"] = 4
                 break
             c_n, nls = F(0), 0
+            ev.update(armijo=2, increased=0, capped=0)
             if C.ls_maxls > 0:
                 if k > 0 and C.ls_reset_option == "increase":
                     s = F(s * F(C.ls_increase_factor))
+                    ev["increased"] = 1
                 if s > F(C.ls_max_stepsize):
                     s = F(C.ls_max_stepsize)
+                    ev["capped"] = 1
+                ev.update(armijo=0, s0=s)
                 for jl in range(C.ls_maxls):
                     xn = proj(fma(-s, g, yk))
                     d1 = xn - yk
@@ -949,27 +958,38 @@ class Restatement:
                     gd = self.dot256(g, d1)
                     nls = jl + 1
                     if c_n <= fma(F(C.ls_coef), gd, c_y):
+                        ev["armijo"] = 1
                         break
                     if jl < C.ls_maxls - 1:
                         s = F(s * F(C.ls_decrease_factor))
             else:
                 s = F(C.stepsize)
+                ev["s0"] = s
                 xn = proj(fma(-s, g, yk))
                 c_n, nls = F(cost_fn(xn)), 1
             sum_ls, sum_s, nit, nls_tot = F(sum_ls + F(nls)), F(sum_s + s), k + 1, nls_tot + nls
             stop = abs(F(c_n - c_x)) <= fma(F(C.rtol), abs(c_x), F(C.atol))
+            ev.update(c_n=c_n, s=s, nls=nls, accepted=int(c_n < c_x), rs=F(0), restart=0, yk_stayed=int(plain and not c_n < c_x),
+                      stop_raised=int(stop), stop_suppressed=0, yk_clamped=0)
             if c_n < c_x:
-                if self.dot256(yk - xn, xn - xk) > 0:
+                ev["rs"] = self.dot256(yk - xn, xn - xk)
+                if ev["rs"] > 0:
                     yk, kr, plain = xn.copy(), 0, True
+                    ev["restart"] = 1
                 else:
-                    yk, kr, plain = proj(fma(beta[kr], xn - xk, xn)), kr + 1, False
+                    free = fma(beta[kr], xn - xk, xn)
+                    yk, kr, plain = proj(free), kr + 1, False
+                    ev["yk_clamped"] = int((free != yk).sum())
                 xk, c_x, noimp = xn.copy(), c_n, 0
             else:
                 if not plain:
+                    ev["stop_suppressed"] = int(stop)
                     stop = False
                 yk, kr, plain, noimp = xk.copy(), 0, True, noimp + 1
+            tol = stop
             if noimp >= C.max_no_improvement_iter:
                 stop = True
+            ev.update(noimp=noimp, cause=2 if tol else 3 if stop else 1 if k + 1 >= C.max_iter else 0)
             if stop:
                 break
         fn = F(nit)

@@ -1104,9 +1104,29 @@ static real cost_grad(const ctx_t* X, const real* x0, const real* u, const real*
 /* SPEC.md §3.6: median of three = fmin(fmax(v,lo),hi); a NaN maps to lo and -0 to +0 when lo = +0, as v_med3_f32 does */
 static inline real clampr(real v, real lo, real hi) { return !(v > lo) ? lo : (v > hi ? hi : v); }
 
+/* Event record of one iteration (tests/solve_paths.py names the paths of SPEC.md §8 on it). ORC_EV floats per iteration, written next to
+ * the 4-float trace and like it a by-product: nothing of the solve reads it. A solve that the non-finite guard ends at iteration k leaves
+ * a record k that holds c_y, the state before the update and the cause only. */
+enum { EV_CY, EV_CN, EV_S, EV_NLS, EV_ARMIJO /* 1 held on the last trial, 0 search exhausted, 2 no line search */, EV_INCREASED, EV_CAPPED,
+       EV_ACCEPTED, EV_RS, EV_RESTART, EV_PLAIN /* before the update */, EV_KR /* before the update */, EV_YK_STAYED, EV_STOP_RAISED,
+       EV_STOP_SUPPRESSED, EV_CAUSE /* 0 goes on, 1 max_iter, 2 tolerance, 3 no improvement, 4 non-finite guard */, EV_YK_CLAMPED /* elements
+       of a momentum yk that sit on a bound because of the projection */, EV_S0 /* step size of trial 1 */, EV_GSQ, EV_NOIMP /* after */, ORC_EV };
+
+/* Wrong optimisers for tests/test_solve_paths_cpu.py (each one line off SPEC.md §8). 0 = the normative path; only orc_set_mutant changes it. */
+enum { MUT_NONE, MUT_ARMIJO_STRICT, MUT_SHRINK_AFTER_LAST, MUT_CAP_BEFORE_INCREASE, MUT_RESTART_ON_ZERO, MUT_KR_KEPT_ON_REJECT,
+       MUT_STOP_NOT_SUPPRESSED, MUT_STALE_GRADIENT, MUT_BETA_NEXT, MUT_NOIMP_KEPT, MUT_YK_UNCLAMPED, MUT_COUNT };
+#ifdef ORC_NO_MUTANTS /* the timing builds (oracle/Makefile): a constant, so every `mu ==` below folds away */
+enum { g_mutant = MUT_NONE };
+#else
+static int g_mutant = MUT_NONE;
+void NAME(set_mutant)(int mu) { g_mutant = (mu > 0 && mu < MUT_COUNT) ? mu : MUT_NONE; }
+#endif
+int NAME(event_stride)(void) { return ORC_EV; }
+
 static void solve(const ctx_t* X, const real* x0, const real* xref, const real* noise,
-                  const real* u_init, real s_in, real* uopt, real* xevol, real* info, real* trace, int trace_cap) {
+                  const real* u_init, real s_in, real* uopt, real* xevol, real* info, real* trace, int trace_cap, real* ev, int ev_cap) {
     const sdempc_cfg* C = X->C;
+    const int mu = g_mutant;
     int H = X->H, m = X->m, N = H * m;
     real *xk = malloc(sizeof(real) * N), *yk = malloc(sizeof(real) * N), *xn = malloc(sizeof(real) * N),
          *g = malloc(sizeof(real) * N), *ub = malloc(sizeof(real) * N), *d1 = malloc(sizeof(real) * N), *d2 = malloc(sizeof(real) * N);
@@ -1120,27 +1140,32 @@ static void solve(const ctx_t* X, const real* x0, const real* xref, const real* 
     }
     for (int e = 0; e < N; ++e) { xk[e] = clampr(u_init[e], (real)C->u_lo[e % m], (real)C->u_hi[e % m]); yk[e] = xk[e]; ub[e] = xk[e]; }
     real c_init = rollout(X, x0, xk, xref, noise, NULL, NULL);
-    real c_x = c_init, s = s_in, gsq = 0, sum_ls = 0, sum_s = 0;
+    real c_x = c_init, s = s_in, gsq = 0, sum_ls = 0, sum_s = 0, c_y = 0;
     int kr = 0, noimp = 0, nit = 0, nls_tot = 0, plain = 1; /* plain: yk == xk (no momentum in yk) */
+    int stale = 0; /* (MUT_STALE_GRADIENT only) */
     for (int k = 0; k < C->max_iter; ++k) {
-        real c_y = cost_grad(X, x0, yk, xref, noise, g);
+        real* E = (ev && k < ev_cap) ? ev + (size_t)ORC_EV * k : NULL;
+        if (!stale) c_y = cost_grad(X, x0, yk, xref, noise, g);
         gsq = dot256(g, g, N);
-        if (!(gsq < (real)INFINITY)) break; /* SPEC.md §8 non-finite guard: no step is taken on a NaN/inf gradient */
-        real c_n = 0;
-        int nls = 0;
+        if (E) { E[EV_CY] = c_y; E[EV_PLAIN] = (real)plain; E[EV_KR] = (real)kr; E[EV_GSQ] = gsq; E[EV_NOIMP] = (real)noimp; }
+        if (!(gsq < (real)INFINITY)) { if (E) E[EV_CAUSE] = 4; break; } /* SPEC.md §8 non-finite guard: no step is taken on a NaN/inf gradient */
+        real c_n = 0, s0 = s;
+        int nls = 0, armijo = 2, increased = 0, capped = 0;
         if (C->ls_maxls > 0) {
-            if (k > 0 && C->ls_reset_option == 1) s = s * (real)C->ls_increase_factor;
-            if (s > (real)C->ls_max_stepsize) s = (real)C->ls_max_stepsize;
+            if (mu == MUT_CAP_BEFORE_INCREASE && s > (real)C->ls_max_stepsize) s = (real)C->ls_max_stepsize;
+            if (k > 0 && C->ls_reset_option == 1) { s = s * (real)C->ls_increase_factor; increased = 1; }
+            if (mu != MUT_CAP_BEFORE_INCREASE && s > (real)C->ls_max_stepsize) { s = (real)C->ls_max_stepsize; capped = 1; }
+            s0 = s; armijo = 0;
             for (int j = 0; j < C->ls_maxls; ++j) {
                 for (int e = 0; e < N; ++e) { xn[e] = clampr(FMA(-s, g[e], yk[e]), (real)C->u_lo[e % m], (real)C->u_hi[e % m]); d1[e] = xn[e] - yk[e]; }
                 c_n = rollout(X, x0, xn, xref, noise, NULL, NULL);
                 real gd = dot256(g, d1, N);
                 nls = j + 1;
-                if (c_n <= FMA((real)C->ls_coef, gd, c_y)) break;
-                if (j < C->ls_maxls - 1) s = s * (real)C->ls_decrease_factor;
+                if (mu == MUT_ARMIJO_STRICT ? c_n < FMA((real)C->ls_coef, gd, c_y) : c_n <= FMA((real)C->ls_coef, gd, c_y)) { armijo = 1; break; }
+                if (j < C->ls_maxls - 1 || mu == MUT_SHRINK_AFTER_LAST) s = s * (real)C->ls_decrease_factor;
             }
         } else {
-            s = (real)C->stepsize;
+            s = (real)C->stepsize; s0 = s;
             for (int e = 0; e < N; ++e) xn[e] = clampr(FMA(-s, g[e], yk[e]), (real)C->u_lo[e % m], (real)C->u_hi[e % m]);
             c_n = rollout(X, x0, xn, xref, noise, NULL, NULL);
             nls = 1;
@@ -1148,29 +1173,48 @@ static void solve(const ctx_t* X, const real* x0, const real* xref, const real* 
         sum_ls = sum_ls + (real)nls; sum_s = sum_s + s; nit = k + 1; nls_tot += nls;
         if (trace && k < trace_cap) { trace[4 * k] = c_y; trace[4 * k + 1] = c_n; trace[4 * k + 2] = s; trace[4 * k + 3] = (real)nls; }
         int stop = (FABS(c_n - c_x) <= FMA((real)C->rtol, FABS(c_x), (real)C->atol));
+        const int raised = stop;
+        int suppressed = 0, accepted = 0, restart = 0, clamped = 0;
+        real rs = 0;
         if (c_n < c_x) {
             /* monotone acceptance: the new iterate lowers the cost of the current one */
+            accepted = 1;
             for (int e = 0; e < N; ++e) { d1[e] = yk[e] - xn[e]; d2[e] = xn[e] - xk[e]; }
-            real rs = dot256(d1, d2, N);
-            if (rs > 0) { /* adaptive restart, gradient scheme */
-                kr = 0; plain = 1;
+            rs = dot256(d1, d2, N);
+            if (mu == MUT_RESTART_ON_ZERO ? rs >= 0 : rs > 0) { /* adaptive restart, gradient scheme */
+                kr = 0; plain = 1; restart = 1;
                 for (int e = 0; e < N; ++e) yk[e] = xn[e];
             } else {
-                real b = beta[kr];
-                for (int e = 0; e < N; ++e) yk[e] = clampr(FMA(b, d2[e], xn[e]), (real)C->u_lo[e % m], (real)C->u_hi[e % m]);
+                real b = beta[mu == MUT_BETA_NEXT ? kr + 1 : kr];
+                for (int e = 0; e < N; ++e) {
+                    real v = FMA(b, d2[e], xn[e]);
+                    yk[e] = clampr(v, (real)C->u_lo[e % m], (real)C->u_hi[e % m]);
+                    if (v != yk[e]) clamped += 1;
+                    if (mu == MUT_YK_UNCLAMPED) yk[e] = v;
+                }
                 kr = kr + 1; plain = 0;
             }
-            c_x = c_n; noimp = 0;
+            c_x = c_n; if (mu != MUT_NOIMP_KEPT) noimp = 0;
             memcpy(xk, xn, sizeof(real) * N);
+            stale = (mu == MUT_STALE_GRADIENT);
         } else {
             /* no decrease: drop the momentum and retry from xk with the (already shrunk) step size;
              * only a failed plain gradient step may signal convergence */
-            if (!plain) stop = 0;
-            kr = 0; plain = 1;
+            if (!plain && mu != MUT_STOP_NOT_SUPPRESSED) { suppressed = stop; stop = 0; }
+            if (mu != MUT_KR_KEPT_ON_REJECT) kr = 0;
+            plain = 1;
             memcpy(yk, xk, sizeof(real) * N);
             noimp = noimp + 1;
+            stale = 0;
         }
+        const int tol = stop;
         if (noimp >= C->max_no_improvement_iter) stop = 1;
+        if (E) {
+            E[EV_CN] = c_n; E[EV_S] = s; E[EV_NLS] = (real)nls; E[EV_ARMIJO] = (real)armijo; E[EV_INCREASED] = (real)increased; E[EV_CAPPED] = (real)capped;
+            E[EV_ACCEPTED] = (real)accepted; E[EV_RS] = rs; E[EV_RESTART] = (real)restart; E[EV_YK_STAYED] = (real)(!accepted && E[EV_PLAIN] != 0);
+            E[EV_STOP_RAISED] = (real)raised; E[EV_STOP_SUPPRESSED] = (real)suppressed; E[EV_YK_CLAMPED] = (real)clamped; E[EV_S0] = s0; E[EV_NOIMP] = (real)noimp;
+            E[EV_CAUSE] = (real)(tol ? 2 : stop ? 3 : k + 1 >= C->max_iter ? 1 : 0);
+        }
         if (stop) break;
     }
     real c_best = c_x;
@@ -1236,21 +1280,36 @@ int NAME(cost_du)(const sdempc_cfg* C, const void* blob, const float* x0, const 
 
 #endif /* !ORC_VEC */
 
-int NAME(solve)(const sdempc_cfg* C, const void* blob, const float* x0, const float* xref, const float* noise,
-                const float* u_init, float stepsize_in, float* uopt, float* xevol, float* info8,
-                float* trace /* [trace_cap][4] or NULL */, int trace_cap) {
+/* trace: [trace_cap][4] or NULL; events: [event_cap][orc_event_stride()] or NULL (rows of iterations that did not run stay as they came in) */
+static int solve_io(const sdempc_cfg* C, const void* blob, const float* x0, const float* xref, const float* noise,
+                    const float* u_init, float stepsize_in, float* uopt, float* xevol, float* info8,
+                    float* trace, int trace_cap, float* events, int event_cap) {
     ctx_t X; int rc = ctx_init(&X, C, blob); if (rc) return rc;
     int H = X.H, P = X.P, m = X.m;
     real *rx0 = to_real(x0, NX), *rxr = to_real(xref, (H + 1) * NX), *rn = to_real(noise, (size_t)P * H * NN), *rui = to_real(u_init, H * m);
     real *ruo = malloc(sizeof(real) * H * m), *rxe = malloc(sizeof(real) * (H + 1) * NX), rinfo[8];
     real* rtr = trace ? calloc((size_t)trace_cap * 4, sizeof(real)) : NULL;
-    solve(&X, rx0, rxr, rn, rui, (real)stepsize_in, ruo, rxe, rinfo, rtr, trace_cap);
+    real* rev = events ? to_real(events, (size_t)event_cap * ORC_EV) : NULL;
+    solve(&X, rx0, rxr, rn, rui, (real)stepsize_in, ruo, rxe, rinfo, rtr, trace_cap, rev, event_cap);
     for (int i = 0; i < H * m; ++i) uopt[i] = (float)ruo[i];
     for (int i = 0; i < (H + 1) * NX; ++i) xevol[i] = (float)rxe[i];
     for (int i = 0; i < 8; ++i) info8[i] = (float)rinfo[i];
     if (trace) { for (int i = 0; i < trace_cap * 4; ++i) trace[i] = (float)rtr[i]; free(rtr); }
+    if (events) { for (int i = 0; i < event_cap * ORC_EV; ++i) events[i] = (float)rev[i]; free(rev); }
     free(rx0); free(rxr); free(rn); free(rui); free(ruo); free(rxe); ctx_free(&X);
     return 0;
+}
+
+int NAME(solve)(const sdempc_cfg* C, const void* blob, const float* x0, const float* xref, const float* noise,
+                const float* u_init, float stepsize_in, float* uopt, float* xevol, float* info8,
+                float* trace /* [trace_cap][4] or NULL */, int trace_cap) {
+    return solve_io(C, blob, x0, xref, noise, u_init, stepsize_in, uopt, xevol, info8, trace, trace_cap, NULL, 0);
+}
+
+/* the same solve with the event record of every iteration (tests only) */
+int NAME(solve_events)(const sdempc_cfg* C, const void* blob, const float* x0, const float* xref, const float* noise,
+                       const float* u_init, float stepsize_in, float* uopt, float* xevol, float* info8, float* events, int event_cap) {
+    return solve_io(C, blob, x0, xref, noise, u_init, stepsize_in, uopt, xevol, info8, NULL, 0, events, event_cap);
 }
 
 /* batch of independent solves, one after another on the calling thread (cpu_baseline timing) */

@@ -92,7 +92,7 @@ struct KArgs {
     int f16;                   // mlp_dtype: 0 f32; 1 fp16-operand MLP contractions in the forward step (SPEC.md §9); 2 layer-2 / W2^T contractions as three-limb bf16 splits (§9b)
     // cooperative latency path (one instance over coop_nwg workgroups; workspace owned by the handle, see sdempc_api.cpp)
     int coop_nwg;
-    int coop_ngrp;             // speculative variant: groups of coop_nwg workgroups per instance (2..5)
+    int coop_ngrp;             // speculative variant: groups of coop_nwg workgroups per instance (2..7: SPEC_GROUPS)
     unsigned* coop_bar;        // [B][COOP_BAR_WORDS]: grid-barrier counter, error flag, arrivals of the streamed hand-off, pad (zeroed before every launch)
     float* ustg;               // [B][H][36] per-step control table in global memory (long horizons: keeps it out of LDS), or NULL
     unsigned coop_spin;        // time one grid barrier may wait before it gives up, in ticks of the 100 MHz s_memrealtime clock (10 ns)

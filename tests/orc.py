@@ -3,6 +3,7 @@
 Test infrastructure only (see oracle/sde_mpc_oracle.c header). Builds the library with
 `make -C oracle` when it is missing or older than its source.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -66,15 +67,16 @@ def lib_vec():
 def lib():
     global _LIB
     if _LIB is None:
-        _LIB = C.CDLL(build())
+        L = C.CDLL(build())
         for pre in ("orc_", "orcd_"):
             ft = C.c_float if pre == "orc_" else C.c_double
             for fn in ("rcp", "rsqrt", "tanh", "sigmoid"):
-                f = getattr(_LIB, pre + fn)
+                f = getattr(L, pre + fn)
                 f.argtypes, f.restype = [ft], ft
-        _LIB.orc_log.argtypes, _LIB.orc_log.restype = [C.c_float], C.c_float
-        _LIB.orc_erfinv.argtypes, _LIB.orc_erfinv.restype = [C.c_float], C.c_float
-        _LIB.orc_bits_to_normal.argtypes, _LIB.orc_bits_to_normal.restype = [C.c_uint32], C.c_float
+        L.orc_log.argtypes, L.orc_log.restype = [C.c_float], C.c_float
+        L.orc_erfinv.argtypes, L.orc_erfinv.restype = [C.c_float], C.c_float
+        L.orc_bits_to_normal.argtypes, L.orc_bits_to_normal.restype = [C.c_uint32], C.c_float
+        _LIB = L                         # only a library whose every prototype is set: a failure above fails every caller alike, not the first alone
     return _LIB
 
 
@@ -185,6 +187,23 @@ def hw_eval(func, x):
     return y
 
 
+# columns of the per-iteration event record (oracle/sde_mpc_oracle.c, EV_*), and the one-line-wrong optimisers behind orc_set_mutant (MUT_*)
+EVENT_FIELDS = ("c_y", "c_n", "s", "nls", "armijo", "increased", "capped", "accepted", "rs", "restart", "plain", "kr", "yk_stayed", "stop_raised",
+                "stop_suppressed", "cause", "yk_clamped", "s0", "gsq", "noimp")
+MUTANTS = ("armijo_strict", "shrink_after_last_trial", "cap_before_increase", "restart_on_zero", "kr_kept_on_rejection", "stop_not_suppressed",
+           "stale_gradient_after_accept", "beta_next", "noimp_not_cleared", "yk_unclamped")
+
+
+@contextlib.contextmanager
+def mutant(name):
+    """The float32 checker as the wrong optimiser `name` inside the block (process-wide; off again on the way out, whatever happened)."""
+    lib().orc_set_mutant(1 + MUTANTS.index(name))
+    try:
+        yield
+    finally:
+        lib().orc_set_mutant(0)
+
+
 class Oracle:
     """Oracle bound to one (config, model blob). double=True selects the float64 build."""
 
@@ -241,6 +260,24 @@ class Oracle:
                                _fp(trace) if trace_cap else None, C.c_int(trace_cap))
         assert rc == 0, rc
         return uopt, xevol, info, trace
+
+    def solve_events(self, x0, xref, noise, u_init, stepsize_in):
+        """solve() with the event record of every iteration that ran: -> uopt, xevol, info, float32 [n][len(EVENT_FIELDS)] (columns: EVENT_FIELDS;
+        a solve that the non-finite guard ended has one more row than info[2] says, the guard's)."""
+        x0, xref, noise, u_init = _f32(x0), _f32(xref), _f32(noise), _f32(u_init)
+        uopt = np.zeros((self.H, self.m), np.float32)
+        xevol = np.zeros((self.H + 1, 13), np.float32)
+        info = np.zeros(8, np.float32)
+        stride, cap = self._fn("event_stride")(), max(1, self.cfg_py.max_iter)
+        assert stride == len(EVENT_FIELDS), stride
+        ev = np.full((cap, stride), -1.0, np.float32)          # (no field of a written row is negative except rs, and the cause of one never is)
+        rc = self._fn("solve_events")(C.byref(self.cfg), self._blobbuf, _fp(x0), _fp(xref), _fp(noise), _fp(u_init),
+                                      C.c_float(stepsize_in), _fp(uopt), _fp(xevol), _fp(info), _fp(ev), C.c_int(cap))
+        assert rc == 0, rc
+        n = int(info[2])
+        if n < self.cfg_py.max_iter and ev[n, EVENT_FIELDS.index("cause")] == 4:
+            n += 1
+        return uopt, xevol, info, ev[:n]
 
     def solve_batch(self, x0, xref, noise, u_init, stepsize_in):
         B = x0.shape[0]
