@@ -176,7 +176,7 @@ int sdempc_device_ready(const sdempc_handle* h);
  *                                                                                          Filled: the workspaces (particle x horizon tensor, activation checkpoint,
  *                                                                                          partial sums, control table), the cooperative layouts' per-particle outputs and
  *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs,
- *                                                                                          the closed loop's key / chunk / plant buffers (the chunk buffer includes the
+ *                                                                                          the closed loop's key / chunk / plant / rate-state buffers (the chunk buffer includes the
  *                                                                                          staged disturbance rows and plant-schedule rows of a scenario). (The particle x horizon tensor is
  *                                                                                          zeroed at allocation otherwise; nothing depends on that.) Keep their initial value:
  *                                                                                          - the work counters and the ticket word: running totals, zero at creation by
@@ -409,6 +409,48 @@ int sdempc_closed_loop_batch_scenario(sdempc_handle* h, const sdempc_scenario_cf
                                       float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][Ns]*/,
                                       float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
                                       uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/);
+
+/* ---- batched closed loop through the rate-setpoint interface (SPEC.md §11d) ----------------------
+ * sdempc_closed_loop_batch_scenario flown the way the reference node flies: every solve is post-processed into a table of mean thrust and predicted body rates
+ * (sde_control.py:428-432) that goes to the vehicle next to the motor values, with weight_motors (srv/FollowTraj.srv:10; it starts at 0, sde_control.py:63: rate
+ * setpoints only), and the vehicle's own rate controller tracks the rates far more often than the MPC solves. Here that controller runs on EVERY plant substep,
+ * in front of the motor lag. Episode b carries, beside (x, r, y, s, a), a rate integrator g[3] and a rate tail wt[H][3]. In substep q = i * substeps + jj of period
+ * j, with r = min(i, H-1) and the source this period's solution when q >= D, else the tail (all float32; fma is the fused one):
+ *   u_r = (q >= D ? uopt_j : y)[r];  cbar = (u_r[0] + ... + u_r[m-1]) * inv_m (sum left to right; inv_m = 1.0f / (float)m);
+ *   wsp = q >= D ? xevol_j[r+1][10..12] : wt[r];           e = wsp - x[10..12] (the CURRENT state);
+ *   g_a = clamp(fma(ki_dt_a, e_a, g_a), -integ_limit_a, integ_limit_a);   tau_a = fma(kp_a, e_a, g_a)   (clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v));
+ *   cw_l = clamp(fma(mixer[l][2], tau_2, fma(mixer[l][1], tau_1, fma(mixer[l][0], tau_0, cbar))), u_lo[l], u_hi[l])  (the handle's input bounds);
+ *   c_l = cw_l if motor_weight == 0; u_r[l] if motor_weight == 1; else fma(motor_weight, u_r[l] - cw_l, cw_l);
+ *   then the substep of sdempc_closed_loop_batch_scenario with command c: motor lag, plant step, disturbance fmas.
+ * After the period wt[t] = xevol_j[min(t + S, H-1) + 1][10..12]. The blend is this build's definition of weight_motors / 100 (its PX4-side meaning is not in the
+ * reference). For m = 4 cbar equals the node's np.sum(...) / m bit for bit; for m in {3, 5, 6, 7} the multiplication by inv_m may differ from a division by 1 ulp.
+ * `scenario` may be NULL (no disturbance, plant_of one row). rate_integ_in [B][3] and rate_tail_in [B][H][3] may be NULL (zeros; the tail is never read when
+ * solve_delay is 0). Outputs beside the scenario entry point's: ws [B][T][4] = (cbar, wsp[3]) in force at each tick's first substep (required);
+ * rate_integ_next [B][3] and rate_tail_next [B][H][3] (each may be NULL), which continue the episodes bit for bit together with the other five when T is a
+ * multiple of S. us stays the motor state at each tick's first substep. Every argument is checked before the first HIP call: SDEMPC_EINVAL for struct_size,
+ * a non-finite gain, limit or mixer entry (rows below the handle's motor count), a negative limit, motor_weight outside [0, 1], inv_m neither 0 nor
+ * (float)1 / (float)m, ws NULL, and for everything sdempc_closed_loop_batch_scenario refuses. No ABI version change: detect the entry point by its symbol. */
+typedef struct sdempc_rate_cfg {
+    int32_t struct_size;                     /* sizeof(sdempc_rate_cfg) */
+    float kp[3];                             /* proportional gain per body axis (roll, pitch, yaw) */
+    float ki_dt[3];                          /* integral gain times the plant's step length, formed by the caller in float32 */
+    float integ_limit[3];                    /* bound of |g_a|, >= 0 */
+    float mixer[SDEMPC_MAX_MOTORS][3];       /* motor l takes mixer[l][a] of the torque demand about axis a */
+    float motor_weight;                      /* weight_motors / 100: 0 rate setpoints only .. 1 motor values only */
+    float inv_m;                             /* (float)1 / (float)m as the caller formed it, or 0: the library forms it */
+} sdempc_rate_cfg;
+int sdempc_closed_loop_batch_rate(sdempc_handle* h, const sdempc_rate_cfg* rate, const sdempc_scenario_cfg* scenario /*or NULL*/,
+                                  const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                  const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                  const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                  const float* xref, int32_t xref_solves, int32_t xref_batch,
+                                  const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                  const float* u_act_in /*[B][m] or NULL*/,
+                                  float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][Ns]*/,
+                                  float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                  uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                  const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                  float* ws /*[B][T][4]*/, float* rate_integ_next /*[B][3] or NULL*/, float* rate_tail_next /*[B][H][3] or NULL*/);
 
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so

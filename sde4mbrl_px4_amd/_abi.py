@@ -73,6 +73,12 @@ class SdempcScenarioCfg(C.Structure):
                 ("plant_ticks", C.c_int32)]
 
 
+class SdempcRateCfg(C.Structure):
+    """sdempc_rate_cfg (SPEC.md §11d): gains, limits, mixer and blend of the rate loop of sdempc_closed_loop_batch_rate."""
+    _fields_ = [("struct_size", C.c_int32), ("kp", _F3), ("ki_dt", _F3), ("integ_limit", _F3), ("mixer", (C.c_float * 3) * MAX_MOTORS),
+                ("motor_weight", C.c_float), ("inv_m", C.c_float)]
+
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -196,6 +202,21 @@ def scenario_entry(lib):
     return fn
 
 
+def rate_entry(lib):
+    """sdempc_closed_loop_batch_rate (SPEC.md §11d) with its prototype set: the scenario entry point's arguments behind a rate cfg (the scenario cfg may be
+    NULL), then rate_integ_in, rate_tail_in, ws, rate_integ_next, rate_tail_next. Detected by symbol and only when a call needs it, as scenario_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_rate
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_rate (SPEC.md §11d): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(scenario_entry(lib).argtypes)
+        fp = C.POINTER(C.c_float)
+        fn.argtypes = [a[0], C.POINTER(SdempcRateCfg)] + a[1:] + [fp] * 5
+        fn.restype = C.c_int
+    return fn
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -203,4 +224,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_grad_batch_dev", "sdempc_last_kernel_ms", "sdempc_last_kernel_name", "sdempc_work_counters", "sdempc_solve_status", "sdempc_layout_fallbacks", "sdempc_noise_to_device_layout_dev", "sdempc_traj_to_canonical_dev",
     "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
     "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed", "sdempc_closed_loop_batch_scenario",
+    "sdempc_closed_loop_batch_rate",
 ]

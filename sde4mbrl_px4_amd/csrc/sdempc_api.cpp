@@ -177,6 +177,8 @@ struct sdempc_handle {
     // step length, plant_of) and the plant noise of a tick, one allocation (grown, never shrunk); plant_stage: its host image, alive until the call returns
     DevBuf d_plant;
     std::vector<char> plant_stage;
+    // closed loop through the rate-setpoint interface (sdempc_closed_loop_batch_rate, allocated on its first use): integrator f32[max_batch][3], rate tail f32[max_batch][H][3]
+    DevBuf d_rate;
     DevBuf d_work;            // u64[4] work counters (KArgs::work)
     // cooperative latency path of the solve (allocated on its first use, sized for coop_cap instances)
     DevBuf d_coop_bar, d_coop_pp, d_coop_ck;
@@ -531,11 +533,19 @@ struct ScenarioRun {
     const int32_t* plant_of;    // [Tp][B] or null (identity); read only when the plant set has more than one member
     int Tp;
 };
+// SPEC.md §11d: the rate loop of one sdempc_closed_loop_batch_rate call (host pointers)
+struct RateRun {
+    const sdempc_rate_cfg* cfg;
+    float inv_m;
+    const float *integ_in, *tail_in;    // [B][3] / [B][H][3] or null (zeros)
+    float *ws, *integ_next, *tail_next; // [B][T][4]; [B][3] / [B][H][3] or null
+};
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves);
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows = 1);
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed = nullptr, const ScenarioRun* scen = nullptr);
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, bool* again);
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed = nullptr, const ScenarioRun* scen = nullptr,
+                         const RateRun* rate = nullptr);
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -628,7 +638,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1072,6 +1082,61 @@ int sdempc_closed_loop_batch_scenario(sdempc_handle* h, const sdempc_scenario_cf
     });
 }
 
+int sdempc_closed_loop_batch_rate(sdempc_handle* h, const sdempc_rate_cfg* rc_, const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc,
+                                  const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T,
+                                  const float* x0, const float* xref, int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init,
+                                  const float* stepsize_in, const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next,
+                                  float* stepsize_next, uint32_t* keys_next, float* u_act_next, const float* rate_integ_in, const float* rate_tail_in,
+                                  float* ws, float* rate_integ_next, float* rate_tail_next) {
+    return guarded(h, [&]() -> int {
+    if (!h) return SDEMPC_EINVAL;
+    // every check happens here, before the first HIP call
+    if (!rc_ || rc_->struct_size != (int32_t)sizeof(sdempc_rate_cfg)) return fail(h, SDEMPC_EINVAL, "rate: cfg NULL or struct_size mismatch%s");
+    auto finite = [](float v) { return fabsf(v) < INFINITY; };
+    for (int a = 0; a < 3; ++a) {
+        if (!finite(rc_->kp[a]) || !finite(rc_->ki_dt[a])) return fail(h, SDEMPC_EINVAL, "rate: kp / ki_dt hold a non-finite gain%s");
+        if (!finite(rc_->integ_limit[a])) return fail(h, SDEMPC_EINVAL, "rate: integ_limit holds a non-finite limit%s");
+        if (rc_->integ_limit[a] < 0.0f) return fail(h, SDEMPC_EINVAL, "rate: integ_limit must be >= 0%s");
+    }
+    for (int l = 0; l < h->m; ++l)
+        for (int a = 0; a < 3; ++a)
+            if (!finite(rc_->mixer[l][a])) return fail(h, SDEMPC_EINVAL, "rate: mixer holds a non-finite entry%s");
+    if (!(rc_->motor_weight >= 0.0f) || !(rc_->motor_weight <= 1.0f)) return fail(h, SDEMPC_EINVAL, "rate: motor_weight must be in [0, 1]%s");
+    const float inv_m = 1.0f / (float)h->m;
+    if (rc_->inv_m != 0.0f && !(rc_->inv_m == inv_m)) return fail(h, SDEMPC_EINVAL, "rate: inv_m must be 0 or (float)1 / (float)num_motors%s");
+    if (!ws) return fail(h, SDEMPC_EINVAL, "rate: ws is NULL%s");
+    if (sc && sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg)) return fail(h, SDEMPC_EINVAL, "scenario: struct_size mismatch%s");
+    if (!tc || tc->struct_size != (int32_t)sizeof(sdempc_timing_cfg)) return fail(h, SDEMPC_EINVAL, "timing: cfg NULL or struct_size mismatch%s");
+    if (tc->solve_period < 1) return fail(h, SDEMPC_EINVAL, "timing: solve_period must be >= 1%s");
+    if (!(tc->lag_alpha >= 0.0f) || !(tc->lag_alpha <= 1.0f)) return fail(h, SDEMPC_EINVAL, "timing: lag_alpha must be 0 (off) or in (0, 1]%s");
+    const LoopIo io{B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    int rc = check_loop_args(h, io, T >= 1 ? loop_solves(T, tc->solve_period) : 1);
+    if (rc) return rc;
+    const int Tp = sc ? sc->plant_ticks : 1;
+    if (Tp != 1 && Tp != T) return fail(h, SDEMPC_EINVAL, "scenario: plant_ticks must be 1 or T%s");
+    if (Tp > 1 && !plant_of) return fail(h, SDEMPC_EINVAL, "scenario: plant_of may not be NULL with plant_ticks > 1%s");
+    if ((rc = check_plant_args(h, pc, plant_blobs, plant_blob_bytes, plant_of, B, Tp))) return rc;
+    if (tc->solve_delay < 0 || (long long)tc->solve_delay > (long long)tc->solve_period * pc->substeps)
+        return fail(h, SDEMPC_EINVAL, "timing: solve_delay must be between 0 and solve_period * substeps (one solve at a time)%s");
+    const float* dist = sc ? sc->dist : nullptr;
+    if (dist) {
+        if (sc->dist_ticks != 1 && sc->dist_ticks != T) return fail(h, SDEMPC_EINVAL, "scenario: dist_ticks must be 1 or T%s");
+        if (sc->dist_batch != 1 && sc->dist_batch != B) return fail(h, SDEMPC_EINVAL, "scenario: dist_batch must be 1 or B%s");
+        const size_t nd = (size_t)sc->dist_ticks * sc->dist_batch * SDEMPC_NNOISE;
+        for (size_t e = 0; e < nd; ++e)
+            if (!finite(dist[e])) return fail(h, SDEMPC_EINVAL, "scenario: dist holds a non-finite entry%s");
+    }
+    if ((rc = ensure_device(h))) return rc;
+    const TimedRun timed{tc->solve_period, tc->solve_delay, tc->lag_alpha, u_act_in, u_act_next};
+    const ScenarioRun scen{dist, dist ? sc->dist_ticks : 1, dist ? sc->dist_batch : 1, plant_of, Tp};
+    const RateRun rate{rc_, inv_m, rate_integ_in, rate_tail_in, ws, rate_integ_next, rate_tail_next};
+    PlantRun run;
+    // (a schedule is staged per chunk by the loop; stage_plants takes the set itself)
+    if ((rc = stage_plants(h, *pc, plant_blobs, nullptr, B, &run, tc->solve_period < T ? tc->solve_period : T))) return rc;
+    return closed_loop_attempts(h, io, &run, &timed, &scen, &rate);
+    });
+}
+
 int sdempc_solve_status(sdempc_handle* h) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1159,10 +1224,10 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
     return 0;
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen) {
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -1227,12 +1292,15 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // periods, info and moving references per solve. Without `timed` a period is one tick and every launch is the one it was (S = 1 below).
 // SPEC.md §11c (scen, with timed and plant): the chunk's disturbance rows and plant-schedule rows (one per TICK) are staged per chunk beside the moving
 // references and counted in the chunk's bytes; a schedule of one row is staged once. The plant step is then launch_loop_scenario.
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, bool* again) {
+// SPEC.md §11d (rate, with scen, timed and plant): the integrator and the rate tail live in d_rate (staged from the inputs, or zeroed, with the other inputs, so that a
+// re-run starts from them again) and carry over period and chunk boundaries there; the chunk's setpoint rows ws sit behind its other outputs and are counted in
+// the chunk's bytes. The plant step is then launch_loop_rate, which reads the solve's mean trajectories where the solve left them (d_xmean).
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
     const int Ns = loop_solves(T, S);
-    const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m) + 8;       // floats per reference window / per episode-period of output
+    const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m + (rate ? 4 : 0)) + 8;       // floats per reference window / per episode-period of output
     const bool xref_moves = io.xref_ticks > 1;
     const bool gust = scen && scen->dist, sched = scen && plant && plant->Q.models;        // (one shared plant: nothing to schedule)
     const bool dist_moves = gust && scen->Td > 1, sched_moves = sched && scen->Tp > 1;
@@ -1251,6 +1319,9 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         dev_free(h->d_loop_chunk);
         if ((rc = dev_alloc(h, h->d_loop_chunk, sizeof(float) * chunk_floats, true))) return rc;
     }
+    if (rate && !h->d_rate.p && (rc = dev_alloc(h, h->d_rate, sizeof(float) * (size_t)h->max_batch * 3 * (1 + H), true))) return rc;
+    float* d_integ = (float*)h->d_rate.p;                            // g [B][3] (SPEC.md §11d)
+    float* d_tail = d_integ ? d_integ + 3 * (size_t)h->max_batch : nullptr;   // wt [B][H][3]
     uint32_t* d_keys = (uint32_t*)h->d_loop.p;                      // r_k, advanced in place
     uint32_t* d_sub = d_keys + 2 * (size_t)h->max_batch;             // the solve's noise keys of the tick
     float* d_xi6 = (float*)(d_sub + 2 * (size_t)h->max_batch);       // plant noise of the tick (SPEC.md §11: six values per episode)
@@ -1263,6 +1334,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* c_xref = c_info + (size_t)Pc * B * 8;                     // [Pc or 1][Bx][H+1][13]
     float* c_dist = c_xref + (xref_moves ? (size_t)Pc : 1) * Bx * XR;         // [Tc or 1][Bd][6] (SPEC.md §11c)
     int32_t* c_sched = (int32_t*)(c_dist + (dist_moves ? Tc : 1) * DR);       // [Tc or 1][B]
+    float* c_ws = (float*)(c_sched + (sched_moves ? Tc : 1) * SR);            // [Tc][B][4] (SPEC.md §11d)
     float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place
     hipStream_t st = h->stream;
     // inputs (host vectors live until the synchronisation at the end of the first chunk)
@@ -1292,6 +1364,12 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         }
         HIPCHK(h, hipMemcpyAsync(d_mot, a_in, sizeof(float) * (size_t)B * m, hipMemcpyHostToDevice, st));
     }
+    if (rate) {                // integrator and rate tail start as given, or at zero
+        if (rate->integ_in) HIPCHK(h, hipMemcpyAsync(d_integ, rate->integ_in, sizeof(float) * (size_t)B * 3, hipMemcpyHostToDevice, st));
+        else HIPCHK(h, hipMemsetAsync(d_integ, 0, sizeof(float) * (size_t)B * 3, st));
+        if (rate->tail_in) HIPCHK(h, hipMemcpyAsync(d_tail, rate->tail_in, sizeof(float) * (size_t)B * H * 3, hipMemcpyHostToDevice, st));
+        else HIPCHK(h, hipMemsetAsync(d_tail, 0, sizeof(float) * (size_t)B * H * 3, st));
+    }
     if (!xref_moves) {
         HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
         if (Bx != B) HIPCHK(h, launch_broadcast_rows(c_xref, (float*)h->d_xref.p, (int)XR, B, st));
@@ -1308,7 +1386,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         HIPCHK(h, hipMemcpyAsync(c_sched, row, sizeof(int32_t) * SR, hipMemcpyHostToDevice, st));
     }
     for (int b = 0; b < B; ++b) memcpy(io.xs + (size_t)b * (T + 1) * NX, io.x0 + (size_t)b * NX, sizeof(float) * NX);
-    std::vector<float> hx, hu, hi;
+    std::vector<float> hx, hu, hi, hw;
     for (int j0 = 0; j0 < Ns; j0 += Pc) {
         const int np = Ns - j0 < Pc ? Ns - j0 : Pc;                                  // periods of this chunk
         const size_t k0 = (size_t)j0 * S;
@@ -1349,6 +1427,18 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                     C.plant = sched ? c_sched + (sched_moves ? t0 * SR : 0) : nullptr;
                     C.plant_tick_stride = sched_moves ? B : 0;
                     C.dtp = plant->dt;
+                    if (rate) {
+                        LoopRate W;
+                        const sdempc_rate_cfg& rc_ = *rate->cfg;
+                        for (int a = 0; a < 3; ++a) { W.kp[a] = rc_.kp[a]; W.ki_dt[a] = rc_.ki_dt[a]; W.glim[a] = rc_.integ_limit[a]; }
+                        for (int l = 0; l < 8; ++l) {
+                            for (int a = 0; a < 3; ++a) W.M[l][a] = l < m ? rc_.mixer[l][a] : 0.0f;
+                            W.lo[l] = l < m ? h->cfg.u_lo[l] : 0.0f; W.hi[l] = l < m ? h->cfg.u_hi[l] : 0.0f;
+                        }
+                        W.inv_m = rate->inv_m; W.w = rc_.motor_weight;
+                        W.xevol = (const float*)h->d_xmean.p; W.wt = d_tail; W.g = d_integ; W.ws = c_ws + t0 * B * 4;
+                        HIPCHK(h, launch_loop_rate(plant->k, L, plant->Q, R, C, W, st));
+                    } else
                     HIPCHK(h, launch_loop_scenario(plant->k, L, plant->Q, R, C, st));
                 } else HIPCHK(h, launch_loop_period(plant->k, L, plant->Q, R, st));
             } else if (plant) HIPCHK(h, launch_loop_plant(plant->k, L, plant->Q, st));
@@ -1360,7 +1450,13 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         HIPCHK(h, hipMemcpyAsync(hu.data(), c_us, sizeof(float) * hu.size(), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipMemcpyAsync(hi.data(), c_info, sizeof(float) * hi.size(), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipMemcpyAsync(&gave_up, d_gave_up, sizeof gave_up, hipMemcpyDeviceToHost, st));
+        if (rate) {
+            hw.resize((size_t)nk * B * 4);
+            HIPCHK(h, hipMemcpyAsync(hw.data(), c_ws, sizeof(float) * hw.size(), hipMemcpyDeviceToHost, st));
+        }
         if (j0 + np == Ns) {
+            if (rate && rate->integ_next) HIPCHK(h, hipMemcpyAsync(rate->integ_next, d_integ, sizeof(float) * (size_t)B * 3, hipMemcpyDeviceToHost, st));
+            if (rate && rate->tail_next) HIPCHK(h, hipMemcpyAsync(rate->tail_next, d_tail, sizeof(float) * (size_t)B * H * 3, hipMemcpyDeviceToHost, st));
             if (io.u_next) HIPCHK(h, hipMemcpyAsync(io.u_next, h->d_u.p, sizeof(float) * (size_t)B * H * m, hipMemcpyDeviceToHost, st));
             if (io.stepsize_next) HIPCHK(h, hipMemcpyAsync(io.stepsize_next, h->d_step.p, sizeof(float) * B, hipMemcpyDeviceToHost, st));
             if (io.keys_next) HIPCHK(h, hipMemcpyAsync(io.keys_next, d_keys, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
@@ -1380,6 +1476,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 const size_t r = (size_t)kc * B + b, k = k0 + kc;
                 memcpy(io.xs + ((size_t)b * (T + 1) + k + 1) * NX, &hx[r * NX], sizeof(float) * NX);
                 memcpy(io.us + ((size_t)b * T + k) * m, &hu[r * m], sizeof(float) * m);
+                if (rate) memcpy(rate->ws + ((size_t)b * T + k) * 4, &hw[r * 4], sizeof(float) * 4);
             }
         for (int jc = 0; jc < np; ++jc)
             for (int b = 0; b < B; ++b)

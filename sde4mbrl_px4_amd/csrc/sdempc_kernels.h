@@ -189,6 +189,23 @@ struct LoopScenario {
     float dtp;                  // the plant's step length (what LoopAdvance's KArgs::dt points at)
 };
 hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st);
+// SPEC.md §11d, the closed loop through the rate-setpoint interface: launch_loop_scenario (C.dist / C.plant may be null: no scenario) with the vehicle's inner
+// rate loop in front of the motor lag. On every plant substep the command is formed from the setpoint row in force — mean thrust of the motor row, body rates
+// of this period's mean trajectory (xevol row r + 1) or, before the solution arrives, of the rate tail (row r) — and the plant's CURRENT body rates: PI on the
+// rate error with a clamped integrator, mixer clamped to the input bounds, blend with the motor row. Gains, mixer and bounds travel by value (wave-uniform
+// kernel arguments); lane l < m reads row l of the mixer and the bounds from the argument itself.
+struct LoopRate {
+    float kp[3], ki_dt[3], glim[3];     // per body axis: proportional gain, integral gain times the plant's step length, integrator limit (>= 0)
+    float M[8][3];                      // mixer: motor l takes M[l][a] of the torque demand about axis a
+    float lo[8], hi[8];                 // input bounds of motor l
+    float inv_m;                        // float32(1) / float32(m)
+    float w;                            // blend weight of the motor row: 0 rate setpoints only, 1 motor values only
+    const float* xevol;                 // [B][H+1][13] this period's mean trajectories (rates at [10..12])
+    float* wt;                          // [B][H][3] rate tail: read before the arrival, then rewritten from xevol shifted by LoopPeriod::shift rows
+    float* g;                           // [B][3] integrator state: in, and out after the period's last substep
+    float* ws;                          // [ticks][B][4] (mean thrust, rates[3]) in force at each tick's first substep
+};
+hipError_t launch_loop_rate(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, const LoopRate& W, hipStream_t st);
 // the tick's key schedule (sdempc_prng.hip): keys r_k -> r_{k+1} in place, the solve's noise keys into sub_dev u32[B][2], the plant noise into
 // xi_dev f32[B][substeps][6]: ONE draw normal(p, 6 * substeps) per episode (SPEC.md §7.1: counter i pairs with i + 3 * substeps), row j for substep j
 hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st, int substeps = 1);

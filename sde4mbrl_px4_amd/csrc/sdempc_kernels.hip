@@ -1097,6 +1097,13 @@ hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const Loop
 hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st) {
     return a.fast ? fastm::launch_loop_scenario(a, L, Q, R, C, st) : exact::launch_loop_scenario(a, L, Q, R, C, st);
 }
+// ... and launch_loop_rate (SPEC.md §11d) likewise
+namespace fastm {
+hipError_t launch_loop_rate(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, const LoopRate& W, hipStream_t st);
+}
+hipError_t launch_loop_rate(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, const LoopRate& W, hipStream_t st) {
+    return a.fast ? fastm::launch_loop_rate(a, L, Q, R, C, W, st) : exact::launch_loop_rate(a, L, Q, R, C, W, st);
+}
 #endif
 #else
 SDEMPC_DUO_PAIR(SDEMPC_DUO_DECL)

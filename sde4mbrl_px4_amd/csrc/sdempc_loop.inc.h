@@ -1,5 +1,5 @@
 // sdempc_loop.inc.h — the plant of the batched closed loop (SPEC.md §11): one Euler–Maruyama step of the handle's own model per episode and
-// tick, plus the hand-over to the next tick's solve (applied control, shifted warm start, step size); §11a: a separate plant; §11b: a whole solve period; §11c: a period with a scenario.
+// tick, plus the hand-over to the next tick's solve (applied control, shifted warm start, step size); §11a: a separate plant; §11b: a whole solve period; §11c: a period with a scenario; §11d: a period flown through the rate-setpoint interface.
 // Fragment of sdempc_kernels.hip, translation unit SDEMPC_TU = 4: included inside namespace sdempc::{exact|fastm} (compiled once per math mode).
 //
 // The step is the rollout's own device code: step_fwd at t = 0 on a control table built by block_prepass, i.e. the arithmetic of step 0
@@ -347,6 +347,175 @@ hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const Loop
             if (e != hipSuccess) return e;
         }
         sdempc_loop_scenario_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q, R, C);
+        return hipGetLastError();
+    });
+}
+
+// SPEC.md §11d: the scenario kernel with the vehicle's inner RATE LOOP in front of the motor lag — the loop the node flies through its thrust and body-rate
+// setpoint interface. Body, hand-over and every argument of sdempc_loop_scenario_kernel (runs of ticks per plant, shared or per-episode LDS carves; C.dist and
+// C.plant null when no scenario is given); what differs:
+//  * the command of a substep is no longer a row of the solution but what the rate loop makes of it and of the plant's CURRENT body rates, so it changes on every
+//    substep and block_prepass reruns on every substep, between the same pair of TeamWave::sync();
+//  * the setpoint row (the m motor values, the three rates) sits at wave-uniform addresses and every lane reads all of it: the thrust is the sum of the m values in
+//    index order in every lane (the order is part of the SPEC: no cross-lane reduction), the rate error, the integrator and the torque demand are wave-uniform
+//    values computed redundantly by every lane from lane 0's copy of omega (readfirstlane), and lane l < m forms motor l's command;
+//  * gains, mixer and bounds are kernel arguments: the gains are read at static indices, row l of the mixer and of the bounds by lane l from the UNTOUCHED argument W
+//    (a load from the argument segment at a computed offset; a copy of W indexed at run time would live in scratch), once, before the tick loop;
+//  * the rate tail W.wt is read inside the substep loop and rewritten, shifted like the warm start, after it, by the same wave; the integrator W.g goes in and out
+//    like the motor state; W.ws takes the setpoint in force at each tick's first substep.
+template <int F16>
+__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_rate_kernel(KArgs a0, LoopAdvance L, LoopPlant Q, LoopPeriod R, LoopScenario C, LoopRate W) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int H = L.H, m = a0.m;
+    const int tid = TeamWave::tid();
+    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
+    const bool per = Q.models != nullptr, live = b < L.B;      // (both wave-uniform)
+    Smem sm = per ? carve(smem + (size_t)TeamWave::team() * smem_floats(1, m, 1), 1, m, 0) : carve(smem, 1, m, TeamWave::team());
+    WaveW ww;
+    KArgs* const lk = reinterpret_cast<KArgs*>(smem + TeamWave::IPB * smem_floats(1, m, 1) + (size_t)TeamWave::team() * plant_kargs_floats());
+    if (!per) {                     // (workgroup-uniform: a kernel argument)
+        load_weights(a0, sm, ww, threadIdx.x, TeamWave::BNT);
+        __syncthreads();
+    }
+    if (!live) return;              // (wave-uniform; no workgroup-wide barrier below)
+    const int lane = tid & 63, h = lane >> 5, n = Q.substeps;
+    const bool lag = R.alpha > 0.0f, mine = lane < m, gust = C.dist != nullptr;
+    const float* uo = L.uopt + (size_t)b * H * m;
+    float* yw = L.u + (size_t)b * H * m;
+    const float* xe = W.xevol + (size_t)b * (H + 1) * NX;
+    float* wt = W.wt + (size_t)b * H * 3;
+    float* act = sm.v[5];           // [m] the applied control of the current substep
+    float am = mine ? R.act[(size_t)b * m + lane] : 0.0f;
+    const int ml = mine ? lane : 0;                             // (lanes >= m compute motor 0's command and drop it)
+    const float M0 = W.M[ml][0], M1 = W.M[ml][1], M2 = W.M[ml][2], ulo = W.lo[ml], uhi = W.hi[ml];
+    float g[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) g[e] = W.g[(size_t)b * 3 + e];
+    float x[NX], xn[NX], xi[NN];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
+    const float* xrow = L.xi + (size_t)b * R.xi_ticks * n * NN;
+    const float* drow = gust ? C.dist + (size_t)b * C.dist_ep_stride : nullptr;
+    const int* prow = per ? C.plant + b : nullptr;
+    int i = 0;
+#pragma nounroll
+    while (i < R.ticks) {           // one run of ticks that name the same plant
+        KArgs a = a0;
+        int iend = R.ticks;
+        if (per) {
+            const int p = __builtin_amdgcn_readfirstlane(prow[(size_t)i * C.plant_tick_stride]);
+            iend = i + 1;
+#pragma nounroll
+            while (iend < R.ticks && __builtin_amdgcn_readfirstlane(prow[(size_t)iend * C.plant_tick_stride]) == p) ++iend;
+            a.M = Q.models[p];
+            a.wts = Q.wts + (size_t)p * Q.wts_stride;
+            a.sdt = Q.sdt + (size_t)p * NN;
+            TeamWave::sync();       // (the previous run's reads of the carve are done)
+            load_weights(a, sm, ww, tid, TeamWave::NT);
+            if (tid == 0) { lk->H = 1; lk->m = m; }
+            const float* msrc = reinterpret_cast<const float*>(Q.models + p);
+            float* mdst = reinterpret_cast<float*>(&lk->M);
+            for (int e = tid; e < (int)(sizeof(ModelK) / sizeof(float)); e += TeamWave::NT) mdst[e] = msrc[e];      // (what block_prepass reads)
+            TeamWave::sync();
+        }
+#pragma nounroll
+        for (; i < iend; ++i) {
+            const int r = i < H - 1 ? i : H - 1, row = r * m;
+            float w[NN];
+#pragma unroll
+            for (int e = 0; e < NN; ++e)
+                w[e] = gust ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, drow[(size_t)i * C.dist_tick_stride + e]))) : 0.0f;
+#pragma nounroll
+            for (int jj = 0; jj < n; ++jj) {
+                const int q = i * n + jj;
+                const bool fresh = q >= R.arrive;               // (wave-uniform: the arrival point is the same for every episode)
+                const float* us_ = (fresh ? uo : yw) + row;     // the motor row in force
+                const float* ws_ = fresh ? xe + (size_t)(r + 1) * NX + 10 : wt + (size_t)r * 3;     // the rate row in force
+                float cbar = us_[0];                            // 1. setpoint: thrust, the sum left to right in every lane
+#pragma nounroll
+                for (int l = 1; l < m; ++l) cbar = cbar + us_[l];
+                cbar = cbar * W.inv_m;
+                float tau[3], wsp[3];
+#pragma unroll
+                for (int e = 0; e < 3; ++e) {
+                    wsp[e] = ws_[e];
+                    const float om = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x[10 + e])));
+                    const float er = wsp[e] - om;               // 2. error, against the state of THIS substep
+                    const float gi = FMA(W.ki_dt[e], er, g[e]), gl = W.glim[e];
+                    g[e] = gi < -gl ? -gl : (gi > gl ? gl : gi);        // 3. integrator
+                    tau[e] = FMA(W.kp[e], er, g[e]);            // 4. torque demand, with the updated integrator
+                }
+                const float ul = us_[ml];
+                const float mx = FMA(M2, tau[2], FMA(M1, tau[1], FMA(M0, tau[0], cbar)));
+                const float cw = mx < ulo ? ulo : (mx > uhi ? uhi : mx);       // 5. mixer, clamped to the input bounds
+                const float c = W.w == 0.0f ? cw : (W.w == 1.0f ? ul : FMA(W.w, ul - cw, cw));      // 6. blend
+                if (mine) {
+                    am = lag ? FMA(R.alpha, c - am, am) : c;
+                    act[lane] = am;
+                }
+                TeamWave::sync();       // (the row is written, the previous substep's reads of the control table are done)
+                if (per) block_prepass<TeamWave>(*lk, sm, act, tid);
+                else block_prepass<TeamWave>(a0, sm, act, tid);
+                TeamWave::sync();
+                if (jj == 0) {
+                    if (mine) L.us[((size_t)i * L.B + b) * m + lane] = am;
+                    if (lane == 0) {
+                        float* wo = W.ws + ((size_t)i * L.B + b) * 4;
+                        wo[0] = cbar; wo[1] = wsp[0]; wo[2] = wsp[1]; wo[3] = wsp[2];
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < NN; ++e) xi[e] = xrow[q * NN + e];
+                StepAux A;
+                step_fwd<F16, false>(a, sm, ww, 0, h, lane, x, xi, xn, A);
+#pragma unroll
+                for (int e = 0; e < NX; ++e) x[e] = xn[e];
+                if (gust) {
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) { x[3 + e] = FMA(w[e], C.dtp, x[3 + e]); x[10 + e] = FMA(w[3 + e], C.dtp, x[10 + e]); }
+                }
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int e = 0; e < NX; ++e) L.xs[((size_t)i * L.B + b) * NX + e] = x[e];
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) L.x[(size_t)b * NX + i] = x[i];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) W.g[(size_t)b * 3 + e] = g[e];
+        L.step[b] = L.info[(size_t)b * 8 + 1];
+        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
+    }
+    if (mine) R.act[(size_t)b * m + lane] = am;
+    for (int e = tid; e < H * m; e += TeamWave::NT) {   // y_{j+1}: row t = uopt_j[min(t + S, H - 1)]
+        const int t = e / m, ts = t + R.shift < H ? t + R.shift : H - 1;
+        yw[e] = uo[ts * m + (e - t * m)];
+    }
+    for (int e = tid; e < H * 3; e += TeamWave::NT) {   // rate tail: row t = xevol_j[min(t + S, H - 1) + 1][10..12]
+        const int t = e / 3, ts = t + R.shift < H ? t + R.shift : H - 1;
+        wt[e] = xe[(size_t)(ts + 1) * NX + 10 + (e - t * 3)];
+    }
+}
+
+hipError_t launch_loop_rate(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, const LoopRate& W, hipStream_t st) {
+    if (L.B < 1 || L.H != a.H || Q.substeps < 1 || (Q.models && (!Q.wts || !Q.sdt || Q.wts_stride < BLOB_FLOATS + VJP_BASE))) return hipErrorInvalidValue;
+    if (!R.act || R.ticks < 1 || R.xi_ticks < R.ticks || R.shift < 1 || R.shift > a.H || R.arrive < 0 || !(R.alpha >= 0.0f && R.alpha <= 1.0f)) return hipErrorInvalidValue;
+    if ((Q.models && !C.plant) || (C.plant_tick_stride != 0 && C.plant_tick_stride != L.B)) return hipErrorInvalidValue;
+    if (C.dist_tick_stride < 0 || (C.dist_ep_stride != 0 && C.dist_ep_stride != NN) || !(C.dtp > 0.0f)) return hipErrorInvalidValue;
+    if (!W.xevol || !W.wt || !W.g || !W.ws || !(W.w >= 0.0f && W.w <= 1.0f) || a.m < 1 || a.m > 8) return hipErrorInvalidValue;
+    KArgs k = a;
+    k.H = 1;
+    const size_t sb = Q.models ? TeamWave::IPB * (smem_bytes(1, k.m, 1) + sizeof(float) * plant_kargs_floats()) : smem_bytes(1, k.m, TeamWave::IPB);
+    const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
+    return with_f16(k.f16, [&](auto F16) {
+        if (sb > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)sdempc_loop_rate_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
+            if (e != hipSuccess) return e;
+        }
+        sdempc_loop_rate_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q, R, C, W);
         return hipGetLastError();
     });
 }

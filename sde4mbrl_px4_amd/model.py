@@ -15,6 +15,12 @@ import numpy as np
 from ._abi import BLOB_FLOATS, BLOB_HEADER_INTS, BLOB_MAGIC, HID, MAX_MOTORS, NNOISE
 
 
+def rate_mixer(rotor_x, rotor_y, rotor_dir) -> np.ndarray:
+    """f32[m][3]: the float64 pseudo-inverse of [[ry_j], [-rx_j], [dir_j]] (3 x m, the float32 rotor tables as a blob holds them), rounded to float32."""
+    E = np.stack([np.asarray(rotor_y, np.float32), -np.asarray(rotor_x, np.float32), np.asarray(rotor_dir, np.float32)]).astype(np.float64)
+    return np.ascontiguousarray(np.linalg.pinv(E), dtype=np.float32)
+
+
 @dataclass
 class RotorSDEModel:
     num_motors: int
@@ -88,6 +94,12 @@ class RotorSDEModel:
         kw["sigma"] = scale(self.sigma, sigma)
         kw["W2"] = scale(self.W2, residual)
         return RotorSDEModel(**kw)
+
+    def rate_mixer(self) -> np.ndarray:
+        """The default mixer of the rate loop (SPEC.md §11d), f32[m][3]: column a spreads a torque demand about body axis a over the motors. It is the
+        float64 pseudo-inverse of the 3 x m effectiveness matrix whose rows are the signs and arms of §5.1's torque sums — roll `ry_j`, pitch `-rx_j`,
+        yaw `dir_j` — rounded to float32."""
+        return rate_mixer(self.rotor_x, self.rotor_y, self.rotor_dir)
 
     def to_blob(self) -> bytes:
         m = self.num_motors

@@ -138,7 +138,7 @@ class MpcProblem:
 
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
-                 plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None):
+                 plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -153,7 +153,10 @@ class MpcProblem:
         disturbance / plant_of: a scenario (SPEC.md §11c) — disturbance f32[T][6] or f32[6], an external linear (world) and angular (body) acceleration per
         tick GIVEN IN THE FRAME OF x (under convert_to_enu the vector rules of enu2ned take it into the solver's frame, exactly: (x, y, z) -> (y, x, -z) and
         (wx, wy, wz) -> (wx, -wy, -wz)); plant_of int[T] names, per tick, which member of the sequence `plant` flies the tick (a payload dropped at
-        tick k: plant=[loaded, empty], plant_of = [0] * k + [1] * (T - k)). Either one makes the call the timed one (info per solve)."""
+        tick k: plant=[loaded, empty], plant_of = [0] * k + [1] * (T - k)). Either one makes the call the timed one (info per solve).
+        rate_loop: a solver.RateLoop (SPEC.md §11d) — the vehicle flies the solution's thrust and body-rate setpoints through its own rate loop on every plant
+        substep, as behind the node's setpoint interface; passed through, the call is then the timed one. Gains and mixer act on body-frame quantities of
+        the solver's frame. The returned values are the same five."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -186,7 +189,7 @@ class MpcProblem:
         xs, us, info, u_next, s_next, k_next = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
             plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag,
-            disturbance=disturbance, plant_of=plant_of)[:6]
+            disturbance=disturbance, plant_of=plant_of, **({} if rate_loop is None else {"rate_loop": rate_loop}))[:6]
         xs = xs[0]
         if self.convert_to_enu:
             xs = np.concatenate([x[None], enu2ned(xs[1:], np)], axis=0)

@@ -41,6 +41,44 @@ def _abi_enum(table, value, what):
     return int(value)
 
 
+class RateLoop:
+    """The vehicle's inner body-rate loop behind the node's thrust and body-rate setpoint interface (SPEC.md §11d): a PI controller on the rate error per
+    body axis, a mixer that spreads its torque demand over the motors around the solution's mean thrust, and the node's `weight_motors` blend between
+    that command and the solution's own motor values. kp / ki / integ_limit: a scalar (all three axes) or three values (roll, pitch, yaw); ki is per second
+    (the loop integrates with the plant's step length); integ_limit bounds the integrator state (0: no integral action survives). mixer f32[m][3]: None
+    takes the controller model's rate_mixer(). motor_weight in [0, 1] is weight_motors / 100: 0 flies the rate setpoints only (the node's default), 1 the
+    motor values only (the integrator still runs). No D-term, no gyro filter, no attitude loop."""
+
+    def __init__(self, kp, ki=0.0, integ_limit=0.0, mixer=None, motor_weight=0.0):
+        def axes(v, what):
+            a = np.asarray(v, np.float32)
+            if a.ndim == 0:
+                a = np.full(3, a, np.float32)
+            if a.shape != (3,):
+                raise ValueError(f"RateLoop: {what} must be a scalar or three values, got shape {a.shape}")
+            if not np.isfinite(a).all():
+                raise ValueError(f"RateLoop: {what} holds a non-finite value")
+            return np.ascontiguousarray(a)
+
+        self.kp, self.ki, self.integ_limit = axes(kp, "kp"), axes(ki, "ki"), axes(integ_limit, "integ_limit")
+        if (self.integ_limit < 0).any():
+            raise ValueError("RateLoop: integ_limit must be >= 0")
+        self.motor_weight = float(np.float32(motor_weight))
+        if not (0.0 <= self.motor_weight <= 1.0):
+            raise ValueError("RateLoop: motor_weight must be in [0, 1] (the node's weight_motors / 100)")
+        self.mixer = None
+        if mixer is not None:
+            mx = np.ascontiguousarray(mixer, dtype=np.float32)
+            if mx.ndim != 2 or mx.shape[1] != 3 or not (1 <= mx.shape[0] <= _abi.MAX_MOTORS):
+                raise ValueError(f"RateLoop: mixer must be f32[m][3], got {mx.shape}")
+            if not np.isfinite(mx).all():
+                raise ValueError("RateLoop: mixer holds a non-finite value")
+            self.mixer = mx
+
+    def __repr__(self):
+        return f"RateLoop(kp={self.kp.tolist()}, ki={self.ki.tolist()}, integ_limit={self.integ_limit.tolist()}, mixer={self.mixer!r}, motor_weight={self.motor_weight})"
+
+
 class SdeMpcSolver:
     """One solver handle = one (MPC config, model). Single-threaded, like the reference's solver
     objects (one blocking call at a time, sde_control.py:420)."""
@@ -164,7 +202,8 @@ class SdeMpcSolver:
         return uopt, xevol, np.frombuffer(info, dtype=np.float32).reshape(B, 8).copy()
 
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
-                    plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None):
+                    plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
+                    rate_loop=None, rate_integ_in=None, rate_tail_in=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -192,7 +231,18 @@ class SdeMpcSolver:
         substep of tick k: fma(w, dt_plant, .). A [B][6] array is not accepted (it cannot be told from [T][6]). plant_of int[T][B] names the plant of every
         tick: a switch at a tick start changes the vehicle only (state, motor state, keys and warm start carry over), and the set may then hold up to B * T
         plants. With disturbance=None and a 1-D plant_of the call takes the routes above, unchanged; otherwise it is the timed call (7-tuple, xref and info
-        per solve, the plant defaulting to the handle's own model) with the schedules applied."""
+        per solve, the plant defaulting to the handle's own model) with the schedules applied.
+
+        rate_loop / rate_integ_in / rate_tail_in (SPEC.md §11d, sdempc_closed_loop_batch_rate): the loop the node flies at its default weight_motors = 0 —
+        the solution goes to the vehicle as a table of mean thrust and predicted body rates, and the vehicle's own rate loop (a RateLoop: PI on the rate
+        error, mixer, blend with the motor values) turns it into motor commands on EVERY plant substep, from the plant's current body rates. So between two
+        solves the vehicle still rejects gusts and model error. With rate_loop given the call is the timed / scenario call (xref and info per solve, the
+        plant defaulting to the handle's own model, every keyword above still applies) and TEN values come back: the seven above, then
+        ws [B][T][4] (the setpoint (mean thrust, rates[3]) in force at each tick's first substep), rate_integ_next [B][3] (the integrator state) and
+        rate_tail_next [B][H][3] (the last solve's predicted rates, shifted as the warm start is: what is flown until the next solution arrives). Carrying
+        those two back in as rate_integ_in / rate_tail_in (default: zeros) with the five items above continues the episodes bit for bit when T is a
+        multiple of solve_period. us stays the motor state at each tick's first substep. rate_integ_in / rate_tail_in without rate_loop raise ValueError;
+        with rate_loop=None nothing of this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -223,7 +273,11 @@ class SdeMpcSolver:
             if plant is None:
                 raise ValueError("closed_loop: plant_of needs plant=...")
         scenario = dist is not None or sched is not None
-        timed = scenario or not (solve_period == 1 and solve_delay == 0 and motor_lag == 0.0 and u_act_in is None)
+        if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
+            raise ValueError("closed_loop: rate_integ_in / rate_tail_in need rate_loop=...")
+        if rate_loop is not None and not isinstance(rate_loop, RateLoop):
+            raise ValueError("closed_loop: rate_loop must be a RateLoop")
+        timed = scenario or rate_loop is not None or not (solve_period == 1 and solve_delay == 0 and motor_lag == 0.0 and u_act_in is None)
         Ns = T
         if timed:
             S_, D_, alpha = int(solve_period), int(solve_delay), float(np.float32(motor_lag))
@@ -282,6 +336,26 @@ class SdeMpcSolver:
         if timed:
             tc = _abi.SdempcTimingCfg(C.sizeof(_abi.SdempcTimingCfg), S_, D_, alpha)
             a_next = np.zeros((B, self.m), np.float32)
+            if rate_loop is not None:
+                rc_, keep = self._rate_cfg(rate_loop, plant_substeps, plant_dt)
+                g_p = t_p = None
+                if rate_integ_in is not None:
+                    rate_integ_in = _f32(rate_integ_in, (B, 3))
+                    g_p = _fp(rate_integ_in)
+                if rate_tail_in is not None:
+                    rate_tail_in = _f32(rate_tail_in, (B, self.H, 3))
+                    t_p = _fp(rate_tail_in)
+                sc = None
+                if scenario:
+                    sc = _abi.SdempcScenarioCfg(C.sizeof(_abi.SdempcScenarioCfg), None if dist is None else _fp(dist), 1 if dist is None else dist.shape[0],
+                                                1 if dist is None else dist.shape[1], 1 if sched is None else sched.shape[0])
+                ws = np.zeros((B, max(T, 0), 4), np.float32)
+                g_next = np.zeros((B, 3), np.float32)
+                t_next = np.zeros((B, self.H, 3), np.float32)
+                self._check(_abi.rate_entry(self.lib)(self._h, C.byref(rc_), None if sc is None else C.byref(sc), C.byref(tc), C.byref(pc),
+                                                      C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *tail[:9], a_p, *tail[9:], _fp(a_next),
+                                                      g_p, t_p, _fp(ws), _fp(g_next), _fp(t_next)))
+                return xs, us, info, u_next, s_next, k_next, a_next, ws, g_next, t_next
             if scenario:
                 sc = _abi.SdempcScenarioCfg(C.sizeof(_abi.SdempcScenarioCfg), None if dist is None else _fp(dist), 1 if dist is None else dist.shape[0],
                                             1 if dist is None else dist.shape[1], 1 if sched is None else sched.shape[0])
@@ -293,6 +367,30 @@ class SdeMpcSolver:
             return xs, us, info, u_next, s_next, k_next, a_next
         self._check(self.lib.sdempc_closed_loop_batch_plant(self._h, C.byref(pc), C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *tail))
         return xs, us, info, u_next, s_next, k_next
+
+    def _rate_cfg(self, rate_loop, plant_substeps, plant_dt):
+        """sdempc_rate_cfg of a RateLoop for this handle: ki_dt = float32(ki) * float32(dt_plant), the default mixer from the controller's rotor tables (as
+        the blob holds them), inv_m = float32(1) / float32(m)."""
+        m = self.m
+        mixer = rate_loop.mixer
+        if mixer is None:
+            from .model import rate_mixer
+            f = np.frombuffer(self._blob.raw, np.float32, _abi.BLOB_FLOATS, 4 * _abi.BLOB_HEADER_INTS)
+            mixer = rate_mixer(f[16:16 + m], f[24:24 + m], f[32:32 + m])
+        if mixer.shape != (m, 3):
+            raise ValueError(f"closed_loop: rate_loop.mixer must be f32[{m}][3], got {mixer.shape}")
+        dt = np.float32(plant_dt) if plant_dt is not None and float(plant_dt) != 0.0 else np.float32(self.cfg_py.time_steps[0]) / np.float32(int(plant_substeps))
+        rc = _abi.SdempcRateCfg()
+        rc.struct_size = C.sizeof(_abi.SdempcRateCfg)
+        ki_dt = (rate_loop.ki * np.float32(dt)).astype(np.float32)
+        for a in range(3):
+            rc.kp[a], rc.ki_dt[a], rc.integ_limit[a] = float(rate_loop.kp[a]), float(ki_dt[a]), float(rate_loop.integ_limit[a])
+        for l in range(m):
+            for a in range(3):
+                rc.mixer[l][a] = float(mixer[l, a])
+        rc.motor_weight = rate_loop.motor_weight
+        rc.inv_m = float(np.float32(1.0) / np.float32(m))
+        return rc, mixer
 
     def noise_from_keys(self, keys):
         """The canonical noise tensors f32[B][P][H][6] the device draws from keys (inspection / parity tests)."""

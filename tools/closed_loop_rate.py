@@ -18,8 +18,10 @@
   5. --disturbance / --plant-switch K: the same loops with a scenario (SPEC.md §11c, sdempc_closed_loop_batch_scenario) — a random disturbance row per tick
      and episode, and / or every episode changing its plant at tick K (--plant self or one: to one perturbed vehicle; per-episode: to its neighbour's).
      They apply to --small-batch and to the C2 loop, where --timed / --period / --delay / --lag now apply too (one reference window per solve).
+  6. --rate-loop: the same loops flown through the rate-setpoint interface (SPEC.md §11d, sdempc_closed_loop_batch_rate): a PI rate loop with the model's own mixer on
+     every plant substep (the control table is re-formed on every substep). Applies to --small-batch and to the C2 loop.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
-                                        [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K]
+                                        [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -52,6 +54,7 @@ ap.add_argument("--delay", type=int, default=0)
 ap.add_argument("--lag", type=float, default=0.0)
 ap.add_argument("--disturbance", action="store_true", help="a disturbance row per tick and episode (SPEC.md §11c)")
 ap.add_argument("--plant-switch", type=int, default=-1, metavar="K", help="every episode changes its plant at tick K (SPEC.md §11c; needs --plant self, one or per-episode)")
+ap.add_argument("--rate-loop", action="store_true", help="fly the thrust and body-rate setpoints through a PI rate loop (SPEC.md §11d)")
 a = ap.parse_args()
 model = synthetic_iris()
 if a.plant == "own" and a.substeps != 1:
@@ -73,6 +76,9 @@ def plant_kw(B):
 def scenario_kw(kw, B, T):
     """kw plus the schedules of --disturbance / --plant-switch for a call of T ticks"""
     kw = dict(kw)
+    if a.rate_loop:
+        from sde4mbrl_px4_amd.solver import RateLoop
+        kw["rate_loop"] = RateLoop(kp=[0.03, 0.03, 0.08], ki=[0.3, 0.3, 0.5], integ_limit=0.05)
     if a.disturbance:
         kw["disturbance"] = np.random.default_rng(2).uniform(-2.0, 2.0, (T, B, 6)).astype(np.float32)
     if a.plant_switch >= 0:
@@ -100,6 +106,8 @@ if a.disturbance:
     tag += " disturbance"
 if a.plant_switch >= 0:
     tag += f" plant-switch at {a.plant_switch}"
+if a.rate_loop:
+    tag += " rate-loop"
 
 if a.small_batch:
     cfg = load_mpc_config(os.path.join(ROOT, "configs", "c1_iris_posctrl_h20_p32.yaml"))
