@@ -514,7 +514,7 @@ struct LoopIo {
 };
 // SPEC.md §11a: the plant set of one sdempc_closed_loop_batch_plant call, staged on the device (stage_plants)
 struct PlantRun {
-    KArgs k;        // argument block of launch_loop_plant: the handle's with the plant's arithmetic and step length (one shared plant: its M / wts / sdt too)
+    KArgs k;        // argument block of launch_loop: the handle's with the plant's arithmetic and step length (one shared plant: its M / wts / sdt too)
     LoopPlant Q;
     float* xi;      // [B][substeps][6] plant noise of a tick
     float dt;       // the plant's step length
@@ -541,10 +541,28 @@ struct RateRun {
     float *ws, *integ_next, *tail_next; // [B][T][4]; [B][3] / [B][H][3] or null
 };
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
+// One closed-loop call as its entry point describes it. The five entry points are five nested layers (SPEC.md §11, §11a .. §11d): each takes everything the one
+// below it takes, so `layer` says which parts are present; the arguments of an absent part stay null.
+enum LoopLayer { LOOP_PLAIN, LOOP_PLANT, LOOP_TIMED, LOOP_SCENARIO, LOOP_RATE };
+struct LoopCall {
+    LoopLayer layer;
+    LoopIo io;                                  // (from LOOP_TIMED on, xref_ticks counts SOLVES)
+    const sdempc_plant_cfg* pc;                 // LOOP_PLANT ..: the plant set
+    const void* const* plant_blobs;
+    const size_t* plant_blob_bytes;
+    const int32_t* plant_of;                    // [B]; from LOOP_SCENARIO on [plant_ticks][B]
+    const sdempc_timing_cfg* tc;                // LOOP_TIMED ..
+    const float* u_act_in;
+    float* u_act_next;
+    const sdempc_scenario_cfg* sc;              // LOOP_SCENARIO ..; LOOP_RATE alone takes NULL (no scenario)
+    const sdempc_rate_cfg* rc;                  // LOOP_RATE
+    const float *rate_integ_in, *rate_tail_in;
+    float *ws, *rate_integ_next, *rate_tail_next;
+};
+int closed_loop_call(sdempc_handle* h, const LoopCall& c);
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves);
-int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows = 1);
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed = nullptr, const ScenarioRun* scen = nullptr,
-                         const RateRun* rate = nullptr);
+int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate);
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
@@ -996,11 +1014,10 @@ int sdempc_closed_loop_batch(sdempc_handle* h, int32_t B, int32_t T, const float
                              const uint32_t* keys, const float* u_init, const float* stepsize_in, float* xs, float* us, sdempc_info* info,
                              float* u_next, float* stepsize_next, uint32_t* keys_next) {
     return guarded(h, [&]() -> int {
-    const LoopIo io{B, T, xref_ticks, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
-    int rc = check_loop_args(h, io, T);
-    if (rc) return rc;
-    if ((rc = ensure_device(h))) return rc;
-    return closed_loop_attempts(h, io, nullptr);       // no plant set: the handle's own model, one step of time_steps[0] per tick (SPEC.md §11)
+    LoopCall c{};                   // no plant set: the handle's own model, one step of time_steps[0] per tick (SPEC.md §11)
+    c.layer = LOOP_PLAIN;
+    c.io = {B, T, xref_ticks, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    return closed_loop_call(h, c);
     });
 }
 
@@ -1009,14 +1026,11 @@ int sdempc_closed_loop_batch_plant(sdempc_handle* h, const sdempc_plant_cfg* pc,
                                    int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in, float* xs, float* us,
                                    sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next) {
     return guarded(h, [&]() -> int {
-    const LoopIo io{B, T, xref_ticks, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
-    int rc = check_loop_args(h, io, T);
-    if (rc) return rc;
-    if ((rc = check_plant_args(h, pc, plant_blobs, plant_blob_bytes, plant_of, B))) return rc;      // (before the first HIP call)
-    if ((rc = ensure_device(h))) return rc;
-    PlantRun run;
-    if ((rc = stage_plants(h, *pc, plant_blobs, plant_of, B, &run))) return rc;
-    return closed_loop_attempts(h, io, &run);
+    LoopCall c{};
+    c.layer = LOOP_PLANT;
+    c.io = {B, T, xref_ticks, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    return closed_loop_call(h, c);
     });
 }
 
@@ -1026,22 +1040,12 @@ int sdempc_closed_loop_batch_timed(sdempc_handle* h, const sdempc_timing_cfg* tc
                                    const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next, float* stepsize_next,
                                    uint32_t* keys_next, float* u_act_next) {
     return guarded(h, [&]() -> int {
-    if (!h) return SDEMPC_EINVAL;
-    // every check happens here, before the first HIP call
-    if (!tc || tc->struct_size != (int32_t)sizeof(sdempc_timing_cfg)) return fail(h, SDEMPC_EINVAL, "timing: cfg NULL or struct_size mismatch%s");
-    if (tc->solve_period < 1) return fail(h, SDEMPC_EINVAL, "timing: solve_period must be >= 1%s");
-    if (!(tc->lag_alpha >= 0.0f) || !(tc->lag_alpha <= 1.0f)) return fail(h, SDEMPC_EINVAL, "timing: lag_alpha must be 0 (off) or in (0, 1]%s");
-    const LoopIo io{B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
-    int rc = check_loop_args(h, io, T >= 1 ? loop_solves(T, tc->solve_period) : 1);
-    if (rc) return rc;
-    if ((rc = check_plant_args(h, pc, plant_blobs, plant_blob_bytes, plant_of, B))) return rc;
-    if (tc->solve_delay < 0 || (long long)tc->solve_delay > (long long)tc->solve_period * pc->substeps)
-        return fail(h, SDEMPC_EINVAL, "timing: solve_delay must be between 0 and solve_period * substeps (one solve at a time)%s");
-    if ((rc = ensure_device(h))) return rc;
-    const TimedRun timed{tc->solve_period, tc->solve_delay, tc->lag_alpha, u_act_in, u_act_next};
-    PlantRun run;
-    if ((rc = stage_plants(h, *pc, plant_blobs, plant_of, B, &run, tc->solve_period < T ? tc->solve_period : T))) return rc;
-    return closed_loop_attempts(h, io, &run, &timed);
+    LoopCall c{};
+    c.layer = LOOP_TIMED;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    return closed_loop_call(h, c);
     });
 }
 
@@ -1051,34 +1055,13 @@ int sdempc_closed_loop_batch_scenario(sdempc_handle* h, const sdempc_scenario_cf
                                       const float* stepsize_in, const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next,
                                       float* stepsize_next, uint32_t* keys_next, float* u_act_next) {
     return guarded(h, [&]() -> int {
-    if (!h) return SDEMPC_EINVAL;
-    // every check happens here, before the first HIP call
-    if (!sc || sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg)) return fail(h, SDEMPC_EINVAL, "scenario: cfg NULL or struct_size mismatch%s");
-    if (!tc || tc->struct_size != (int32_t)sizeof(sdempc_timing_cfg)) return fail(h, SDEMPC_EINVAL, "timing: cfg NULL or struct_size mismatch%s");
-    if (tc->solve_period < 1) return fail(h, SDEMPC_EINVAL, "timing: solve_period must be >= 1%s");
-    if (!(tc->lag_alpha >= 0.0f) || !(tc->lag_alpha <= 1.0f)) return fail(h, SDEMPC_EINVAL, "timing: lag_alpha must be 0 (off) or in (0, 1]%s");
-    const LoopIo io{B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
-    int rc = check_loop_args(h, io, T >= 1 ? loop_solves(T, tc->solve_period) : 1);
-    if (rc) return rc;
-    if (sc->plant_ticks != 1 && sc->plant_ticks != T) return fail(h, SDEMPC_EINVAL, "scenario: plant_ticks must be 1 or T%s");
-    if (sc->plant_ticks > 1 && !plant_of) return fail(h, SDEMPC_EINVAL, "scenario: plant_of may not be NULL with plant_ticks > 1%s");
-    if ((rc = check_plant_args(h, pc, plant_blobs, plant_blob_bytes, plant_of, B, sc->plant_ticks))) return rc;
-    if (tc->solve_delay < 0 || (long long)tc->solve_delay > (long long)tc->solve_period * pc->substeps)
-        return fail(h, SDEMPC_EINVAL, "timing: solve_delay must be between 0 and solve_period * substeps (one solve at a time)%s");
-    if (sc->dist) {
-        if (sc->dist_ticks != 1 && sc->dist_ticks != T) return fail(h, SDEMPC_EINVAL, "scenario: dist_ticks must be 1 or T%s");
-        if (sc->dist_batch != 1 && sc->dist_batch != B) return fail(h, SDEMPC_EINVAL, "scenario: dist_batch must be 1 or B%s");
-        const size_t nd = (size_t)sc->dist_ticks * sc->dist_batch * SDEMPC_NNOISE;
-        for (size_t e = 0; e < nd; ++e)
-            if (!(fabsf(sc->dist[e]) < INFINITY)) return fail(h, SDEMPC_EINVAL, "scenario: dist holds a non-finite entry%s");
-    }
-    if ((rc = ensure_device(h))) return rc;
-    const TimedRun timed{tc->solve_period, tc->solve_delay, tc->lag_alpha, u_act_in, u_act_next};
-    const ScenarioRun scen{sc->dist, sc->dist ? sc->dist_ticks : 1, sc->dist ? sc->dist_batch : 1, plant_of, sc->plant_ticks};
-    PlantRun run;
-    // (a schedule is staged per chunk by the loop; stage_plants takes the set itself)
-    if ((rc = stage_plants(h, *pc, plant_blobs, nullptr, B, &run, tc->solve_period < T ? tc->solve_period : T))) return rc;
-    return closed_loop_attempts(h, io, &run, &timed, &scen);
+    LoopCall c{};
+    c.layer = LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    return closed_loop_call(h, c);
     });
 }
 
@@ -1089,51 +1072,14 @@ int sdempc_closed_loop_batch_rate(sdempc_handle* h, const sdempc_rate_cfg* rc_, 
                                   float* stepsize_next, uint32_t* keys_next, float* u_act_next, const float* rate_integ_in, const float* rate_tail_in,
                                   float* ws, float* rate_integ_next, float* rate_tail_next) {
     return guarded(h, [&]() -> int {
-    if (!h) return SDEMPC_EINVAL;
-    // every check happens here, before the first HIP call
-    if (!rc_ || rc_->struct_size != (int32_t)sizeof(sdempc_rate_cfg)) return fail(h, SDEMPC_EINVAL, "rate: cfg NULL or struct_size mismatch%s");
-    auto finite = [](float v) { return fabsf(v) < INFINITY; };
-    for (int a = 0; a < 3; ++a) {
-        if (!finite(rc_->kp[a]) || !finite(rc_->ki_dt[a])) return fail(h, SDEMPC_EINVAL, "rate: kp / ki_dt hold a non-finite gain%s");
-        if (!finite(rc_->integ_limit[a])) return fail(h, SDEMPC_EINVAL, "rate: integ_limit holds a non-finite limit%s");
-        if (rc_->integ_limit[a] < 0.0f) return fail(h, SDEMPC_EINVAL, "rate: integ_limit must be >= 0%s");
-    }
-    for (int l = 0; l < h->m; ++l)
-        for (int a = 0; a < 3; ++a)
-            if (!finite(rc_->mixer[l][a])) return fail(h, SDEMPC_EINVAL, "rate: mixer holds a non-finite entry%s");
-    if (!(rc_->motor_weight >= 0.0f) || !(rc_->motor_weight <= 1.0f)) return fail(h, SDEMPC_EINVAL, "rate: motor_weight must be in [0, 1]%s");
-    const float inv_m = 1.0f / (float)h->m;
-    if (rc_->inv_m != 0.0f && !(rc_->inv_m == inv_m)) return fail(h, SDEMPC_EINVAL, "rate: inv_m must be 0 or (float)1 / (float)num_motors%s");
-    if (!ws) return fail(h, SDEMPC_EINVAL, "rate: ws is NULL%s");
-    if (sc && sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg)) return fail(h, SDEMPC_EINVAL, "scenario: struct_size mismatch%s");
-    if (!tc || tc->struct_size != (int32_t)sizeof(sdempc_timing_cfg)) return fail(h, SDEMPC_EINVAL, "timing: cfg NULL or struct_size mismatch%s");
-    if (tc->solve_period < 1) return fail(h, SDEMPC_EINVAL, "timing: solve_period must be >= 1%s");
-    if (!(tc->lag_alpha >= 0.0f) || !(tc->lag_alpha <= 1.0f)) return fail(h, SDEMPC_EINVAL, "timing: lag_alpha must be 0 (off) or in (0, 1]%s");
-    const LoopIo io{B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
-    int rc = check_loop_args(h, io, T >= 1 ? loop_solves(T, tc->solve_period) : 1);
-    if (rc) return rc;
-    const int Tp = sc ? sc->plant_ticks : 1;
-    if (Tp != 1 && Tp != T) return fail(h, SDEMPC_EINVAL, "scenario: plant_ticks must be 1 or T%s");
-    if (Tp > 1 && !plant_of) return fail(h, SDEMPC_EINVAL, "scenario: plant_of may not be NULL with plant_ticks > 1%s");
-    if ((rc = check_plant_args(h, pc, plant_blobs, plant_blob_bytes, plant_of, B, Tp))) return rc;
-    if (tc->solve_delay < 0 || (long long)tc->solve_delay > (long long)tc->solve_period * pc->substeps)
-        return fail(h, SDEMPC_EINVAL, "timing: solve_delay must be between 0 and solve_period * substeps (one solve at a time)%s");
-    const float* dist = sc ? sc->dist : nullptr;
-    if (dist) {
-        if (sc->dist_ticks != 1 && sc->dist_ticks != T) return fail(h, SDEMPC_EINVAL, "scenario: dist_ticks must be 1 or T%s");
-        if (sc->dist_batch != 1 && sc->dist_batch != B) return fail(h, SDEMPC_EINVAL, "scenario: dist_batch must be 1 or B%s");
-        const size_t nd = (size_t)sc->dist_ticks * sc->dist_batch * SDEMPC_NNOISE;
-        for (size_t e = 0; e < nd; ++e)
-            if (!finite(dist[e])) return fail(h, SDEMPC_EINVAL, "scenario: dist holds a non-finite entry%s");
-    }
-    if ((rc = ensure_device(h))) return rc;
-    const TimedRun timed{tc->solve_period, tc->solve_delay, tc->lag_alpha, u_act_in, u_act_next};
-    const ScenarioRun scen{dist, dist ? sc->dist_ticks : 1, dist ? sc->dist_batch : 1, plant_of, Tp};
-    const RateRun rate{rc_, inv_m, rate_integ_in, rate_tail_in, ws, rate_integ_next, rate_tail_next};
-    PlantRun run;
-    // (a schedule is staged per chunk by the loop; stage_plants takes the set itself)
-    if ((rc = stage_plants(h, *pc, plant_blobs, nullptr, B, &run, tc->solve_period < T ? tc->solve_period : T))) return rc;
-    return closed_loop_attempts(h, io, &run, &timed, &scen, &rate);
+    LoopCall c{};
+    c.layer = LOOP_RATE;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    return closed_loop_call(h, c);
     });
 }
 
@@ -1189,7 +1135,67 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
 }
-// argument checks shared by the two closed-loop entry points; no HIP call
+// The one path behind the five closed-loop entry points: every check of the call's parts, in one fixed order (rate, scenario struct, timing, loop arguments,
+// plant_ticks, plant set, solve_delay, disturbance; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
+int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
+    if (!h) return SDEMPC_EINVAL;
+    const LoopIo& io = c.io;
+    const int B = io.B, T = io.T;
+    const bool timed = c.layer >= LOOP_TIMED, scenario = c.layer >= LOOP_SCENARIO, rated = c.layer == LOOP_RATE;
+    const sdempc_rate_cfg* rc_ = c.rc;
+    const sdempc_scenario_cfg* sc = c.sc;
+    const sdempc_timing_cfg* tc = c.tc;
+    auto finite = [](float v) { return fabsf(v) < INFINITY; };
+    const float inv_m = 1.0f / (float)h->m;
+    if (rated) {
+        if (!rc_ || rc_->struct_size != (int32_t)sizeof(sdempc_rate_cfg)) return fail(h, SDEMPC_EINVAL, "rate: cfg NULL or struct_size mismatch%s");
+        for (int a = 0; a < 3; ++a) {
+            if (!finite(rc_->kp[a]) || !finite(rc_->ki_dt[a])) return fail(h, SDEMPC_EINVAL, "rate: kp / ki_dt hold a non-finite gain%s");
+            if (!finite(rc_->integ_limit[a])) return fail(h, SDEMPC_EINVAL, "rate: integ_limit holds a non-finite limit%s");
+            if (rc_->integ_limit[a] < 0.0f) return fail(h, SDEMPC_EINVAL, "rate: integ_limit must be >= 0%s");
+        }
+        for (int l = 0; l < h->m; ++l)
+            for (int a = 0; a < 3; ++a)
+                if (!finite(rc_->mixer[l][a])) return fail(h, SDEMPC_EINVAL, "rate: mixer holds a non-finite entry%s");
+        if (!(rc_->motor_weight >= 0.0f) || !(rc_->motor_weight <= 1.0f)) return fail(h, SDEMPC_EINVAL, "rate: motor_weight must be in [0, 1]%s");
+        if (rc_->inv_m != 0.0f && !(rc_->inv_m == inv_m)) return fail(h, SDEMPC_EINVAL, "rate: inv_m must be 0 or (float)1 / (float)num_motors%s");
+        if (!c.ws) return fail(h, SDEMPC_EINVAL, "rate: ws is NULL%s");
+        if (sc && sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg)) return fail(h, SDEMPC_EINVAL, "scenario: struct_size mismatch%s");
+    } else if (scenario) {
+        if (!sc || sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg)) return fail(h, SDEMPC_EINVAL, "scenario: cfg NULL or struct_size mismatch%s");
+    }
+    if (timed) {
+        if (!tc || tc->struct_size != (int32_t)sizeof(sdempc_timing_cfg)) return fail(h, SDEMPC_EINVAL, "timing: cfg NULL or struct_size mismatch%s");
+        if (tc->solve_period < 1) return fail(h, SDEMPC_EINVAL, "timing: solve_period must be >= 1%s");
+        if (!(tc->lag_alpha >= 0.0f) || !(tc->lag_alpha <= 1.0f)) return fail(h, SDEMPC_EINVAL, "timing: lag_alpha must be 0 (off) or in (0, 1]%s");
+    }
+    int rc = check_loop_args(h, io, !timed ? T : (T >= 1 ? loop_solves(T, tc->solve_period) : 1));
+    if (rc) return rc;
+    const int Tp = scenario && sc ? sc->plant_ticks : 1;           // rows of plant_of
+    if (Tp != 1 && Tp != T) return fail(h, SDEMPC_EINVAL, "scenario: plant_ticks must be 1 or T%s");
+    if (Tp > 1 && !c.plant_of) return fail(h, SDEMPC_EINVAL, "scenario: plant_of may not be NULL with plant_ticks > 1%s");
+    if (c.layer >= LOOP_PLANT && (rc = check_plant_args(h, c.pc, c.plant_blobs, c.plant_blob_bytes, c.plant_of, B, Tp))) return rc;
+    if (timed && (tc->solve_delay < 0 || (long long)tc->solve_delay > (long long)tc->solve_period * c.pc->substeps))
+        return fail(h, SDEMPC_EINVAL, "timing: solve_delay must be between 0 and solve_period * substeps (one solve at a time)%s");
+    const float* dist = scenario && sc ? sc->dist : nullptr;
+    if (dist) {
+        if (sc->dist_ticks != 1 && sc->dist_ticks != T) return fail(h, SDEMPC_EINVAL, "scenario: dist_ticks must be 1 or T%s");
+        if (sc->dist_batch != 1 && sc->dist_batch != B) return fail(h, SDEMPC_EINVAL, "scenario: dist_batch must be 1 or B%s");
+        const size_t nd = (size_t)sc->dist_ticks * sc->dist_batch * SDEMPC_NNOISE;
+        for (size_t e = 0; e < nd; ++e)
+            if (!finite(dist[e])) return fail(h, SDEMPC_EINVAL, "scenario: dist holds a non-finite entry%s");
+    }
+    if ((rc = ensure_device(h))) return rc;
+    if (c.layer == LOOP_PLAIN) return closed_loop_attempts(h, io, nullptr, nullptr, nullptr, nullptr);
+    const TimedRun run_t{timed ? tc->solve_period : 1, timed ? tc->solve_delay : 0, timed ? tc->lag_alpha : 0.0f, c.u_act_in, c.u_act_next};
+    const ScenarioRun run_s{dist, dist ? sc->dist_ticks : 1, dist ? sc->dist_batch : 1, c.plant_of, Tp};
+    const RateRun run_r{rc_, inv_m, c.rate_integ_in, c.rate_tail_in, c.ws, c.rate_integ_next, c.rate_tail_next};
+    PlantRun run;
+    // (a schedule is staged per chunk by the loop, where stage_plants takes the set itself; the noise of a whole solve period sits beside the set)
+    if ((rc = stage_plants(h, *c.pc, c.plant_blobs, scenario ? nullptr : c.plant_of, B, &run, !timed ? 1 : (tc->solve_period < T ? tc->solve_period : T)))) return rc;
+    return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr);
+}
+// argument checks every closed-loop entry point shares; no HIP call
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves) {
     int rc = check_batch(h, io.B);
     if (rc) return rc;
@@ -1200,7 +1206,7 @@ int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves) {
     if (!io.x0 || !io.xref || !io.keys || !io.xs || !io.us || !io.info) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
     return 0;
 }
-// every check of a plant set (SPEC.md §11a), shared by the two entry points that take one; no HIP call
+// every check of a plant set (SPEC.md §11a), shared by the four entry points that take one; no HIP call
 // sched_rows: rows of plant_of (SPEC.md §11c: a plant index per tick and episode; 1 everywhere else)
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows) {
     int rc;
@@ -1291,10 +1297,10 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // SPEC.md §11b (timed): the unit of work is a solve PERIOD of S ticks — one key schedule, one solve and one plant launch per period, chunks of whole
 // periods, info and moving references per solve. Without `timed` a period is one tick and every launch is the one it was (S = 1 below).
 // SPEC.md §11c (scen, with timed and plant): the chunk's disturbance rows and plant-schedule rows (one per TICK) are staged per chunk beside the moving
-// references and counted in the chunk's bytes; a schedule of one row is staged once. The plant step is then launch_loop_scenario.
+// references and counted in the chunk's bytes; a schedule of one row is staged once. The plant launch then takes a LoopScenario.
 // SPEC.md §11d (rate, with scen, timed and plant): the integrator and the rate tail live in d_rate (staged from the inputs, or zeroed, with the other inputs, so that a
 // re-run starts from them again) and carry over period and chunk boundaries there; the chunk's setpoint rows ws sit behind its other outputs and are counted in
-// the chunk's bytes. The plant step is then launch_loop_rate, which reads the solve's mean trajectories where the solve left them (d_xmean).
+// the chunk's bytes. The plant launch then takes a LoopRate and reads the solve's mean trajectories where the solve left them (d_xmean).
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
@@ -1386,6 +1392,30 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         HIPCHK(h, hipMemcpyAsync(c_sched, row, sizeof(int32_t) * SR, hipMemcpyHostToDevice, st));
     }
     for (int b = 0; b < B; ++b) memcpy(io.xs + (size_t)b * (T + 1) * NX, io.x0 + (size_t)b * NX, sizeof(float) * NX);
+    // the plant launch's arguments: built once, only pointers and `ticks` move from period to period
+    LoopAdvance L;
+    L.uopt = (const float*)h->d_uopt.p; L.xi = d_xi;
+    L.x = d_x; L.u = (float*)h->d_u.p; L.step = (float*)h->d_step.p; L.gave_up = d_gave_up;
+    L.B = B; L.H = H;
+    LoopPeriod R{};
+    LoopScenario C{};
+    LoopRate W{};
+    if (timed) { R.act = d_mot; R.alpha = timed->alpha; R.xi_ticks = S; R.shift = timed->S < H ? timed->S : H; }
+    if (scen) {
+        C.dist_tick_stride = dist_moves ? (int)DR : 0; C.dist_ep_stride = gust && scen->Bd > 1 ? SDEMPC_NNOISE : 0;
+        C.plant_tick_stride = sched_moves ? B : 0;
+        C.dtp = plant->dt;
+    }
+    if (rate) {
+        const sdempc_rate_cfg& rc_ = *rate->cfg;
+        for (int a = 0; a < 3; ++a) { W.kp[a] = rc_.kp[a]; W.ki_dt[a] = rc_.ki_dt[a]; W.glim[a] = rc_.integ_limit[a]; }
+        for (int l = 0; l < 8; ++l) {
+            for (int a = 0; a < 3; ++a) W.M[l][a] = l < m ? rc_.mixer[l][a] : 0.0f;
+            W.lo[l] = l < m ? h->cfg.u_lo[l] : 0.0f; W.hi[l] = l < m ? h->cfg.u_hi[l] : 0.0f;
+        }
+        W.inv_m = rate->inv_m; W.w = rc_.motor_weight;
+        W.xevol = (const float*)h->d_xmean.p; W.wt = d_tail; W.g = d_integ;
+    }
     std::vector<float> hx, hu, hi, hw;
     for (int j0 = 0; j0 < Ns; j0 += Pc) {
         const int np = Ns - j0 < Pc ? Ns - j0 : Pc;                                  // periods of this chunk
@@ -1408,41 +1438,19 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             }
             float* info_j = c_info + (size_t)jc * B * 8;
             if ((rc = sdempc_solve_batch_dev(h, B, d_x, xr, h->d_noise.p, h->d_u.p, h->d_step.p, h->d_uopt.p, h->d_xmean.p, info_j, st))) return rc;
-            LoopAdvance L;
-            L.uopt = (const float*)h->d_uopt.p; L.info = info_j; L.xi = d_xi;
-            L.coop_bar = h->last_coop_B > 0 ? (const unsigned*)h->d_coop_bar.p : nullptr;
-            L.x = d_x; L.u = (float*)h->d_u.p; L.step = (float*)h->d_step.p;
-            L.xs = c_xs + (size_t)jc * S * B * NX; L.us = c_us + (size_t)jc * S * B * m; L.gave_up = d_gave_up;
-            L.B = B; L.H = H;
+            L.info = info_j; L.coop_bar = h->last_coop_B > 0 ? (const unsigned*)h->d_coop_bar.p : nullptr;
+            L.xs = c_xs + (size_t)jc * S * B * NX; L.us = c_us + (size_t)jc * S * B * m;
             if (timed) {
-                LoopPeriod R;
-                R.act = d_mot; R.alpha = timed->alpha; R.ticks = ticks; R.xi_ticks = S; R.shift = timed->S < H ? timed->S : H;
+                const size_t t0 = (size_t)jc * S;                                    // first tick row of this period inside the chunk
                 const long long never = (long long)ticks * plant->Q.substeps;       // (a solution that arrives at the period's end is flown by the next period, as its tail)
-                R.arrive = (int)(timed->D < never ? timed->D : never);
+                R.ticks = ticks; R.arrive = (int)(timed->D < never ? timed->D : never);
                 if (scen) {
-                    const size_t t0 = (size_t)jc * S;                                // first tick row of this period inside the chunk
-                    LoopScenario C;
                     C.dist = gust ? c_dist + (dist_moves ? t0 * DR : 0) : nullptr;
-                    C.dist_tick_stride = dist_moves ? (int)DR : 0; C.dist_ep_stride = gust && scen->Bd > 1 ? SDEMPC_NNOISE : 0;
                     C.plant = sched ? c_sched + (sched_moves ? t0 * SR : 0) : nullptr;
-                    C.plant_tick_stride = sched_moves ? B : 0;
-                    C.dtp = plant->dt;
-                    if (rate) {
-                        LoopRate W;
-                        const sdempc_rate_cfg& rc_ = *rate->cfg;
-                        for (int a = 0; a < 3; ++a) { W.kp[a] = rc_.kp[a]; W.ki_dt[a] = rc_.ki_dt[a]; W.glim[a] = rc_.integ_limit[a]; }
-                        for (int l = 0; l < 8; ++l) {
-                            for (int a = 0; a < 3; ++a) W.M[l][a] = l < m ? rc_.mixer[l][a] : 0.0f;
-                            W.lo[l] = l < m ? h->cfg.u_lo[l] : 0.0f; W.hi[l] = l < m ? h->cfg.u_hi[l] : 0.0f;
-                        }
-                        W.inv_m = rate->inv_m; W.w = rc_.motor_weight;
-                        W.xevol = (const float*)h->d_xmean.p; W.wt = d_tail; W.g = d_integ; W.ws = c_ws + t0 * B * 4;
-                        HIPCHK(h, launch_loop_rate(plant->k, L, plant->Q, R, C, W, st));
-                    } else
-                    HIPCHK(h, launch_loop_scenario(plant->k, L, plant->Q, R, C, st));
-                } else HIPCHK(h, launch_loop_period(plant->k, L, plant->Q, R, st));
-            } else if (plant) HIPCHK(h, launch_loop_plant(plant->k, L, plant->Q, st));
-            else HIPCHK(h, launch_loop_advance(h->base, L, st));
+                }
+                if (rate) W.ws = c_ws + t0 * B * 4;
+            }
+            HIPCHK(h, launch_loop(plant ? plant->k : h->base, L, plant ? &plant->Q : nullptr, timed ? &R : nullptr, scen ? &C : nullptr, rate ? &W : nullptr, st));
         }
         hx.resize((size_t)nk * B * NX); hu.resize((size_t)nk * B * m); hi.resize((size_t)np * B * 8);
         unsigned gave_up = 0;

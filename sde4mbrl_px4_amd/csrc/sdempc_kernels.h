@@ -150,10 +150,9 @@ struct LoopAdvance {
     unsigned* gave_up;          // one word, sticky: a grid barrier of a cooperative-layout solve of this loop gave up
     int B, H;
 };
-hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
 // SPEC.md §11a, the closed loop against a separate plant: which model steps episode b, and how often per tick. LoopAdvance::xi is [B][substeps][6] here.
 // models == null: ONE plant for every episode — the launch's KArgs carry it (M, wts, sdt) and the four episodes of a workgroup share its LDS images,
-// as in launch_loop_advance. Otherwise episode b is stepped by plant p = plant_of ? plant_of[b] : b, and every wave stages its own images.
+// as without a plant set. Otherwise episode b is stepped by plant p = plant_of ? plant_of[b] : b, and every wave stages its own images.
 struct LoopPlant {
     const ModelK* models;       // [Np] physics prior and output-layer constants of each prepared plant, or null
     const float* wts;           // [Np][wts_stride] prepared blob payloads (math_mode fast: forward block, then the block of the vector-Jacobian products)
@@ -162,8 +161,6 @@ struct LoopPlant {
     int wts_stride;             // floats between two plants' payloads
     int substeps;               // Euler–Maruyama steps per tick, the applied control held (>= 1)
 };
-// `a`: the handle's argument block with the PLANT's arithmetic (f16, fast), dt -> one float (the plant's step length) and, for one shared plant, its M / wts / sdt
-hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st);
 // SPEC.md §11b, the closed loop at the node's timing: ONE launch advances a whole solve period — `ticks` control ticks of Q.substeps plant steps each —
 // flying the previous solution's tail (LoopAdvance::u, the warm start y_j) until plant substep `arrive` of the period and this period's solution
 // (LoopAdvance::uopt) from then on, through a first-order motor lag. Here LoopAdvance::xi is [B][xi_ticks][substeps][6], xs / us are [ticks][B][13] / [ticks][B][m]
@@ -176,8 +173,7 @@ struct LoopPeriod {
     int shift;                  // rows the warm start moves up: min(S, H) (row t <- uopt[min(t + shift, H - 1)])
     int arrive;                 // substep index inside the period at which the command source switches from y_j to uopt_j; >= ticks * substeps: never
 };
-hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st);
-// SPEC.md §11c, the closed loop with a scenario: launch_loop_period plus a disturbance row per control tick and a plant index per control tick. Both
+// SPEC.md §11c, the closed loop with a scenario: the period launch plus a disturbance row per control tick and a plant index per control tick. Both
 // pointers address the PERIOD's first tick (the host steps them from period to period); tick i of the period reads row i, or row 0 when the stride is 0.
 struct LoopScenario {
     const float* dist;          // (w_v[3], w_omega[3]) of tick i, episode b at dist[i * dist_tick_stride + b * dist_ep_stride + 0..5], or null: no disturbance
@@ -188,8 +184,7 @@ struct LoopScenario {
     int plant_tick_stride;      // B, or 0 (one row for every tick)
     float dtp;                  // the plant's step length (what LoopAdvance's KArgs::dt points at)
 };
-hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st);
-// SPEC.md §11d, the closed loop through the rate-setpoint interface: launch_loop_scenario (C.dist / C.plant may be null: no scenario) with the vehicle's inner
+// SPEC.md §11d, the closed loop through the rate-setpoint interface: the scenario launch (C.dist / C.plant may be null: no scenario) with the vehicle's inner
 // rate loop in front of the motor lag. On every plant substep the command is formed from the setpoint row in force — mean thrust of the motor row, body rates
 // of this period's mean trajectory (xevol row r + 1) or, before the solution arrives, of the rate tail (row r) — and the plant's CURRENT body rates: PI on the
 // rate error with a clamped integrator, mixer clamped to the input bounds, blend with the motor row. Gains, mixer and bounds travel by value (wave-uniform
@@ -205,7 +200,10 @@ struct LoopRate {
     float* g;                           // [B][3] integrator state: in, and out after the period's last substep
     float* ws;                          // [ticks][B][4] (mean thrust, rates[3]) in force at each tick's first substep
 };
-hipError_t launch_loop_rate(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, const LoopRate& W, hipStream_t st);
+// The plant launch of every closed loop. Q null: the handle's own model, one step per tick (SPEC.md §11); otherwise `a` is the handle's argument block with the PLANT's
+// arithmetic (f16, fast: the plant's math mode picks the kernel's), dt -> one float (the plant's step length) and, for one shared plant, its M / wts / sdt.
+// R null: one control tick; otherwise a whole solve period, with a scenario if C is given (needs R) and through the rate loop if W is given (needs C).
+hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st);
 // the tick's key schedule (sdempc_prng.hip): keys r_k -> r_{k+1} in place, the solve's noise keys into sub_dev u32[B][2], the plant noise into
 // xi_dev f32[B][substeps][6]: ONE draw normal(p, 6 * substeps) per episode (SPEC.md §7.1: counter i pairs with i + 3 * substeps), row j for substep j
 hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st, int substeps = 1);

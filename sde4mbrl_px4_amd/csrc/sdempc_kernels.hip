@@ -1090,19 +1090,12 @@ SDEMPC_DUO_HEX(SDEMPC_DUO_DEF)
 #include "sdempc_loop.inc.h"
 }  // namespace exact / fastm
 #if !SDEMPC_FAST
-// launch_loop_scenario (SPEC.md §11c) picks its math mode here, in the loop unit of the exact build (a.fast: the PLANT's math mode)
+// launch_loop picks its math mode here, in the loop unit of the exact build (a.fast: the PLANT's math mode)
 namespace fastm {
-hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st);
+hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st);
 }
-hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st) {
-    return a.fast ? fastm::launch_loop_scenario(a, L, Q, R, C, st) : exact::launch_loop_scenario(a, L, Q, R, C, st);
-}
-// ... and launch_loop_rate (SPEC.md §11d) likewise
-namespace fastm {
-hipError_t launch_loop_rate(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, const LoopRate& W, hipStream_t st);
-}
-hipError_t launch_loop_rate(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, const LoopRate& W, hipStream_t st) {
-    return a.fast ? fastm::launch_loop_rate(a, L, Q, R, C, W, st) : exact::launch_loop_rate(a, L, Q, R, C, W, st);
+hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st) {
+    return a.fast ? fastm::launch_loop(a, L, Q, R, C, W, st) : exact::launch_loop(a, L, Q, R, C, W, st);
 }
 #endif
 #else
@@ -1438,12 +1431,7 @@ hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int 
 #else
 }  // namespace exact
 // The entry points of sdempc_kernels.h. Those that depend on the math mode take it from KArgs::fast here, and only here: fastm is this unit
-// built with SDEMPC_FAST=1, launch_loop_advance lives in the loop unit of either mode (SDEMPC_TU = 4).
-namespace exact {
-hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
-hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st);
-hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st);
-}
+// built with SDEMPC_FAST=1. (launch_loop lives in the loop unit, SDEMPC_TU = 4, and picks its mode there.)
 namespace fastm {
 hipError_t launch_rollout(const KArgs& a, int B, hipStream_t st);
 hipError_t launch_grad(const KArgs& a, int B, hipStream_t st);
@@ -1451,9 +1439,6 @@ hipError_t launch_solve(const KArgs& a, int B, hipStream_t st);
 int solve_workspace_rows(const KArgs& a, int B);
 hipError_t launch_solve_coop(const KArgs& a, int B, hipStream_t st);
 hipError_t launch_solve_spec(const KArgs& a, int B, hipStream_t st);
-hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st);
-hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st);
-hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st);
 }
 static thread_local const void* g_last_kernel_fn = nullptr;
 void note_kernel(const void* host_fn) { g_last_kernel_fn = host_fn; }
@@ -1471,15 +1456,6 @@ size_t coop_ck_floats(int H, int P) { return exact::coop_ck_floats(H, P); }
 hipError_t launch_solve_coop(const KArgs& a, int B, hipStream_t st) { return a.fast ? fastm::launch_solve_coop(a, B, st) : exact::launch_solve_coop(a, B, st); }
 int spec_max_instances(int P, int H, int m, const LaunchOpts& o) { return exact::spec_max_instances(P, H, m, o); }
 hipError_t launch_solve_spec(const KArgs& a, int B, hipStream_t st) { return a.fast ? fastm::launch_solve_spec(a, B, st) : exact::launch_solve_spec(a, B, st); }
-hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st) {
-    return a.fast ? fastm::launch_loop_advance(a, L, st) : exact::launch_loop_advance(a, L, st);
-}
-hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st) {      // (a.fast: the PLANT's math mode)
-    return a.fast ? fastm::launch_loop_plant(a, L, Q, st) : exact::launch_loop_plant(a, L, Q, st);
-}
-hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st) {      // (a.fast: the PLANT's math mode)
-    return a.fast ? fastm::launch_loop_period(a, L, Q, R, st) : exact::launch_loop_period(a, L, Q, R, st);
-}
 hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int P, int G, int C, hipStream_t st) {
     return exact::launch_relayout(to_dev, in, out, B, P, G, C, st);
 }

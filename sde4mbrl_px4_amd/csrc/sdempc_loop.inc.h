@@ -4,358 +4,160 @@
 //
 // The step is the rollout's own device code: step_fwd at t = 0 on a control table built by block_prepass, i.e. the arithmetic of step 0
 // of every rollout (Oracle.step(x, u, xi, t=0)), in every mlp_dtype and math mode. One wave per episode, four episodes per workgroup
-// (TeamWave): all 32 particle columns of the tile carry the same state and noise, and lane 0's copy is the result. The kernel gets the
+// (TeamWave): all 32 particle columns of the tile carry the same state and noise, and lane 0's copy is the result. The kernels get the
 // handle's argument block with H = 1 (a one-step horizon: the staged tables and the control table hold step 0 only); L.H is the solve's horizon.
-// Arguments: LoopAdvance (sdempc_kernels.h).
-template <int F16>
-__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_advance_kernel(KArgs a, LoopAdvance L) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int H = L.H, m = a.m;
-    const int tid = TeamWave::tid();
-    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
-    Smem sm = carve(smem, 1, m, TeamWave::team());
+//
+// Two kernels, built from the four pieces below (prologue, stage_plant, prepass + substep, hand-over), each of which exists once:
+//  * sdempc_loop_tick_kernel (§11, §11a): one control tick, the prepass straight from the solution's first row;
+//  * sdempc_loop_period_kernel<F16, SCEN, RATE> (§11b, §11c, §11d): a whole solve period, the command going through the motor lag and an LDS row.
+// Arguments: LoopAdvance, LoopPlant, LoopPeriod, LoopScenario, LoopRate (sdempc_kernels.h).
+//
+// The plant set (§11a). The argument block a0 arrives with the PLANT's arithmetic (the kernel's namespace and F16 are the plant's, independent of the solve's) and
+// dt -> the plant's step length. With one shared plant (Q.models == null) a0 carries it and the four episodes of a workgroup share one LDS carve. With per-episode
+// plants the workgroup's LDS holds four carves of one team each (16 KB per episode, 64 KB per workgroup: two workgroups per CU) and every wave stages the plant
+// it flies into its own (stage_plant). block_prepass indexes the rotor tables of its argument block by a run-time motor index, which a kernel argument serves by a
+// scalar load at a computed offset but a modified copy could only serve from scratch: the per-episode path hands it the wave's argument block in LDS
+// (plant_kargs_floats() floats per wave behind the carves) and keeps the register copy for step_fwd, whose indices are all static. So a0 stays the UNTOUCHED
+// kernel argument everywhere: it is what the shared-plant prepass indexes at run time.
+__host__ __device__ constexpr int plant_kargs_floats() { return (int)((sizeof(KArgs) + 15) / 16 * 4); }
+
+// what a wave knows of itself and of its LDS once the prologue is through
+struct LoopWave {
+    Smem sm;                // the carve the wave steps in: the workgroup's (one shared plant) or its own (per-episode plants)
     WaveW ww;
-    load_weights(a, sm, ww, threadIdx.x, TeamWave::BNT);
-    __syncthreads();
-    if (b >= L.B) return;           // (wave-uniform; no workgroup-wide barrier below)
-    const int lane = tid & 63, h = lane >> 5;
-    const float* uo = L.uopt + (size_t)b * H * m;
-    block_prepass<TeamWave>(a, sm, uo, tid);          // control table row 0 from uopt_k[0]
-    float x[NX], xn[NX], xi[NN];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
-#pragma unroll
-    for (int i = 0; i < NN; ++i) xi[i] = L.xi[(size_t)b * NN + i];
-    TeamWave::sync();
-    StepAux A;
-    step_fwd<F16, false>(a, sm, ww, 0, h, lane, x, xi, xn, A);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i) { L.x[(size_t)b * NX + i] = xn[i]; L.xs[(size_t)b * NX + i] = xn[i]; }
-        L.step[b] = L.info[(size_t)b * 8 + 1];
-        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
+    KArgs* lk;              // per-episode plants: the wave's argument block in LDS (what block_prepass reads)
+    int b, tid, lane, h;    // episode (wave-uniform), thread of the team, lane, lane half
+    bool per;               // per-episode plants (wave-uniform: a kernel argument)
+};
+
+// Prologue: the wave's episode, its carve and its argument block in LDS; one shared plant is staged here, by the whole workgroup. Returns whether the wave has an
+// episode: the kernel returns at once if not (wave-uniform), so every barrier after the prologue is TeamWave::sync(), never __syncthreads().
+DI bool loop_prologue(float* smem, const KArgs& a0, const LoopAdvance& L, const LoopPlant& Q, LoopWave& w) {
+    const int m = a0.m;
+    w.tid = TeamWave::tid(); w.lane = w.tid & 63; w.h = w.lane >> 5;
+    w.b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
+    w.per = Q.models != nullptr;
+    w.sm = w.per ? carve(smem + (size_t)TeamWave::team() * smem_floats(1, m, 1), 1, m, 0) : carve(smem, 1, m, TeamWave::team());
+    w.lk = reinterpret_cast<KArgs*>(smem + TeamWave::IPB * smem_floats(1, m, 1) + (size_t)TeamWave::team() * plant_kargs_floats());
+    if (!w.per) {                   // (workgroup-uniform)
+        load_weights(a0, w.sm, w.ww, threadIdx.x, TeamWave::BNT);
+        __syncthreads();
     }
-    if (lane < m) L.us[(size_t)b * m + lane] = uo[lane];
-    float* un = L.u + (size_t)b * H * m;
-    for (int e = tid; e < H * m; e += TeamWave::NT) {   // y_{k+1} = [uopt_k[1:], uopt_k[H-1]]
-        const int t = e / m;
-        un[e] = uo[(t + 1 < H ? t + 1 : t) * m + (e - t * m)];
+    return w.b < L.B;
+}
+
+// Per-episode plants: the wave takes plant p. `a` (a copy of a0) gets p's M, wts and sdt, read through the readfirstlane'd index (wave-uniform addresses: scalar
+// loads, so the model constants stay in SGPRs as the kernel arguments they replace do); the wave's own carve gets p's images and tables (sigma sqrt(dt) travels
+// with the weights: sm.sdt) and the wave's argument block in LDS p's rotor tables, from global memory lane by lane (no register copy indexed at run time, hence
+// no scratch on its way). TeamWave::sync on both sides: the earlier reads of the carve are done, the new images are written.
+DI void stage_plant(const LoopPlant& Q, int p, KArgs& a, LoopWave& w) {
+    a.M = Q.models[p];
+    a.wts = Q.wts + (size_t)p * Q.wts_stride;
+    a.sdt = Q.sdt + (size_t)p * NN;
+    TeamWave::sync();
+    load_weights(a, w.sm, w.ww, w.tid, TeamWave::NT);
+    if (w.tid == 0) { w.lk->H = 1; w.lk->m = a.m; }
+    const float* msrc = reinterpret_cast<const float*>(Q.models + p);
+    float* mdst = reinterpret_cast<float*>(&w.lk->M);
+    for (int e = w.tid; e < (int)(sizeof(ModelK) / sizeof(float)); e += TeamWave::NT) mdst[e] = msrc[e];      // (what block_prepass reads)
+    TeamWave::sync();
+}
+
+// Control table row 0 from the m applied controls at u, with the wave's plant's polynomials and W1u. The first sync: u is written (where it is an LDS row) and
+// the previous substep's reads of the control table are done.
+DI void loop_prepass(const KArgs& a0, const LoopWave& w, const float* u) {
+    TeamWave::sync();
+    if (w.per) block_prepass<TeamWave>(*w.lk, w.sm, u, w.tid);
+    else block_prepass<TeamWave>(a0, w.sm, u, w.tid);
+    TeamWave::sync();
+}
+
+// One Euler–Maruyama step of the plant on the control table as it stands: step_fwd at t = 0 under the noise row xi_row, the new state fed back into x. With a
+// disturbance (gust; SPEC.md §11c) the register copy of x then takes v_e <- fma(wd[e], dtp, v_e) and omega_e <- fma(wd[3 + e], dtp, omega_e), dtp the plant's
+// step length: six fmas, applied whenever a schedule is given (zero rows included).
+template <int F16>
+DI void loop_substep(const KArgs& a, const LoopWave& w, const float* xi_row, float* x, bool gust, const float* wd, float dtp) {
+    float xn[NX], xi[NN];
+#pragma unroll
+    for (int e = 0; e < NN; ++e) xi[e] = xi_row[e];
+    StepAux A;
+    step_fwd<F16, false>(a, w.sm, w.ww, 0, w.h, w.lane, x, xi, xn, A);
+#pragma unroll
+    for (int e = 0; e < NX; ++e) x[e] = xn[e];
+    if (gust) {
+#pragma unroll
+        for (int e = 0; e < 3; ++e) { x[3 + e] = FMA(wd[e], dtp, x[3 + e]); x[10 + e] = FMA(wd[3 + e], dtp, x[10 + e]); }
     }
 }
 
-// SPEC.md §11a: the same hand-over behind a SEPARATE plant — episode b is stepped by the model Q names for it, Q.substeps times at the plant's own step
-// length and in the plant's own arithmetic (this kernel's namespace and F16 are the plant's, independent of the solve's), the applied control held.
-// The argument block arrives as for the kernel above (H = 1; dt -> the plant's step length) and the wave works on a copy `a`: with per-episode plants (Q.models) the wave
-// replaces a.M, a.wts and a.sdt by its plant's, read through a readfirstlane'd index (wave-uniform addresses, before the kernel's first store: scalar
-// loads, so the model constants stay in SGPRs as the kernel arguments they replace do), and stages its OWN LDS images — the workgroup's LDS holds four
-// carves of one team each instead of one carve of four teams (16 KB per episode, 64 KB per workgroup: two workgroups per CU). With one shared plant the
-// four episodes share one carve, as above. block_prepass indexes the rotor tables of a.M by a run-time motor index, which a kernel argument serves by a
-// scalar load at a computed offset but a modified copy could only serve from scratch: the per-episode path hands it the wave's argument block in LDS
-// (plant_kargs_floats() floats per wave behind the carves) and keeps the register copy for step_fwd, whose indices are all static.
-// The prepass runs once per tick (control table row 0 from uopt_k[0] with the plant's polynomials and W1u); every substep is step_fwd at t = 0, xn fed back.
-__host__ __device__ constexpr int plant_kargs_floats() { return (int)((sizeof(KArgs) + 15) / 16 * 4); }
-template <int F16>
-__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_plant_kernel(KArgs a0, LoopAdvance L, LoopPlant Q) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    KArgs a = a0;                   // (a0 stays the untouched kernel argument: the shared-plant prepass indexes it at run time)
-    const int H = L.H, m = a.m;
-    const int tid = TeamWave::tid();
-    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
-    const bool per = Q.models != nullptr, live = b < L.B;      // (both wave-uniform)
-    if (per && live) {
-        const int p = __builtin_amdgcn_readfirstlane(Q.plant_of ? Q.plant_of[b] : b);
-        a.M = Q.models[p];
-        a.wts = Q.wts + (size_t)p * Q.wts_stride;
-        a.sdt = Q.sdt + (size_t)p * NN;
+// Hand-over to the next solve: the state, the step size (info[1]), the sticky gave_up flag from the cooperative barrier word, the motor state (act: [B][m], or
+// null) and the warm start, row t <- uopt[min(t + shift, H - 1)]. Every read of the warm start by this wave has happened before: it is rewritten here.
+DI void loop_handover(const LoopAdvance& L, const LoopWave& w, int m, const float* x, const float* uo, int shift, float* act, float am) {
+    const int H = L.H, b = w.b;
+    if (w.lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) L.x[(size_t)b * NX + i] = x[i];
+        L.step[b] = L.info[(size_t)b * 8 + 1];
+        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
     }
-    Smem sm = per ? carve(smem + (size_t)TeamWave::team() * smem_floats(1, m, 1), 1, m, 0) : carve(smem, 1, m, TeamWave::team());
-    WaveW ww;
-    load_weights(a, sm, ww, per ? tid : (int)threadIdx.x, per ? TeamWave::NT : TeamWave::BNT);
-    KArgs* const lk = reinterpret_cast<KArgs*>(smem + TeamWave::IPB * smem_floats(1, m, 1) + (size_t)TeamWave::team() * plant_kargs_floats());
-    if (per && tid == 0) { lk->H = 1; lk->m = m; lk->M = a.M; }        // (what block_prepass reads)
-    __syncthreads();
-    if (!live) return;              // (wave-uniform; no workgroup-wide barrier below)
-    const int lane = tid & 63, h = lane >> 5;
+    if (act && w.lane < m) act[(size_t)b * m + w.lane] = am;
+    float* un = L.u + (size_t)b * H * m;
+    for (int e = w.tid; e < H * m; e += TeamWave::NT) {
+        const int t = e / m, ts = t + shift < H ? t + shift : H - 1;
+        un[e] = uo[ts * m + (e - t * m)];
+    }
+}
+
+// SPEC.md §11, §11a: one control tick. Episode b is stepped by the model Q names for it (the handle's own: Q.models null, Q.substeps 1), Q.substeps times at the
+// plant's own step length, the applied control uopt_k[0] held: the prepass runs once per tick, straight from the solution (no LDS row in between), and every
+// substep is step_fwd at t = 0, xn fed back. The plant index is read before the kernel's first store. L.xi is [B][substeps][6].
+// PLANT false: the plain loop (§11) as an instantiation of its own — no plant set and one substep known at compile time, which keeps it at the registers (and, in
+// exact f32 / f16, the four waves per SIMD) it has always had; Q is not read.
+template <int F16, bool PLANT>
+__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_tick_kernel(KArgs a0, LoopAdvance L, LoopPlant Q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if constexpr (!PLANT) { Q = LoopPlant{}; Q.substeps = 1; }
+    LoopWave w;
+    if (!loop_prologue(smem, a0, L, Q, w)) return;
+    const int H = L.H, m = a0.m, b = w.b;
+    KArgs a = a0;
+    if (w.per) stage_plant(Q, __builtin_amdgcn_readfirstlane(Q.plant_of ? Q.plant_of[b] : b), a, w);
     const float* uo = L.uopt + (size_t)b * H * m;
-    if (per) block_prepass<TeamWave>(*lk, sm, uo, tid);
-    else block_prepass<TeamWave>(a0, sm, uo, tid);
-    float x[NX], xn[NX], xi[NN];
+    float x[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
-    TeamWave::sync();
+    loop_prepass(a0, w, uo);
     const float* xrow = L.xi + (size_t)b * Q.substeps * NN;
 #pragma nounroll
-    for (int j = 0; j < Q.substeps; ++j) {
+    for (int j = 0; j < Q.substeps; ++j) loop_substep<F16>(a, w, xrow + j * NN, x, false, nullptr, 0.0f);
+    if (w.lane == 0) {
 #pragma unroll
-        for (int i = 0; i < NN; ++i) xi[i] = xrow[j * NN + i];
-        StepAux A;
-        step_fwd<F16, false>(a, sm, ww, 0, h, lane, x, xi, xn, A);
-#pragma unroll
-        for (int i = 0; i < NX; ++i) x[i] = xn[i];
+        for (int i = 0; i < NX; ++i) L.xs[(size_t)b * NX + i] = x[i];
     }
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i) { L.x[(size_t)b * NX + i] = x[i]; L.xs[(size_t)b * NX + i] = x[i]; }
-        L.step[b] = L.info[(size_t)b * 8 + 1];
-        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
-    }
-    if (lane < m) L.us[(size_t)b * m + lane] = uo[lane];
-    float* un = L.u + (size_t)b * H * m;
-    for (int e = tid; e < H * m; e += TeamWave::NT) {   // y_{k+1} = [uopt_k[1:], uopt_k[H-1]]
-        const int t = e / m;
-        un[e] = uo[(t + 1 < H ? t + 1 : t) * m + (e - t * m)];
-    }
-}
-
-hipError_t launch_loop_plant(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st) {
-    if (L.B < 1 || L.H != a.H || Q.substeps < 1 || (Q.models && (!Q.wts || !Q.sdt || Q.wts_stride < BLOB_FLOATS + VJP_BASE))) return hipErrorInvalidValue;
-    KArgs k = a;
-    k.H = 1;
-    const size_t sb = Q.models ? TeamWave::IPB * (smem_bytes(1, k.m, 1) + sizeof(float) * plant_kargs_floats()) : smem_bytes(1, k.m, TeamWave::IPB);
-    const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
-    return with_f16(k.f16, [&](auto F16) {
-        if (sb > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)sdempc_loop_plant_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
-            if (e != hipSuccess) return e;
-        }
-        sdempc_loop_plant_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q);
-        return hipGetLastError();
-    });
+    if (w.lane < m) L.us[(size_t)b * m + w.lane] = uo[w.lane];
+    loop_handover(L, w, m, x, uo, 1, nullptr, 0.0f);      // y_{k+1} = [uopt_k[1:], uopt_k[H-1]]
 }
 
 // SPEC.md §11b: a whole solve period behind the same plant set — R.ticks control ticks of Q.substeps Euler–Maruyama steps each in ONE launch, so that a loop
-// whose ticks are millisecond-scale solves does not pay a launch per plant step. The prologue is the kernel's above (shared or per-episode LDS carves, the
-// wave's argument block in LDS for the per-episode prepass). Substep q = i * substeps + jj of the period flies row min(i, H - 1) of the previous solution's
-// tail (L.u: the warm start y_j) while q < R.arrive and of this period's solution (L.uopt) from then on; the arrival point is the same for every episode,
-// so the choice is wave-uniform. Lane l < m carries motor l's state: a_l <- fma(alpha, c_l - a_l, a_l) before every substep, or a_l = c_l with the lag off.
-// The applied control row lives in the team's sm.v[5] (an optimiser vector the step does not use) and block_prepass reruns whenever it can have changed:
+// whose ticks are millisecond-scale solves does not pay a launch per plant step. Substep q = i * substeps + jj of the period flies row min(i, H - 1) of the
+// previous solution's tail (L.u: the warm start y_j) while q < R.arrive and of this period's solution (L.uopt) from then on; the arrival point is the same for
+// every episode, so the choice is wave-uniform. Lane l < m carries motor l's state: a_l <- fma(alpha, c_l - a_l, a_l) before every substep, or a_l = c_l with the
+// lag off. The applied control row lives in the team's sm.v[5] (an optimiser vector the step does not use) and the prepass reruns whenever it can have changed:
 // every substep with the lag on, at tick starts and at the arrival substep otherwise (rerunning it on an unchanged row writes the same table).
 // Every read of the warm start precedes its rewrite: the commands are read inside the substep loop, the shifted rows are written after it, by the same wave.
-template <int F16>
-__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_period_kernel(KArgs a0, LoopAdvance L, LoopPlant Q, LoopPeriod R) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    KArgs a = a0;
-    const int H = L.H, m = a.m;
-    const int tid = TeamWave::tid();
-    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
-    const bool per = Q.models != nullptr, live = b < L.B;      // (both wave-uniform)
-    if (per && live) {
-        const int p = __builtin_amdgcn_readfirstlane(Q.plant_of ? Q.plant_of[b] : b);
-        a.M = Q.models[p];
-        a.wts = Q.wts + (size_t)p * Q.wts_stride;
-        a.sdt = Q.sdt + (size_t)p * NN;
-    }
-    Smem sm = per ? carve(smem + (size_t)TeamWave::team() * smem_floats(1, m, 1), 1, m, 0) : carve(smem, 1, m, TeamWave::team());
-    WaveW ww;
-    load_weights(a, sm, ww, per ? tid : (int)threadIdx.x, per ? TeamWave::NT : TeamWave::BNT);
-    KArgs* const lk = reinterpret_cast<KArgs*>(smem + TeamWave::IPB * smem_floats(1, m, 1) + (size_t)TeamWave::team() * plant_kargs_floats());
-    if (per && tid == 0) { lk->H = 1; lk->m = m; lk->M = a.M; }        // (what block_prepass reads)
-    __syncthreads();
-    if (!live) return;              // (wave-uniform; no workgroup-wide barrier below)
-    const int lane = tid & 63, h = lane >> 5, n = Q.substeps;
-    const bool lag = R.alpha > 0.0f, mine = lane < m;
-    const float* uo = L.uopt + (size_t)b * H * m;
-    float* yw = L.u + (size_t)b * H * m;
-    float* act = sm.v[5];           // [m] the applied control of the current substep
-    float am = mine ? R.act[(size_t)b * m + lane] : 0.0f;
-    float x[NX], xn[NX], xi[NN];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
-    const float* xrow = L.xi + (size_t)b * R.xi_ticks * n * NN;
-#pragma nounroll
-    for (int i = 0; i < R.ticks; ++i) {
-        const int row = (i < H - 1 ? i : H - 1) * m;
-#pragma nounroll
-        for (int jj = 0; jj < n; ++jj) {
-            const int q = i * n + jj;
-            if (lag || jj == 0 || q == R.arrive) {
-                if (mine) {
-                    const float c = (q >= R.arrive ? uo : yw)[row + lane];
-                    am = lag ? FMA(R.alpha, c - am, am) : c;
-                    act[lane] = am;
-                }
-                TeamWave::sync();       // (the row is written, the previous substep's reads of the control table are done)
-                if (per) block_prepass<TeamWave>(*lk, sm, act, tid);
-                else block_prepass<TeamWave>(a0, sm, act, tid);
-                TeamWave::sync();
-            }
-            if (jj == 0 && mine) L.us[((size_t)i * L.B + b) * m + lane] = am;
-#pragma unroll
-            for (int e = 0; e < NN; ++e) xi[e] = xrow[q * NN + e];
-            StepAux A;
-            step_fwd<F16, false>(a, sm, ww, 0, h, lane, x, xi, xn, A);
-#pragma unroll
-            for (int e = 0; e < NX; ++e) x[e] = xn[e];
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int e = 0; e < NX; ++e) L.xs[((size_t)i * L.B + b) * NX + e] = x[e];
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i) L.x[(size_t)b * NX + i] = x[i];
-        L.step[b] = L.info[(size_t)b * 8 + 1];
-        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
-    }
-    if (mine) R.act[(size_t)b * m + lane] = am;
-    for (int e = tid; e < H * m; e += TeamWave::NT) {   // y_{j+1}: row t = uopt_j[min(t + S, H - 1)]
-        const int t = e / m, ts = t + R.shift < H ? t + R.shift : H - 1;
-        yw[e] = uo[ts * m + (e - t * m)];
-    }
-}
-
-hipError_t launch_loop_period(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, hipStream_t st) {
-    if (L.B < 1 || L.H != a.H || Q.substeps < 1 || (Q.models && (!Q.wts || !Q.sdt || Q.wts_stride < BLOB_FLOATS + VJP_BASE))) return hipErrorInvalidValue;
-    if (!R.act || R.ticks < 1 || R.xi_ticks < R.ticks || R.shift < 1 || R.shift > a.H || R.arrive < 0 || !(R.alpha >= 0.0f && R.alpha <= 1.0f)) return hipErrorInvalidValue;
-    KArgs k = a;
-    k.H = 1;
-    const size_t sb = Q.models ? TeamWave::IPB * (smem_bytes(1, k.m, 1) + sizeof(float) * plant_kargs_floats()) : smem_bytes(1, k.m, TeamWave::IPB);
-    const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
-    return with_f16(k.f16, [&](auto F16) {
-        if (sb > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)sdempc_loop_period_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
-            if (e != hipSuccess) return e;
-        }
-        sdempc_loop_period_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q, R);
-        return hipGetLastError();
-    });
-}
-
-// SPEC.md §11c: the period kernel with a SCENARIO — per control tick an external acceleration on the state (a disturbance row, held over the tick's substeps)
-// and the plant that flies the tick (a plant index per tick and episode). Body, hand-over and every argument of sdempc_loop_period_kernel; what differs:
-//  * the disturbance row of tick i is six floats at a wave-uniform address; after every step_fwd the register copy of x takes v_e <- fma(w_v[e], dtp, v_e)
-//    and omega_e <- fma(w_om[e], dtp, omega_e), dtp the plant's step length — six fmas, applied whenever a schedule is given (zero rows included);
-//  * the ticks of the period are walked in RUNS of ticks that name one plant. A run starts by staging that plant into the wave's own LDS carve (load_weights,
-//    WaveW, the wave's argument block for the prepass; TeamWave::sync on both sides), so inside a run the model constants are what they are in the period kernel:
-//    values defined before the tick loop, not loop-carried ones. The first run's staging is the period kernel's prologue. The state x, the motor state, the
-//    applied-control row and the noise rows carry over a switch untouched; sigma sqrt(dt) travels with the weights (sm.sdt), the rotor tables with lk->M.
-//    The wave's argument block goes from global memory to LDS lane by lane (no register copy indexed at run time, hence no scratch on its way).
-//  * one shared plant (Q.models == null): nothing to switch, the four episodes share one carve as before and C.plant is not read.
-template <int F16>
-__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_scenario_kernel(KArgs a0, LoopAdvance L, LoopPlant Q, LoopPeriod R, LoopScenario C) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int H = L.H, m = a0.m;
-    const int tid = TeamWave::tid();
-    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
-    const bool per = Q.models != nullptr, live = b < L.B;      // (both wave-uniform)
-    Smem sm = per ? carve(smem + (size_t)TeamWave::team() * smem_floats(1, m, 1), 1, m, 0) : carve(smem, 1, m, TeamWave::team());
-    WaveW ww;
-    KArgs* const lk = reinterpret_cast<KArgs*>(smem + TeamWave::IPB * smem_floats(1, m, 1) + (size_t)TeamWave::team() * plant_kargs_floats());
-    if (!per) {                     // (workgroup-uniform: a kernel argument)
-        load_weights(a0, sm, ww, threadIdx.x, TeamWave::BNT);
-        __syncthreads();
-    }
-    if (!live) return;              // (wave-uniform; no workgroup-wide barrier below)
-    const int lane = tid & 63, h = lane >> 5, n = Q.substeps;
-    const bool lag = R.alpha > 0.0f, mine = lane < m, gust = C.dist != nullptr;
-    const float* uo = L.uopt + (size_t)b * H * m;
-    float* yw = L.u + (size_t)b * H * m;
-    float* act = sm.v[5];           // [m] the applied control of the current substep
-    float am = mine ? R.act[(size_t)b * m + lane] : 0.0f;
-    float x[NX], xn[NX], xi[NN];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
-    const float* xrow = L.xi + (size_t)b * R.xi_ticks * n * NN;
-    const float* drow = gust ? C.dist + (size_t)b * C.dist_ep_stride : nullptr;
-    const int* prow = per ? C.plant + b : nullptr;
-    int i = 0;
-#pragma nounroll
-    while (i < R.ticks) {           // one run of ticks that name the same plant
-        KArgs a = a0;
-        int iend = R.ticks;
-        if (per) {
-            const int p = __builtin_amdgcn_readfirstlane(prow[(size_t)i * C.plant_tick_stride]);
-            iend = i + 1;
-#pragma nounroll
-            while (iend < R.ticks && __builtin_amdgcn_readfirstlane(prow[(size_t)iend * C.plant_tick_stride]) == p) ++iend;
-            a.M = Q.models[p];
-            a.wts = Q.wts + (size_t)p * Q.wts_stride;
-            a.sdt = Q.sdt + (size_t)p * NN;
-            TeamWave::sync();       // (the previous run's reads of the carve are done)
-            load_weights(a, sm, ww, tid, TeamWave::NT);
-            if (tid == 0) { lk->H = 1; lk->m = m; }
-            const float* msrc = reinterpret_cast<const float*>(Q.models + p);
-            float* mdst = reinterpret_cast<float*>(&lk->M);
-            for (int e = tid; e < (int)(sizeof(ModelK) / sizeof(float)); e += TeamWave::NT) mdst[e] = msrc[e];      // (what block_prepass reads)
-            TeamWave::sync();
-        }
-#pragma nounroll
-        for (; i < iend; ++i) {
-            const int row = (i < H - 1 ? i : H - 1) * m;
-            float w[NN];
-#pragma unroll
-            for (int e = 0; e < NN; ++e)
-                w[e] = gust ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, drow[(size_t)i * C.dist_tick_stride + e]))) : 0.0f;
-#pragma nounroll
-            for (int jj = 0; jj < n; ++jj) {
-                const int q = i * n + jj;
-                if (lag || jj == 0 || q == R.arrive) {
-                    if (mine) {
-                        const float c = (q >= R.arrive ? uo : yw)[row + lane];
-                        am = lag ? FMA(R.alpha, c - am, am) : c;
-                        act[lane] = am;
-                    }
-                    TeamWave::sync();       // (the row is written, the previous substep's reads of the control table are done)
-                    if (per) block_prepass<TeamWave>(*lk, sm, act, tid);
-                    else block_prepass<TeamWave>(a0, sm, act, tid);
-                    TeamWave::sync();
-                }
-                if (jj == 0 && mine) L.us[((size_t)i * L.B + b) * m + lane] = am;
-#pragma unroll
-                for (int e = 0; e < NN; ++e) xi[e] = xrow[q * NN + e];
-                StepAux A;
-                step_fwd<F16, false>(a, sm, ww, 0, h, lane, x, xi, xn, A);
-#pragma unroll
-                for (int e = 0; e < NX; ++e) x[e] = xn[e];
-                if (gust) {
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) { x[3 + e] = FMA(w[e], C.dtp, x[3 + e]); x[10 + e] = FMA(w[3 + e], C.dtp, x[10 + e]); }
-                }
-            }
-            if (lane == 0) {
-#pragma unroll
-                for (int e = 0; e < NX; ++e) L.xs[((size_t)i * L.B + b) * NX + e] = x[e];
-            }
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i) L.x[(size_t)b * NX + i] = x[i];
-        L.step[b] = L.info[(size_t)b * 8 + 1];
-        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
-    }
-    if (mine) R.act[(size_t)b * m + lane] = am;
-    for (int e = tid; e < H * m; e += TeamWave::NT) {   // y_{j+1}: row t = uopt_j[min(t + S, H - 1)]
-        const int t = e / m, ts = t + R.shift < H ? t + R.shift : H - 1;
-        yw[e] = uo[ts * m + (e - t * m)];
-    }
-}
-
-hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, hipStream_t st) {
-    if (L.B < 1 || L.H != a.H || Q.substeps < 1 || (Q.models && (!Q.wts || !Q.sdt || Q.wts_stride < BLOB_FLOATS + VJP_BASE))) return hipErrorInvalidValue;
-    if (!R.act || R.ticks < 1 || R.xi_ticks < R.ticks || R.shift < 1 || R.shift > a.H || R.arrive < 0 || !(R.alpha >= 0.0f && R.alpha <= 1.0f)) return hipErrorInvalidValue;
-    if ((Q.models && !C.plant) || (C.plant_tick_stride != 0 && C.plant_tick_stride != L.B)) return hipErrorInvalidValue;
-    if (C.dist_tick_stride < 0 || (C.dist_ep_stride != 0 && C.dist_ep_stride != NN) || !(C.dtp > 0.0f)) return hipErrorInvalidValue;
-    KArgs k = a;
-    k.H = 1;
-    const size_t sb = Q.models ? TeamWave::IPB * (smem_bytes(1, k.m, 1) + sizeof(float) * plant_kargs_floats()) : smem_bytes(1, k.m, TeamWave::IPB);
-    const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
-    return with_f16(k.f16, [&](auto F16) {
-        if (sb > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)sdempc_loop_scenario_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
-            if (e != hipSuccess) return e;
-        }
-        sdempc_loop_scenario_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q, R, C);
-        return hipGetLastError();
-    });
-}
-
-// SPEC.md §11d: the scenario kernel with the vehicle's inner RATE LOOP in front of the motor lag — the loop the node flies through its thrust and body-rate
-// setpoint interface. Body, hand-over and every argument of sdempc_loop_scenario_kernel (runs of ticks per plant, shared or per-episode LDS carves; C.dist and
-// C.plant null when no scenario is given); what differs:
+//
+// The ticks of the period are walked in RUNS of ticks that name one plant. A run starts by staging that plant (stage_plant), so inside a run the model constants
+// are values defined before the tick loop, not loop-carried ones. The state x, the motor state, the applied-control row and the noise rows carry over a switch
+// untouched. Without SCEN the period is one run, flown by plant Q.plant_of[b] (or b); with one shared plant (Q.models == null) there is nothing to stage or to
+// switch, and neither Q.plant_of nor C.plant is read.
+//
+// SCEN (SPEC.md §11c): a scenario — the plant that flies each tick (C.plant: a plant index per tick and episode, which replaces Q.plant_of) and per control tick an
+// external acceleration on the state (C.dist: a disturbance row, six floats at a wave-uniform address, held over the tick's substeps; see loop_substep).
+//
+// RATE (SPEC.md §11d, with SCEN; C.dist and C.plant null when no scenario is given): the vehicle's inner RATE LOOP in front of the motor lag — the loop the node
+// flies through its thrust and body-rate setpoint interface.
 //  * the command of a substep is no longer a row of the solution but what the rate loop makes of it and of the plant's CURRENT body rates, so it changes on every
-//    substep and block_prepass reruns on every substep, between the same pair of TeamWave::sync();
+//    substep and the prepass reruns on every substep;
 //  * the setpoint row (the m motor values, the three rates) sits at wave-uniform addresses and every lane reads all of it: the thrust is the sum of the m values in
 //    index order in every lane (the order is part of the SPEC: no cross-lane reduction), the rate error, the integrator and the torque demand are wave-uniform
 //    values computed redundantly by every lane from lane 0's copy of omega (readfirstlane), and lane l < m forms motor l's command;
@@ -363,171 +165,187 @@ hipError_t launch_loop_scenario(const KArgs& a, const LoopAdvance& L, const Loop
 //    (a load from the argument segment at a computed offset; a copy of W indexed at run time would live in scratch), once, before the tick loop;
 //  * the rate tail W.wt is read inside the substep loop and rewritten, shifted like the warm start, after it, by the same wave; the integrator W.g goes in and out
 //    like the motor state; W.ws takes the setpoint in force at each tick's first substep.
-template <int F16>
-__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_rate_kernel(KArgs a0, LoopAdvance L, LoopPlant Q, LoopPeriod R, LoopScenario C, LoopRate W) {
+// Without SCEN / RATE the kernel takes an empty LoopAbsent in place of C / W: its argument segment is what the feature needs, no more.
+struct LoopAbsent {};
+template <int F16, bool SCEN, bool RATE>
+__global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_period_kernel(KArgs a0, LoopAdvance L, LoopPlant Q, LoopPeriod R, std::conditional_t<SCEN, LoopScenario, LoopAbsent> C,
+                                                                           std::conditional_t<RATE, LoopRate, LoopAbsent> W) {
+    static_assert(SCEN || !RATE, "the rate loop comes with the scenario's arguments");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int H = L.H, m = a0.m;
-    const int tid = TeamWave::tid();
-    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * TeamWave::IPB + TeamWave::team());
-    const bool per = Q.models != nullptr, live = b < L.B;      // (both wave-uniform)
-    Smem sm = per ? carve(smem + (size_t)TeamWave::team() * smem_floats(1, m, 1), 1, m, 0) : carve(smem, 1, m, TeamWave::team());
-    WaveW ww;
-    KArgs* const lk = reinterpret_cast<KArgs*>(smem + TeamWave::IPB * smem_floats(1, m, 1) + (size_t)TeamWave::team() * plant_kargs_floats());
-    if (!per) {                     // (workgroup-uniform: a kernel argument)
-        load_weights(a0, sm, ww, threadIdx.x, TeamWave::BNT);
-        __syncthreads();
+    LoopWave w;
+    if (!loop_prologue(smem, a0, L, Q, w)) return;
+    const int H = L.H, m = a0.m, b = w.b, lane = w.lane, n = Q.substeps;
+    const bool lag = R.alpha > 0.0f, mine = lane < m;
+    bool gust = false;              // a disturbance schedule is given
+    float dtp = 0.0f;
+    const float* drow = nullptr;
+    if constexpr (SCEN) {
+        gust = C.dist != nullptr;
+        dtp = C.dtp;
+        if (gust) drow = C.dist + (size_t)b * C.dist_ep_stride;
     }
-    if (!live) return;              // (wave-uniform; no workgroup-wide barrier below)
-    const int lane = tid & 63, h = lane >> 5, n = Q.substeps;
-    const bool lag = R.alpha > 0.0f, mine = lane < m, gust = C.dist != nullptr;
     const float* uo = L.uopt + (size_t)b * H * m;
     float* yw = L.u + (size_t)b * H * m;
-    const float* xe = W.xevol + (size_t)b * (H + 1) * NX;
-    float* wt = W.wt + (size_t)b * H * 3;
-    float* act = sm.v[5];           // [m] the applied control of the current substep
+    const float* xe = nullptr;
+    float* wt = nullptr;
+    float* act = w.sm.v[5];         // [m] the applied control of the current substep
     float am = mine ? R.act[(size_t)b * m + lane] : 0.0f;
     const int ml = mine ? lane : 0;                             // (lanes >= m compute motor 0's command and drop it)
-    const float M0 = W.M[ml][0], M1 = W.M[ml][1], M2 = W.M[ml][2], ulo = W.lo[ml], uhi = W.hi[ml];
-    float g[3];
+    float M0 = 0.0f, M1 = 0.0f, M2 = 0.0f, ulo = 0.0f, uhi = 0.0f, g[3] = {0.0f, 0.0f, 0.0f};
+    if constexpr (RATE) {
+        xe = W.xevol + (size_t)b * (H + 1) * NX;
+        wt = W.wt + (size_t)b * H * 3;
+        M0 = W.M[ml][0]; M1 = W.M[ml][1]; M2 = W.M[ml][2]; ulo = W.lo[ml]; uhi = W.hi[ml];
 #pragma unroll
-    for (int e = 0; e < 3; ++e) g[e] = W.g[(size_t)b * 3 + e];
-    float x[NX], xn[NX], xi[NN];
+        for (int e = 0; e < 3; ++e) g[e] = W.g[(size_t)b * 3 + e];
+    }
+    float x[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
     const float* xrow = L.xi + (size_t)b * R.xi_ticks * n * NN;
-    const float* drow = gust ? C.dist + (size_t)b * C.dist_ep_stride : nullptr;
-    const int* prow = per ? C.plant + b : nullptr;
     int i = 0;
-#pragma nounroll
-    while (i < R.ticks) {           // one run of ticks that name the same plant
-        KArgs a = a0;
-        int iend = R.ticks;
-        if (per) {
-            const int p = __builtin_amdgcn_readfirstlane(prow[(size_t)i * C.plant_tick_stride]);
-            iend = i + 1;
-#pragma nounroll
-            while (iend < R.ticks && __builtin_amdgcn_readfirstlane(prow[(size_t)iend * C.plant_tick_stride]) == p) ++iend;
-            a.M = Q.models[p];
-            a.wts = Q.wts + (size_t)p * Q.wts_stride;
-            a.sdt = Q.sdt + (size_t)p * NN;
-            TeamWave::sync();       // (the previous run's reads of the carve are done)
-            load_weights(a, sm, ww, tid, TeamWave::NT);
-            if (tid == 0) { lk->H = 1; lk->m = m; }
-            const float* msrc = reinterpret_cast<const float*>(Q.models + p);
-            float* mdst = reinterpret_cast<float*>(&lk->M);
-            for (int e = tid; e < (int)(sizeof(ModelK) / sizeof(float)); e += TeamWave::NT) mdst[e] = msrc[e];      // (what block_prepass reads)
-            TeamWave::sync();
-        }
+    auto fly = [&](const KArgs& a, int iend) __attribute__((always_inline)) {      // the ticks [i, iend) of one run: `a` holds the plant that flies them
 #pragma nounroll
         for (; i < iend; ++i) {
             const int r = i < H - 1 ? i : H - 1, row = r * m;
-            float w[NN];
+            float wd[NN];
 #pragma unroll
-            for (int e = 0; e < NN; ++e)
-                w[e] = gust ? __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, drow[(size_t)i * C.dist_tick_stride + e]))) : 0.0f;
+            for (int e = 0; e < NN; ++e) wd[e] = 0.0f;
+            if constexpr (SCEN) {
+                if (gust) {
+#pragma unroll
+                    for (int e = 0; e < NN; ++e)
+                        wd[e] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, drow[(size_t)i * C.dist_tick_stride + e])));
+                }
+            }
 #pragma nounroll
             for (int jj = 0; jj < n; ++jj) {
                 const int q = i * n + jj;
                 const bool fresh = q >= R.arrive;               // (wave-uniform: the arrival point is the same for every episode)
-                const float* us_ = (fresh ? uo : yw) + row;     // the motor row in force
-                const float* ws_ = fresh ? xe + (size_t)(r + 1) * NX + 10 : wt + (size_t)r * 3;     // the rate row in force
-                float cbar = us_[0];                            // 1. setpoint: thrust, the sum left to right in every lane
+                bool moved = true;                              // the command can have changed since the last prepass
+                float c = 0.0f;
+                if constexpr (RATE) {
+                    const float* us_ = (fresh ? uo : yw) + row;     // the motor row in force
+                    const float* ws_ = fresh ? xe + (size_t)(r + 1) * NX + 10 : wt + (size_t)r * 3;     // the rate row in force
+                    float cbar = us_[0];                            // 1. setpoint: thrust, the sum left to right in every lane
 #pragma nounroll
-                for (int l = 1; l < m; ++l) cbar = cbar + us_[l];
-                cbar = cbar * W.inv_m;
-                float tau[3], wsp[3];
+                    for (int l = 1; l < m; ++l) cbar = cbar + us_[l];
+                    cbar = cbar * W.inv_m;
+                    float tau[3], wsp[3];
 #pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    wsp[e] = ws_[e];
-                    const float om = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x[10 + e])));
-                    const float er = wsp[e] - om;               // 2. error, against the state of THIS substep
-                    const float gi = FMA(W.ki_dt[e], er, g[e]), gl = W.glim[e];
-                    g[e] = gi < -gl ? -gl : (gi > gl ? gl : gi);        // 3. integrator
-                    tau[e] = FMA(W.kp[e], er, g[e]);            // 4. torque demand, with the updated integrator
-                }
-                const float ul = us_[ml];
-                const float mx = FMA(M2, tau[2], FMA(M1, tau[1], FMA(M0, tau[0], cbar)));
-                const float cw = mx < ulo ? ulo : (mx > uhi ? uhi : mx);       // 5. mixer, clamped to the input bounds
-                const float c = W.w == 0.0f ? cw : (W.w == 1.0f ? ul : FMA(W.w, ul - cw, cw));      // 6. blend
-                if (mine) {
-                    am = lag ? FMA(R.alpha, c - am, am) : c;
-                    act[lane] = am;
-                }
-                TeamWave::sync();       // (the row is written, the previous substep's reads of the control table are done)
-                if (per) block_prepass<TeamWave>(*lk, sm, act, tid);
-                else block_prepass<TeamWave>(a0, sm, act, tid);
-                TeamWave::sync();
-                if (jj == 0) {
-                    if (mine) L.us[((size_t)i * L.B + b) * m + lane] = am;
-                    if (lane == 0) {
+                    for (int e = 0; e < 3; ++e) {
+                        wsp[e] = ws_[e];
+                        const float om = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x[10 + e])));
+                        const float er = wsp[e] - om;               // 2. error, against the state of THIS substep
+                        const float gi = FMA(W.ki_dt[e], er, g[e]), gl = W.glim[e];
+                        g[e] = gi < -gl ? -gl : (gi > gl ? gl : gi);        // 3. integrator
+                        tau[e] = FMA(W.kp[e], er, g[e]);            // 4. torque demand, with the updated integrator
+                    }
+                    const float ul = us_[ml];
+                    const float mx = FMA(M2, tau[2], FMA(M1, tau[1], FMA(M0, tau[0], cbar)));
+                    const float cw = mx < ulo ? ulo : (mx > uhi ? uhi : mx);       // 5. mixer, clamped to the input bounds
+                    c = W.w == 0.0f ? cw : (W.w == 1.0f ? ul : FMA(W.w, ul - cw, cw));      // 6. blend
+                    if (jj == 0 && lane == 0) {
                         float* wo = W.ws + ((size_t)i * L.B + b) * 4;
                         wo[0] = cbar; wo[1] = wsp[0]; wo[2] = wsp[1]; wo[3] = wsp[2];
                     }
+                } else {
+                    moved = lag || jj == 0 || q == R.arrive;
+                    if (moved && mine) c = (fresh ? uo : yw)[row + lane];
                 }
-#pragma unroll
-                for (int e = 0; e < NN; ++e) xi[e] = xrow[q * NN + e];
-                StepAux A;
-                step_fwd<F16, false>(a, sm, ww, 0, h, lane, x, xi, xn, A);
-#pragma unroll
-                for (int e = 0; e < NX; ++e) x[e] = xn[e];
-                if (gust) {
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) { x[3 + e] = FMA(w[e], C.dtp, x[3 + e]); x[10 + e] = FMA(w[3 + e], C.dtp, x[10 + e]); }
+                if (moved) {
+                    if (mine) {
+                        am = lag ? FMA(R.alpha, c - am, am) : c;
+                        act[lane] = am;
+                    }
+                    loop_prepass(a0, w, act);
                 }
+                if (jj == 0 && mine) L.us[((size_t)i * L.B + b) * m + lane] = am;
+                loop_substep<F16>(a, w, xrow + q * NN, x, gust, wd, dtp);
             }
             if (lane == 0) {
 #pragma unroll
                 for (int e = 0; e < NX; ++e) L.xs[((size_t)i * L.B + b) * NX + e] = x[e];
             }
         }
+    };
+    if constexpr (SCEN) {
+#pragma nounroll
+        while (i < R.ticks) {       // one run of ticks that name the same plant
+            KArgs a = a0;
+            int iend = R.ticks;
+            if (w.per) {
+                const int* prow = C.plant + b;
+                const int p = __builtin_amdgcn_readfirstlane(prow[(size_t)i * C.plant_tick_stride]);
+                iend = i + 1;
+#pragma nounroll
+                while (iend < R.ticks && __builtin_amdgcn_readfirstlane(prow[(size_t)iend * C.plant_tick_stride]) == p) ++iend;
+                stage_plant(Q, p, a, w);
+            }
+            fly(a, iend);
+        }
+    } else {                        // one run, staged before the kernel's first store
+        KArgs a = a0;
+        if (w.per) stage_plant(Q, __builtin_amdgcn_readfirstlane(Q.plant_of ? Q.plant_of[b] : b), a, w);
+        fly(a, R.ticks);
     }
-    if (lane == 0) {
+    if constexpr (RATE) {
+        if (lane == 0) {
 #pragma unroll
-        for (int i = 0; i < NX; ++i) L.x[(size_t)b * NX + i] = x[i];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) W.g[(size_t)b * 3 + e] = g[e];
-        L.step[b] = L.info[(size_t)b * 8 + 1];
-        if (L.coop_bar && L.coop_bar[(size_t)COOP_BAR_WORDS * b + 1] != 0u) *L.gave_up = 1u;
+            for (int e = 0; e < 3; ++e) W.g[(size_t)b * 3 + e] = g[e];
+        }
     }
-    if (mine) R.act[(size_t)b * m + lane] = am;
-    for (int e = tid; e < H * m; e += TeamWave::NT) {   // y_{j+1}: row t = uopt_j[min(t + S, H - 1)]
-        const int t = e / m, ts = t + R.shift < H ? t + R.shift : H - 1;
-        yw[e] = uo[ts * m + (e - t * m)];
-    }
-    for (int e = tid; e < H * 3; e += TeamWave::NT) {   // rate tail: row t = xevol_j[min(t + S, H - 1) + 1][10..12]
-        const int t = e / 3, ts = t + R.shift < H ? t + R.shift : H - 1;
-        wt[e] = xe[(size_t)(ts + 1) * NX + 10 + (e - t * 3)];
+    loop_handover(L, w, m, x, uo, R.shift, R.act, am);     // y_{j+1}: row t = uopt_j[min(t + S, H - 1)]
+    if constexpr (RATE) {
+        for (int e = w.tid; e < H * 3; e += TeamWave::NT) {   // rate tail: row t = xevol_j[min(t + S, H - 1) + 1][10..12]
+            const int t = e / 3, ts = t + R.shift < H ? t + R.shift : H - 1;
+            wt[e] = xe[(size_t)(ts + 1) * NX + 10 + (e - t * 3)];
+        }
     }
 }
 
-hipError_t launch_loop_rate(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, const LoopPeriod& R, const LoopScenario& C, const LoopRate& W, hipStream_t st) {
-    if (L.B < 1 || L.H != a.H || Q.substeps < 1 || (Q.models && (!Q.wts || !Q.sdt || Q.wts_stride < BLOB_FLOATS + VJP_BASE))) return hipErrorInvalidValue;
-    if (!R.act || R.ticks < 1 || R.xi_ticks < R.ticks || R.shift < 1 || R.shift > a.H || R.arrive < 0 || !(R.alpha >= 0.0f && R.alpha <= 1.0f)) return hipErrorInvalidValue;
-    if ((Q.models && !C.plant) || (C.plant_tick_stride != 0 && C.plant_tick_stride != L.B)) return hipErrorInvalidValue;
-    if (C.dist_tick_stride < 0 || (C.dist_ep_stride != 0 && C.dist_ep_stride != NN) || !(C.dtp > 0.0f)) return hipErrorInvalidValue;
-    if (!W.xevol || !W.wt || !W.g || !W.ws || !(W.w >= 0.0f && W.w <= 1.0f) || a.m < 1 || a.m > 8) return hipErrorInvalidValue;
+// what a launch refuses, per argument struct (each checked where its struct is used)
+inline bool loop_ok(const KArgs& a, const LoopAdvance& L, const LoopPlant& Q) {
+    return !(L.B < 1 || L.H != a.H || Q.substeps < 1 || (Q.models && (!Q.wts || !Q.sdt || Q.wts_stride < BLOB_FLOATS + VJP_BASE)));
+}
+inline bool loop_ok(const KArgs& a, const LoopPeriod& R) {
+    return !(!R.act || R.ticks < 1 || R.xi_ticks < R.ticks || R.shift < 1 || R.shift > a.H || R.arrive < 0 || !(R.alpha >= 0.0f && R.alpha <= 1.0f));
+}
+inline bool loop_ok(const LoopAdvance& L, const LoopPlant& Q, const LoopScenario& C) {
+    return !((Q.models && !C.plant) || (C.plant_tick_stride != 0 && C.plant_tick_stride != L.B)) &&
+           !(C.dist_tick_stride < 0 || (C.dist_ep_stride != 0 && C.dist_ep_stride != NN) || !(C.dtp > 0.0f));
+}
+inline bool loop_ok(const KArgs& a, const LoopRate& W) {
+    return !(!W.xevol || !W.wt || !W.g || !W.ws || !(W.w >= 0.0f && W.w <= 1.0f) || a.m < 1 || a.m > 8);
+}
+
+// LDS of a workgroup (one carve of four teams, or four carves of one team and the four argument blocks), the opt-in above 64 KB, one wave per episode, the launch.
+// `more`: the kernel's arguments after (KArgs, LoopAdvance, LoopPlant).
+template <class Kernel, class... More>
+hipError_t loop_launch(Kernel kernel, const KArgs& a, const LoopAdvance& L, const LoopPlant& Q, hipStream_t st, const More&... more) {
     KArgs k = a;
     k.H = 1;
     const size_t sb = Q.models ? TeamWave::IPB * (smem_bytes(1, k.m, 1) + sizeof(float) * plant_kargs_floats()) : smem_bytes(1, k.m, TeamWave::IPB);
     const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
-    return with_f16(k.f16, [&](auto F16) {
-        if (sb > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)sdempc_loop_rate_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
-            if (e != hipSuccess) return e;
-        }
-        sdempc_loop_rate_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L, Q, R, C, W);
-        return hipGetLastError();
-    });
+    if (sb > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sb);
+        if (e != hipSuccess) return e;
+    }
+    kernel<<<grid, TeamWave::BNT, sb, st>>>(k, L, Q, more...);
+    return hipGetLastError();
 }
 
-hipError_t launch_loop_advance(const KArgs& a, const LoopAdvance& L, hipStream_t st) {
-    if (L.B < 1 || L.H != a.H) return hipErrorInvalidValue;
-    KArgs k = a;
-    k.H = 1;
-    const size_t sb = smem_bytes(1, k.m, TeamWave::IPB);
-    const dim3 grid((L.B + TeamWave::IPB - 1) / TeamWave::IPB);
-    return with_f16(k.f16, [&](auto F16) {
-        sdempc_loop_advance_kernel<F16><<<grid, TeamWave::BNT, sb, st>>>(k, L);
-        return hipGetLastError();
+// launch_loop of sdempc_kernels.h in this math mode
+hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st) {
+    LoopPlant own{};                // no plant set: the handle's own model (a's), one step per tick
+    own.substeps = 1;
+    const LoopPlant& q = Q ? *Q : own;
+    if (!loop_ok(a, L, q) || (R && !loop_ok(a, *R)) || (C && !loop_ok(L, q, *C)) || (W && !loop_ok(a, *W))) return hipErrorInvalidValue;
+    if ((C && !R) || (W && !C)) return hipErrorInvalidValue;
+    return with_f16(a.f16, [&](auto F16) {
+        if (!R) return Q ? loop_launch(sdempc_loop_tick_kernel<F16, true>, a, L, q, st) : loop_launch(sdempc_loop_tick_kernel<F16, false>, a, L, q, st);
+        if (W) return loop_launch(sdempc_loop_period_kernel<F16, true, true>, a, L, q, st, *R, *C, *W);
+        if (C) return loop_launch(sdempc_loop_period_kernel<F16, true, false>, a, L, q, st, *R, *C, LoopAbsent{});
+        return loop_launch(sdempc_loop_period_kernel<F16, false, false>, a, L, q, st, *R, LoopAbsent{}, LoopAbsent{});
     });
 }

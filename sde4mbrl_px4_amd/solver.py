@@ -310,13 +310,14 @@ class SdeMpcSolver:
         s_next = np.zeros(B, np.float32)
         k_next = np.zeros((B, 2), np.uint32)
         u32p = C.POINTER(C.c_uint32)
-        tail = (B, T, _fp(x0), _fp(xref), int(xref.shape[0]), int(xref.shape[1]), keys.ctypes.data_as(u32p), u_p, s_p,
-                _fp(xs), _fp(us), info.ctypes.data_as(C.POINTER(SdempcInfo)), _fp(u_next), _fp(s_next), k_next.ctypes.data_as(u32p))
+        common = (B, T, _fp(x0), _fp(xref), int(xref.shape[0]), int(xref.shape[1]), keys.ctypes.data_as(u32p), u_p, s_p)
+        outs = (_fp(xs), _fp(us), info.ctypes.data_as(C.POINTER(SdempcInfo)), _fp(u_next), _fp(s_next), k_next.ctypes.data_as(u32p))
+        ret = (xs, us, info, u_next, s_next, k_next)
         if plant is None:
             if plant_of is not None or plant_substeps != 1 or plant_dt is not None or plant_mlp_dtype is not None or plant_math_mode is not None:
                 raise ValueError("closed_loop: plant_of / plant_substeps / plant_dt / plant_mlp_dtype / plant_math_mode need plant=...")
-            self._check(self.lib.sdempc_closed_loop_batch(self._h, *tail))
-            return xs, us, info, u_next, s_next, k_next
+            self._check(self.lib.sdempc_closed_loop_batch(self._h, *common, *outs))
+            return ret
         plants = [plant] if hasattr(plant, "to_blob") or isinstance(plant, (bytes, bytearray, memoryview)) else list(plant)
         blobs = [p.to_blob() if hasattr(p, "to_blob") else bytes(p) for p in plants]
         Np = len(blobs)
@@ -333,40 +334,42 @@ class SdeMpcSolver:
         pc = _abi.SdempcPlantCfg(C.sizeof(_abi.SdempcPlantCfg), Np, int(plant_substeps), 0.0 if plant_dt is None else float(np.float32(plant_dt)),
                                  -1 if plant_mlp_dtype is None else _abi_enum(MLP_DTYPES, plant_mlp_dtype, "plant_mlp_dtype"),
                                  -1 if plant_math_mode is None else _abi_enum(MATH_MODES, plant_math_mode, "plant_math_mode"))
+        # Each layer puts one more configuration pointer in front of the layer below (include/sdempc.h); from the timed one on u_act_in sits before
+        # the outputs, and the layer's own outputs follow them in the C call as in the returned tuple.
+        lead, u_act, more = [C.byref(pc)], (), ()
         if timed:
             tc = _abi.SdempcTimingCfg(C.sizeof(_abi.SdempcTimingCfg), S_, D_, alpha)
             a_next = np.zeros((B, self.m), np.float32)
-            if rate_loop is not None:
-                rc_, keep = self._rate_cfg(rate_loop, plant_substeps, plant_dt)
-                g_p = t_p = None
-                if rate_integ_in is not None:
-                    rate_integ_in = _f32(rate_integ_in, (B, 3))
-                    g_p = _fp(rate_integ_in)
-                if rate_tail_in is not None:
-                    rate_tail_in = _f32(rate_tail_in, (B, self.H, 3))
-                    t_p = _fp(rate_tail_in)
-                sc = None
-                if scenario:
-                    sc = _abi.SdempcScenarioCfg(C.sizeof(_abi.SdempcScenarioCfg), None if dist is None else _fp(dist), 1 if dist is None else dist.shape[0],
-                                                1 if dist is None else dist.shape[1], 1 if sched is None else sched.shape[0])
-                ws = np.zeros((B, max(T, 0), 4), np.float32)
-                g_next = np.zeros((B, 3), np.float32)
-                t_next = np.zeros((B, self.H, 3), np.float32)
-                self._check(_abi.rate_entry(self.lib)(self._h, C.byref(rc_), None if sc is None else C.byref(sc), C.byref(tc), C.byref(pc),
-                                                      C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *tail[:9], a_p, *tail[9:], _fp(a_next),
-                                                      g_p, t_p, _fp(ws), _fp(g_next), _fp(t_next)))
-                return xs, us, info, u_next, s_next, k_next, a_next, ws, g_next, t_next
-            if scenario:
-                sc = _abi.SdempcScenarioCfg(C.sizeof(_abi.SdempcScenarioCfg), None if dist is None else _fp(dist), 1 if dist is None else dist.shape[0],
-                                            1 if dist is None else dist.shape[1], 1 if sched is None else sched.shape[0])
-                self._check(_abi.scenario_entry(self.lib)(self._h, C.byref(sc), C.byref(tc), C.byref(pc), C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p,
-                                                          *tail[:9], a_p, *tail[9:], _fp(a_next)))
-                return xs, us, info, u_next, s_next, k_next, a_next
-            self._check(_abi.timed_entry(self.lib)(self._h, C.byref(tc), C.byref(pc), C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *tail[:9], a_p,
-                                                    *tail[9:], _fp(a_next)))
-            return xs, us, info, u_next, s_next, k_next, a_next
-        self._check(self.lib.sdempc_closed_loop_batch_plant(self._h, C.byref(pc), C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *tail))
-        return xs, us, info, u_next, s_next, k_next
+            lead, u_act, more, ret = [C.byref(tc)] + lead, (a_p,), (_fp(a_next),), ret + (a_next,)
+        if scenario:
+            sc = _abi.SdempcScenarioCfg(C.sizeof(_abi.SdempcScenarioCfg), None if dist is None else _fp(dist), 1 if dist is None else dist.shape[0],
+                                        1 if dist is None else dist.shape[1], 1 if sched is None else sched.shape[0])
+            lead = [C.byref(sc)] + lead
+        if rate_loop is not None:
+            rc_, keep = self._rate_cfg(rate_loop, plant_substeps, plant_dt)
+            g_p = t_p = None
+            if rate_integ_in is not None:
+                rate_integ_in = _f32(rate_integ_in, (B, 3))
+                g_p = _fp(rate_integ_in)
+            if rate_tail_in is not None:
+                rate_tail_in = _f32(rate_tail_in, (B, self.H, 3))
+                t_p = _fp(rate_tail_in)
+            ws = np.zeros((B, max(T, 0), 4), np.float32)
+            g_next = np.zeros((B, 3), np.float32)
+            t_next = np.zeros((B, self.H, 3), np.float32)
+            lead = [C.byref(rc_)] + (lead if scenario else [None] + lead)       # (no scenario: a NULL scenario cfg)
+            more, ret = more + (g_p, t_p, _fp(ws), _fp(g_next), _fp(t_next)), ret + (ws, g_next, t_next)
+        # the entry point, from (timed, scenario, rate_loop) alone; only the one that is called is looked up
+        if rate_loop is not None:
+            entry = _abi.rate_entry(self.lib)
+        elif scenario:
+            entry = _abi.scenario_entry(self.lib)
+        elif timed:
+            entry = _abi.timed_entry(self.lib)
+        else:
+            entry = self.lib.sdempc_closed_loop_batch_plant
+        self._check(entry(self._h, *lead, C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *common, *u_act, *outs, *more))
+        return ret
 
     def _rate_cfg(self, rate_loop, plant_substeps, plant_dt):
         """sdempc_rate_cfg of a RateLoop for this handle: ki_dt = float32(ki) * float32(dt_plant), the default mixer from the controller's rotor tables (as

@@ -1,12 +1,14 @@
 """Batched closed loop on the GPU (SPEC.md §11, sdempc_closed_loop_batch): bit for bit against the CPU reference of tests/closed_loop_ref.py
 (a composition of the oracle's solve and step), against a host loop of single-tick GPU solves, in every layout, across
 continuation, with diverging episodes and at a batch size that needs ticketed persistent launches."""
+import functools
 import os
 
 import numpy as np
 import pytest
 
 import orc
+import loop_cases
 from cases import CDIR, bits_differ, diverging_single_rotor_case
 from closed_loop_ref import closed_loop_ref
 from sde4mbrl_px4_amd import load_mpc_config, prng, synthetic_iris
@@ -28,15 +30,7 @@ def episodes(cfg, B, seed):
     return x0, xref, keys
 
 
-def assert_same(got, want, eps=None):
-    names = ("xs", "us", "info", "u_next", "stepsize_next", "keys_next")
-    for n, g, w in zip(names, got, want):
-        if eps is not None:
-            g, w = g[eps], w[eps]
-        if n == "keys_next":
-            assert np.array_equal(g, w), n
-        else:
-            assert bits_differ(g, w) == 0, (n, bits_differ(g, w))
+assert_same = functools.partial(loop_cases.same, names=loop_cases.NAMES[:6])
 
 
 @pytest.mark.parametrize("math_mode", ["exact", "fast"])

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from cases import bits_differ, diverging_single_rotor_case
+from loop_cases import ARITH
 from plant_loop_ref import plant_loop_ref
 from sde4mbrl_px4_amd import prng, synthetic_iris
 from sde4mbrl_px4_amd import workload as W
@@ -15,7 +16,6 @@ from test_gpu_closed_loop import LAYOUTS, assert_same, episodes, small_cfg
 
 pytestmark = pytest.mark.gpu
 
-ARITH = [(d, mth) for d in ("f32", "f16", "f32x3") for mth in ("exact", "fast")]
 AMOUNTS = dict(mass=0.2, inertia=0.2, thrust=0.2, residual=0.2)
 
 

@@ -5,12 +5,15 @@ plants; every arithmetic; scenario and rate loop together; lag on and off; every
 chunk boundaries, a handle with a past, and the C entry point against the timed one. The gains are those of tests/rate_loop_cases.py, whose census (asserted in
 tests/test_rate_loop_cpu.py) shows that the reference reaches both clamps on these inputs."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 
+import loop_cases
 from cases import CDIR, asymmetric_cfg, asymmetric_model, bits_differ
+from loop_cases import ARITH, NAMES, same
 from rate_loop_cases import (ALPHA, B5, S3, SCHEDULE, T7, WEIGHTS, disturbance, episodes, full_mixer, integ_state, motor_state, perturbed_plants, rate_loop,
                              rate_tail, small_cfg, timing)
 from rate_loop_ref import rate_loop_ref
@@ -21,27 +24,7 @@ from test_gpu_closed_loop import LAYOUTS
 
 pytestmark = pytest.mark.gpu
 
-ARITH = [(d, mth) for d in ("f32", "f16", "f32x3") for mth in ("exact", "fast")]
-NAMES = ("xs", "us", "info", "u_next", "stepsize_next", "keys_next", "u_act_next", "ws", "rate_integ_next", "rate_tail_next")
-REF_NAME = dict(plant="plants", plant_substeps="substeps", solve_period="S", solve_delay="D", motor_lag="alpha", plant_mlp_dtype="mlp_dtype",
-                plant_math_mode="math_mode", plant_dt="dt")
-
-
-def same(got, want, eps=None, names=NAMES):
-    assert len(got) == len(want) == len(names)
-    for n, g, w in zip(names, got, want):
-        if eps is not None:
-            g, w = g[eps], w[eps]
-        assert g.shape == w.shape, (n, g.shape, w.shape)
-        if n == "keys_next":
-            assert np.array_equal(g, w), n
-        else:
-            assert bits_differ(g, w) == 0, (n, bits_differ(g, w))
-
-
-def ref(cfg, model, x0, xref, keys, T, episodes=None, **kw):
-    """The reference for the keyword arguments of SdeMpcSolver.closed_loop."""
-    return rate_loop_ref(cfg, model, x0=x0, xref=xref, keys=keys, T=T, episodes=episodes, **{"plants": None, **{REF_NAME.get(k, k): v for k, v in kw.items()}})
+ref = functools.partial(loop_cases.ref, rate_loop_ref)
 
 
 @pytest.mark.parametrize("per_episode", [False, True], ids=["shared", "per_episode"])

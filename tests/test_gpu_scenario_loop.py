@@ -4,12 +4,15 @@ tests/test_gpu_timed_loop.py: H = 4 with S = 3, T = 7 (a partial last period), B
 D = n + 1, alpha = 0.35; every shape of the disturbance tensor, a plant schedule with every kind of switch, every arithmetic, every solve layout,
 continuation, chunk boundaries, a handle with a past, simulate's frame conversion and the C entry point with both schedules absent."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 
+import loop_cases
 from cases import CDIR, bits_differ
+from loop_cases import ARITH, NAMES
 from scenario_cases import ALPHA, B5, S3, SCHEDULE, T7, disturbance, episodes, motor_state, perturbed_plants, small_cfg, switch_ticks
 from scenario_loop_ref import scenario_loop_ref
 from sde4mbrl_px4_amd import _abi, load_mpc_config, prng, synthetic_hexa, synthetic_iris
@@ -20,27 +23,8 @@ from test_gpu_closed_loop import LAYOUTS
 
 pytestmark = pytest.mark.gpu
 
-ARITH = [(d, mth) for d in ("f32", "f16", "f32x3") for mth in ("exact", "fast")]
-NAMES = ("xs", "us", "info", "u_next", "stepsize_next", "keys_next", "u_act_next")
-REF_NAME = dict(plant="plants", plant_substeps="substeps", solve_period="S", solve_delay="D", motor_lag="alpha", plant_mlp_dtype="mlp_dtype",
-                plant_math_mode="math_mode", plant_dt="dt")
-
-
-def same(got, want, eps=None):
-    assert len(got) == len(want) == 7
-    for n, g, w in zip(NAMES, got, want):
-        if eps is not None:
-            g, w = g[eps], w[eps]
-        assert g.shape == w.shape, (n, g.shape, w.shape)
-        if n == "keys_next":
-            assert np.array_equal(g, w), n
-        else:
-            assert bits_differ(g, w) == 0, (n, bits_differ(g, w))
-
-
-def ref(cfg, model, x0, xref, keys, T, episodes=None, **kw):
-    """The reference for the keyword arguments of SdeMpcSolver.closed_loop."""
-    return scenario_loop_ref(cfg, model, x0=x0, xref=xref, keys=keys, T=T, episodes=episodes, **{"plants": None, **{REF_NAME.get(k, k): v for k, v in kw.items()}})
+same = functools.partial(loop_cases.same, names=NAMES[:7])
+ref = functools.partial(loop_cases.ref, scenario_loop_ref)
 
 
 def timing(n):

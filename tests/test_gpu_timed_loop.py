@@ -2,12 +2,15 @@
 tests/timed_loop_ref.py (a composition of the oracle's solve and step with float32 arithmetic for the motor lag). Shapes: H = 4 with S = 3 (the
 shift clamp fires; at H = 2 the command-row clamp fires too), T = 7 (a partial last period), B = 5 (a partly empty last workgroup), P in {1, 33},
 n in {1, 3}, every kind of arrival point, shared and per-episode plants, both lag values, every arithmetic, every solve layout, continuation."""
+import functools
 import os
 
 import numpy as np
 import pytest
 
+import loop_cases
 from cases import CDIR, bits_differ
+from loop_cases import ARITH, NAMES
 from sde4mbrl_px4_amd import load_mpc_config, prng, synthetic_hexa, synthetic_iris
 from sde4mbrl_px4_amd import workload as W
 from sde4mbrl_px4_amd.solver import SdeMpcSolver
@@ -16,27 +19,14 @@ from timed_loop_ref import lag_step, num_solves, timed_loop_ref
 
 pytestmark = pytest.mark.gpu
 
-ARITH = [(d, mth) for d in ("f32", "f16", "f32x3") for mth in ("exact", "fast")]
 AMOUNTS = dict(mass=0.2, inertia=0.2, thrust=0.2, residual=0.2)
-NAMES = ("xs", "us", "info", "u_next", "stepsize_next", "keys_next", "u_act_next")
 S3, T7 = 3, 7
+same = functools.partial(loop_cases.same, names=NAMES[:7])
 
 
 def small_cfg(**kw):
     c1 = load_mpc_config(os.path.join(CDIR, "c1_iris_posctrl_h20_p32.yaml"))
     return c1.replace(**{"horizon": 4, "num_short_dt": 4, "num_particles": 33, "max_iter": 3, "max_no_improvement_iter": 3, **kw})
-
-
-def same(got, want, eps=None):
-    assert len(got) == len(want)
-    for n, g, w in zip(NAMES, got, want):
-        if eps is not None:
-            g, w = g[eps], w[eps]
-        assert g.shape == w.shape, (n, g.shape, w.shape)
-        if n == "keys_next":
-            assert np.array_equal(g, w), n
-        else:
-            assert bits_differ(g, w) == 0, (n, bits_differ(g, w))
 
 
 def perturbed_plants(model, n, seed=1):
@@ -63,7 +53,7 @@ def test_period_one_no_delay_no_lag_is_the_existing_loop(mlp_dtype, math_mode):
         old = S.closed_loop(x0, xref, keys, T, **kw)
         new = S.closed_loop(x0, xref, keys, T, u_act_in=ua, **kw)
         assert len(old) == 6 and len(new) == 7
-        same(new[:6], old)
+        loop_cases.same(new[:6], old, names=NAMES[:6])
         assert bits_differ(new[6], old[1][:, -1]) == 0
     S.solve_status()
     S.close()
