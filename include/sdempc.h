@@ -452,6 +452,46 @@ int sdempc_closed_loop_batch_rate(sdempc_handle* h, const sdempc_rate_cfg* rate,
                                   const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
                                   float* ws /*[B][T][4]*/, float* rate_integ_next /*[B][3] or NULL*/, float* rate_tail_next /*[B][H][3] or NULL*/);
 
+/* ---- batched closed loop with per-motor actuator faults and substep-resolution states (SPEC.md §11e) ---
+ * sdempc_closed_loop_batch_rate (`rate` given) or sdempc_closed_loop_batch_scenario (`rate` NULL; `scenario` may be NULL here too) with two optional additions.
+ * With fault_cfg NULL (or fault_cfg->fault NULL) and xsub NULL the call is that entry point bit for bit.
+ *   Fault schedule: fault f32[fault_ticks][fault_batch][m][2], fault_ticks 1 or T (per control TICK, not per solve), fault_batch 1 or B, tick-major like dist; an
+ *   index into a size-1 axis is 0. Row (k, b, l) = (kappa_l, beta_l). In every plant substep of tick k the motor state a is updated first (the lag of
+ *   sdempc_closed_loop_batch_timed, behind the rate loop's command if one is given); then
+ *     at_l = fma(kappa_l, a_l, beta_l);   x = step_plant(x, at, Xi[jj]);   then the disturbance fmas, if dist is given.
+ *   The motor state does not change: a itself is the lag state, the next substep's a, us[b][k] and u_act_next. The fault sits between the command and the rotor,
+ *   and nobody is told: neither the solve nor the rate loop sees it except through the state. A dead motor is (0, 0) (thrust ct0, moment 0, the plant's W1u sees 0),
+ *   a loss of effectiveness (kappa, 0) with 0 < kappa < 1, a motor stuck at c (0, c), a bias (1, delta). Rows change at tick starts only (ticks inside a solve
+ *   period included). The fma is applied whenever a schedule is given, neutral rows (1, 0) included (a neutral row changes nothing but an a_l of -0, which
+ *   reaches the plant as +0). Nothing is clamped: what reaches the plant is the caller's statement.
+ *   Substep states: xsub f32[B][T * substeps][13], xsub[b][k * substeps + jj] = the plant state after substep jj of tick k, disturbance fmas included; so
+ *   xsub[b][k * substeps + substeps - 1] is xs[b][k+1] bit for bit. Available with or without a fault schedule and with or without a rate loop.
+ * With `rate` NULL the five rate-only pointers (rate_integ_in, rate_tail_in, ws, rate_integ_next, rate_tail_next) must be NULL. Key schedule, solve, warm start,
+ * step size, rate tail, integrator, chunking, continuation (bit-exact when T is a multiple of S, the schedules sliced at T) and the plant schedule are those of
+ * the entry points above. The chunk's fault rows are staged per chunk like dist; its xsub rows are counted in the chunk's bytes and copied back with the other
+ * outputs. Every argument is checked before the first HIP call: SDEMPC_EINVAL for struct_size, fault_ticks not 1 or T, fault_batch not 1 or B, a non-finite
+ * fault entry, a rate-only pointer without `rate`, and for everything sdempc_closed_loop_batch_rate / _scenario refuse. No ABI version change: detect the
+ * entry point by its symbol. */
+typedef struct sdempc_fault_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_fault_cfg) */
+    const float* fault;    /* [fault_ticks][fault_batch][m][2] = (kappa, beta), or NULL: no fault */
+    int32_t fault_ticks;   /* 1 or T (ignored when fault is NULL) */
+    int32_t fault_batch;   /* 1 or B (ignored when fault is NULL) */
+} sdempc_fault_cfg;
+int sdempc_closed_loop_batch_fault(sdempc_handle* h, const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*or NULL*/,
+                                   const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                   const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                   const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                   const float* xref, int32_t xref_solves, int32_t xref_batch,
+                                   const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                   const float* u_act_in /*[B][m] or NULL*/,
+                                   float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][Ns]*/,
+                                   float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                   uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                   const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                   float* ws /*[B][T][4]; NULL without rate*/, float* rate_integ_next /*[B][3] or NULL*/, float* rate_tail_next /*[B][H][3] or NULL*/,
+                                   float* xsub /*[B][T * substeps][13] or NULL*/);
+
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so
  * repeating the call runs in the one-workgroup-per-instance layout. Also SDEMPC_EDEVICE when a large throughput launch that hands its

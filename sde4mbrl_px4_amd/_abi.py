@@ -79,6 +79,11 @@ class SdempcRateCfg(C.Structure):
                 ("motor_weight", C.c_float), ("inv_m", C.c_float)]
 
 
+class SdempcFaultCfg(C.Structure):
+    """sdempc_fault_cfg (SPEC.md §11e): the per-motor fault schedule of sdempc_closed_loop_batch_fault."""
+    _fields_ = [("struct_size", C.c_int32), ("fault", C.POINTER(C.c_float)), ("fault_ticks", C.c_int32), ("fault_batch", C.c_int32)]
+
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -217,6 +222,20 @@ def rate_entry(lib):
     return fn
 
 
+def fault_entry(lib):
+    """sdempc_closed_loop_batch_fault (SPEC.md §11e) with its prototype set: the rate entry point's arguments (the rate cfg and the scenario cfg may be NULL)
+    behind a fault cfg (may be NULL), then xsub. Detected by symbol and only when a call needs it, as rate_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_fault
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_fault (SPEC.md §11e): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(rate_entry(lib).argtypes)
+        fn.argtypes = [a[0], C.POINTER(SdempcFaultCfg)] + a[1:] + [C.POINTER(C.c_float)]
+        fn.restype = C.c_int
+    return fn
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -224,5 +243,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_grad_batch_dev", "sdempc_last_kernel_ms", "sdempc_last_kernel_name", "sdempc_work_counters", "sdempc_solve_status", "sdempc_layout_fallbacks", "sdempc_noise_to_device_layout_dev", "sdempc_traj_to_canonical_dev",
     "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
     "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed", "sdempc_closed_loop_batch_scenario",
-    "sdempc_closed_loop_batch_rate",
+    "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault",
 ]

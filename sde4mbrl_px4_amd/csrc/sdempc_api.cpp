@@ -540,6 +540,13 @@ struct RateRun {
     const float *integ_in, *tail_in;    // [B][3] / [B][H][3] or null (zeros)
     float *ws, *integ_next, *tail_next; // [B][T][4]; [B][3] / [B][H][3] or null
 };
+// SPEC.md §11e: the additions of one sdempc_closed_loop_batch_fault call (host pointers; the fault rows are staged per chunk by closed_loop_run). Given only when
+// at least one of the two is: with both absent the call is the rate / scenario call, launch for launch.
+struct FaultRun {
+    const float* fault;         // [Tf][Bf][m][2] or null
+    int Tf, Bf;
+    float* xsub;                // [B][T * substeps][13] or null
+};
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
 // One closed-loop call as its entry point describes it. The five entry points are five nested layers (SPEC.md §11, §11a .. §11d): each takes everything the one
 // below it takes, so `layer` says which parts are present; the arguments of an absent part stay null.
@@ -558,12 +565,15 @@ struct LoopCall {
     const sdempc_rate_cfg* rc;                  // LOOP_RATE
     const float *rate_integ_in, *rate_tail_in;
     float *ws, *rate_integ_next, *rate_tail_next;
+    bool faulted;                               // sdempc_closed_loop_batch_fault (SPEC.md §11e): LOOP_RATE or LOOP_SCENARIO (sc may then be NULL too) with fc / xsub
+    const sdempc_fault_cfg* fc;                 // or NULL: no fault
+    float* xsub;                                // or NULL
 };
 int closed_loop_call(sdempc_handle* h, const LoopCall& c);
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves);
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate);
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, bool* again);
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr);
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -1083,6 +1093,25 @@ int sdempc_closed_loop_batch_rate(sdempc_handle* h, const sdempc_rate_cfg* rc_, 
     });
 }
 
+int sdempc_closed_loop_batch_fault(sdempc_handle* h, const sdempc_fault_cfg* fc, const sdempc_rate_cfg* rc_, const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc,
+                                   const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T,
+                                   const float* x0, const float* xref, int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init,
+                                   const float* stepsize_in, const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next,
+                                   float* stepsize_next, uint32_t* keys_next, float* u_act_next, const float* rate_integ_in, const float* rate_tail_in,
+                                   float* ws, float* rate_integ_next, float* rate_tail_next, float* xsub) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    return closed_loop_call(h, c);
+    });
+}
+
 int sdempc_solve_status(sdempc_handle* h) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1135,8 +1164,8 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
 }
-// The one path behind the five closed-loop entry points: every check of the call's parts, in one fixed order (rate, scenario struct, timing, loop arguments,
-// plant_ticks, plant set, solve_delay, disturbance; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
+// The one path behind the six closed-loop entry points: every check of the call's parts, in one fixed order (fault struct, rate, scenario struct, timing, loop arguments,
+// plant_ticks, plant set, solve_delay, disturbance, fault schedule; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
 int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     if (!h) return SDEMPC_EINVAL;
     const LoopIo& io = c.io;
@@ -1147,6 +1176,11 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    if (c.faulted) {
+        if (c.fc && c.fc->struct_size != (int32_t)sizeof(sdempc_fault_cfg)) return fail(h, SDEMPC_EINVAL, "fault: struct_size mismatch%s");
+        if (!rated && (c.rate_integ_in || c.rate_tail_in || c.ws || c.rate_integ_next || c.rate_tail_next))
+            return fail(h, SDEMPC_EINVAL, "fault: rate_integ_in / rate_tail_in / ws / rate_integ_next / rate_tail_next must be NULL without a rate cfg%s");
+    }
     if (rated) {
         if (!rc_ || rc_->struct_size != (int32_t)sizeof(sdempc_rate_cfg)) return fail(h, SDEMPC_EINVAL, "rate: cfg NULL or struct_size mismatch%s");
         for (int a = 0; a < 3; ++a) {
@@ -1162,7 +1196,7 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
         if (!c.ws) return fail(h, SDEMPC_EINVAL, "rate: ws is NULL%s");
         if (sc && sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg)) return fail(h, SDEMPC_EINVAL, "scenario: struct_size mismatch%s");
     } else if (scenario) {
-        if (!sc || sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg)) return fail(h, SDEMPC_EINVAL, "scenario: cfg NULL or struct_size mismatch%s");
+        if ((!sc && !c.faulted) || (sc && sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg))) return fail(h, SDEMPC_EINVAL, "scenario: cfg NULL or struct_size mismatch%s");
     }
     if (timed) {
         if (!tc || tc->struct_size != (int32_t)sizeof(sdempc_timing_cfg)) return fail(h, SDEMPC_EINVAL, "timing: cfg NULL or struct_size mismatch%s");
@@ -1185,15 +1219,24 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
         for (size_t e = 0; e < nd; ++e)
             if (!finite(dist[e])) return fail(h, SDEMPC_EINVAL, "scenario: dist holds a non-finite entry%s");
     }
+    const float* fault = c.faulted && c.fc ? c.fc->fault : nullptr;
+    if (fault) {
+        if (c.fc->fault_ticks != 1 && c.fc->fault_ticks != T) return fail(h, SDEMPC_EINVAL, "fault: fault_ticks must be 1 or T%s");
+        if (c.fc->fault_batch != 1 && c.fc->fault_batch != B) return fail(h, SDEMPC_EINVAL, "fault: fault_batch must be 1 or B%s");
+        const size_t nf = (size_t)c.fc->fault_ticks * c.fc->fault_batch * h->m * 2;
+        for (size_t e = 0; e < nf; ++e)
+            if (!finite(fault[e])) return fail(h, SDEMPC_EINVAL, "fault: the schedule holds a non-finite entry%s");
+    }
     if ((rc = ensure_device(h))) return rc;
     if (c.layer == LOOP_PLAIN) return closed_loop_attempts(h, io, nullptr, nullptr, nullptr, nullptr);
     const TimedRun run_t{timed ? tc->solve_period : 1, timed ? tc->solve_delay : 0, timed ? tc->lag_alpha : 0.0f, c.u_act_in, c.u_act_next};
     const ScenarioRun run_s{dist, dist ? sc->dist_ticks : 1, dist ? sc->dist_batch : 1, c.plant_of, Tp};
     const RateRun run_r{rc_, inv_m, c.rate_integ_in, c.rate_tail_in, c.ws, c.rate_integ_next, c.rate_tail_next};
+    const FaultRun run_f{fault, fault ? c.fc->fault_ticks : 1, fault ? c.fc->fault_batch : 1, c.faulted ? c.xsub : nullptr};
     PlantRun run;
     // (a schedule is staged per chunk by the loop, where stage_plants takes the set itself; the noise of a whole solve period sits beside the set)
     if ((rc = stage_plants(h, *c.pc, c.plant_blobs, scenario ? nullptr : c.plant_of, B, &run, !timed ? 1 : (tc->solve_period < T ? tc->solve_period : T)))) return rc;
-    return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr);
+    return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr, run_f.fault || run_f.xsub ? &run_f : nullptr);
 }
 // argument checks every closed-loop entry point shares; no HIP call
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves) {
@@ -1230,10 +1273,10 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
     return 0;
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate) {
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, rate, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -1301,18 +1344,26 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // SPEC.md §11d (rate, with scen, timed and plant): the integrator and the rate tail live in d_rate (staged from the inputs, or zeroed, with the other inputs, so that a
 // re-run starts from them again) and carry over period and chunk boundaries there; the chunk's setpoint rows ws sit behind its other outputs and are counted in
 // the chunk's bytes. The plant launch then takes a LoopRate and reads the solve's mean trajectories where the solve left them (d_xmean).
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, bool* again) {
+// SPEC.md §11e (flt, with scen, timed and plant; with or without rate): the chunk's fault rows (one per TICK) are staged like the disturbance rows, behind the
+// setpoint rows; the chunk's substep states xsub (substeps rows per tick) sit behind them, are counted in the chunk's bytes and copied back with the other outputs.
+// The plant launch then takes a LoopFault.
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
     const int Ns = loop_solves(T, S);
-    const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m + (rate ? 4 : 0)) + 8;       // floats per reference window / per episode-period of output
+    const bool faulty = flt && flt->fault, subs = flt && flt->xsub;
+    const int nsub = plant ? plant->Q.substeps : 1;
+    const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m + (rate ? 4 : 0) + (subs ? (size_t)nsub * NX : 0)) + 8;       // floats per reference window / per episode-period of output
     const bool xref_moves = io.xref_ticks > 1;
     const bool gust = scen && scen->dist, sched = scen && plant && plant->Q.models;        // (one shared plant: nothing to schedule)
     const bool dist_moves = gust && scen->Td > 1, sched_moves = sched && scen->Tp > 1;
     const size_t DR = gust ? (size_t)scen->Bd * SDEMPC_NNOISE : 0, SR = sched ? (size_t)B : 0;       // floats per tick row of the disturbance / words of the schedule
-    const size_t per_period = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0);
-    const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR);
+    const bool fault_moves = faulty && flt->Tf > 1;
+    const size_t FR = faulty ? (size_t)flt->Bf * m * 2 : 0;                                          // floats per tick row of the fault schedule
+    const size_t per_period = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0) +
+                              (fault_moves ? (size_t)S * FR : 0);
+    const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR) + (fault_moves ? 0 : FR);
     const size_t cap = (h->loop_chunk_bytes < 0 ? LOOP_CHUNK_BYTES : (size_t)h->loop_chunk_bytes) / sizeof(float);
     const size_t fit = cap > fixed ? (cap - fixed) / per_period : 0;
     const int Pc = (int)(fit < 1 ? 1 : (fit < (size_t)Ns ? fit : (size_t)Ns));      // periods per chunk
@@ -1341,6 +1392,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* c_dist = c_xref + (xref_moves ? (size_t)Pc : 1) * Bx * XR;         // [Tc or 1][Bd][6] (SPEC.md §11c)
     int32_t* c_sched = (int32_t*)(c_dist + (dist_moves ? Tc : 1) * DR);       // [Tc or 1][B]
     float* c_ws = (float*)(c_sched + (sched_moves ? Tc : 1) * SR);            // [Tc][B][4] (SPEC.md §11d)
+    float* c_fault = c_ws + (rate ? Tc * B * 4 : 0);                          // [Tc or 1][Bf][m][2] (SPEC.md §11e)
+    float* c_xsub = c_fault + (fault_moves ? Tc : 1) * FR;                    // [Tc * nsub][B][13]
     float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place
     hipStream_t st = h->stream;
     // inputs (host vectors live until the synchronisation at the end of the first chunk)
@@ -1382,6 +1435,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     }
     std::vector<int32_t> ident;
     if (gust && !dist_moves) HIPCHK(h, hipMemcpyAsync(c_dist, scen->dist, sizeof(float) * DR, hipMemcpyHostToDevice, st));
+    if (faulty && !fault_moves) HIPCHK(h, hipMemcpyAsync(c_fault, flt->fault, sizeof(float) * FR, hipMemcpyHostToDevice, st));
     if (sched && !sched_moves) {
         const int32_t* row = scen->plant_of;
         if (!row) {                // (no plant_of: num_plants == B, the identity)
@@ -1400,6 +1454,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     LoopPeriod R{};
     LoopScenario C{};
     LoopRate W{};
+    LoopFault V{};
+    if (flt) { V.fault_tick_stride = fault_moves ? (int)FR : 0; V.fault_ep_stride = faulty && flt->Bf > 1 ? 2 * m : 0; }
     if (timed) { R.act = d_mot; R.alpha = timed->alpha; R.xi_ticks = S; R.shift = timed->S < H ? timed->S : H; }
     if (scen) {
         C.dist_tick_stride = dist_moves ? (int)DR : 0; C.dist_ep_stride = gust && scen->Bd > 1 ? SDEMPC_NNOISE : 0;
@@ -1416,7 +1472,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         W.inv_m = rate->inv_m; W.w = rc_.motor_weight;
         W.xevol = (const float*)h->d_xmean.p; W.wt = d_tail; W.g = d_integ;
     }
-    std::vector<float> hx, hu, hi, hw;
+    std::vector<float> hx, hu, hi, hw, hs;
     for (int j0 = 0; j0 < Ns; j0 += Pc) {
         const int np = Ns - j0 < Pc ? Ns - j0 : Pc;                                  // periods of this chunk
         const size_t k0 = (size_t)j0 * S;
@@ -1424,6 +1480,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if (xref_moves) HIPCHK(h, hipMemcpyAsync(c_xref, io.xref + (size_t)j0 * Bx * XR, sizeof(float) * np * Bx * XR, hipMemcpyHostToDevice, st));
         if (dist_moves) HIPCHK(h, hipMemcpyAsync(c_dist, scen->dist + k0 * DR, sizeof(float) * nk * DR, hipMemcpyHostToDevice, st));
         if (sched_moves) HIPCHK(h, hipMemcpyAsync(c_sched, scen->plant_of + k0 * SR, sizeof(int32_t) * nk * SR, hipMemcpyHostToDevice, st));
+        if (fault_moves) HIPCHK(h, hipMemcpyAsync(c_fault, flt->fault + k0 * FR, sizeof(float) * nk * FR, hipMemcpyHostToDevice, st));
         for (int jc = 0; jc < np; ++jc) {
             const int ticks = nk - jc * S < S ? nk - jc * S : S;                    // (the last period of the run may be partial)
             if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st));
@@ -1449,8 +1506,13 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                     C.plant = sched ? c_sched + (sched_moves ? t0 * SR : 0) : nullptr;
                 }
                 if (rate) W.ws = c_ws + t0 * B * 4;
+                if (flt) {
+                    V.fault = faulty ? c_fault + (fault_moves ? t0 * FR : 0) : nullptr;
+                    V.xsub = subs ? c_xsub + t0 * nsub * B * NX : nullptr;
+                }
             }
-            HIPCHK(h, launch_loop(plant ? plant->k : h->base, L, plant ? &plant->Q : nullptr, timed ? &R : nullptr, scen ? &C : nullptr, rate ? &W : nullptr, st));
+            HIPCHK(h, launch_loop(plant ? plant->k : h->base, L, plant ? &plant->Q : nullptr, timed ? &R : nullptr, scen ? &C : nullptr, rate ? &W : nullptr, st,
+                                  flt && timed && scen ? &V : nullptr));
         }
         hx.resize((size_t)nk * B * NX); hu.resize((size_t)nk * B * m); hi.resize((size_t)np * B * 8);
         unsigned gave_up = 0;
@@ -1461,6 +1523,10 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if (rate) {
             hw.resize((size_t)nk * B * 4);
             HIPCHK(h, hipMemcpyAsync(hw.data(), c_ws, sizeof(float) * hw.size(), hipMemcpyDeviceToHost, st));
+        }
+        if (subs) {
+            hs.resize((size_t)nk * nsub * B * NX);
+            HIPCHK(h, hipMemcpyAsync(hs.data(), c_xsub, sizeof(float) * hs.size(), hipMemcpyDeviceToHost, st));
         }
         if (j0 + np == Ns) {
             if (rate && rate->integ_next) HIPCHK(h, hipMemcpyAsync(rate->integ_next, d_integ, sizeof(float) * (size_t)B * 3, hipMemcpyDeviceToHost, st));
@@ -1486,6 +1552,10 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 memcpy(io.us + ((size_t)b * T + k) * m, &hu[r * m], sizeof(float) * m);
                 if (rate) memcpy(rate->ws + ((size_t)b * T + k) * 4, &hw[r * 4], sizeof(float) * 4);
             }
+        if (subs)
+            for (size_t rr = 0; rr < (size_t)nk * nsub; ++rr)
+                for (int b = 0; b < B; ++b)
+                    memcpy(flt->xsub + ((size_t)b * T * nsub + k0 * nsub + rr) * NX, &hs[(rr * B + b) * NX], sizeof(float) * NX);
         for (int jc = 0; jc < np; ++jc)
             for (int b = 0; b < B; ++b)
                 memcpy((float*)io.info + ((size_t)b * Ns + j0 + jc) * 8, &hi[((size_t)jc * B + b) * 8], sizeof(float) * 8);

@@ -200,10 +200,22 @@ struct LoopRate {
     float* g;                           // [B][3] integrator state: in, and out after the period's last substep
     float* ws;                          // [ticks][B][4] (mean thrust, rates[3]) in force at each tick's first substep
 };
+// SPEC.md §11e, per-motor actuator faults and substep-resolution states: the scenario or rate launch with two optional additions, either pointer may be null.
+// A fault row (kappa_l, beta_l) per control tick, episode and motor sits between the motor state and the rotor: what the plant's control table is formed from
+// is fma(kappa_l, a_l, beta_l), the motor state a_l itself (the lag state, us, u_act_next) is untouched. Like LoopScenario's pointers, both address the PERIOD's
+// first tick (first substep row); tick i of the period reads row i, or row 0 when the stride is 0.
+struct LoopFault {
+    const float* fault;         // (kappa, beta) of tick i, episode b, motor l at fault[i * fault_tick_stride + b * fault_ep_stride + 2 * l + 0..1], or null: no fault
+    int fault_tick_stride;      // floats between two ticks' rows: Bf * m * 2, or 0 (one row for every tick)
+    int fault_ep_stride;        // floats between two episodes' rows: m * 2, or 0 (one row for every episode)
+    float* xsub;                // [ticks * substeps][B][13] the state after every plant substep (disturbance fmas included), substep rows B episodes apart, or null
+};
 // The plant launch of every closed loop. Q null: the handle's own model, one step per tick (SPEC.md §11); otherwise `a` is the handle's argument block with the PLANT's
 // arithmetic (f16, fast: the plant's math mode picks the kernel's), dt -> one float (the plant's step length) and, for one shared plant, its M / wts / sdt.
 // R null: one control tick; otherwise a whole solve period, with a scenario if C is given (needs R) and through the rate loop if W is given (needs C).
-hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st);
+// V given (needs C): the FAULT instantiations of the period kernel; V null: the launches of §11 .. §11d, whatever they were.
+hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st,
+                       const LoopFault* V = nullptr);
 // the tick's key schedule (sdempc_prng.hip): keys r_k -> r_{k+1} in place, the solve's noise keys into sub_dev u32[B][2], the plant noise into
 // xi_dev f32[B][substeps][6]: ONE draw normal(p, 6 * substeps) per episode (SPEC.md §7.1: counter i pairs with i + 3 * substeps), row j for substep j
 hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st, int substeps = 1);

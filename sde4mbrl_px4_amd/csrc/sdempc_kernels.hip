@@ -46,7 +46,7 @@
 // unit; the solve kernel has ~90 instantiations of ~25k instructions each): SDEMPC_TU = 0 — every kernel except the duo solve
 // kernels, and all launchers; 1 — the duo solve kernels of the two-wave teams (TeamPair, TeamBlock2); 2 — those of the four-wave
 // team (TeamBlock); 3 — those of the six-team workgroup (TeamHex). Units 1 to 3 hold nothing but explicit instantiations (list macros below), unit 0 declares them `extern template`.
-// 4 — the plant steps of the batched closed loop and their launchers (sdempc_loop.inc.h, SPEC.md §11, §11a, §11b, §11c).
+// 4 — the plant steps of the batched closed loop and their launchers (sdempc_loop.inc.h, SPEC.md §11, §11a .. §11e).
 #ifndef SDEMPC_TU
 #define SDEMPC_TU 0
 #endif
@@ -1092,10 +1092,10 @@ SDEMPC_DUO_HEX(SDEMPC_DUO_DEF)
 #if !SDEMPC_FAST
 // launch_loop picks its math mode here, in the loop unit of the exact build (a.fast: the PLANT's math mode)
 namespace fastm {
-hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st);
+hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st, const LoopFault* V);
 }
-hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st) {
-    return a.fast ? fastm::launch_loop(a, L, Q, R, C, W, st) : exact::launch_loop(a, L, Q, R, C, W, st);
+hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st, const LoopFault* V) {
+    return a.fast ? fastm::launch_loop(a, L, Q, R, C, W, st, V) : exact::launch_loop(a, L, Q, R, C, W, st, V);
 }
 #endif
 #else

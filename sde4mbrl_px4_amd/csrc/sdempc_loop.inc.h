@@ -1,5 +1,5 @@
 // sdempc_loop.inc.h — the plant of the batched closed loop (SPEC.md §11): one Euler–Maruyama step of the handle's own model per episode and
-// tick, plus the hand-over to the next tick's solve (applied control, shifted warm start, step size); §11a: a separate plant; §11b: a whole solve period; §11c: a period with a scenario; §11d: a period flown through the rate-setpoint interface.
+// tick, plus the hand-over to the next tick's solve (applied control, shifted warm start, step size); §11a: a separate plant; §11b: a whole solve period; §11c: a period with a scenario; §11d: a period flown through the rate-setpoint interface; §11e: per-motor actuator faults and substep-resolution states.
 // Fragment of sdempc_kernels.hip, translation unit SDEMPC_TU = 4: included inside namespace sdempc::{exact|fastm} (compiled once per math mode).
 //
 // The step is the rollout's own device code: step_fwd at t = 0 on a control table built by block_prepass, i.e. the arithmetic of step 0
@@ -9,8 +9,8 @@
 //
 // Two kernels, built from the four pieces below (prologue, stage_plant, prepass + substep, hand-over), each of which exists once:
 //  * sdempc_loop_tick_kernel (§11, §11a): one control tick, the prepass straight from the solution's first row;
-//  * sdempc_loop_period_kernel<F16, SCEN, RATE> (§11b, §11c, §11d): a whole solve period, the command going through the motor lag and an LDS row.
-// Arguments: LoopAdvance, LoopPlant, LoopPeriod, LoopScenario, LoopRate (sdempc_kernels.h).
+//  * sdempc_loop_period_kernel<F16, SCEN, RATE, FAULT> (§11b .. §11e): a whole solve period, the command going through the motor lag and an LDS row.
+// Arguments: LoopAdvance, LoopPlant, LoopPeriod, LoopScenario, LoopRate, LoopFault (sdempc_kernels.h).
 //
 // The plant set (§11a). The argument block a0 arrives with the PLANT's arithmetic (the kernel's namespace and F16 are the plant's, independent of the solve's) and
 // dt -> the plant's step length. With one shared plant (Q.models == null) a0 carries it and the four episodes of a workgroup share one LDS carve. With per-episode
@@ -165,12 +165,20 @@ __global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_tick_kernel(KArgs a
 //    (a load from the argument segment at a computed offset; a copy of W indexed at run time would live in scratch), once, before the tick loop;
 //  * the rate tail W.wt is read inside the substep loop and rewritten, shifted like the warm start, after it, by the same wave; the integrator W.g goes in and out
 //    like the motor state; W.ws takes the setpoint in force at each tick's first substep.
-// Without SCEN / RATE the kernel takes an empty LoopAbsent in place of C / W: its argument segment is what the feature needs, no more.
+//
+// FAULT (SPEC.md §11e, with SCEN; with or without RATE): two optional additions, each behind a pointer that may be null.
+//  * V.fault: a row (kappa_l, beta_l) per control tick, episode and motor. Lane l < m loads its pair once per tick, before the substep loop, and what it writes
+//    into the LDS command row the prepass reads is fma(kappa_l, a_l, beta_l) — NOT into its motor state: the lag, us and the hand-over keep a_l. Without lag and
+//    without rate loop the row is rewritten only when `moved`; a fault row changes at a tick start, which always is one, so the faulted value is what is in the
+//    row whenever the control table is formed. The fma is applied whenever a schedule is given, neutral rows (1, 0) included.
+//  * V.xsub: lane 0 stores the state after every substep (after the gust fmas), substep rows B episodes apart like the tick rows of L.xs.
+// Without SCEN / RATE / FAULT the kernel takes an empty LoopAbsent in place of C / W / V: its argument segment is what the feature needs, no more.
 struct LoopAbsent {};
-template <int F16, bool SCEN, bool RATE>
+template <int F16, bool SCEN, bool RATE, bool FAULT>
 __global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_period_kernel(KArgs a0, LoopAdvance L, LoopPlant Q, LoopPeriod R, std::conditional_t<SCEN, LoopScenario, LoopAbsent> C,
-                                                                           std::conditional_t<RATE, LoopRate, LoopAbsent> W) {
+                                                                           std::conditional_t<RATE, LoopRate, LoopAbsent> W, std::conditional_t<FAULT, LoopFault, LoopAbsent> V) {
     static_assert(SCEN || !RATE, "the rate loop comes with the scenario's arguments");
+    static_assert(SCEN || !FAULT, "faults and substep states come with the scenario's arguments");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     LoopWave w;
     if (!loop_prologue(smem, a0, L, Q, w)) return;
@@ -203,6 +211,14 @@ __global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_period_kernel(KArgs
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = L.x[(size_t)b * NX + i];
     const float* xrow = L.xi + (size_t)b * R.xi_ticks * n * NN;
+    bool faulty = false;            // a fault schedule is given
+    const float* frow = nullptr;
+    float* xsub = nullptr;
+    if constexpr (FAULT) {
+        faulty = V.fault != nullptr;
+        if (faulty) frow = V.fault + (size_t)b * V.fault_ep_stride + 2 * ml;
+        if (V.xsub) xsub = V.xsub + (size_t)b * NX;
+    }
     int i = 0;
     auto fly = [&](const KArgs& a, int iend) __attribute__((always_inline)) {      // the ticks [i, iend) of one run: `a` holds the plant that flies them
 #pragma nounroll
@@ -217,6 +233,10 @@ __global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_period_kernel(KArgs
                     for (int e = 0; e < NN; ++e)
                         wd[e] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, drow[(size_t)i * C.dist_tick_stride + e])));
                 }
+            }
+            float fk = 1.0f, fb = 0.0f;                         // the fault row of this tick: lane l < m holds motor l's (kappa, beta)
+            if constexpr (FAULT) {
+                if (faulty) { fk = frow[(size_t)i * V.fault_tick_stride]; fb = frow[(size_t)i * V.fault_tick_stride + 1]; }
             }
 #pragma nounroll
             for (int jj = 0; jj < n; ++jj) {
@@ -256,12 +276,19 @@ __global__ void __launch_bounds__(TeamWave::BNT) sdempc_loop_period_kernel(KArgs
                 if (moved) {
                     if (mine) {
                         am = lag ? FMA(R.alpha, c - am, am) : c;
-                        act[lane] = am;
+                        if constexpr (FAULT) act[lane] = faulty ? FMA(fk, am, fb) : am;      // (between the command and the rotor: am stays the lag state)
+                        else act[lane] = am;
                     }
                     loop_prepass(a0, w, act);
                 }
                 if (jj == 0 && mine) L.us[((size_t)i * L.B + b) * m + lane] = am;
                 loop_substep<F16>(a, w, xrow + q * NN, x, gust, wd, dtp);
+                if constexpr (FAULT) {
+                    if (xsub && lane == 0) {
+#pragma unroll
+                        for (int e = 0; e < NX; ++e) xsub[(size_t)q * L.B * NX + e] = x[e];
+                    }
+                }
             }
             if (lane == 0) {
 #pragma unroll
@@ -318,6 +345,9 @@ inline bool loop_ok(const LoopAdvance& L, const LoopPlant& Q, const LoopScenario
 inline bool loop_ok(const KArgs& a, const LoopRate& W) {
     return !(!W.xevol || !W.wt || !W.g || !W.ws || !(W.w >= 0.0f && W.w <= 1.0f) || a.m < 1 || a.m > 8);
 }
+inline bool loop_ok(const KArgs& a, const LoopFault& V) {
+    return !(V.fault_tick_stride < 0 || (V.fault_ep_stride != 0 && V.fault_ep_stride != 2 * a.m) || a.m < 1 || a.m > 8);
+}
 
 // LDS of a workgroup (one carve of four teams, or four carves of one team and the four argument blocks), the opt-in above 64 KB, one wave per episode, the launch.
 // `more`: the kernel's arguments after (KArgs, LoopAdvance, LoopPlant).
@@ -336,16 +366,18 @@ hipError_t loop_launch(Kernel kernel, const KArgs& a, const LoopAdvance& L, cons
 }
 
 // launch_loop of sdempc_kernels.h in this math mode
-hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st) {
+hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q, const LoopPeriod* R, const LoopScenario* C, const LoopRate* W, hipStream_t st, const LoopFault* V) {
     LoopPlant own{};                // no plant set: the handle's own model (a's), one step per tick
     own.substeps = 1;
     const LoopPlant& q = Q ? *Q : own;
-    if (!loop_ok(a, L, q) || (R && !loop_ok(a, *R)) || (C && !loop_ok(L, q, *C)) || (W && !loop_ok(a, *W))) return hipErrorInvalidValue;
-    if ((C && !R) || (W && !C)) return hipErrorInvalidValue;
+    if (!loop_ok(a, L, q) || (R && !loop_ok(a, *R)) || (C && !loop_ok(L, q, *C)) || (W && !loop_ok(a, *W)) || (V && !loop_ok(a, *V))) return hipErrorInvalidValue;
+    if ((C && !R) || (W && !C) || (V && !C)) return hipErrorInvalidValue;
     return with_f16(a.f16, [&](auto F16) {
         if (!R) return Q ? loop_launch(sdempc_loop_tick_kernel<F16, true>, a, L, q, st) : loop_launch(sdempc_loop_tick_kernel<F16, false>, a, L, q, st);
-        if (W) return loop_launch(sdempc_loop_period_kernel<F16, true, true>, a, L, q, st, *R, *C, *W);
-        if (C) return loop_launch(sdempc_loop_period_kernel<F16, true, false>, a, L, q, st, *R, *C, LoopAbsent{});
-        return loop_launch(sdempc_loop_period_kernel<F16, false, false>, a, L, q, st, *R, LoopAbsent{}, LoopAbsent{});
+        if (V && W) return loop_launch(sdempc_loop_period_kernel<F16, true, true, true>, a, L, q, st, *R, *C, *W, *V);
+        if (V) return loop_launch(sdempc_loop_period_kernel<F16, true, false, true>, a, L, q, st, *R, *C, LoopAbsent{}, *V);
+        if (W) return loop_launch(sdempc_loop_period_kernel<F16, true, true, false>, a, L, q, st, *R, *C, *W, LoopAbsent{});
+        if (C) return loop_launch(sdempc_loop_period_kernel<F16, true, false, false>, a, L, q, st, *R, *C, LoopAbsent{}, LoopAbsent{});
+        return loop_launch(sdempc_loop_period_kernel<F16, false, false, false>, a, L, q, st, *R, LoopAbsent{}, LoopAbsent{}, LoopAbsent{});
     });
 }

@@ -138,7 +138,8 @@ class MpcProblem:
 
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
-                 plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None):
+                 plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,
+                 fault=None, substep_states=False):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -156,7 +157,11 @@ class MpcProblem:
         tick k: plant=[loaded, empty], plant_of = [0] * k + [1] * (T - k)). Either one makes the call the timed one (info per solve).
         rate_loop: a solver.RateLoop (SPEC.md §11d) — the vehicle flies the solution's thrust and body-rate setpoints through its own rate loop on every plant
         substep, as behind the node's setpoint interface; passed through, the call is then the timed one. Gains and mixer act on body-frame quantities of
-        the solver's frame. The returned values are the same five."""
+        the solver's frame. The returned values are the same five.
+        fault / substep_states (SPEC.md §11e): fault f32[T][m][2] or f32[m][2], a per-motor row (kappa, beta) per tick — what reaches rotor l is
+        fma(kappa, a_l, beta) (solver.fault_schedule has the recipes: dead, weakened, stuck, biased); motor commands have no frame, so nothing is converted.
+        substep_states=True appends xsub f32[T * plant_substeps][13], the plant state after every substep, as a SIXTH value, flipped into the frame of x row by
+        row like xs[1:]. Either one makes the call the timed one."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -186,17 +191,31 @@ class MpcProblem:
             if plant_of.shape != (T,):
                 raise ValueError(f"MpcProblem.simulate: plant_of must be int[{T}] (one episode: the plant of every tick), got {plant_of.shape}")
             plant_of = plant_of[:, None]
-        xs, us, info, u_next, s_next, k_next = self.solver().closed_loop(
+        more = {} if rate_loop is None else {"rate_loop": rate_loop}
+        if fault is not None:
+            f = np.asarray(fault, np.float32)
+            m = self.cfg.num_motors
+            if f.shape not in ((m, 2), (T, m, 2)):
+                raise ValueError(f"MpcProblem.simulate: fault must be f32[{T}][{m}][2] or f32[{m}][2], got {f.shape}")
+            more["fault"] = f[None, None] if f.ndim == 2 else f[:, None]
+        if substep_states:
+            more["substep_states"] = True
+        out = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
             plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag,
-            disturbance=disturbance, plant_of=plant_of, **({} if rate_loop is None else {"rate_loop": rate_loop}))[:6]
+            disturbance=disturbance, plant_of=plant_of, **more)
+        xs, us, info, u_next, s_next, k_next = out[:6]
         xs = xs[0]
         if self.convert_to_enu:
             xs = np.concatenate([x[None], enu2ned(xs[1:], np)], axis=0)
         i = info[0, -1]
         st = OptState(_arr(u_next[0]), np.float32(i[0]), np.float32(s_next[0]), np.float32(i[2]), np.float32(i[3]), np.float32(i[4]),
                       np.float32(i[5]), np.float32(i[6]), np.float32(i[7]))
-        return _arr(xs), _arr(us[0]), _arr(info[0]), st, k_next[0].copy()
+        ret = (_arr(xs), _arr(us[0]), _arr(info[0]), st, k_next[0].copy())
+        if substep_states:
+            xsub = out[-1][0]
+            ret += (_arr(enu2ned(xsub, np) if self.convert_to_enu else xsub),)
+        return ret
 
 def _allow_synthetic(flag) -> bool:
     return bool(flag) if flag is not None else os.environ.get("SDEMPC_ALLOW_SYNTHETIC") == "1"

@@ -79,6 +79,20 @@ class RateLoop:
         return f"RateLoop(kp={self.kp.tolist()}, ki={self.ki.tolist()}, integ_limit={self.integ_limit.tolist()}, mixer={self.mixer!r}, motor_weight={self.motor_weight})"
 
 
+def fault_schedule(T, B, m):
+    """The neutral per-motor fault schedule f32[T][B][m][2] of closed_loop(fault=...) (SPEC.md §11e): every row (kappa, beta) = (1, 0), to be edited in place.
+    Row (k, b, l) acts on every plant substep of control tick k of episode b: what reaches rotor l is fma(kappa, a_l, beta), a_l the motor state (which
+    the fault does not change, and of which neither the solve nor the rate loop is told). Recipes, for motor l of episode b from tick k on:
+        a dead motor                 f[k:, b, l] = (0, 0)        (thrust ct0, no moment, the plant's residual sees a command of 0)
+        a loss of effectiveness      f[k:, b, l] = (kappa, 0)    with 0 < kappa < 1
+        a motor stuck at c           f[k:, b, l] = (0, c)
+        a bias                       f[k:, b, l] = (1, delta)
+    Rows change at tick starts only (ticks inside a solve period included); nothing is clamped."""
+    f = np.zeros((int(T), int(B), int(m), 2), np.float32)
+    f[..., 0] = 1.0
+    return f
+
+
 class SdeMpcSolver:
     """One solver handle = one (MPC config, model). Single-threaded, like the reference's solver
     objects (one blocking call at a time, sde_control.py:420)."""
@@ -203,7 +217,7 @@ class SdeMpcSolver:
 
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
-                    rate_loop=None, rate_integ_in=None, rate_tail_in=None):
+                    rate_loop=None, rate_integ_in=None, rate_tail_in=None, fault=None, substep_states=False):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -242,7 +256,16 @@ class SdeMpcSolver:
         rate_tail_next [B][H][3] (the last solve's predicted rates, shifted as the warm start is: what is flown until the next solution arrives). Carrying
         those two back in as rate_integ_in / rate_tail_in (default: zeros) with the five items above continues the episodes bit for bit when T is a
         multiple of solve_period. us stays the motor state at each tick's first substep. rate_integ_in / rate_tail_in without rate_loop raise ValueError;
-        with rate_loop=None nothing of this paragraph is touched."""
+        with rate_loop=None nothing of this paragraph is touched.
+
+        fault / substep_states (SPEC.md §11e, sdempc_closed_loop_batch_fault): fault is a per-motor schedule f32[Tf][Bf][m][2] with Tf in {1, T} (per control
+        TICK) and Bf in {1, B}, or [T][m][2] (shared by all episodes), or [m][2] (constant); row (k, b, l) = (kappa, beta), and in every plant substep of tick k
+        what reaches rotor l is fma(kappa, a_l, beta) — see fault_schedule() for the neutral array and the recipes (dead, weakened, stuck, biased). The motor
+        state a (us, u_act_next, the lag) is untouched, and neither the solve nor the rate loop is told: they see the fault through the state only.
+        substep_states=True appends xsub [B][T * plant_substeps][13] as the LAST returned value: the plant state after every substep, so
+        xsub[:, plant_substeps - 1::plant_substeps] is xs[:, 1:] bit for bit. Either one makes the call the timed one (xref and info per solve, the plant
+        defaulting to the handle's own model; every keyword above still applies); fault alone does not change the returned tuple. With fault=None and
+        substep_states=False nothing of this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -273,11 +296,25 @@ class SdeMpcSolver:
             if plant is None:
                 raise ValueError("closed_loop: plant_of needs plant=...")
         scenario = dist is not None or sched is not None
+        flt = None
+        if fault is not None:
+            flt = _f32(fault)
+            if flt.ndim == 2 and flt.shape == (self.m, 2):
+                flt = flt[None, None]
+            elif flt.ndim == 3 and flt.shape == (T, self.m, 2):
+                flt = flt[:, None]
+            if flt.ndim != 4 or flt.shape[2:] != (self.m, 2) or flt.shape[0] not in (1, T) or flt.shape[1] not in (1, B):
+                raise ValueError(f"closed_loop: fault must be f32[Tf][Bf][{self.m}][2] with Tf in (1, {T}) and Bf in (1, {B}), f32[{T}][{self.m}][2] or "
+                                 f"f32[{self.m}][2], got {np.shape(fault)}")
+            if not np.isfinite(flt).all():
+                raise ValueError("closed_loop: fault holds a non-finite entry")
+            flt = np.ascontiguousarray(flt)
+        faulted = flt is not None or bool(substep_states)
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
             raise ValueError("closed_loop: rate_integ_in / rate_tail_in need rate_loop=...")
         if rate_loop is not None and not isinstance(rate_loop, RateLoop):
             raise ValueError("closed_loop: rate_loop must be a RateLoop")
-        timed = scenario or rate_loop is not None or not (solve_period == 1 and solve_delay == 0 and motor_lag == 0.0 and u_act_in is None)
+        timed = scenario or faulted or rate_loop is not None or not (solve_period == 1 and solve_delay == 0 and motor_lag == 0.0 and u_act_in is None)
         Ns = T
         if timed:
             S_, D_, alpha = int(solve_period), int(solve_delay), float(np.float32(motor_lag))
@@ -359,8 +396,20 @@ class SdeMpcSolver:
             t_next = np.zeros((B, self.H, 3), np.float32)
             lead = [C.byref(rc_)] + (lead if scenario else [None] + lead)       # (no scenario: a NULL scenario cfg)
             more, ret = more + (g_p, t_p, _fp(ws), _fp(g_next), _fp(t_next)), ret + (ws, g_next, t_next)
-        # the entry point, from (timed, scenario, rate_loop) alone; only the one that is called is looked up
-        if rate_loop is not None:
+        if faulted:                 # the rate entry point's arguments (rate cfg, scenario cfg: NULL where absent) behind the fault cfg, then xsub
+            if rate_loop is None:
+                lead, more = [None] + (lead if scenario else [None] + lead), more + (None,) * 5
+            fc = None
+            if flt is not None:
+                fc = _abi.SdempcFaultCfg(C.sizeof(_abi.SdempcFaultCfg), _fp(flt), flt.shape[0], flt.shape[1])
+            xsub = np.zeros((B, max(T, 0) * int(plant_substeps), 13), np.float32) if substep_states else None
+            lead, more = [None if fc is None else C.byref(fc)] + lead, more + (None if xsub is None else _fp(xsub),)
+            if substep_states:
+                ret = ret + (xsub,)
+        # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
+        if faulted:
+            entry = _abi.fault_entry(self.lib)
+        elif rate_loop is not None:
             entry = _abi.rate_entry(self.lib)
         elif scenario:
             entry = _abi.scenario_entry(self.lib)

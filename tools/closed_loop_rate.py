@@ -20,8 +20,12 @@
      They apply to --small-batch and to the C2 loop, where --timed / --period / --delay / --lag now apply too (one reference window per solve).
   6. --rate-loop: the same loops flown through the rate-setpoint interface (SPEC.md §11d, sdempc_closed_loop_batch_rate): a PI rate loop with the model's own mixer on
      every plant substep (the control table is re-formed on every substep). Applies to --small-batch and to the C2 loop.
+  7. --fault / --substep-states: the same loops through sdempc_closed_loop_batch_fault (SPEC.md §11e) — a fault schedule with a row per tick and episode (every
+     episode loses one motor at tick T / 2, the motor drawn per episode, and flies a biased one throughout) and / or the state after every plant substep copied back.
+     Applies to --small-batch and to the C2 loop; either one makes the call the timed one.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
+                                        [--fault] [--substep-states]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -55,6 +59,8 @@ ap.add_argument("--lag", type=float, default=0.0)
 ap.add_argument("--disturbance", action="store_true", help="a disturbance row per tick and episode (SPEC.md §11c)")
 ap.add_argument("--plant-switch", type=int, default=-1, metavar="K", help="every episode changes its plant at tick K (SPEC.md §11c; needs --plant self, one or per-episode)")
 ap.add_argument("--rate-loop", action="store_true", help="fly the thrust and body-rate setpoints through a PI rate loop (SPEC.md §11d)")
+ap.add_argument("--fault", action="store_true", help="a per-motor fault row per tick and episode (SPEC.md §11e)")
+ap.add_argument("--substep-states", action="store_true", help="copy the state after every plant substep back (SPEC.md §11e)")
 a = ap.parse_args()
 model = synthetic_iris()
 if a.plant == "own" and a.substeps != 1:
@@ -79,6 +85,15 @@ def scenario_kw(kw, B, T):
     if a.rate_loop:
         from sde4mbrl_px4_amd.solver import RateLoop
         kw["rate_loop"] = RateLoop(kp=[0.03, 0.03, 0.08], ki=[0.3, 0.3, 0.5], integ_limit=0.05)
+    if a.fault:
+        from sde4mbrl_px4_amd.solver import fault_schedule
+        rng = np.random.default_rng(6)
+        f = fault_schedule(T, B, model.num_motors)
+        f[T // 2:, np.arange(B), rng.integers(0, model.num_motors, B)] = (0.0, 0.0)
+        f[:, np.arange(B), rng.integers(0, model.num_motors, B), 1] += np.float32(0.03)
+        kw["fault"] = f
+    if a.substep_states:
+        kw["substep_states"] = True
     if a.disturbance:
         kw["disturbance"] = np.random.default_rng(2).uniform(-2.0, 2.0, (T, B, 6)).astype(np.float32)
     if a.plant_switch >= 0:
@@ -108,6 +123,10 @@ if a.plant_switch >= 0:
     tag += f" plant-switch at {a.plant_switch}"
 if a.rate_loop:
     tag += " rate-loop"
+if a.fault:
+    tag += " fault"
+if a.substep_states:
+    tag += " substep-states"
 
 if a.small_batch:
     cfg = load_mpc_config(os.path.join(ROOT, "configs", "c1_iris_posctrl_h20_p32.yaml"))
