@@ -53,22 +53,24 @@ def poison_problem(cfg, B, seed):
 
 # ---- A. the scripted life of one handle (max_batch = 48, P = 70: three particle groups, the last one ragged, a duo pair without a group B) ----
 LIFE_P, LIFE_MAX_BATCH = 70, 48
-# (kind, B, options set on the live handle before the call, seed, substrings of last_kernel_name() in the f32 modes)
+SPEC, COOP = "sdempc_solve_spec_kernel<4, false>", "sdempc_solve_kernel<TeamBlock, 4, 0, {pk}, 2, false>"
+# (kind, B, options set on the live handle before the call, seed, normalised last_kernel_name() in the f32 modes (tests/kernel_census.py: normalise;
+# {pk}: true while B x coop_nwg(P) workgroups leave one per CU, launch_coop_m))
 LIFE = [
-    ("solve", 1, {}, 101, ("spec",)),
-    ("solve", 3, {"spec": 0}, 102, ("TeamBlock, 4, 0, ", ", 2, false>")),                   # plain cooperative
-    ("poison", 40, {"coop": 0, "duo": 1}, 103, ("TeamPairT<2>, 4, 0, false, 3, false>",)),  # the first B = 40: the workspaces grow here
-    ("poison", 2, {"coop": 1}, 104, ("TeamBlock, 4, 0, ", ", 2, false>")),
-    ("solve", 2, {"spec": 1}, 105, ("spec",)),
-    ("solve", 3, {"spec": 0}, 106, ("TeamBlock, 4, 0, ", ", 2, false>")),
+    ("solve", 1, {}, 101, SPEC),
+    ("solve", 3, {"spec": 0}, 102, COOP),                   # plain cooperative
+    ("poison", 40, {"coop": 0, "duo": 1}, 103, "sdempc_solve_kernel<TeamPairT<2>, 4, 0, false, 3, false>"),  # the first B = 40: the workspaces grow here
+    ("poison", 2, {"coop": 1}, 104, COOP),
+    ("solve", 2, {"spec": 1}, 105, SPEC),
+    ("solve", 3, {"spec": 0}, 106, COOP),
     ("rollout", 5, {}, 107, None),
     ("grad", 7, {}, 108, None),
-    ("solve", 40, {"coop": 0, "duo": 1}, 109, ("TeamPairT<2>, 4, 0, false, 3, false>",)),   # rows the poison call left NaN in
-    ("solve", 40, {"duo": 0}, 110, ("TeamBlock, 4, 0, ", ", 0, false>")),
-    ("solve", 4, {"ustg": 1}, 111, ("TeamBlock, 4, 0, false, 0, true>",)),
-    ("solve", 2, {"ustg": -1, "duo": -1, "spec": 1, "coop": 1}, 112, ("spec",)),
-    ("closed_loop", 3, {}, 113, ("spec",)),
-    ("solve_keys", 6, {}, 114, ("spec",)),
+    ("solve", 40, {"coop": 0, "duo": 1}, 109, "sdempc_solve_kernel<TeamPairT<2>, 4, 0, false, 3, false>"),   # rows the poison call left NaN in
+    ("solve", 40, {"duo": 0}, 110, "sdempc_solve_kernel<TeamBlock, 4, 0, false, 0, false>"),
+    ("solve", 4, {"ustg": 1}, 111, "sdempc_solve_kernel<TeamBlock, 4, 0, false, 0, true>"),
+    ("solve", 2, {"ustg": -1, "duo": -1, "spec": 1, "coop": 1}, 112, SPEC),
+    ("closed_loop", 3, {}, 113, SPEC),
+    ("solve_keys", 6, {}, 114, SPEC),
     ("rollout", 2, {}, 115, None),
 ]
 LOOP_T = 3

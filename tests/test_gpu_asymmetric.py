@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import kernel_census as kc
 import orc
 from cases import asymmetric_cfg, asymmetric_model, asymmetric_mutants, asymmetric_problem, bits_differ
 from closed_loop_ref import closed_loop_ref
@@ -65,6 +66,16 @@ def _run(cfg, model, prob, options):
     return roll, grad, sol, kname
 
 
+@functools.lru_cache(maxsize=None)
+def _device_cus():
+    cfg, model, prob, _ = _reference(4, "f32", "exact", 1)
+    S = SdeMpcSolver(cfg, model, max_batch=B)
+    S.rollout(prob[0], prob[3], prob[1], prob[2])
+    cus = S.get_option("device_cus")
+    S.close()
+    return cus
+
+
 def _check(m, mlp, math, P, options):
     cfg, model, prob, ref = _reference(m, mlp, math, P)
     (cost, traj, xmean), (gc, grad), (uopt, xevol, info), kname = _run(cfg, model, prob, options)
@@ -101,15 +112,18 @@ def test_every_layout_and_arithmetic(layout, mlp, math):
     kname = _check(4, mlp, math, P, options)
     md = MODE[mlp]
     if layout == "lanes":
-        assert (f"TeamWave, 4, 0, false, 1," if mlp == "f32" else f"TeamWave, 4, {md}, false, 0,") in kname, kname     # MODE 1: lane layout
-    elif layout in ("coop", "spec") and mlp == "f32":
-        assert ("spec" in kname) == (layout == "spec") and (layout == "spec" or ("TeamBlock, 4, 0, " in kname and ", 2, false>" in kname)), kname    # MODE 2: cooperative
+        want = "sdempc_solve_kernel<TeamWave, 4, 0, false, 1, false>" if mlp == "f32" else f"sdempc_solve_kernel<TeamWave, 4, {md}, false, 0, false>"     # MODE 1: lane layout
+    elif layout == "spec" and mlp == "f32":
+        want = "sdempc_solve_spec_kernel<4, false>"
+    elif layout == "coop" and mlp == "f32":
+        want = kc.coop_kernel(4, P, B, _device_cus())                                                  # MODE 2: cooperative
     elif layout in ("coop", "spec", "tile", "one_group_per_wave"):
-        assert f"TeamBlock, 4, {md}, " in kname and ", 0, false>" in kname, kname                 # MODE 0: one group per wave, control table in LDS
+        want = f"sdempc_solve_kernel<TeamBlock, 4, {md}, false, 0, false>"                             # MODE 0: one group per wave, control table in LDS
     elif layout == "duo":
-        assert f"TeamPairT<2>, 4, {md}, false, 3, false>" in kname, kname
+        want = f"sdempc_solve_kernel<TeamPairT<2>, 4, {md}, false, 3, false>"
     else:
-        assert f"TeamBlock, 4, {md}, false, 0, true>" in kname, kname
+        want = f"sdempc_solve_kernel<TeamBlock, 4, {md}, false, 0, true>"
+    assert kc.normalise(kname) == (want, math), kname
 
 
 @pytest.mark.parametrize("mlp,math", [(d, mth) for d in ("f32", "f32x3") for mth in ("exact", "fast")])
@@ -120,7 +134,8 @@ def test_motor_counts(m, layout, mlp, math):
     every slot of which holds a different uref / bound / rotor here. P = 45: a ragged second group."""
     kname = _check(m, mlp, math, 45, dict(lane=0, coop=0) if layout == "tile" else dict(coop=0, pk=0, duo=1))
     if m == 6:
-        assert (f"TeamPairT<2>, 6, {MODE[mlp]}, false, 3, false>" if layout == "duo" else f"TeamBlock, 6, {MODE[mlp]}, ") in kname, kname
+        want = f"sdempc_solve_kernel<TeamPairT<2>, 6, {MODE[mlp]}, false, 3, false>" if layout == "duo" else f"sdempc_solve_kernel<TeamBlock, 6, {MODE[mlp]}, false, 0, false>"
+        assert kc.normalise(kname) == (want, math), kname
     else:
         assert f", 8, {MODE[mlp]}, " in kname, kname                  # (the default build carries the generic count in the one-group-per-wave tiles only)
 
@@ -151,10 +166,10 @@ def test_six_team_workgroups(m, mlp, math):
     negated quaternion) against the oracle; the whole batch against the same launch in two-team workgroups."""
     Bt = 1700
     S, out, kname, args = _throughput(m, mlp, math, Bt, 7, 70, (0, 1535, 1536, Bt - 1))
-    assert f"TeamPairT<6>, {m}, {MODE[mlp]}, false, 3, false" in kname, kname
+    assert kc.normalise(kname) == (f"sdempc_solve_kernel<TeamPairT<6>, {m}, {MODE[mlp]}, false, 3, false>", math), kname
     S.set_option("hex", 0)
     o2 = S.solve_keys(*args)
-    assert "TeamPairT<2>" in S.last_kernel_name(), S.last_kernel_name()
+    assert kc.normalise(S.last_kernel_name()) == (f"sdempc_solve_kernel<TeamPairT<2>, {m}, {MODE[mlp]}, false, 3, false>", math), S.last_kernel_name()
     assert bits_differ(out[0], o2[0]) == 0 and bits_differ(out[1], o2[1]) == 0 and bits_differ(out[2], o2[2]) == 0
     S.close()
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import handle_state_cases as hs
+import kernel_census as kc
 import orc
 from cases import bits_differ
 from sde4mbrl_px4_amd import prng, synthetic_iris
@@ -77,7 +78,7 @@ def test_scripted_life_of_one_handle(mlp, math, fill):
         got = _life_call(S, kind, hs.life_inputs(cfg, i))
         what = (i, kind, B)
         if mlp == "f32" and marker is not None:
-            assert all(mk in S.last_kernel_name() for mk in marker), (what, S.last_kernel_name())
+            assert kc.normalise(S.last_kernel_name()) == (_kernel(marker, B, hs.LIFE_P, S), math), (what, S.last_kernel_name())
         S.solve_status()
         idx, want = ref[i]
         _same(tuple(np.asarray(g)[idx] for g in got), want, what)
@@ -142,14 +143,19 @@ def _stream0():
     return torch.cuda.current_stream().cuda_stream
 
 
-# name -> (P, handle options, substrings of the kernel name)
+# name -> (P, handle options, the normalised kernel name)
 DEV_LAYOUTS = {
-    "lane": (1, dict(coop=0), ("TeamWave, 4, 0, false, 1,",)),
-    "spec": (33, dict(), ("spec",)),
-    "coop": (33, dict(spec=0), ("TeamBlock, 4, 0, ", ", 2, false>")),
-    "tile": (33, dict(lane=0, coop=0), ("TeamBlock, 4, 0, ", ", 0, false>")),
-    "duo": (70, dict(coop=0, pk=0, duo=1), ("TeamPairT<2>, 4, 0, false, 3, false>",)),
+    "lane": (1, dict(coop=0), "sdempc_solve_kernel<TeamWave, 4, 0, false, 1, false>"),
+    "spec": (33, dict(), hs.SPEC),
+    "coop": (33, dict(spec=0), hs.COOP),
+    "tile": (33, dict(lane=0, coop=0), "sdempc_solve_kernel<TeamBlock, 4, 0, false, 0, false>"),
+    "duo": (70, dict(coop=0, pk=0, duo=1), "sdempc_solve_kernel<TeamPairT<2>, 4, 0, false, 3, false>"),
 }
+
+
+def _kernel(marker, B, P, S):
+    """{pk} of a cooperative kernel's name: launch_coop_m's choice for this batch on this device"""
+    return marker.format(pk="true" if B * ((P + 3) // 4) <= S.get_option("device_cus") else "false")
 
 
 def _solve_dev_guarded(S, B, prob, noise_dev_host, stream=None, what=None):
@@ -172,7 +178,7 @@ def test_solve_dev_stays_inside_its_buffers(layout, B):
     cfg, model, prob, ref = hs.small_reference(P)
     S = SdeMpcSolver(cfg, model, max_batch=8, options={"test_ws_fill": 255, **opts})
     got = _solve_dev_guarded(S, B, prob, S.noise_to_device_layout(prob[2]), what=(layout, B))
-    assert all(mk in S.last_kernel_name() for mk in marker), S.last_kernel_name()
+    assert kc.normalise(S.last_kernel_name()) == (_kernel(marker, B, P, S), "exact"), S.last_kernel_name()
     _same(got, tuple(a[:B] for a in ref["solve"]), (layout, B))
     S.close()
 

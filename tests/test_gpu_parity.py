@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import kernel_census as kc
 import orc
 from cases import CDIR, bits_differ, golden_cases, load_golden
 from sde4mbrl_px4_amd import MPCConfig, load_mpc_config, synthetic_hexa, synthetic_iris, synthetic_multirotor
@@ -657,7 +658,7 @@ def test_c3_single_instance_speculative_kernel_bit_exact(math_mode):
     yk, i0 = S.reset()
     s0 = np.array([i0["stepsize"]], np.float32)
     uopt, xevol, info = S.solve_keys(x0, xref, key, yk[None], s0)
-    assert "spec" in S.last_kernel_name(), S.last_kernel_name()
+    assert kc.normalise(S.last_kernel_name()) == ("sdempc_solve_spec_kernel<6, false>", math_mode), S.last_kernel_name()
     noise = orc.noise_from_key(key[0], cfg.num_particles, cfg.horizon)
     orc.set_threads(min(os.cpu_count() or 1, 8))          # (the oracle's particle loops on every core: same bits)
     try:
@@ -736,7 +737,8 @@ def test_absent_workgroup_gives_up_within_a_few_budgets(spec):
     run = lambda: S.solve_dev(B, d["x0"].data_ptr(), d["xref"].data_ptr(), d["nd"].data_ptr(), d["u"].data_ptr(), d["s"].data_ptr(),
                               uopt.data_ptr(), xev.data_ptr(), info.data_ptr(), torch.cuda.current_stream().cuda_stream)
     run(); torch.cuda.synchronize(); S.solve_status()              # healthy launch first (module load, workspaces): the oracle's bits, a cooperative kernel
-    assert bits_differ(uopt.cpu().numpy(), uo) == 0 and ("spec_kernel" in S.last_kernel_name() or ", 2, false>" in S.last_kernel_name()), S.last_kernel_name()
+    want = "sdempc_solve_spec_kernel<4, false>" if spec == "1" else kc.coop_kernel(4, 72, B, S.get_option("device_cus"))
+    assert bits_differ(uopt.cpu().numpy(), uo) == 0 and kc.normalise(S.last_kernel_name()) == (want, "exact"), S.last_kernel_name()
     S.set_option("test_absent_wg", 1)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -826,6 +828,8 @@ def _full_size_case(cfg_name, B, iters, mlp="f32", sample=(0, 1), seed=0, stepsi
     assert kname.startswith(f"sdempc::{ns}::sdempc_solve_kernel<sdempc::{ns}::Team") and f", {cfg.num_motors}, {mode}, false" in kname, kname
     if P > 32:                                                            # scalar-tanh (throughput) instantiation of the duo layout: MODE 3 (noise
         assert ", false, 3, " in kname or ", false, 4, " in kname, kname  # through LDS staging rows) or, when LDS has no room for them (C5), MODE 4
+    # ... and exactly the instantiation the dispatcher's LDS arithmetic picks for this shape and batch (tests/kernel_census.py)
+    assert kc.normalise(kname) == (kc.throughput_kernel(H, P, cfg.num_motors, mode, B, S.get_option("device_cus")), "exact" if math == "exact" else "fast"), kname
     assert np.all(info[:, 2] == iters) and np.all(info[:, 6] <= info[:, 5]) and uopt.min() >= 1e-4 and uopt.max() <= 1.0
     O = orc.Oracle(cfg, model)                                            # (math_mode fast: through the instruction model, SPEC.md §10a)
     res = []
@@ -867,10 +871,12 @@ def test_batches_that_fit_resident_run_one_group_per_wave(mlp):
     s0 = np.full(B, i0["stepsize"], np.float32)
     uopt, xevol, info = S.solve_keys(x0, xref, keys, u0, s0)
     kn = S.last_kernel_name()
-    assert "TeamBlock," in kn and "TeamPairT" not in kn and ", false, 0, false" in kn, kn
+    f16 = kc.F16_OF[mlp]
+    assert kc.normalise(kn) == (f"sdempc_solve_kernel<TeamBlock, 4, {f16}, false, 0, false>", "exact"), kn
     S.set_option("duo", 1)
     u2, x2, i2 = S.solve_keys(x0, xref, keys, u0, s0)
-    assert "TeamPairT<2>" in S.last_kernel_name() and bits_differ(uopt, u2) == 0 and bits_differ(xevol, x2) == 0 and bits_differ(info, i2) == 0
+    assert kc.normalise(S.last_kernel_name()) == (f"sdempc_solve_kernel<TeamPairT<2>, 4, {f16}, false, 3, false>", "exact"), S.last_kernel_name()
+    assert bits_differ(uopt, u2) == 0 and bits_differ(xevol, x2) == 0 and bits_differ(info, i2) == 0
     O = orc.Oracle(cfg, model)
     for b in (0, 299):
         uo, xe, io = O.solve(x0[b], xref[b], orc.noise_from_key(keys[b], P, H), u0[b], float(s0[b]))[:3]
@@ -928,12 +934,13 @@ def test_ticketed_persistent_launch_matches_striped_launches_bit_for_bit():
     s0 = np.full(B, i0["stepsize"], np.float32)
     S.work_counters(reset=True)
     uopt, xevol, info = S.solve_keys(x0, xref, keys, u0, s0)
-    assert ", false, 3, " in S.last_kernel_name() and 3 * 6 * S.get_option("device_cus") <= B
-    assert "TeamPairT<6>" in S.last_kernel_name()                         # a launch that fills the device: one six-team workgroup per CU
+    assert 3 * 6 * S.get_option("device_cus") <= B
+    assert kc.normalise(S.last_kernel_name()) == ("sdempc_solve_kernel<TeamPairT<6>, 4, 0, false, 3, false>", "exact")    # a launch that fills the device: one six-team workgroup per CU
     assert S.work_counters()[0] == B                                      # every instance solved exactly once
     S.set_option("hex", 0)                                                # the same launch in two-team workgroups (three per CU): same bits
     uh, xh, ih = S.solve_keys(x0, xref, keys, u0, s0)
-    assert "TeamPairT<2>" in S.last_kernel_name() and bits_differ(uopt, uh) == 0 and bits_differ(xevol, xh) == 0 and bits_differ(info, ih) == 0
+    assert kc.normalise(S.last_kernel_name()) == ("sdempc_solve_kernel<TeamPairT<2>, 4, 0, false, 3, false>", "exact"), S.last_kernel_name()
+    assert bits_differ(uopt, uh) == 0 and bits_differ(xevol, xh) == 0 and bits_differ(info, ih) == 0
     S.set_option("hex", 1)
     S.work_counters(reset=True)
     assert S.solve_keys(x0, xref, keys, u0, s0)[0].tobytes() == uopt.tobytes() and S.work_counters()[0] == B
@@ -973,12 +980,13 @@ def test_six_team_workgroups_every_motor_count_and_contraction_mode(m, mlp):
     if m == 8 and not (_abi.load_library().sdempc_build_flags() & 1):
         # the default build carries the generic motor count in the one-group-per-wave tile layouts only (make EXTRA=-DSDEMPC_ALL_VARIANTS=1 adds the rest;
         # include/sdempc.h: sdempc_build_flags): same bits from another layout
-        assert f"TeamBlock, 8, {dict(f32=0, f16=1, f32x3=2)[mlp]}, false, 0, " in S.last_kernel_name(), S.last_kernel_name()
+        assert kc.normalise(S.last_kernel_name()) == (f"sdempc_solve_kernel<TeamBlock, 8, {kc.F16_OF[mlp]}, false, 0, false>", "exact"), S.last_kernel_name()
     else:
-        assert f"TeamPairT<6>, {m}, {dict(f32=0, f16=1, f32x3=2)[mlp]}, false, 3, false" in S.last_kernel_name(), S.last_kernel_name()
+        assert kc.normalise(S.last_kernel_name()) == (f"sdempc_solve_kernel<TeamPairT<6>, {m}, {kc.F16_OF[mlp]}, false, 3, false>", "exact"), S.last_kernel_name()
         S.set_option("hex", 0)
         u2, x2, i2 = S.solve_keys(x0, xref, keys, u0, s0)
-        assert "TeamPairT<2>" in S.last_kernel_name() and bits_differ(uopt, u2) == 0 and bits_differ(xevol, x2) == 0 and bits_differ(info, i2) == 0
+        assert kc.normalise(S.last_kernel_name()) == (f"sdempc_solve_kernel<TeamPairT<2>, {m}, {kc.F16_OF[mlp]}, false, 3, false>", "exact"), S.last_kernel_name()
+        assert bits_differ(uopt, u2) == 0 and bits_differ(xevol, x2) == 0 and bits_differ(info, i2) == 0
     O = orc.Oracle(cfg, model)
     for b in (0, 5, 1535, 1536, B - 1):
         uo, xe, io = O.solve(x0[b], xref[b], orc.noise_from_key(keys[b], P, H), u0[b], float(s0[b]))[:3]
