@@ -176,7 +176,7 @@ int sdempc_device_ready(const sdempc_handle* h);
  *                                                                                          Filled: the workspaces (particle x horizon tensor, activation checkpoint,
  *                                                                                          partial sums, control table), the cooperative layouts' per-particle outputs and
  *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs,
- *                                                                                          the closed loop's key / chunk / plant / rate-state buffers (the chunk buffer includes the
+ *                                                                                          the closed loop's key / chunk / plant / rate-state / observation buffers (the chunk buffer includes the
  *                                                                                          staged disturbance rows and plant-schedule rows of a scenario). (The particle x horizon tensor is
  *                                                                                          zeroed at allocation otherwise; nothing depends on that.) Keep their initial value:
  *                                                                                          - the work counters and the ticket word: running totals, zero at creation by
@@ -491,6 +491,59 @@ int sdempc_closed_loop_batch_fault(sdempc_handle* h, const sdempc_fault_cfg* fau
                                    const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
                                    float* ws /*[B][T][4]; NULL without rate*/, float* rate_integ_next /*[B][3] or NULL*/, float* rate_tail_next /*[B][H][3] or NULL*/,
                                    float* xsub /*[B][T * substeps][13] or NULL*/);
+
+/* ---- batched closed loop on a measured state (SPEC.md §11f) -------------------------------------------
+ * sdempc_closed_loop_batch_fault with a controller that reads an ESTIMATE of the state, as the reference node does (its mpc_state_callback gets the FCU's
+ * estimate, not the truth): noise, bias and dropouts on the state that goes INTO each solve. The plant is untouched, and the rate loop keeps reading the
+ * plant's current body rates. With `obs` NULL the call is sdempc_closed_loop_batch_fault bit for bit; obs_keys, xmeas_in, xmeas, obs_keys_next and xmeas_next
+ * must then be NULL. Beside the state of that entry point episode b carries an observation key q (a chain of its own: the main chain is never disturbed) and
+ * the held measurement xm[13]. At solve j, with x the plant state at the period's first tick (all float32; fma is the fused one):
+ *   (q, me) = split(q)                                   at EVERY solve, valid or not
+ *   if valid[j or 0][b or 0]:
+ *     xi = normal(me, (12,))                             (SPEC.md §7.1: counter i pairs with i + 6)
+ *     e_i = fma(sigma_i, xi_i, beta_i), i = 0..11        rows sigma[j or 0][b or 0], beta[j or 0][b or 0], in the order p, v, theta, omega
+ *     xm[0..2] = x[0..2] + e[0..2];  xm[3..5] = x[3..5] + e[3..5];  xm[10..12] = x[10..12] + e[9..11]
+ *     h_a = 0.5f * e[6 + a];  (w, x, y, z) = x[6..9]     the attitude times (1, h) from the right: a small body-frame rotation, NOT renormalised
+ *     xm[6] = fma(-z, h2, fma(-y, h1, fma(-x, h0, w)));  xm[7] = fma(-z, h1, fma(y, h2, fma(w, h0, x)));
+ *     xm[8] = fma(-x, h2, fma(z, h0, fma(w, h1, y)));    xm[9] = fma(-y, h0, fma(x, h1, fma(w, h2, z)))
+ *   else xm stays as it is                               a dropout: the estimator repeats its last output
+ *   solve j starts from xm instead of x; everything else is sdempc_closed_loop_batch_fault.
+ * sigma (noise scale, finite and >= 0) and beta (bias, finite) are f32[obs_solves][obs_batch][12], obs_solves 1 or Ns, obs_batch 1 or B, solve-major like xref;
+ * valid is int32[valid_solves][valid_batch] with the same axis rule; an index into a size-1 axis is 0. sigma or beta NULL: zeros; valid NULL: always valid.
+ * The held measurement starts as xmeas_in [B][13] (NULL: x0). The formulas run whenever `obs` is given: a neutral observation (sigma and beta zero, always
+ * valid) reproduces sdempc_closed_loop_batch_fault bit for bit except that a component of x equal to -0 reaches the solve as +0. Nothing is clamped or
+ * renormalised: what reaches the solver is the caller's statement. The main key chain depends on S and T only, the observation chain on the number of solves
+ * only. Outputs: xmeas [B][Ns][13] = what solve j was started from (a held row on a dropout; may be NULL); obs_keys_next u32[B][2] and xmeas_next [B][13]
+ * (each may be NULL) continue the episodes bit for bit, together with the other continuation values, when T is a multiple of S. The chunk's sigma / beta / valid
+ * rows are staged per chunk when they move, like moving references; its xmeas rows are counted in the chunk's bytes and copied back with info. Every argument
+ * is checked before the first HIP call: SDEMPC_EINVAL for struct_size, obs_solves / valid_solves not 1 or Ns, obs_batch / valid_batch not 1 or B, a non-finite
+ * or negative sigma, a non-finite beta, a valid entry other than 0 / 1, obs_keys NULL with `obs` given, an observation pointer without `obs`, and for
+ * everything sdempc_closed_loop_batch_fault refuses. No ABI version change: detect the entry point by its symbol. */
+typedef struct sdempc_obs_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_obs_cfg) */
+    const float* sigma;    /* [obs_solves][obs_batch][12] noise scale, or NULL: zeros */
+    const float* beta;     /* [obs_solves][obs_batch][12] bias, or NULL: zeros */
+    int32_t obs_solves;    /* 1 or Ns (ignored when sigma and beta are NULL) */
+    int32_t obs_batch;     /* 1 or B (ignored when sigma and beta are NULL) */
+    const int32_t* valid;  /* [valid_solves][valid_batch] 1: a measurement, 0: a dropout; or NULL: always valid */
+    int32_t valid_solves;  /* 1 or Ns (ignored when valid is NULL) */
+    int32_t valid_batch;   /* 1 or B (ignored when valid is NULL) */
+} sdempc_obs_cfg;
+int sdempc_closed_loop_batch_observed(sdempc_handle* h, const sdempc_obs_cfg* obs /*or NULL*/, const uint32_t* obs_keys /*[B][2]*/, const float* xmeas_in /*[B][13] or NULL*/,
+                                      const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*or NULL*/,
+                                      const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                      const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                      const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                      const float* xref, int32_t xref_solves, int32_t xref_batch,
+                                      const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                      const float* u_act_in /*[B][m] or NULL*/,
+                                      float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][Ns]*/,
+                                      float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                      uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                      const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                      float* ws /*[B][T][4]; NULL without rate*/, float* rate_integ_next /*[B][3] or NULL*/, float* rate_tail_next /*[B][H][3] or NULL*/,
+                                      float* xsub /*[B][T * substeps][13] or NULL*/,
+                                      float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/);
 
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so

@@ -84,6 +84,12 @@ class SdempcFaultCfg(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("fault", C.POINTER(C.c_float)), ("fault_ticks", C.c_int32), ("fault_batch", C.c_int32)]
 
 
+class SdempcObsCfg(C.Structure):
+    """sdempc_obs_cfg (SPEC.md §11f): noise scale, bias and validity of the measured state of sdempc_closed_loop_batch_observed."""
+    _fields_ = [("struct_size", C.c_int32), ("sigma", C.POINTER(C.c_float)), ("beta", C.POINTER(C.c_float)), ("obs_solves", C.c_int32), ("obs_batch", C.c_int32),
+                ("valid", C.POINTER(C.c_int32)), ("valid_solves", C.c_int32), ("valid_batch", C.c_int32)]
+
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -236,6 +242,21 @@ def fault_entry(lib):
     return fn
 
 
+def observed_entry(lib):
+    """sdempc_closed_loop_batch_observed (SPEC.md §11f) with its prototype set: an obs cfg (may be NULL), obs_keys and xmeas_in in front of the fault entry point's
+    arguments, then xmeas, obs_keys_next, xmeas_next. Detected by symbol and only when a call needs it, as fault_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_observed
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_observed (SPEC.md §11f): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(fault_entry(lib).argtypes)
+        fp, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        fn.argtypes = [a[0], C.POINTER(SdempcObsCfg), u32p, fp] + a[1:] + [fp, u32p, fp]
+        fn.restype = C.c_int
+    return fn
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -243,5 +264,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_grad_batch_dev", "sdempc_last_kernel_ms", "sdempc_last_kernel_name", "sdempc_work_counters", "sdempc_solve_status", "sdempc_layout_fallbacks", "sdempc_noise_to_device_layout_dev", "sdempc_traj_to_canonical_dev",
     "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
     "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed", "sdempc_closed_loop_batch_scenario",
-    "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault",
+    "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault", "sdempc_closed_loop_batch_observed",
 ]

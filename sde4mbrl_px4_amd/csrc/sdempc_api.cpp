@@ -179,6 +179,8 @@ struct sdempc_handle {
     std::vector<char> plant_stage;
     // closed loop through the rate-setpoint interface (sdempc_closed_loop_batch_rate, allocated on its first use): integrator f32[max_batch][3], rate tail f32[max_batch][H][3]
     DevBuf d_rate;
+    // closed loop on a measured state (sdempc_closed_loop_batch_observed, allocated on its first use): observation keys u32[max_batch][2], held measurement f32[max_batch][13]
+    DevBuf d_obs;
     DevBuf d_work;            // u64[4] work counters (KArgs::work)
     // cooperative latency path of the solve (allocated on its first use, sized for coop_cap instances)
     DevBuf d_coop_bar, d_coop_pp, d_coop_ck;
@@ -547,6 +549,19 @@ struct FaultRun {
     int Tf, Bf;
     float* xsub;                // [B][T * substeps][13] or null
 };
+// SPEC.md §11f: the observation of one sdempc_closed_loop_batch_observed call (host pointers; the sigma / beta / valid rows are staged per chunk by closed_loop_run
+// when they move). Given only when the call has an obs cfg: without one the call is the fault call, launch for launch.
+struct ObsRun {
+    const float *sigma, *beta;  // [To][Bo][12] or null (zeros)
+    int To, Bo;
+    const int32_t* valid;       // [Tv][Bv] or null (always valid)
+    int Tv, Bv;
+    const uint32_t* keys;       // [B][2]
+    const float* xmeas_in;      // [B][13] or null (x0)
+    float* xmeas;               // [B][Ns][13] or null
+    uint32_t* keys_next;        // [B][2] or null
+    float* xmeas_next;          // [B][13] or null
+};
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
 // One closed-loop call as its entry point describes it. The five entry points are five nested layers (SPEC.md §11, §11a .. §11d): each takes everything the one
 // below it takes, so `layer` says which parts are present; the arguments of an absent part stay null.
@@ -568,12 +583,21 @@ struct LoopCall {
     bool faulted;                               // sdempc_closed_loop_batch_fault (SPEC.md §11e): LOOP_RATE or LOOP_SCENARIO (sc may then be NULL too) with fc / xsub
     const sdempc_fault_cfg* fc;                 // or NULL: no fault
     float* xsub;                                // or NULL
+    bool observed;                              // sdempc_closed_loop_batch_observed (SPEC.md §11f): the fault call with oc and the five observation pointers
+    const sdempc_obs_cfg* oc;                   // or NULL: no observation (the five pointers must then be NULL)
+    const uint32_t* obs_keys;
+    const float* xmeas_in;
+    float* xmeas;
+    uint32_t* obs_keys_next;
+    float* xmeas_next;
 };
 int closed_loop_call(sdempc_handle* h, const LoopCall& c);
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves);
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr);
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, bool* again);
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr,
+                         const ObsRun* obs = nullptr);
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
+                    bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -666,7 +690,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1112,6 +1136,27 @@ int sdempc_closed_loop_batch_fault(sdempc_handle* h, const sdempc_fault_cfg* fc,
     });
 }
 
+int sdempc_closed_loop_batch_observed(sdempc_handle* h, const sdempc_obs_cfg* oc, const uint32_t* obs_keys, const float* xmeas_in, const sdempc_fault_cfg* fc,
+                                      const sdempc_rate_cfg* rc_, const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc,
+                                      const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T, const float* x0,
+                                      const float* xref, int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in,
+                                      const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next,
+                                      float* u_act_next, const float* rate_integ_in, const float* rate_tail_in, float* ws, float* rate_integ_next, float* rate_tail_next,
+                                      float* xsub, float* xmeas, uint32_t* obs_keys_next, float* xmeas_next) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    c.observed = true; c.oc = oc; c.obs_keys = obs_keys; c.xmeas_in = xmeas_in; c.xmeas = xmeas; c.obs_keys_next = obs_keys_next; c.xmeas_next = xmeas_next;
+    return closed_loop_call(h, c);
+    });
+}
+
 int sdempc_solve_status(sdempc_handle* h) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1164,8 +1209,8 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
 }
-// The one path behind the six closed-loop entry points: every check of the call's parts, in one fixed order (fault struct, rate, scenario struct, timing, loop arguments,
-// plant_ticks, plant set, solve_delay, disturbance, fault schedule; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
+// The one path behind the seven closed-loop entry points: every check of the call's parts, in one fixed order (observation struct, fault struct, rate, scenario struct, timing,
+// loop arguments, plant_ticks, plant set, solve_delay, disturbance, fault schedule, observation rows; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
 int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     if (!h) return SDEMPC_EINVAL;
     const LoopIo& io = c.io;
@@ -1176,6 +1221,12 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    if (c.observed) {
+        if (c.oc && c.oc->struct_size != (int32_t)sizeof(sdempc_obs_cfg)) return fail(h, SDEMPC_EINVAL, "obs: struct_size mismatch%s");
+        if (!c.oc && (c.obs_keys || c.xmeas_in || c.xmeas || c.obs_keys_next || c.xmeas_next))
+            return fail(h, SDEMPC_EINVAL, "obs: obs_keys / xmeas_in / xmeas / obs_keys_next / xmeas_next must be NULL without an obs cfg%s");
+        if (c.oc && !c.obs_keys) return fail(h, SDEMPC_EINVAL, "obs: obs_keys is NULL%s");
+    }
     if (c.faulted) {
         if (c.fc && c.fc->struct_size != (int32_t)sizeof(sdempc_fault_cfg)) return fail(h, SDEMPC_EINVAL, "fault: struct_size mismatch%s");
         if (!rated && (c.rate_integ_in || c.rate_tail_in || c.ws || c.rate_integ_next || c.rate_tail_next))
@@ -1227,16 +1278,40 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
         for (size_t e = 0; e < nf; ++e)
             if (!finite(fault[e])) return fail(h, SDEMPC_EINVAL, "fault: the schedule holds a non-finite entry%s");
     }
+    const sdempc_obs_cfg* oc = c.observed ? c.oc : nullptr;
+    if (oc) {
+        const int Ns = loop_solves(T, tc->solve_period);
+        if (oc->sigma || oc->beta) {
+            if (oc->obs_solves != 1 && oc->obs_solves != Ns) return fail(h, SDEMPC_EINVAL, "obs: obs_solves must be 1 or ceil(T / solve_period)%s");
+            if (oc->obs_batch != 1 && oc->obs_batch != B) return fail(h, SDEMPC_EINVAL, "obs: obs_batch must be 1 or B%s");
+            const size_t no = (size_t)oc->obs_solves * oc->obs_batch * 12;
+            for (size_t e = 0; oc->sigma && e < no; ++e)
+                if (!finite(oc->sigma[e]) || oc->sigma[e] < 0.0f) return fail(h, SDEMPC_EINVAL, "obs: sigma holds a non-finite or negative entry%s");
+            for (size_t e = 0; oc->beta && e < no; ++e)
+                if (!finite(oc->beta[e])) return fail(h, SDEMPC_EINVAL, "obs: beta holds a non-finite entry%s");
+        }
+        if (oc->valid) {
+            if (oc->valid_solves != 1 && oc->valid_solves != Ns) return fail(h, SDEMPC_EINVAL, "obs: valid_solves must be 1 or ceil(T / solve_period)%s");
+            if (oc->valid_batch != 1 && oc->valid_batch != B) return fail(h, SDEMPC_EINVAL, "obs: valid_batch must be 1 or B%s");
+            const size_t nv = (size_t)oc->valid_solves * oc->valid_batch;
+            for (size_t e = 0; e < nv; ++e)
+                if (oc->valid[e] != 0 && oc->valid[e] != 1) return fail(h, SDEMPC_EINVAL, "obs: valid holds an entry other than 0 / 1%s");
+        }
+    }
     if ((rc = ensure_device(h))) return rc;
     if (c.layer == LOOP_PLAIN) return closed_loop_attempts(h, io, nullptr, nullptr, nullptr, nullptr);
     const TimedRun run_t{timed ? tc->solve_period : 1, timed ? tc->solve_delay : 0, timed ? tc->lag_alpha : 0.0f, c.u_act_in, c.u_act_next};
     const ScenarioRun run_s{dist, dist ? sc->dist_ticks : 1, dist ? sc->dist_batch : 1, c.plant_of, Tp};
     const RateRun run_r{rc_, inv_m, c.rate_integ_in, c.rate_tail_in, c.ws, c.rate_integ_next, c.rate_tail_next};
     const FaultRun run_f{fault, fault ? c.fc->fault_ticks : 1, fault ? c.fc->fault_batch : 1, c.faulted ? c.xsub : nullptr};
+    const bool rows = oc && (oc->sigma || oc->beta);
+    const ObsRun run_o{oc ? oc->sigma : nullptr, oc ? oc->beta : nullptr, rows ? oc->obs_solves : 1, rows ? oc->obs_batch : 1, oc ? oc->valid : nullptr,
+                       oc && oc->valid ? oc->valid_solves : 1, oc && oc->valid ? oc->valid_batch : 1, c.obs_keys, c.xmeas_in, c.xmeas, c.obs_keys_next, c.xmeas_next};
     PlantRun run;
     // (a schedule is staged per chunk by the loop, where stage_plants takes the set itself; the noise of a whole solve period sits beside the set)
     if ((rc = stage_plants(h, *c.pc, c.plant_blobs, scenario ? nullptr : c.plant_of, B, &run, !timed ? 1 : (tc->solve_period < T ? tc->solve_period : T)))) return rc;
-    return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr, run_f.fault || run_f.xsub ? &run_f : nullptr);
+    return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr, run_f.fault || run_f.xsub ? &run_f : nullptr,
+                                oc ? &run_o : nullptr);
 }
 // argument checks every closed-loop entry point shares; no HIP call
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves) {
@@ -1273,10 +1348,11 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
     return 0;
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
-int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt) {
+int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt,
+                         const ObsRun* obs) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -1347,23 +1423,33 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // SPEC.md §11e (flt, with scen, timed and plant; with or without rate): the chunk's fault rows (one per TICK) are staged like the disturbance rows, behind the
 // setpoint rows; the chunk's substep states xsub (substeps rows per tick) sit behind them, are counted in the chunk's bytes and copied back with the other outputs.
 // The plant launch then takes a LoopFault.
-int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, bool* again) {
+// SPEC.md §11f (obs, with scen-or-not, timed and plant): the observation keys and the held measurement live in d_obs (staged from the inputs with the other inputs, so that a
+// re-run starts from them again); the period's key schedule forms the measurement (LoopObserve) and the solve starts from it (d_xm) instead of d_x, which stays the
+// plant's. The chunk's xmeas rows (one per SOLVE) sit behind xsub, are counted in the chunk's bytes and copied back with info; the sigma / beta / valid rows sit
+// behind them, staged per chunk when they move (one per solve, like moving references) and once otherwise.
+int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
+                    bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
     const int Ns = loop_solves(T, S);
     const bool faulty = flt && flt->fault, subs = flt && flt->xsub;
     const int nsub = plant ? plant->Q.substeps : 1;
-    const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m + (rate ? 4 : 0) + (subs ? (size_t)nsub * NX : 0)) + 8;       // floats per reference window / per episode-period of output
+    const bool seen = obs && timed;
+    const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m + (rate ? 4 : 0) + (subs ? (size_t)nsub * NX : 0)) + 8 + (seen ? NX : 0);       // floats per reference window / per episode-period of output
     const bool xref_moves = io.xref_ticks > 1;
     const bool gust = scen && scen->dist, sched = scen && plant && plant->Q.models;        // (one shared plant: nothing to schedule)
     const bool dist_moves = gust && scen->Td > 1, sched_moves = sched && scen->Tp > 1;
     const size_t DR = gust ? (size_t)scen->Bd * SDEMPC_NNOISE : 0, SR = sched ? (size_t)B : 0;       // floats per tick row of the disturbance / words of the schedule
     const bool fault_moves = faulty && flt->Tf > 1;
     const size_t FR = faulty ? (size_t)flt->Bf * m * 2 : 0;                                          // floats per tick row of the fault schedule
+    const bool noisy = seen && obs->sigma, biased = seen && obs->beta, gated = seen && obs->valid;
+    const bool obs_moves = (noisy || biased) && obs->To > 1, valid_moves = gated && obs->Tv > 1;
+    const size_t OR = noisy || biased ? (size_t)obs->Bo * 12 : 0, VR = gated ? (size_t)obs->Bv : 0;   // floats per solve row of sigma / of beta; words per solve row of valid
+    const size_t ORS = (noisy ? OR : 0) + (biased ? OR : 0);
     const size_t per_period = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0) +
-                              (fault_moves ? (size_t)S * FR : 0);
-    const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR) + (fault_moves ? 0 : FR);
+                              (fault_moves ? (size_t)S * FR : 0) + (obs_moves ? ORS : 0) + (valid_moves ? VR : 0);
+    const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR) + (fault_moves ? 0 : FR) + (obs_moves ? 0 : ORS) + (valid_moves ? 0 : VR);
     const size_t cap = (h->loop_chunk_bytes < 0 ? LOOP_CHUNK_BYTES : (size_t)h->loop_chunk_bytes) / sizeof(float);
     const size_t fit = cap > fixed ? (cap - fixed) / per_period : 0;
     const int Pc = (int)(fit < 1 ? 1 : (fit < (size_t)Ns ? fit : (size_t)Ns));      // periods per chunk
@@ -1377,6 +1463,9 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if ((rc = dev_alloc(h, h->d_loop_chunk, sizeof(float) * chunk_floats, true))) return rc;
     }
     if (rate && !h->d_rate.p && (rc = dev_alloc(h, h->d_rate, sizeof(float) * (size_t)h->max_batch * 3 * (1 + H), true))) return rc;
+    if (seen && !h->d_obs.p && (rc = dev_alloc(h, h->d_obs, (sizeof(uint32_t) * 2 + sizeof(float) * NX) * (size_t)h->max_batch, true))) return rc;
+    uint32_t* d_q = (uint32_t*)h->d_obs.p;                           // q [B][2] (SPEC.md §11f)
+    float* d_xm = d_q ? (float*)(d_q + 2 * (size_t)h->max_batch) : nullptr;   // xm [B][13]
     float* d_integ = (float*)h->d_rate.p;                            // g [B][3] (SPEC.md §11d)
     float* d_tail = d_integ ? d_integ + 3 * (size_t)h->max_batch : nullptr;   // wt [B][H][3]
     uint32_t* d_keys = (uint32_t*)h->d_loop.p;                      // r_k, advanced in place
@@ -1394,7 +1483,11 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* c_ws = (float*)(c_sched + (sched_moves ? Tc : 1) * SR);            // [Tc][B][4] (SPEC.md §11d)
     float* c_fault = c_ws + (rate ? Tc * B * 4 : 0);                          // [Tc or 1][Bf][m][2] (SPEC.md §11e)
     float* c_xsub = c_fault + (fault_moves ? Tc : 1) * FR;                    // [Tc * nsub][B][13]
-    float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place
+    float* c_xmeas = c_xsub + (subs ? Tc * nsub * B * NX : 0);                // [Pc][B][13] (SPEC.md §11f)
+    float* c_sigma = c_xmeas + (seen ? (size_t)Pc * B * NX : 0);              // [Pc or 1][Bo][12]
+    float* c_beta = c_sigma + (noisy ? (obs_moves ? (size_t)Pc : 1) * OR : 0);        // [Pc or 1][Bo][12]
+    int32_t* c_valid = (int32_t*)(c_beta + (biased ? (obs_moves ? (size_t)Pc : 1) * OR : 0));    // [Pc or 1][Bv]
+    float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place (SPEC.md §11f: the plant's; the solve reads d_xm)
     hipStream_t st = h->stream;
     // inputs (host vectors live until the synchronisation at the end of the first chunk)
     std::vector<float> u0, s0, a0;
@@ -1429,6 +1522,13 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if (rate->tail_in) HIPCHK(h, hipMemcpyAsync(d_tail, rate->tail_in, sizeof(float) * (size_t)B * H * 3, hipMemcpyHostToDevice, st));
         else HIPCHK(h, hipMemsetAsync(d_tail, 0, sizeof(float) * (size_t)B * H * 3, st));
     }
+    if (seen) {                // the observation chain and the held measurement start as given (xmeas_in NULL: x0)
+        HIPCHK(h, hipMemcpyAsync(d_q, obs->keys, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d_xm, obs->xmeas_in ? obs->xmeas_in : io.x0, sizeof(float) * B * NX, hipMemcpyHostToDevice, st));
+        if (noisy && !obs_moves) HIPCHK(h, hipMemcpyAsync(c_sigma, obs->sigma, sizeof(float) * OR, hipMemcpyHostToDevice, st));
+        if (biased && !obs_moves) HIPCHK(h, hipMemcpyAsync(c_beta, obs->beta, sizeof(float) * OR, hipMemcpyHostToDevice, st));
+        if (gated && !valid_moves) HIPCHK(h, hipMemcpyAsync(c_valid, obs->valid, sizeof(int32_t) * VR, hipMemcpyHostToDevice, st));
+    }
     if (!xref_moves) {
         HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
         if (Bx != B) HIPCHK(h, launch_broadcast_rows(c_xref, (float*)h->d_xref.p, (int)XR, B, st));
@@ -1455,6 +1555,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     LoopScenario C{};
     LoopRate W{};
     LoopFault V{};
+    LoopObserve O{};           // (q null: absent)
+    if (seen) { O.q = d_q; O.x = d_x; O.xm = d_xm; O.ep_stride = obs->Bo > 1 ? 12 : 0; O.valid_ep_stride = obs->Bv > 1 ? 1 : 0; }
     if (flt) { V.fault_tick_stride = fault_moves ? (int)FR : 0; V.fault_ep_stride = faulty && flt->Bf > 1 ? 2 * m : 0; }
     if (timed) { R.act = d_mot; R.alpha = timed->alpha; R.xi_ticks = S; R.shift = timed->S < H ? timed->S : H; }
     if (scen) {
@@ -1472,7 +1574,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         W.inv_m = rate->inv_m; W.w = rc_.motor_weight;
         W.xevol = (const float*)h->d_xmean.p; W.wt = d_tail; W.g = d_integ;
     }
-    std::vector<float> hx, hu, hi, hw, hs;
+    std::vector<float> hx, hu, hi, hw, hs, hm;
     for (int j0 = 0; j0 < Ns; j0 += Pc) {
         const int np = Ns - j0 < Pc ? Ns - j0 : Pc;                                  // periods of this chunk
         const size_t k0 = (size_t)j0 * S;
@@ -1481,9 +1583,18 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if (dist_moves) HIPCHK(h, hipMemcpyAsync(c_dist, scen->dist + k0 * DR, sizeof(float) * nk * DR, hipMemcpyHostToDevice, st));
         if (sched_moves) HIPCHK(h, hipMemcpyAsync(c_sched, scen->plant_of + k0 * SR, sizeof(int32_t) * nk * SR, hipMemcpyHostToDevice, st));
         if (fault_moves) HIPCHK(h, hipMemcpyAsync(c_fault, flt->fault + k0 * FR, sizeof(float) * nk * FR, hipMemcpyHostToDevice, st));
+        if (obs_moves && noisy) HIPCHK(h, hipMemcpyAsync(c_sigma, obs->sigma + (size_t)j0 * OR, sizeof(float) * np * OR, hipMemcpyHostToDevice, st));
+        if (obs_moves && biased) HIPCHK(h, hipMemcpyAsync(c_beta, obs->beta + (size_t)j0 * OR, sizeof(float) * np * OR, hipMemcpyHostToDevice, st));
+        if (valid_moves) HIPCHK(h, hipMemcpyAsync(c_valid, obs->valid + (size_t)j0 * VR, sizeof(int32_t) * np * VR, hipMemcpyHostToDevice, st));
         for (int jc = 0; jc < np; ++jc) {
             const int ticks = nk - jc * S < S ? nk - jc * S : S;                    // (the last period of the run may be partial)
-            if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st));
+            if (seen) {
+                O.xmeas = c_xmeas + (size_t)jc * B * NX;
+                O.sigma = noisy ? c_sigma + (obs_moves ? (size_t)jc * OR : 0) : nullptr;
+                O.beta = biased ? c_beta + (obs_moves ? (size_t)jc * OR : 0) : nullptr;
+                O.valid = gated ? c_valid + (valid_moves ? (size_t)jc * VR : 0) : nullptr;
+            }
+            if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st, O));
             else if (plant) HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st, plant->Q.substeps));
             else HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st));
             HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));
@@ -1494,7 +1605,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 xr = (const float*)h->d_xref.p;
             }
             float* info_j = c_info + (size_t)jc * B * 8;
-            if ((rc = sdempc_solve_batch_dev(h, B, d_x, xr, h->d_noise.p, h->d_u.p, h->d_step.p, h->d_uopt.p, h->d_xmean.p, info_j, st))) return rc;
+            if ((rc = sdempc_solve_batch_dev(h, B, seen ? d_xm : d_x, xr, h->d_noise.p, h->d_u.p, h->d_step.p, h->d_uopt.p, h->d_xmean.p, info_j, st))) return rc;
             L.info = info_j; L.coop_bar = h->last_coop_B > 0 ? (const unsigned*)h->d_coop_bar.p : nullptr;
             L.xs = c_xs + (size_t)jc * S * B * NX; L.us = c_us + (size_t)jc * S * B * m;
             if (timed) {
@@ -1528,7 +1639,13 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             hs.resize((size_t)nk * nsub * B * NX);
             HIPCHK(h, hipMemcpyAsync(hs.data(), c_xsub, sizeof(float) * hs.size(), hipMemcpyDeviceToHost, st));
         }
+        if (seen && obs->xmeas) {
+            hm.resize((size_t)np * B * NX);
+            HIPCHK(h, hipMemcpyAsync(hm.data(), c_xmeas, sizeof(float) * hm.size(), hipMemcpyDeviceToHost, st));
+        }
         if (j0 + np == Ns) {
+            if (seen && obs->keys_next) HIPCHK(h, hipMemcpyAsync(obs->keys_next, d_q, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
+            if (seen && obs->xmeas_next) HIPCHK(h, hipMemcpyAsync(obs->xmeas_next, d_xm, sizeof(float) * B * NX, hipMemcpyDeviceToHost, st));
             if (rate && rate->integ_next) HIPCHK(h, hipMemcpyAsync(rate->integ_next, d_integ, sizeof(float) * (size_t)B * 3, hipMemcpyDeviceToHost, st));
             if (rate && rate->tail_next) HIPCHK(h, hipMemcpyAsync(rate->tail_next, d_tail, sizeof(float) * (size_t)B * H * 3, hipMemcpyDeviceToHost, st));
             if (io.u_next) HIPCHK(h, hipMemcpyAsync(io.u_next, h->d_u.p, sizeof(float) * (size_t)B * H * m, hipMemcpyDeviceToHost, st));
@@ -1559,6 +1676,10 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         for (int jc = 0; jc < np; ++jc)
             for (int b = 0; b < B; ++b)
                 memcpy((float*)io.info + ((size_t)b * Ns + j0 + jc) * 8, &hi[((size_t)jc * B + b) * 8], sizeof(float) * 8);
+        if (seen && obs->xmeas)
+            for (int jc = 0; jc < np; ++jc)
+                for (int b = 0; b < B; ++b)
+                    memcpy(obs->xmeas + ((size_t)b * Ns + j0 + jc) * NX, &hm[((size_t)jc * B + b) * NX], sizeof(float) * NX);
     }
     return 0;
 }

@@ -221,7 +221,24 @@ hipError_t launch_loop(const KArgs& a, const LoopAdvance& L, const LoopPlant* Q,
 hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, hipStream_t st, int substeps = 1);
 // SPEC.md §11b: the key schedule of one solve period — tick 0 is the schedule above, every later tick advances the key by ONE split (no solve, no solve
 // key) and draws its plant noise the same way. xi_dev f32[B][xi_ticks][substeps][6], rows 0 .. ticks-1 written.
-hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st);
+// SPEC.md §11f, the closed loop on a measured state: what the period's key-schedule thread of episode b does beside its schedule, right before solve j. It
+// advances the observation key q_b by one split and, unless valid says 0, rewrites the held measurement xm_b from the plant state x_b: additive errors
+// e_i = fma(sigma_i, xi_i, beta_i) on position, velocity and body rates, a small body-frame rotation on the attitude (xi = normal(me, (12,))). The solve
+// then starts from xm instead of x. The row pointers address SOLVE j's rows (the host steps them from period to period). q null: absent — the kernel then
+// makes no memory access it did not make before.
+struct LoopObserve {
+    uint32_t* q;                // [B][2] observation keys, advanced in place at every solve; null: no observation
+    const float* x;             // [B][13] the plant state at the period's first tick
+    float* xm;                  // [B][13] the held measurement: in, and out (what the solve reads)
+    float* xmeas;               // [B][13] output row of this solve: xm after the update
+    const float* sigma;         // noise scale of episode b at sigma[b * ep_stride + 0..11] (p, v, theta, omega), or null: zeros
+    const float* beta;          // bias, same layout, or null: zeros
+    int ep_stride;              // floats between two episodes' rows of sigma / beta: 12, or 0 (one row for every episode)
+    const int32_t* valid;       // valid[b * valid_ep_stride] == 0: a dropout, xm stays as it is; null: always valid
+    int valid_ep_stride;        // 1, or 0 (one flag for every episode)
+};
+hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st,
+                                   const LoopObserve& O = LoopObserve{});
 // rows_dev[b][0..n) = row_dev[0..n) for b < B
 hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st);
 // canonical [B][P][C] <-> device [B][G][C][32] (to_dev: zero-pads particles >= P)

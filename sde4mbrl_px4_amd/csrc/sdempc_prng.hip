@@ -201,10 +201,47 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
 
 // SPEC.md §11b: the schedule of one solve period of `ticks` control ticks. Tick 0 is the tick of the kernels above ((r', s) = split(r), (r, p) = split(r'));
 // every later tick has no solve: (r, p) = split(r). Each tick draws normal(p, (n, 6)) as above. xi: [B][xi_ticks][n][6], rows 0 .. ticks-1 written.
+// SPEC.md §11f (O.q given): the same thread first forms the measurement the period's solve starts from — (q, me) = split(q) on the observation chain, at every
+// solve; unless the solve's valid flag is 0, xi = normal(me, (12,)) (random_bits(me, 12) pairs counter i with i + 6), e_i = fma(sigma_i, xi_i, beta_i), added to
+// position, velocity and body rates, and the attitude multiplied by (1, e[6..8] / 2) from the right, not renormalised. O.q null: not one access more.
 __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int ticks,
-                                                                      int xi_ticks, int n) {
+                                                                      int xi_ticks, int n, LoopObserve O) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
+    if (O.q) {
+        uint32_t q2[2], me[2];
+        split2(O.q[2 * b], O.q[2 * b + 1], q2, me);
+        O.q[2 * b] = q2[0]; O.q[2 * b + 1] = q2[1];
+        float* xm = O.xm + (size_t)b * 13;
+        if (!O.valid || O.valid[(size_t)b * O.valid_ep_stride] != 0) {
+            const float* x = O.x + (size_t)b * 13;
+            const float* sg = O.sigma ? O.sigma + (size_t)b * O.ep_stride : nullptr;
+            const float* bt = O.beta ? O.beta + (size_t)b * O.ep_stride : nullptr;
+            float e[12];
+#pragma unroll
+            for (uint32_t i = 0; i < 6; ++i) {
+                uint32_t x0 = i, x1 = i + 6u;
+                threefry2x32(me[0], me[1], x0, x1);
+                e[i] = FMA(sg ? sg[i] : 0.0f, bits_to_normal(x0), bt ? bt[i] : 0.0f);
+                e[i + 6] = FMA(sg ? sg[i + 6] : 0.0f, bits_to_normal(x1), bt ? bt[i + 6] : 0.0f);
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                xm[i] = x[i] + e[i];
+                xm[3 + i] = x[3 + i] + e[3 + i];
+                xm[10 + i] = x[10 + i] + e[9 + i];
+            }
+            const float h0 = 0.5f * e[6], h1 = 0.5f * e[7], h2 = 0.5f * e[8];
+            const float qw = x[6], qx = x[7], qy = x[8], qz = x[9];
+            xm[6] = FMA(-qz, h2, FMA(-qy, h1, FMA(-qx, h0, qw)));
+            xm[7] = FMA(-qz, h1, FMA(qy, h2, FMA(qw, h0, qx)));
+            xm[8] = FMA(-qx, h2, FMA(qz, h0, FMA(qw, h1, qy)));
+            xm[9] = FMA(-qy, h0, FMA(qx, h1, FMA(qw, h2, qz)));
+        }
+        float* row = O.xmeas + (size_t)b * 13;       // (a dropout: the held row; xm was written by this thread or before this launch)
+#pragma unroll
+        for (int i = 0; i < 13; ++i) row[i] = xm[i];
+    }
     uint32_t r[2] = {keys[2 * b], keys[2 * b + 1]};
     const uint32_t half = 3u * (uint32_t)n;
     for (int i = 0; i < ticks; ++i) {
@@ -227,9 +264,10 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
     keys[2 * b] = r[0]; keys[2 * b + 1] = r[1];
 }
 
-hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st) {
+hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st, const LoopObserve& O) {
     if (B < 1 || substeps < 1 || ticks < 1 || xi_ticks < ticks) return hipErrorInvalidValue;
-    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps);
+    if (O.q && (!O.x || !O.xm || !O.xmeas || (O.ep_stride != 0 && O.ep_stride != 12) || (O.valid_ep_stride != 0 && O.valid_ep_stride != 1))) return hipErrorInvalidValue;
+    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O);
     return hipGetLastError();
 }
 

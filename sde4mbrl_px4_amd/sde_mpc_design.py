@@ -139,7 +139,7 @@ class MpcProblem:
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
                  plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,
-                 fault=None, substep_states=False):
+                 fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -161,7 +161,14 @@ class MpcProblem:
         fault / substep_states (SPEC.md §11e): fault f32[T][m][2] or f32[m][2], a per-motor row (kappa, beta) per tick — what reaches rotor l is
         fma(kappa, a_l, beta) (solver.fault_schedule has the recipes: dead, weakened, stuck, biased); motor commands have no frame, so nothing is converted.
         substep_states=True appends xsub f32[T * plant_substeps][13], the plant state after every substep, as a SIXTH value, flipped into the frame of x row by
-        row like xs[1:]. Either one makes the call the timed one."""
+        row like xs[1:]. Either one makes the call the timed one.
+        meas_noise / meas_bias / meas_valid / meas_rng (SPEC.md §11f): the controller solves from an ESTIMATE of the state — meas_noise (sigma >= 0) and meas_bias
+        f32[Ns][12] or f32[12] in the order p, v, theta, omega, GIVEN IN THE FRAME OF x (under convert_to_enu the p and v triples follow the world-vector rule
+        (x, y, z) -> (y, x, -z) and the theta and omega triples the body-vector rule (wx, wy, wz) -> (wx, -wy, -wz), exactly as `disturbance`; a scale takes the
+        permutation without the sign), meas_valid int[Ns] (0: a dropout, the last estimate is held; initially x itself), meas_rng uint32[2] the observation key
+        (required with any of the three; the main key `rng` is never disturbed). Any of the three makes the call the timed one and appends TWO values behind the
+        five: xmeas f32[Ns][13], what each solve started from, flipped into the frame of x row by row like xs[1:], and the observation key after the last solve
+        (xmeas[-1] is the held measurement that continues the run). xsub, when requested, stays the LAST value."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -200,6 +207,31 @@ class MpcProblem:
             more["fault"] = f[None, None] if f.ndim == 2 else f[:, None]
         if substep_states:
             more["substep_states"] = True
+        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None
+        if observed:
+            if meas_rng is None:
+                raise ValueError("MpcProblem.simulate: meas_rng (uint32[2], the observation key) is required with meas_noise / meas_bias / meas_valid")
+            Ns = -(-T // max(int(solve_period), 1))
+            for name, v, signed in (("meas_noise", meas_noise, False), ("meas_bias", meas_bias, True)):
+                if v is None:
+                    continue
+                e = np.asarray(v, np.float32)
+                if e.shape not in ((12,), (Ns, 12)):
+                    raise ValueError(f"MpcProblem.simulate: {name} must be f32[{Ns}][12] or f32[12], got {e.shape}")
+                if self.convert_to_enu:
+                    sg = np.float32(-1.0 if signed else 1.0)
+                    e = np.stack([e[..., 1], e[..., 0], sg * e[..., 2], e[..., 4], e[..., 3], sg * e[..., 5], e[..., 6], sg * e[..., 7], sg * e[..., 8],
+                                  e[..., 9], sg * e[..., 10], sg * e[..., 11]], axis=-1)
+                e = np.ascontiguousarray(e, np.float32)
+                more[name] = e[None, None] if e.ndim == 1 else e[:, None]
+            if meas_valid is not None:
+                v = np.asarray(meas_valid)
+                if v.shape != (Ns,):
+                    raise ValueError(f"MpcProblem.simulate: meas_valid must be int[{Ns}] (one episode: a flag per solve), got {v.shape}")
+                more["meas_valid"] = v[:, None]
+            more["meas_keys"] = np.asarray(meas_rng, dtype=np.uint32).reshape(1, 2)
+        elif meas_rng is not None:
+            raise ValueError("MpcProblem.simulate: meas_rng needs one of meas_noise / meas_bias / meas_valid")
         out = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
             plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag,
@@ -212,6 +244,9 @@ class MpcProblem:
         st = OptState(_arr(u_next[0]), np.float32(i[0]), np.float32(s_next[0]), np.float32(i[2]), np.float32(i[3]), np.float32(i[4]),
                       np.float32(i[5]), np.float32(i[6]), np.float32(i[7]))
         ret = (_arr(xs), _arr(us[0]), _arr(info[0]), st, k_next[0].copy())
+        if observed:
+            xmeas, q_next = out[-4 if substep_states else -3][0], out[-3 if substep_states else -2][0]
+            ret += (_arr(enu2ned(xmeas, np) if self.convert_to_enu else xmeas), q_next.copy())
         if substep_states:
             xsub = out[-1][0]
             ret += (_arr(enu2ned(xsub, np) if self.convert_to_enu else xsub),)

@@ -217,7 +217,8 @@ class SdeMpcSolver:
 
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
-                    rate_loop=None, rate_integ_in=None, rate_tail_in=None, fault=None, substep_states=False):
+                    rate_loop=None, rate_integ_in=None, rate_tail_in=None, fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None,
+                    meas_keys=None, xmeas_in=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -265,7 +266,20 @@ class SdeMpcSolver:
         substep_states=True appends xsub [B][T * plant_substeps][13] as the LAST returned value: the plant state after every substep, so
         xsub[:, plant_substeps - 1::plant_substeps] is xs[:, 1:] bit for bit. Either one makes the call the timed one (xref and info per solve, the plant
         defaulting to the handle's own model; every keyword above still applies); fault alone does not change the returned tuple. With fault=None and
-        substep_states=False nothing of this paragraph is touched."""
+        substep_states=False nothing of this paragraph is touched.
+
+        meas_noise / meas_bias / meas_valid / meas_keys / xmeas_in (SPEC.md §11f, sdempc_closed_loop_batch_observed): the controller reads an ESTIMATE of the state, as
+        the node does, not the plant's state to the last bit. meas_noise (the scale sigma, finite and >= 0) and meas_bias (beta, finite) are f32[No][Bo][12] with No
+        in {1, Ns} (per SOLVE) and Bo in {1, B}, or [Ns][12] (shared by all episodes), or [12] (constant), in the order p, v, theta, omega; meas_valid is
+        int[Nv][Bv] with the same axis rule, or [Ns]: 1 a measurement, 0 a dropout. Solve j starts from xm instead of the plant state x: on a valid solve
+        e = fma(sigma, normal(me, (12,)), beta) with (q, me) = split(q) on the observation chain meas_keys uint32[B][2] (required; it advances at every solve, valid
+        or not, and never touches `keys`), xm = x + e on position, velocity and body rates, and the attitude times (1, e[6:9] / 2) from the right, not renormalised;
+        on a dropout xm stays what it was (initially xmeas_in [B][13]; None: x0). The plant and the rate loop are untouched: they see the estimate through the
+        solves only. Either of the first three makes the call the timed one (xref and info per solve, the plant defaulting to the handle's own model; every keyword
+        above still applies), and xmeas [B][Ns][13] (what each solve started from), meas_keys_next uint32[B][2] and xmeas_next [B][13] are appended to the returned
+        tuple; xsub, when requested, stays the LAST value. Carrying the last two back in with the items above continues the episodes bit for bit when T is a multiple
+        of solve_period. meas_keys or xmeas_in without one of the first three, or one of them without meas_keys, raise ValueError; with none of the five given
+        nothing of this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -309,7 +323,44 @@ class SdeMpcSolver:
             if not np.isfinite(flt).all():
                 raise ValueError("closed_loop: fault holds a non-finite entry")
             flt = np.ascontiguousarray(flt)
-        faulted = flt is not None or bool(substep_states)
+        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None
+        if not observed and (meas_keys is not None or xmeas_in is not None):
+            raise ValueError("closed_loop: meas_keys / xmeas_in need one of meas_noise / meas_bias / meas_valid")
+        if observed:
+            if meas_keys is None:
+                raise ValueError("closed_loop: meas_keys (uint32[B][2], the observation chain) is required with meas_noise / meas_bias / meas_valid")
+            meas_keys = self._keys(meas_keys, B)
+            Ns_o = -(-max(T, 0) // max(int(solve_period), 1))
+
+            def rows(v, what, tail, dtype):
+                a = np.ascontiguousarray(v, dtype=dtype)
+                if a.ndim == len(tail) and a.shape == tail:
+                    a = a[None, None]
+                elif a.ndim == len(tail) + 1 and a.shape == (Ns_o,) + tail:
+                    a = a[:, None]
+                if a.ndim != len(tail) + 2 or a.shape[2:] != tail or a.shape[0] not in (1, Ns_o) or a.shape[1] not in (1, B):
+                    t = "".join(f"[{n}]" for n in tail)
+                    raise ValueError(f"closed_loop: {what} must be [No][Bo]{t} with No in (1, {Ns_o}) and Bo in (1, {B}), [{Ns_o}]{t}" + (f" or {t}" if tail else "") +
+                                     f", got {np.shape(v)}")
+                return np.ascontiguousarray(a)
+            obs_sigma = None if meas_noise is None else rows(meas_noise, "meas_noise", (12,), np.float32)
+            obs_beta = None if meas_bias is None else rows(meas_bias, "meas_bias", (12,), np.float32)
+            obs_valid = None
+            if meas_valid is not None:
+                obs_valid = rows(np.asarray(meas_valid).astype(np.int64), "meas_valid", (), np.int64)
+                if not np.isin(obs_valid, (0, 1)).all():
+                    raise ValueError("closed_loop: meas_valid holds an entry other than 0 / 1")
+                obs_valid = np.ascontiguousarray(obs_valid, dtype=np.int32)
+            if obs_sigma is not None and not (np.isfinite(obs_sigma).all() and (obs_sigma >= 0).all()):
+                raise ValueError("closed_loop: meas_noise holds a non-finite or negative entry")
+            if obs_beta is not None and not np.isfinite(obs_beta).all():
+                raise ValueError("closed_loop: meas_bias holds a non-finite entry")
+            if obs_sigma is not None and obs_beta is not None and obs_sigma.shape != obs_beta.shape:      # (one pair of axes for both: sdempc_obs_cfg)
+                shape = (max(obs_sigma.shape[0], obs_beta.shape[0]), max(obs_sigma.shape[1], obs_beta.shape[1]), 12)
+                obs_sigma, obs_beta = np.ascontiguousarray(np.broadcast_to(obs_sigma, shape)), np.ascontiguousarray(np.broadcast_to(obs_beta, shape))
+            if xmeas_in is not None:
+                xmeas_in = _f32(xmeas_in, (B, 13))
+        faulted = flt is not None or bool(substep_states) or observed
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
             raise ValueError("closed_loop: rate_integ_in / rate_tail_in need rate_loop=...")
         if rate_loop is not None and not isinstance(rate_loop, RateLoop):
@@ -404,10 +455,23 @@ class SdeMpcSolver:
                 fc = _abi.SdempcFaultCfg(C.sizeof(_abi.SdempcFaultCfg), _fp(flt), flt.shape[0], flt.shape[1])
             xsub = np.zeros((B, max(T, 0) * int(plant_substeps), 13), np.float32) if substep_states else None
             lead, more = [None if fc is None else C.byref(fc)] + lead, more + (None if xsub is None else _fp(xsub),)
+            if observed:            # the fault entry point's arguments behind (obs cfg, obs_keys, xmeas_in), then xmeas, obs_keys_next, xmeas_next
+                rows_ = obs_sigma if obs_sigma is not None else obs_beta
+                oc = _abi.SdempcObsCfg(C.sizeof(_abi.SdempcObsCfg), None if obs_sigma is None else _fp(obs_sigma), None if obs_beta is None else _fp(obs_beta),
+                                       1 if rows_ is None else rows_.shape[0], 1 if rows_ is None else rows_.shape[1],
+                                       None if obs_valid is None else obs_valid.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       1 if obs_valid is None else obs_valid.shape[0], 1 if obs_valid is None else obs_valid.shape[1])
+                xmeas = np.zeros((B, max(Ns, 0), 13), np.float32)
+                q_next = np.zeros((B, 2), np.uint32)
+                xm_next = np.zeros((B, 13), np.float32)
+                lead = [C.byref(oc), meas_keys.ctypes.data_as(u32p), None if xmeas_in is None else _fp(xmeas_in)] + lead
+                more, ret = more + (_fp(xmeas), q_next.ctypes.data_as(u32p), _fp(xm_next)), ret + (xmeas, q_next, xm_next)
             if substep_states:
                 ret = ret + (xsub,)
         # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
-        if faulted:
+        if observed:
+            entry = _abi.observed_entry(self.lib)
+        elif faulted:
             entry = _abi.fault_entry(self.lib)
         elif rate_loop is not None:
             entry = _abi.rate_entry(self.lib)

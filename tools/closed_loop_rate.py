@@ -23,9 +23,11 @@
   7. --fault / --substep-states: the same loops through sdempc_closed_loop_batch_fault (SPEC.md §11e) — a fault schedule with a row per tick and episode (every
      episode loses one motor at tick T / 2, the motor drawn per episode, and flies a biased one throughout) and / or the state after every plant substep copied back.
      Applies to --small-batch and to the C2 loop; either one makes the call the timed one.
+  8. --observe: the same loops on a measured state (SPEC.md §11f, sdempc_closed_loop_batch_observed) — a noise and a bias row per solve and episode, and every
+     episode's estimator dropping one solve in four. Applies to --small-batch and to the C2 loop; it makes the call the timed one.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
-                                        [--fault] [--substep-states]
+                                        [--fault] [--substep-states] [--observe]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -61,6 +63,7 @@ ap.add_argument("--plant-switch", type=int, default=-1, metavar="K", help="every
 ap.add_argument("--rate-loop", action="store_true", help="fly the thrust and body-rate setpoints through a PI rate loop (SPEC.md §11d)")
 ap.add_argument("--fault", action="store_true", help="a per-motor fault row per tick and episode (SPEC.md §11e)")
 ap.add_argument("--substep-states", action="store_true", help="copy the state after every plant substep back (SPEC.md §11e)")
+ap.add_argument("--observe", action="store_true", help="solve from a measured state: noise, bias and dropouts per solve and episode (SPEC.md §11f)")
 a = ap.parse_args()
 model = synthetic_iris()
 if a.plant == "own" and a.substeps != 1:
@@ -94,6 +97,14 @@ def scenario_kw(kw, B, T):
         kw["fault"] = f
     if a.substep_states:
         kw["substep_states"] = True
+    if a.observe:
+        Ns = -(-T // max(a.period, 1))
+        rng = np.random.default_rng(7)
+        scale = np.repeat(np.array([0.05, 0.1, 0.02, 0.05], np.float32), 3)          # p [m], v [m/s], theta [rad], omega [rad/s]
+        kw["meas_noise"] = (scale * rng.uniform(0.5, 1.5, (Ns, B, 12))).astype(np.float32)
+        kw["meas_bias"] = (scale * rng.uniform(-0.5, 0.5, (Ns, B, 12))).astype(np.float32)
+        kw["meas_valid"] = (rng.integers(0, 4, (Ns, B)) != 0).astype(np.int32)
+        kw["meas_keys"] = np.stack([prng.PRNGKey(9000 + b) for b in range(B)])
     if a.disturbance:
         kw["disturbance"] = np.random.default_rng(2).uniform(-2.0, 2.0, (T, B, 6)).astype(np.float32)
     if a.plant_switch >= 0:
@@ -127,6 +138,8 @@ if a.fault:
     tag += " fault"
 if a.substep_states:
     tag += " substep-states"
+if a.observe:
+    tag += " observe"
 
 if a.small_batch:
     cfg = load_mpc_config(os.path.join(ROOT, "configs", "c1_iris_posctrl_h20_p32.yaml"))
