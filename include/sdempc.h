@@ -176,7 +176,7 @@ int sdempc_device_ready(const sdempc_handle* h);
  *                                                                                          Filled: the workspaces (particle x horizon tensor, activation checkpoint,
  *                                                                                          partial sums, control table), the cooperative layouts' per-particle outputs and
  *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs,
- *                                                                                          the closed loop's key / chunk / plant / rate-state / observation buffers (the chunk buffer includes the
+ *                                                                                          the closed loop's key / chunk / plant / rate-state / observation / history buffers (the chunk buffer includes the
  *                                                                                          staged disturbance rows and plant-schedule rows of a scenario). (The particle x horizon tensor is
  *                                                                                          zeroed at allocation otherwise; nothing depends on that.) Keep their initial value:
  *                                                                                          - the work counters and the ticket word: running totals, zero at creation by
@@ -544,6 +544,53 @@ int sdempc_closed_loop_batch_observed(sdempc_handle* h, const sdempc_obs_cfg* ob
                                       float* ws /*[B][T][4]; NULL without rate*/, float* rate_integ_next /*[B][3] or NULL*/, float* rate_tail_next /*[B][H][3] or NULL*/,
                                       float* xsub /*[B][T * substeps][13] or NULL*/,
                                       float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/);
+
+/* ---- batched closed loop from an aged, renormalised state estimate (SPEC.md §11g) -----------------------
+ * sdempc_closed_loop_batch_observed with INPUT-side latency: the state the estimate is an estimate OF is already old when the solve starts (the reference node's
+ * mpc_state_callback hands the solver a state stamped msg.time_usec), and a real estimator emits a unit quaternion. solve_delay models the other half, the
+ * solution arriving late. With `age_cfg` NULL the call is sdempc_closed_loop_batch_observed bit for bit, with the same launches; xhist_in and xhist_next must
+ * then be NULL. Let n = plant substeps, S = solve_period and z_k episode b's plant state after global plant substep k (gust fmas included), so z_0 = x0 and
+ * z_{T n} = xs[b][T]; solve j happens at c = j S n. Beside the state of that entry point episode b carries the last age_max substep states before c: for k < 0,
+ * z_k = xhist_in[b][age_max + k] (oldest first; xhist_in NULL: every row is x0, the vehicle sat there). At solve j, when the solve is valid:
+ *   A  = age[j or 0][b or 0]                   0 <= A <= age_max, in plant substeps
+ *   x  = z_{c - A}                             (A = 0: the plant state, the observed entry point exactly)
+ *   xm = the formulas of that entry point on this x (chain, draws, e, sums, attitude product: unchanged)
+ *   if renormalise: (q0..q3) = xm[6..9]; s = fma(q3, q3, fma(q2, q2, fma(q1, q1, q0 * q0))); r = rsqrt(s) (SPEC.md §3.2, the software form whatever the handle's
+ *                   math_mode); xm[6 + i] = q_i * r
+ * On a dropout nothing of this runs: xm is held, the observation chain still advances. The plant, the rate loop, the main key chain and the observation chain are
+ * untouched. age is int32[age_solves][age_batch], age_solves 1 or Ns, age_batch 1 or B, solve-major, an index into a size-1 axis is 0; NULL: every age 0.
+ * 0 <= age_max <= min(S, T) * n: one period of memory. Output xhist_next [B][age_max][13] = z_{T n - age_max} .. z_{T n - 1} (may be NULL): carried back in as
+ * xhist_in with the other continuation values it continues the episodes bit for bit when T is a multiple of S. Every age 0 and renormalise 0 reproduce
+ * sdempc_closed_loop_batch_observed bit for bit, whatever age_max is. With age_max > 0 the history is fed on the device from the substep rows of the chunk (the
+ * xsub region then exists in the chunk, and counts in its bytes, whether or not xsub is asked for). Every argument is checked before the first HIP call:
+ * SDEMPC_EINVAL for struct_size, an age cfg without `obs`, a history pointer without an age cfg, age_max outside [0, min(S, T) * n], age_solves not 1 or Ns,
+ * age_batch not 1 or B, an age entry outside [0, age_max], renormalise other than 0 / 1, a history pointer with age_max 0, and for everything
+ * sdempc_closed_loop_batch_observed refuses. No ABI version change: detect the entry point by its symbol. */
+typedef struct sdempc_age_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_age_cfg) */
+    const int32_t* age;    /* [age_solves][age_batch] age of the estimate in plant substeps, or NULL: every age 0 */
+    int32_t age_solves;    /* 1 or Ns (ignored when age is NULL) */
+    int32_t age_batch;     /* 1 or B (ignored when age is NULL) */
+    int32_t age_max;       /* rows of the history, 0 .. min(S, T) * substeps */
+    int32_t renormalise;   /* 1: the attitude of xm is scaled to unit length; 0: left as the product gives it */
+} sdempc_age_cfg;
+int sdempc_closed_loop_batch_aged(sdempc_handle* h, const sdempc_age_cfg* age_cfg /*or NULL*/, const float* xhist_in /*[B][age_max][13] or NULL*/,
+                                  const sdempc_obs_cfg* obs /*or NULL*/, const uint32_t* obs_keys /*[B][2]*/, const float* xmeas_in /*[B][13] or NULL*/,
+                                  const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*or NULL*/,
+                                  const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                  const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                  const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                  const float* xref, int32_t xref_solves, int32_t xref_batch,
+                                  const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                  const float* u_act_in /*[B][m] or NULL*/,
+                                  float* xs /*[B][T+1][13]*/, float* us /*[B][T][m]*/, sdempc_info* info /*[B][Ns]*/,
+                                  float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                  uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                  const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                  float* ws /*[B][T][4]; NULL without rate*/, float* rate_integ_next /*[B][3] or NULL*/, float* rate_tail_next /*[B][H][3] or NULL*/,
+                                  float* xsub /*[B][T * substeps][13] or NULL*/,
+                                  float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
+                                  float* xhist_next /*[B][age_max][13] or NULL*/);
 
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so

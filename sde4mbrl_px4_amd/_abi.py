@@ -90,6 +90,12 @@ class SdempcObsCfg(C.Structure):
                 ("valid", C.POINTER(C.c_int32)), ("valid_solves", C.c_int32), ("valid_batch", C.c_int32)]
 
 
+class SdempcAgeCfg(C.Structure):
+    """sdempc_age_cfg (SPEC.md §11g): the age of the estimate per solve and episode, the depth of the history and the renormalise flag of sdempc_closed_loop_batch_aged."""
+    _fields_ = [("struct_size", C.c_int32), ("age", C.POINTER(C.c_int32)), ("age_solves", C.c_int32), ("age_batch", C.c_int32), ("age_max", C.c_int32),
+                ("renormalise", C.c_int32)]
+
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -257,6 +263,21 @@ def observed_entry(lib):
     return fn
 
 
+def aged_entry(lib):
+    """sdempc_closed_loop_batch_aged (SPEC.md §11g) with its prototype set: an age cfg (may be NULL) and xhist_in in front of the observed entry point's arguments,
+    then xhist_next. Detected by symbol and only when a call needs it, as observed_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_aged
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_aged (SPEC.md §11g): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(observed_entry(lib).argtypes)
+        fp = C.POINTER(C.c_float)
+        fn.argtypes = [a[0], C.POINTER(SdempcAgeCfg), fp] + a[1:] + [fp]
+        fn.restype = C.c_int
+    return fn
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -265,4 +286,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
     "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed", "sdempc_closed_loop_batch_scenario",
     "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault", "sdempc_closed_loop_batch_observed",
+    "sdempc_closed_loop_batch_aged",
 ]

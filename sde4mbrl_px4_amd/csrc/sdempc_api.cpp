@@ -181,6 +181,9 @@ struct sdempc_handle {
     DevBuf d_rate;
     // closed loop on a measured state (sdempc_closed_loop_batch_observed, allocated on its first use): observation keys u32[max_batch][2], held measurement f32[max_batch][13]
     DevBuf d_obs;
+    // closed loop from an aged estimate (sdempc_closed_loop_batch_aged, allocated on its first use and grown with age_max): the last age_max substep states
+    // f32[age_max][B][13], oldest first
+    DevBuf d_hist;
     DevBuf d_work;            // u64[4] work counters (KArgs::work)
     // cooperative latency path of the solve (allocated on its first use, sized for coop_cap instances)
     DevBuf d_coop_bar, d_coop_pp, d_coop_ck;
@@ -561,6 +564,13 @@ struct ObsRun {
     float* xmeas;               // [B][Ns][13] or null
     uint32_t* keys_next;        // [B][2] or null
     float* xmeas_next;          // [B][13] or null
+    // SPEC.md §11g (sdempc_closed_loop_batch_aged with an age cfg; all absent otherwise): the age rows are staged per chunk when they move, like valid
+    const int32_t* age;         // [Ta][Ba] or null (every age 0)
+    int Ta, Ba;
+    int age_max;                // rows of the history; 0: no history
+    bool renorm;
+    const float* xhist_in;      // [B][age_max][13] or null (every row x0)
+    float* xhist_next;          // [B][age_max][13] or null
 };
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
 // One closed-loop call as its entry point describes it. The five entry points are five nested layers (SPEC.md §11, §11a .. §11d): each takes everything the one
@@ -590,6 +600,10 @@ struct LoopCall {
     float* xmeas;
     uint32_t* obs_keys_next;
     float* xmeas_next;
+    bool aged;                                  // sdempc_closed_loop_batch_aged (SPEC.md §11g): the observed call with ac and the two history pointers
+    const sdempc_age_cfg* ac;                   // or NULL: no age (the two pointers must then be NULL)
+    const float* xhist_in;
+    float* xhist_next;
 };
 int closed_loop_call(sdempc_handle* h, const LoopCall& c);
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves);
@@ -690,7 +704,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1157,6 +1171,28 @@ int sdempc_closed_loop_batch_observed(sdempc_handle* h, const sdempc_obs_cfg* oc
     });
 }
 
+int sdempc_closed_loop_batch_aged(sdempc_handle* h, const sdempc_age_cfg* ac, const float* xhist_in, const sdempc_obs_cfg* oc, const uint32_t* obs_keys, const float* xmeas_in,
+                                  const sdempc_fault_cfg* fc, const sdempc_rate_cfg* rc_, const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc,
+                                  const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T, const float* x0,
+                                  const float* xref, int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in,
+                                  const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next,
+                                  float* u_act_next, const float* rate_integ_in, const float* rate_tail_in, float* ws, float* rate_integ_next, float* rate_tail_next,
+                                  float* xsub, float* xmeas, uint32_t* obs_keys_next, float* xmeas_next, float* xhist_next) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    c.observed = true; c.oc = oc; c.obs_keys = obs_keys; c.xmeas_in = xmeas_in; c.xmeas = xmeas; c.obs_keys_next = obs_keys_next; c.xmeas_next = xmeas_next;
+    c.aged = true; c.ac = ac; c.xhist_in = xhist_in; c.xhist_next = xhist_next;
+    return closed_loop_call(h, c);
+    });
+}
+
 int sdempc_solve_status(sdempc_handle* h) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1209,8 +1245,8 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
 }
-// The one path behind the seven closed-loop entry points: every check of the call's parts, in one fixed order (observation struct, fault struct, rate, scenario struct, timing,
-// loop arguments, plant_ticks, plant set, solve_delay, disturbance, fault schedule, observation rows; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
+// The one path behind the eight closed-loop entry points: every check of the call's parts, in one fixed order (age struct, observation struct, fault struct, rate, scenario struct,
+// timing, loop arguments, plant_ticks, plant set, solve_delay, disturbance, fault schedule, observation rows, age rows; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
 int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     if (!h) return SDEMPC_EINVAL;
     const LoopIo& io = c.io;
@@ -1221,6 +1257,11 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    if (c.aged) {
+        if (c.ac && c.ac->struct_size != (int32_t)sizeof(sdempc_age_cfg)) return fail(h, SDEMPC_EINVAL, "age: struct_size mismatch%s");
+        if (c.ac && !c.oc) return fail(h, SDEMPC_EINVAL, "age: an age cfg needs an obs cfg%s");
+        if (!c.ac && (c.xhist_in || c.xhist_next)) return fail(h, SDEMPC_EINVAL, "age: xhist_in / xhist_next must be NULL without an age cfg%s");
+    }
     if (c.observed) {
         if (c.oc && c.oc->struct_size != (int32_t)sizeof(sdempc_obs_cfg)) return fail(h, SDEMPC_EINVAL, "obs: struct_size mismatch%s");
         if (!c.oc && (c.obs_keys || c.xmeas_in || c.xmeas || c.obs_keys_next || c.xmeas_next))
@@ -1298,6 +1339,21 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
                 if (oc->valid[e] != 0 && oc->valid[e] != 1) return fail(h, SDEMPC_EINVAL, "obs: valid holds an entry other than 0 / 1%s");
         }
     }
+    const sdempc_age_cfg* ac = c.aged ? c.ac : nullptr;
+    if (ac) {
+        const int Ns = loop_solves(T, tc->solve_period);
+        const long long lim = (long long)(tc->solve_period < T ? tc->solve_period : T) * c.pc->substeps;        // one period of memory
+        if (ac->age_max < 0 || ac->age_max > lim) return fail(h, SDEMPC_EINVAL, "age: age_max must be between 0 and min(solve_period, T) * substeps%s");
+        if (ac->age) {
+            if (ac->age_solves != 1 && ac->age_solves != Ns) return fail(h, SDEMPC_EINVAL, "age: age_solves must be 1 or ceil(T / solve_period)%s");
+            if (ac->age_batch != 1 && ac->age_batch != B) return fail(h, SDEMPC_EINVAL, "age: age_batch must be 1 or B%s");
+            const size_t na = (size_t)ac->age_solves * ac->age_batch;
+            for (size_t e = 0; e < na; ++e)
+                if (ac->age[e] < 0 || ac->age[e] > ac->age_max) return fail(h, SDEMPC_EINVAL, "age: age holds an entry outside [0, age_max]%s");
+        }
+        if (ac->renormalise != 0 && ac->renormalise != 1) return fail(h, SDEMPC_EINVAL, "age: renormalise must be 0 or 1%s");
+        if (ac->age_max == 0 && (c.xhist_in || c.xhist_next)) return fail(h, SDEMPC_EINVAL, "age: xhist_in / xhist_next must be NULL with age_max 0%s");
+    }
     if ((rc = ensure_device(h))) return rc;
     if (c.layer == LOOP_PLAIN) return closed_loop_attempts(h, io, nullptr, nullptr, nullptr, nullptr);
     const TimedRun run_t{timed ? tc->solve_period : 1, timed ? tc->solve_delay : 0, timed ? tc->lag_alpha : 0.0f, c.u_act_in, c.u_act_next};
@@ -1306,7 +1362,9 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const FaultRun run_f{fault, fault ? c.fc->fault_ticks : 1, fault ? c.fc->fault_batch : 1, c.faulted ? c.xsub : nullptr};
     const bool rows = oc && (oc->sigma || oc->beta);
     const ObsRun run_o{oc ? oc->sigma : nullptr, oc ? oc->beta : nullptr, rows ? oc->obs_solves : 1, rows ? oc->obs_batch : 1, oc ? oc->valid : nullptr,
-                       oc && oc->valid ? oc->valid_solves : 1, oc && oc->valid ? oc->valid_batch : 1, c.obs_keys, c.xmeas_in, c.xmeas, c.obs_keys_next, c.xmeas_next};
+                       oc && oc->valid ? oc->valid_solves : 1, oc && oc->valid ? oc->valid_batch : 1, c.obs_keys, c.xmeas_in, c.xmeas, c.obs_keys_next, c.xmeas_next,
+                       ac ? ac->age : nullptr, ac && ac->age ? ac->age_solves : 1, ac && ac->age ? ac->age_batch : 1, ac ? ac->age_max : 0, ac && ac->renormalise != 0,
+                       c.xhist_in, c.xhist_next};
     PlantRun run;
     // (a schedule is staged per chunk by the loop, where stage_plants takes the set itself; the noise of a whole solve period sits beside the set)
     if ((rc = stage_plants(h, *c.pc, c.plant_blobs, scenario ? nullptr : c.plant_of, B, &run, !timed ? 1 : (tc->solve_period < T ? tc->solve_period : T)))) return rc;
@@ -1427,15 +1485,21 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // re-run starts from them again); the period's key schedule forms the measurement (LoopObserve) and the solve starts from it (d_xm) instead of d_x, which stays the
 // plant's. The chunk's xmeas rows (one per SOLVE) sit behind xsub, are counted in the chunk's bytes and copied back with info; the sigma / beta / valid rows sit
 // behind them, staged per chunk when they move (one per solve, like moving references) and once otherwise.
+// SPEC.md §11g (obs with an age cfg): the last age_max substep states before the coming solve live in d_hist as [age_max][B][13], oldest first (staged from xhist_in or
+// x0 with the other inputs, so that a re-run starts from them again). With age_max > 0 the run takes the §11e kernels with an xsub region in the chunk whether or not the
+// caller asked for xsub (copied back only if they did): after each plant launch the history is refilled, by device-to-device copies on the stream, from the period's
+// substep rows — and, where it reaches back that far, from the plant state before the launch and from its own newer rows (a partial last period). So it carries over
+// period and chunk boundaries in d_hist alone. The age rows sit behind the valid rows, staged like them.
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
                     bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
     const int Ns = loop_solves(T, S);
-    const bool faulty = flt && flt->fault, subs = flt && flt->xsub;
-    const int nsub = plant ? plant->Q.substeps : 1;
     const bool seen = obs && timed;
+    const int AM = seen ? obs->age_max : 0;                                 // rows of the history (SPEC.md §11g)
+    const bool faulty = flt && flt->fault, subs_out = flt && flt->xsub, subs = subs_out || AM > 0;      // (the history is fed from the chunk's substep rows)
+    const int nsub = plant ? plant->Q.substeps : 1;
     const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m + (rate ? 4 : 0) + (subs ? (size_t)nsub * NX : 0)) + 8 + (seen ? NX : 0);       // floats per reference window / per episode-period of output
     const bool xref_moves = io.xref_ticks > 1;
     const bool gust = scen && scen->dist, sched = scen && plant && plant->Q.models;        // (one shared plant: nothing to schedule)
@@ -1447,9 +1511,11 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     const bool obs_moves = (noisy || biased) && obs->To > 1, valid_moves = gated && obs->Tv > 1;
     const size_t OR = noisy || biased ? (size_t)obs->Bo * 12 : 0, VR = gated ? (size_t)obs->Bv : 0;   // floats per solve row of sigma / of beta; words per solve row of valid
     const size_t ORS = (noisy ? OR : 0) + (biased ? OR : 0);
+    const bool old = seen && obs->age, age_moves = old && obs->Ta > 1;
+    const size_t AR = old ? (size_t)obs->Ba : 0;                                                       // words per solve row of age
     const size_t per_period = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0) +
-                              (fault_moves ? (size_t)S * FR : 0) + (obs_moves ? ORS : 0) + (valid_moves ? VR : 0);
-    const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR) + (fault_moves ? 0 : FR) + (obs_moves ? 0 : ORS) + (valid_moves ? 0 : VR);
+                              (fault_moves ? (size_t)S * FR : 0) + (obs_moves ? ORS : 0) + (valid_moves ? VR : 0) + (age_moves ? AR : 0);
+    const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR) + (fault_moves ? 0 : FR) + (obs_moves ? 0 : ORS) + (valid_moves ? 0 : VR) + (age_moves ? 0 : AR);
     const size_t cap = (h->loop_chunk_bytes < 0 ? LOOP_CHUNK_BYTES : (size_t)h->loop_chunk_bytes) / sizeof(float);
     const size_t fit = cap > fixed ? (cap - fixed) / per_period : 0;
     const int Pc = (int)(fit < 1 ? 1 : (fit < (size_t)Ns ? fit : (size_t)Ns));      // periods per chunk
@@ -1464,6 +1530,13 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     }
     if (rate && !h->d_rate.p && (rc = dev_alloc(h, h->d_rate, sizeof(float) * (size_t)h->max_batch * 3 * (1 + H), true))) return rc;
     if (seen && !h->d_obs.p && (rc = dev_alloc(h, h->d_obs, (sizeof(uint32_t) * 2 + sizeof(float) * NX) * (size_t)h->max_batch, true))) return rc;
+    const size_t HR = (size_t)B * NX;                                // floats per history row
+    if (AM > 0 && h->d_hist.bytes < sizeof(float) * (size_t)AM * h->max_batch * NX) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        dev_free(h->d_hist);
+        if ((rc = dev_alloc(h, h->d_hist, sizeof(float) * (size_t)AM * h->max_batch * NX, true))) return rc;
+    }
+    float* d_hist = AM > 0 ? (float*)h->d_hist.p : nullptr;          // [AM][B][13] (SPEC.md §11g)
     uint32_t* d_q = (uint32_t*)h->d_obs.p;                           // q [B][2] (SPEC.md §11f)
     float* d_xm = d_q ? (float*)(d_q + 2 * (size_t)h->max_batch) : nullptr;   // xm [B][13]
     float* d_integ = (float*)h->d_rate.p;                            // g [B][3] (SPEC.md §11d)
@@ -1487,10 +1560,11 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* c_sigma = c_xmeas + (seen ? (size_t)Pc * B * NX : 0);              // [Pc or 1][Bo][12]
     float* c_beta = c_sigma + (noisy ? (obs_moves ? (size_t)Pc : 1) * OR : 0);        // [Pc or 1][Bo][12]
     int32_t* c_valid = (int32_t*)(c_beta + (biased ? (obs_moves ? (size_t)Pc : 1) * OR : 0));    // [Pc or 1][Bv]
+    int32_t* c_age = c_valid + (gated ? (valid_moves ? (size_t)Pc : 1) * VR : 0);                // [Pc or 1][Ba] (SPEC.md §11g)
     float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place (SPEC.md §11f: the plant's; the solve reads d_xm)
     hipStream_t st = h->stream;
     // inputs (host vectors live until the synchronisation at the end of the first chunk)
-    std::vector<float> u0, s0, a0;
+    std::vector<float> u0, s0, a0, hh;
     const float* u_in = io.u_init;
     const float* s_in = io.stepsize_in;
     if (!u_in) {               // sdempc_reset: uref tiled
@@ -1528,6 +1602,14 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if (noisy && !obs_moves) HIPCHK(h, hipMemcpyAsync(c_sigma, obs->sigma, sizeof(float) * OR, hipMemcpyHostToDevice, st));
         if (biased && !obs_moves) HIPCHK(h, hipMemcpyAsync(c_beta, obs->beta, sizeof(float) * OR, hipMemcpyHostToDevice, st));
         if (gated && !valid_moves) HIPCHK(h, hipMemcpyAsync(c_valid, obs->valid, sizeof(int32_t) * VR, hipMemcpyHostToDevice, st));
+        if (old && !age_moves) HIPCHK(h, hipMemcpyAsync(c_age, obs->age, sizeof(int32_t) * AR, hipMemcpyHostToDevice, st));
+    }
+    if (AM > 0) {              // the history starts as given, row-major on the device (xhist_in NULL: the vehicle sat at x0)
+        hh.resize((size_t)AM * HR);
+        for (int i = 0; i < AM; ++i)
+            for (int b = 0; b < B; ++b)
+                memcpy(&hh[(size_t)i * HR + (size_t)b * NX], obs->xhist_in ? obs->xhist_in + ((size_t)b * AM + i) * NX : io.x0 + (size_t)b * NX, sizeof(float) * NX);
+        HIPCHK(h, hipMemcpyAsync(d_hist, hh.data(), sizeof(float) * hh.size(), hipMemcpyHostToDevice, st));
     }
     if (!xref_moves) {
         HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
@@ -1556,7 +1638,11 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     LoopRate W{};
     LoopFault V{};
     LoopObserve O{};           // (q null: absent)
-    if (seen) { O.q = d_q; O.x = d_x; O.xm = d_xm; O.ep_stride = obs->Bo > 1 ? 12 : 0; O.valid_ep_stride = obs->Bv > 1 ? 1 : 0; }
+    if (seen) {
+        O.q = d_q; O.x = d_x; O.xm = d_xm; O.ep_stride = obs->Bo > 1 ? 12 : 0; O.valid_ep_stride = obs->Bv > 1 ? 1 : 0;
+        O.renorm = obs->renorm ? 1 : 0;
+        if (old && AM > 0) { O.hist = d_hist; O.hist_row_stride = (int)HR; O.age_ep_stride = obs->Ba > 1 ? 1 : 0; O.age_max = AM; }      // (age_max 0: every age is 0)
+    }
     if (flt) { V.fault_tick_stride = fault_moves ? (int)FR : 0; V.fault_ep_stride = faulty && flt->Bf > 1 ? 2 * m : 0; }
     if (timed) { R.act = d_mot; R.alpha = timed->alpha; R.xi_ticks = S; R.shift = timed->S < H ? timed->S : H; }
     if (scen) {
@@ -1574,7 +1660,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         W.inv_m = rate->inv_m; W.w = rc_.motor_weight;
         W.xevol = (const float*)h->d_xmean.p; W.wt = d_tail; W.g = d_integ;
     }
-    std::vector<float> hx, hu, hi, hw, hs, hm;
+    std::vector<float> hx, hu, hi, hw, hs, hm, hn;
     for (int j0 = 0; j0 < Ns; j0 += Pc) {
         const int np = Ns - j0 < Pc ? Ns - j0 : Pc;                                  // periods of this chunk
         const size_t k0 = (size_t)j0 * S;
@@ -1586,6 +1672,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if (obs_moves && noisy) HIPCHK(h, hipMemcpyAsync(c_sigma, obs->sigma + (size_t)j0 * OR, sizeof(float) * np * OR, hipMemcpyHostToDevice, st));
         if (obs_moves && biased) HIPCHK(h, hipMemcpyAsync(c_beta, obs->beta + (size_t)j0 * OR, sizeof(float) * np * OR, hipMemcpyHostToDevice, st));
         if (valid_moves) HIPCHK(h, hipMemcpyAsync(c_valid, obs->valid + (size_t)j0 * VR, sizeof(int32_t) * np * VR, hipMemcpyHostToDevice, st));
+        if (age_moves) HIPCHK(h, hipMemcpyAsync(c_age, obs->age + (size_t)j0 * AR, sizeof(int32_t) * np * AR, hipMemcpyHostToDevice, st));
         for (int jc = 0; jc < np; ++jc) {
             const int ticks = nk - jc * S < S ? nk - jc * S : S;                    // (the last period of the run may be partial)
             if (seen) {
@@ -1593,6 +1680,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 O.sigma = noisy ? c_sigma + (obs_moves ? (size_t)jc * OR : 0) : nullptr;
                 O.beta = biased ? c_beta + (obs_moves ? (size_t)jc * OR : 0) : nullptr;
                 O.valid = gated ? c_valid + (valid_moves ? (size_t)jc * VR : 0) : nullptr;
+                if (O.hist) O.age = c_age + (age_moves ? (size_t)jc * AR : 0);
             }
             if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st, O));
             else if (plant) HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st, plant->Q.substeps));
@@ -1617,13 +1705,27 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                     C.plant = sched ? c_sched + (sched_moves ? t0 * SR : 0) : nullptr;
                 }
                 if (rate) W.ws = c_ws + t0 * B * 4;
-                if (flt) {
+                if (flt || AM > 0) {
                     V.fault = faulty ? c_fault + (fault_moves ? t0 * FR : 0) : nullptr;
                     V.xsub = subs ? c_xsub + t0 * nsub * B * NX : nullptr;
                 }
             }
+            // SPEC.md §11g: with d = ticks * nsub substeps in this period, row i of the history after it is z_{c + d - AM + i}: an old row i + d (a partial last
+            // period: moved down in blocks no longer than the shift, in ascending order), the plant state before the launch (i = AM - d), or substep row d - AM + i - 1
+            const int d = ticks * nsub;
+            if (AM > 0 && d <= AM) {
+                for (int i = 0; i < AM - d; i += d) {
+                    const int len = AM - d - i < d ? AM - d - i : d;
+                    HIPCHK(h, hipMemcpyAsync(d_hist + (size_t)i * HR, d_hist + (size_t)(i + d) * HR, sizeof(float) * len * HR, hipMemcpyDeviceToDevice, st));
+                }
+                HIPCHK(h, hipMemcpyAsync(d_hist + (size_t)(AM - d) * HR, d_x, sizeof(float) * HR, hipMemcpyDeviceToDevice, st));
+            }
             HIPCHK(h, launch_loop(plant ? plant->k : h->base, L, plant ? &plant->Q : nullptr, timed ? &R : nullptr, scen ? &C : nullptr, rate ? &W : nullptr, st,
-                                  flt && timed && scen ? &V : nullptr));
+                                  (flt || AM > 0) && timed && scen ? &V : nullptr));
+            if (AM > 0) {
+                const int i0 = AM - d + 1 > 0 ? AM - d + 1 : 0;
+                if (i0 < AM) HIPCHK(h, hipMemcpyAsync(d_hist + (size_t)i0 * HR, V.xsub + (size_t)(d - AM + i0 - 1) * HR, sizeof(float) * (AM - i0) * HR, hipMemcpyDeviceToDevice, st));
+            }
         }
         hx.resize((size_t)nk * B * NX); hu.resize((size_t)nk * B * m); hi.resize((size_t)np * B * 8);
         unsigned gave_up = 0;
@@ -1635,7 +1737,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             hw.resize((size_t)nk * B * 4);
             HIPCHK(h, hipMemcpyAsync(hw.data(), c_ws, sizeof(float) * hw.size(), hipMemcpyDeviceToHost, st));
         }
-        if (subs) {
+        if (subs_out) {
             hs.resize((size_t)nk * nsub * B * NX);
             HIPCHK(h, hipMemcpyAsync(hs.data(), c_xsub, sizeof(float) * hs.size(), hipMemcpyDeviceToHost, st));
         }
@@ -1644,6 +1746,10 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             HIPCHK(h, hipMemcpyAsync(hm.data(), c_xmeas, sizeof(float) * hm.size(), hipMemcpyDeviceToHost, st));
         }
         if (j0 + np == Ns) {
+            if (AM > 0 && obs->xhist_next) {
+                hn.resize((size_t)AM * HR);
+                HIPCHK(h, hipMemcpyAsync(hn.data(), d_hist, sizeof(float) * hn.size(), hipMemcpyDeviceToHost, st));
+            }
             if (seen && obs->keys_next) HIPCHK(h, hipMemcpyAsync(obs->keys_next, d_q, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
             if (seen && obs->xmeas_next) HIPCHK(h, hipMemcpyAsync(obs->xmeas_next, d_xm, sizeof(float) * B * NX, hipMemcpyDeviceToHost, st));
             if (rate && rate->integ_next) HIPCHK(h, hipMemcpyAsync(rate->integ_next, d_integ, sizeof(float) * (size_t)B * 3, hipMemcpyDeviceToHost, st));
@@ -1669,7 +1775,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 memcpy(io.us + ((size_t)b * T + k) * m, &hu[r * m], sizeof(float) * m);
                 if (rate) memcpy(rate->ws + ((size_t)b * T + k) * 4, &hw[r * 4], sizeof(float) * 4);
             }
-        if (subs)
+        if (subs_out)
             for (size_t rr = 0; rr < (size_t)nk * nsub; ++rr)
                 for (int b = 0; b < B; ++b)
                     memcpy(flt->xsub + ((size_t)b * T * nsub + k0 * nsub + rr) * NX, &hs[(rr * B + b) * NX], sizeof(float) * NX);
@@ -1680,6 +1786,10 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             for (int jc = 0; jc < np; ++jc)
                 for (int b = 0; b < B; ++b)
                     memcpy(obs->xmeas + ((size_t)b * Ns + j0 + jc) * NX, &hm[((size_t)jc * B + b) * NX], sizeof(float) * NX);
+        if (!hn.empty())
+            for (int i = 0; i < AM; ++i)
+                for (int b = 0; b < B; ++b)
+                    memcpy(obs->xhist_next + ((size_t)b * AM + i) * NX, &hn[(size_t)i * HR + (size_t)b * NX], sizeof(float) * NX);
     }
     return 0;
 }

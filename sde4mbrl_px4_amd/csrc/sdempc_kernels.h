@@ -226,6 +226,10 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
 // e_i = fma(sigma_i, xi_i, beta_i) on position, velocity and body rates, a small body-frame rotation on the attitude (xi = normal(me, (12,))). The solve
 // then starts from xm instead of x. The row pointers address SOLVE j's rows (the host steps them from period to period). q null: absent — the kernel then
 // makes no memory access it did not make before.
+// SPEC.md §11g, an aged and renormalised estimate: with `age` given the measurement of episode b is formed from the plant state A = age[b * age_ep_stride] plant
+// substeps before the solve — history row age_max - A (row i holds every episode's state age_max - i substeps back) — instead of x; A = 0 reads x. With
+// `renorm` set the attitude of xm is scaled by the software rsqrt (SPEC.md §3.2) of its squared length after the product. Neither happens on a dropout. The
+// defaults (null, 0) mean absent: an un-aged, un-normalised run makes no memory access it did not make before.
 struct LoopObserve {
     uint32_t* q;                // [B][2] observation keys, advanced in place at every solve; null: no observation
     const float* x;             // [B][13] the plant state at the period's first tick
@@ -236,6 +240,12 @@ struct LoopObserve {
     int ep_stride;              // floats between two episodes' rows of sigma / beta: 12, or 0 (one row for every episode)
     const int32_t* valid;       // valid[b * valid_ep_stride] == 0: a dropout, xm stays as it is; null: always valid
     int valid_ep_stride;        // 1, or 0 (one flag for every episode)
+    const float* hist;          // [age_max][hist_row_stride] the last age_max substep states before this solve, oldest first, episode b at + b * 13; read only where A > 0
+    int hist_row_stride;        // floats between two history rows (>= B * 13)
+    const int32_t* age;         // age[b * age_ep_stride] in [0, age_max]: the age of episode b's estimate at this solve, in plant substeps; null: every age 0
+    int age_ep_stride;          // 1, or 0 (one age for every episode)
+    int age_max;                // rows of hist
+    int renorm;                 // 1: renormalise the attitude of xm (wave-uniform); 0: leave the product as it is
 };
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st,
                                    const LoopObserve& O = LoopObserve{});

@@ -72,6 +72,14 @@ DI float sqrt_spec(float a) {
     const float r = FMA(-s, s, a);
     return FMA(r, 0.5f * y, s);
 }
+// SPEC.md §3.2 restated (the software form, whatever the handle's math_mode): sqrt_spec above is this y followed by one correction step
+DI float rsqrt_spec(float a) {
+    float y = __uint_as_float(0x5F3759DFu - (__float_as_uint(a) >> 1));
+    const float h = 0.5f * a;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { float t = y * y; t = FMA(-h, t, 1.5f); y = y * t; }
+    return y;
+}
 DI float erfinv_spec(float u) {
     float w = -log_spec(FMA(-u, u, 1.0f));
     float p;
@@ -204,6 +212,8 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
 // SPEC.md §11f (O.q given): the same thread first forms the measurement the period's solve starts from — (q, me) = split(q) on the observation chain, at every
 // solve; unless the solve's valid flag is 0, xi = normal(me, (12,)) (random_bits(me, 12) pairs counter i with i + 6), e_i = fma(sigma_i, xi_i, beta_i), added to
 // position, velocity and body rates, and the attitude multiplied by (1, e[6..8] / 2) from the right, not renormalised. O.q null: not one access more.
+// SPEC.md §11g (O.age / O.renorm given): the state the measurement is formed from is A = age[b] plant substeps old — row age_max - A of the history (a per-thread
+// gather; A = 0 reads O.x as before) — and the attitude of xm is scaled to unit length with the software rsqrt. O.age null and O.renorm 0: not one access more.
 __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int ticks,
                                                                       int xi_ticks, int n, LoopObserve O) {
     const int b = blockIdx.x * 256 + threadIdx.x;
@@ -215,6 +225,10 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
         float* xm = O.xm + (size_t)b * 13;
         if (!O.valid || O.valid[(size_t)b * O.valid_ep_stride] != 0) {
             const float* x = O.x + (size_t)b * 13;
+            if (O.age) {
+                const int A = O.age[(size_t)b * O.age_ep_stride];
+                if (A > 0) x = O.hist + (size_t)(O.age_max - A) * O.hist_row_stride + (size_t)b * 13;
+            }
             const float* sg = O.sigma ? O.sigma + (size_t)b * O.ep_stride : nullptr;
             const float* bt = O.beta ? O.beta + (size_t)b * O.ep_stride : nullptr;
             float e[12];
@@ -237,6 +251,11 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
             xm[7] = FMA(-qz, h1, FMA(qy, h2, FMA(qw, h0, qx)));
             xm[8] = FMA(-qx, h2, FMA(qz, h0, FMA(qw, h1, qy)));
             xm[9] = FMA(-qy, h0, FMA(qx, h1, FMA(qw, h2, qz)));
+            if (O.renorm) {                              // (wave-uniform)
+                const float q0 = xm[6], q1 = xm[7], q2 = xm[8], q3 = xm[9];
+                const float r = rsqrt_spec(FMA(q3, q3, FMA(q2, q2, FMA(q1, q1, q0 * q0))));
+                xm[6] = q0 * r; xm[7] = q1 * r; xm[8] = q2 * r; xm[9] = q3 * r;
+            }
         }
         float* row = O.xmeas + (size_t)b * 13;       // (a dropout: the held row; xm was written by this thread or before this launch)
 #pragma unroll
@@ -267,6 +286,8 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st, const LoopObserve& O) {
     if (B < 1 || substeps < 1 || ticks < 1 || xi_ticks < ticks) return hipErrorInvalidValue;
     if (O.q && (!O.x || !O.xm || !O.xmeas || (O.ep_stride != 0 && O.ep_stride != 12) || (O.valid_ep_stride != 0 && O.valid_ep_stride != 1))) return hipErrorInvalidValue;
+    if ((O.age || O.renorm) && !O.q) return hipErrorInvalidValue;
+    if (O.age && (!O.hist || O.age_max < 1 || O.hist_row_stride < B * 13 || (O.age_ep_stride != 0 && O.age_ep_stride != 1))) return hipErrorInvalidValue;
     sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O);
     return hipGetLastError();
 }

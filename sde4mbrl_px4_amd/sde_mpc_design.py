@@ -139,7 +139,7 @@ class MpcProblem:
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
                  plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,
-                 fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None):
+                 fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None, meas_age=None, meas_renorm=False):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -168,7 +168,11 @@ class MpcProblem:
         permutation without the sign), meas_valid int[Ns] (0: a dropout, the last estimate is held; initially x itself), meas_rng uint32[2] the observation key
         (required with any of the three; the main key `rng` is never disturbed). Any of the three makes the call the timed one and appends TWO values behind the
         five: xmeas f32[Ns][13], what each solve started from, flipped into the frame of x row by row like xs[1:], and the observation key after the last solve
-        (xmeas[-1] is the held measurement that continues the run). xsub, when requested, stays the LAST value."""
+        (xmeas[-1] is the held measurement that continues the run). xsub, when requested, stays the LAST value.
+        meas_age / meas_renorm (SPEC.md §11g; each needs one of the three above): meas_age, an int or int[Ns], is the age of the estimate in PLANT SUBSTEPS — a
+        valid solve measures the state that many substeps back (before the run the vehicle sat at x; at most min(solve_period, T) * plant_substeps) —, and
+        meas_renorm=True scales the measured attitude to unit length. Ages have no frame. With a largest age A > 0 the last A substep states before the run's end,
+        f32[A][13], oldest first, follow the observation key, flipped into the frame of x row by row like xs[1:]; xsub stays the LAST value."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -232,6 +236,17 @@ class MpcProblem:
             more["meas_keys"] = np.asarray(meas_rng, dtype=np.uint32).reshape(1, 2)
         elif meas_rng is not None:
             raise ValueError("MpcProblem.simulate: meas_rng needs one of meas_noise / meas_bias / meas_valid")
+        if (meas_age is not None or meas_renorm) and not observed:
+            raise ValueError("MpcProblem.simulate: meas_age / meas_renorm need one of meas_noise / meas_bias / meas_valid")
+        hist = False
+        if meas_age is not None:
+            a = np.asarray(meas_age)
+            if a.dtype.kind not in "iu" or a.shape not in ((), (Ns,)):
+                raise ValueError(f"MpcProblem.simulate: meas_age must be an int or int[{Ns}] (plant substeps), got {a.dtype}{a.shape}")
+            more["meas_age"] = a.reshape(1, 1) if a.ndim == 0 else a[:, None]
+            hist = int(a.max()) > 0
+        if meas_renorm:
+            more["meas_renorm"] = True
         out = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
             plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag,
@@ -245,8 +260,13 @@ class MpcProblem:
                       np.float32(i[5]), np.float32(i[6]), np.float32(i[7]))
         ret = (_arr(xs), _arr(us[0]), _arr(info[0]), st, k_next[0].copy())
         if observed:
-            xmeas, q_next = out[-4 if substep_states else -3][0], out[-3 if substep_states else -2][0]
+            o = out[:-1] if substep_states else out
+            if hist:
+                o, xhist = o[:-1], o[-1][0]
+            xmeas, q_next = o[-3][0], o[-2][0]
             ret += (_arr(enu2ned(xmeas, np) if self.convert_to_enu else xmeas), q_next.copy())
+            if hist:
+                ret += (_arr(enu2ned(xhist, np) if self.convert_to_enu else xhist),)
         if substep_states:
             xsub = out[-1][0]
             ret += (_arr(enu2ned(xsub, np) if self.convert_to_enu else xsub),)

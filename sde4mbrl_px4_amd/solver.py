@@ -93,6 +93,29 @@ def fault_schedule(T, B, m):
     return f
 
 
+def gauss_markov_bias(Ns, B, std, tau, solve_dt, rng, state=None):
+    """COLOURED estimator noise for closed_loop(meas_bias=...) (SPEC.md §11g): beta f32[Ns][B][12], a first-order Gauss-Markov process per component and episode,
+    sampled once per solve. With rho = exp(-solve_dt / tau) (solve_dt the time between two solves, tau the correlation time, both in seconds):
+        b_j = rho * b_{j-1} + std * sqrt(1 - rho^2) * w_j,   w_j standard normal from `rng` (a numpy Generator),
+    so that every b_j has deviation std (the stationary one) and consecutive rows correlate with rho. std and tau are scalars or broadcast against [B][12] (order p, v,
+    theta, omega, as meas_bias). `state` f64[B][12] is b_{-1} (the second value a previous call returned, to continue a run); None draws it from the stationary
+    distribution. Computed in float64 and cast once. Returns (beta, state): the rows and the last b in float64. This is the answer to "coloured noise": the device
+    loop needs no keyword for it, since meas_bias rows carry any error sequence the caller draws; add white noise on top with meas_noise."""
+    Ns, B = int(Ns), int(B)
+    std = np.broadcast_to(np.asarray(std, np.float64), (B, 12))
+    tau = np.broadcast_to(np.asarray(tau, np.float64), (B, 12))
+    if Ns < 1 or B < 1 or not (np.isfinite(std).all() and (std >= 0).all()) or not (tau > 0).all() or not float(solve_dt) > 0:
+        raise ValueError("gauss_markov_bias: Ns, B >= 1, std finite and >= 0, tau > 0 and solve_dt > 0 are required")
+    rho = np.exp(-float(solve_dt) / tau)
+    scale = std * np.sqrt(1.0 - rho * rho)
+    b = std * rng.standard_normal((B, 12)) if state is None else np.array(state, np.float64).reshape(B, 12)
+    out = np.empty((Ns, B, 12), np.float64)
+    for j in range(Ns):
+        b = rho * b + scale * rng.standard_normal((B, 12))
+        out[j] = b
+    return out.astype(np.float32), b
+
+
 class SdeMpcSolver:
     """One solver handle = one (MPC config, model). Single-threaded, like the reference's solver
     objects (one blocking call at a time, sde_control.py:420)."""
@@ -218,7 +241,7 @@ class SdeMpcSolver:
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
                     rate_loop=None, rate_integ_in=None, rate_tail_in=None, fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None,
-                    meas_keys=None, xmeas_in=None):
+                    meas_keys=None, xmeas_in=None, meas_age=None, meas_age_max=None, meas_renorm=False, xhist_in=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -279,7 +302,18 @@ class SdeMpcSolver:
         above still applies), and xmeas [B][Ns][13] (what each solve started from), meas_keys_next uint32[B][2] and xmeas_next [B][13] are appended to the returned
         tuple; xsub, when requested, stays the LAST value. Carrying the last two back in with the items above continues the episodes bit for bit when T is a multiple
         of solve_period. meas_keys or xmeas_in without one of the first three, or one of them without meas_keys, raise ValueError; with none of the five given
-        nothing of this paragraph is touched."""
+        nothing of this paragraph is touched.
+
+        meas_age / meas_age_max / meas_renorm / xhist_in (SPEC.md §11g, sdempc_closed_loop_batch_aged): INPUT-side latency and a unit attitude. meas_age is the age of
+        the estimate in PLANT SUBSTEPS: an int, int[Ns] (per solve) or int[Na][Ba] with Na in {1, Ns} and Ba in {1, B}. A valid solve with age A forms its measurement
+        from the plant state A substeps before the solve, not from the current one (solve_delay is the other half: the solution arriving late). The loop keeps the last
+        meas_age_max substep states (default: the largest entry; at most min(solve_period, T) * plant_substeps, one period of memory); before the run they are
+        xhist_in [B][age_max][13], oldest first (None: the vehicle sat at x0). meas_renorm=True scales the attitude of the measurement to unit length (software
+        rsqrt). A dropout does neither. Each of the four needs the observation keywords above (ValueError otherwise). With age_max > 0, xhist_next
+        [B][age_max][13] (the last age_max substep states before the run's end) is appended after xmeas_next; xsub stays the LAST value; carried back in as xhist_in
+        with the other continuation values it continues the episodes bit for bit when T is a multiple of solve_period. Every age 0 without meas_renorm reproduces
+        the paragraph above bit for bit. Coloured estimator noise needs no keyword: gauss_markov_bias draws meas_bias rows of a first-order Gauss-Markov process.
+        With none of the four given nothing of this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -360,6 +394,30 @@ class SdeMpcSolver:
                 obs_sigma, obs_beta = np.ascontiguousarray(np.broadcast_to(obs_sigma, shape)), np.ascontiguousarray(np.broadcast_to(obs_beta, shape))
             if xmeas_in is not None:
                 xmeas_in = _f32(xmeas_in, (B, 13))
+        aged = meas_age is not None or meas_age_max is not None or bool(meas_renorm) or xhist_in is not None
+        if aged and not observed:
+            raise ValueError("closed_loop: meas_age / meas_age_max / meas_renorm / xhist_in need one of meas_noise / meas_bias / meas_valid (and meas_keys)")
+        age_rows, age_max = None, 0
+        if aged:
+            if meas_age is not None:
+                a = np.asarray(meas_age)
+                if a.dtype.kind not in "iu":
+                    raise ValueError("closed_loop: meas_age must hold integers (plant substeps)")
+                age_rows = rows(a.astype(np.int64).reshape(1, 1) if a.ndim == 0 else a.astype(np.int64), "meas_age", (), np.int64)
+                if age_rows.min() < 0:
+                    raise ValueError("closed_loop: meas_age holds a negative entry")
+            age_max = int(meas_age_max) if meas_age_max is not None else (0 if age_rows is None else int(age_rows.max()))
+            lim = min(max(int(solve_period), 1), max(T, 1)) * int(plant_substeps)
+            if age_max < 0 or age_max > lim:
+                raise ValueError(f"closed_loop: meas_age_max must be between 0 and min(solve_period, T) * plant_substeps = {lim} (one period of memory), got {age_max}")
+            if age_rows is not None:
+                if age_rows.max() > age_max:
+                    raise ValueError(f"closed_loop: meas_age holds an entry above meas_age_max = {age_max}")
+                age_rows = np.ascontiguousarray(age_rows, dtype=np.int32)
+            if xhist_in is not None:
+                if age_max == 0:
+                    raise ValueError("closed_loop: xhist_in needs meas_age_max > 0")
+                xhist_in = _f32(xhist_in, (B, age_max, 13))
         faulted = flt is not None or bool(substep_states) or observed
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
             raise ValueError("closed_loop: rate_integ_in / rate_tail_in need rate_loop=...")
@@ -466,10 +524,20 @@ class SdeMpcSolver:
                 xm_next = np.zeros((B, 13), np.float32)
                 lead = [C.byref(oc), meas_keys.ctypes.data_as(u32p), None if xmeas_in is None else _fp(xmeas_in)] + lead
                 more, ret = more + (_fp(xmeas), q_next.ctypes.data_as(u32p), _fp(xm_next)), ret + (xmeas, q_next, xm_next)
+            if aged:                # the observed entry point's arguments behind (age cfg, xhist_in), then xhist_next
+                ac = _abi.SdempcAgeCfg(C.sizeof(_abi.SdempcAgeCfg), None if age_rows is None else age_rows.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       1 if age_rows is None else age_rows.shape[0], 1 if age_rows is None else age_rows.shape[1], age_max, int(bool(meas_renorm)))
+                xh_next = np.zeros((B, age_max, 13), np.float32) if age_max > 0 else None
+                lead = [C.byref(ac), None if xhist_in is None else _fp(xhist_in)] + lead
+                more = more + (None if xh_next is None else _fp(xh_next),)
+                if xh_next is not None:
+                    ret = ret + (xh_next,)
             if substep_states:
                 ret = ret + (xsub,)
         # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
-        if observed:
+        if aged:
+            entry = _abi.aged_entry(self.lib)
+        elif observed:
             entry = _abi.observed_entry(self.lib)
         elif faulted:
             entry = _abi.fault_entry(self.lib)

@@ -25,9 +25,12 @@
      Applies to --small-batch and to the C2 loop; either one makes the call the timed one.
   8. --observe: the same loops on a measured state (SPEC.md §11f, sdempc_closed_loop_batch_observed) — a noise and a bias row per solve and episode, and every
      episode's estimator dropping one solve in four. Applies to --small-batch and to the C2 loop; it makes the call the timed one.
+  9. --age A [--renorm]: with --observe, the estimate of every valid solve is up to A plant substeps old (SPEC.md §11g, sdempc_closed_loop_batch_aged) — an age per
+     solve and episode drawn from 0 .. A, a history of A rows — and --renorm scales its attitude to unit length. A <= min(period, T) * substeps. With A > 0 the run
+     takes the §11e kernels with a substep region in the chunk.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
-                                        [--fault] [--substep-states] [--observe]
+                                        [--fault] [--substep-states] [--observe] [--age A] [--renorm]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -64,7 +67,11 @@ ap.add_argument("--rate-loop", action="store_true", help="fly the thrust and bod
 ap.add_argument("--fault", action="store_true", help="a per-motor fault row per tick and episode (SPEC.md §11e)")
 ap.add_argument("--substep-states", action="store_true", help="copy the state after every plant substep back (SPEC.md §11e)")
 ap.add_argument("--observe", action="store_true", help="solve from a measured state: noise, bias and dropouts per solve and episode (SPEC.md §11f)")
+ap.add_argument("--age", type=int, default=-1, metavar="A", help="with --observe: estimates up to A plant substeps old, an age per solve and episode (SPEC.md §11g)")
+ap.add_argument("--renorm", action="store_true", help="with --observe: renormalise the measured attitude (SPEC.md §11g)")
 a = ap.parse_args()
+if (a.age >= 0 or a.renorm) and not a.observe:
+    ap.error("--age / --renorm need --observe")
 model = synthetic_iris()
 if a.plant == "own" and a.substeps != 1:
     ap.error("--substeps needs --plant one or per-episode")
@@ -105,6 +112,11 @@ def scenario_kw(kw, B, T):
         kw["meas_bias"] = (scale * rng.uniform(-0.5, 0.5, (Ns, B, 12))).astype(np.float32)
         kw["meas_valid"] = (rng.integers(0, 4, (Ns, B)) != 0).astype(np.int32)
         kw["meas_keys"] = np.stack([prng.PRNGKey(9000 + b) for b in range(B)])
+        if a.age >= 0:
+            kw["meas_age"] = rng.integers(0, a.age + 1, (Ns, B)).astype(np.int32)
+            kw["meas_age_max"] = a.age
+        if a.renorm:
+            kw["meas_renorm"] = True
     if a.disturbance:
         kw["disturbance"] = np.random.default_rng(2).uniform(-2.0, 2.0, (T, B, 6)).astype(np.float32)
     if a.plant_switch >= 0:
@@ -140,6 +152,10 @@ if a.substep_states:
     tag += " substep-states"
 if a.observe:
     tag += " observe"
+if a.age >= 0:
+    tag += f" age<={a.age}"
+if a.renorm:
+    tag += " renorm"
 
 if a.small_batch:
     cfg = load_mpc_config(os.path.join(ROOT, "configs", "c1_iris_posctrl_h20_p32.yaml"))
