@@ -592,6 +592,66 @@ int sdempc_closed_loop_batch_aged(sdempc_handle* h, const sdempc_age_cfg* age_cf
                                   float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
                                   float* xhist_next /*[B][age_max][13] or NULL*/);
 
+/* ---- batched closed loop scored on the device, per-row outputs optional (SPEC.md §11h) -------------------
+ * sdempc_closed_loop_batch_aged plus the evaluator: per episode a score row of 16 32-bit words, formed on the device from the rows the loop already holds, so that a
+ * campaign's questions (did the episode leave a radius, tip over, spin up, go non-finite — and when; how far off was it; how hard did the solver work) cost B * 64 bytes
+ * of output whatever T is. With `score` NULL the call IS sdempc_closed_loop_batch_aged bit for bit, with the same launches; score_in and score_out must then be NULL and
+ * no per-row output may be. With `score` given each of xs, us, info, ws, xsub and xmeas may be NULL: a NULL output is neither copied to the host nor scattered; every
+ * other output, and every value of those that are given, is what the call without a score gives. The continuation outputs keep their meaning.
+ * Scored rows, in time order: with substeps = 0 the tick states x_{k+1} (xs[b][k + 1]), k = 0 .. T-1; with substeps = 1 the plant's substep states (xsub[b][.], n per
+ * tick; the xsub region then exists in the chunk, and counts in its bytes, whether or not xsub is asked for). Each row x of tick k is compared with the target
+ * g = score_ref[k or 0][b or 0] (13 floats in the solver's frame; position and velocity are read), in float32, every fma explicit:
+ *   e_i = x_i - g_i (i < 3); dp = fma(e2, e2, fma(e1, e1, e0 e0)); dv likewise on indices 3..5
+ *   c  = fma(-2, qx qx + qy qy, 1)     (qx = x[7], qy = x[8]: the cosine of the tilt, SPEC.md §5.2);   w2 = fma(w2, w2, fma(w1, w1, w0 w0)) on x[10..12]
+ *   nf = some component of x fails |x_i| < inf
+ *   cause = 1 if !(dp <= r2_pos) | 2 if !(c >= cos_min) | 4 if !(w2 <= w2_max) | 8 if nf          (a NaN fails every comparison)
+ * The thresholds arrive squared / as a cosine (no device sqrt or acos); +inf, -inf, +inf switch a criterion off. The words of episode b:
+ *    0 u32 rows scored so far (its value before the increment is the row's index r)      8 u32 r of the first row with a non-zero cause; 0xffffffff: none
+ *    1 f32 sum of dp, plain adds in row order                                             9 u32 OR of all causes
+ *    2 f32 max dp (dp > max replaces it; initially 0)                                    10 u32 rows with a non-zero cause
+ *    3 u32 r of that maximum (first occurrence)                                          11 u32 per tick, from us: motors with u_j <= u_lo_j or u_j >= u_hi_j
+ *    4 f32 dp of the last row                                                            12 f32 per tick: a = 0; a = fma(d_j, d_j, a), d_j = u_j - uref_j, j ascending; sum + a
+ *    5 f32 sum of dv                                                                     13 u32 per solve, from info: sum of (u32)num_steps
+ *    6 f32 min c (c < min replaces it; initially +inf)                                   14 u32 per solve: sum of (u32)num_ls_trials
+ *    7 f32 max w2 (initially 0)                                                          15 u32 per solve: solves with !(opt_cost < init_cost)
+ * ((u32)v is v itself where 0 <= v < 2^32 and 0 otherwise, a NaN included.) score_in NULL starts from the initial row (zeros, word 6 = +inf, word 8 = 0xffffffff); carrying
+ * score_out back in as score_in with the other continuation values continues the score word for word when T is a multiple of solve_period. The score does not depend on B,
+ * on chunking, on the layout of the solves or on which outputs were requested. score_ref is [ref_ticks][ref_batch][13], ref_ticks 1 or T, ref_batch 1 or B, tick-major, an
+ * index into a size-1 axis is 0. Every argument is checked before the first HIP call: SDEMPC_EINVAL for struct_size, substeps outside 0 / 1, ref_ticks not 1 or T, ref_batch
+ * not 1 or B, score_ref or score_out NULL, a NaN threshold, score_in or score_out without `score`, a NULL xs / us / info (ws with a rate cfg) without `score`, and for everything
+ * sdempc_closed_loop_batch_aged refuses. No ABI version change: detect the entry point by its symbol. */
+#define SDEMPC_SCORE_WORDS 16
+typedef struct sdempc_score_cfg {
+    int32_t struct_size;     /* sizeof(sdempc_score_cfg) */
+    int32_t substeps;        /* 0: the tick states are scored; 1: the plant's substep states */
+    float r2_pos;            /* squared position radius [m^2]; +inf: off */
+    float cos_min;           /* cosine of the largest tilt; -inf: off */
+    float w2_max;            /* squared body-rate limit [rad^2/s^2]; +inf: off */
+    const float* score_ref;  /* [ref_ticks][ref_batch][13] the target of each tick */
+    int32_t ref_ticks;       /* 1 or T */
+    int32_t ref_batch;       /* 1 or B */
+} sdempc_score_cfg;
+int sdempc_closed_loop_batch_scored(sdempc_handle* h, const sdempc_score_cfg* score /*or NULL*/, const uint32_t* score_in /*[B][16] or NULL*/,
+                                    const sdempc_age_cfg* age_cfg /*or NULL*/, const float* xhist_in /*[B][age_max][13] or NULL*/,
+                                    const sdempc_obs_cfg* obs /*or NULL*/, const uint32_t* obs_keys /*[B][2]; NULL without obs*/, const float* xmeas_in /*[B][13] or NULL*/,
+                                    const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*or NULL*/,
+                                    const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                    const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                    const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                    const float* xref, int32_t xref_solves, int32_t xref_batch,
+                                    const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                    const float* u_act_in /*[B][m] or NULL*/,
+                                    float* xs /*[B][T+1][13]; may be NULL with score*/, float* us /*[B][T][m]; may be NULL with score*/,
+                                    sdempc_info* info /*[B][Ns]; may be NULL with score*/,
+                                    float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                    uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                    const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                    float* ws /*[B][T][4]; NULL without rate; may be NULL with score*/, float* rate_integ_next /*[B][3] or NULL*/,
+                                    float* rate_tail_next /*[B][H][3] or NULL*/,
+                                    float* xsub /*[B][T * substeps][13] or NULL*/,
+                                    float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
+                                    float* xhist_next /*[B][age_max][13] or NULL*/, uint32_t* score_out /*[B][16]; NULL without score*/);
+
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so
  * repeating the call runs in the one-workgroup-per-instance layout. Also SDEMPC_EDEVICE when a large throughput launch that hands its

@@ -96,6 +96,18 @@ class SdempcAgeCfg(C.Structure):
                 ("renormalise", C.c_int32)]
 
 
+class SdempcScoreCfg(C.Structure):
+    """sdempc_score_cfg (SPEC.md §11h): which rows are scored, the three thresholds and the target rows of sdempc_closed_loop_batch_scored."""
+    _fields_ = [("struct_size", C.c_int32), ("substeps", C.c_int32), ("r2_pos", C.c_float), ("cos_min", C.c_float), ("w2_max", C.c_float),
+                ("score_ref", C.POINTER(C.c_float)), ("ref_ticks", C.c_int32), ("ref_batch", C.c_int32)]
+
+
+SCORE_WORDS = 16         # include/sdempc.h: SDEMPC_SCORE_WORDS
+# the score row of an episode as a structured array: the word table of SPEC.md §11h, in order
+SCORE_FIELDS = [("rows", "<u4"), ("sum_dp", "<f4"), ("max_dp", "<f4"), ("max_dp_row", "<u4"), ("last_dp", "<f4"), ("sum_dv", "<f4"), ("min_cos_tilt", "<f4"),
+                ("max_w2", "<f4"), ("first_fail_row", "<u4"), ("causes", "<u4"), ("fail_rows", "<u4"), ("saturated", "<u4"), ("sum_du2", "<f4"),
+                ("sum_steps", "<u4"), ("sum_ls_trials", "<u4"), ("no_decrease", "<u4")]
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -278,6 +290,21 @@ def aged_entry(lib):
     return fn
 
 
+def scored_entry(lib):
+    """sdempc_closed_loop_batch_scored (SPEC.md §11h) with its prototype set: a score cfg (may be NULL) and score_in in front of the aged entry point's arguments,
+    then score_out. Detected by symbol and only when a call needs it, as aged_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_scored
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_scored (SPEC.md §11h): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(aged_entry(lib).argtypes)
+        u32p = C.POINTER(C.c_uint32)
+        fn.argtypes = [a[0], C.POINTER(SdempcScoreCfg), u32p] + a[1:] + [u32p]
+        fn.restype = C.c_int
+    return fn
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -286,5 +313,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
     "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed", "sdempc_closed_loop_batch_scenario",
     "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault", "sdempc_closed_loop_batch_observed",
-    "sdempc_closed_loop_batch_aged",
+    "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored",
 ]

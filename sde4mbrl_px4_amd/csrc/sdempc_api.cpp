@@ -184,6 +184,8 @@ struct sdempc_handle {
     // closed loop from an aged estimate (sdempc_closed_loop_batch_aged, allocated on its first use and grown with age_max): the last age_max substep states
     // f32[age_max][B][13], oldest first
     DevBuf d_hist;
+    // closed loop scored on the device (sdempc_closed_loop_batch_scored with a score cfg, allocated on its first use): the score words u32[max_batch][16]
+    DevBuf d_score;
     DevBuf d_work;            // u64[4] work counters (KArgs::work)
     // cooperative latency path of the solve (allocated on its first use, sized for coop_cap instances)
     DevBuf d_coop_bar, d_coop_pp, d_coop_ck;
@@ -572,6 +574,13 @@ struct ObsRun {
     const float* xhist_in;      // [B][age_max][13] or null (every row x0)
     float* xhist_next;          // [B][age_max][13] or null
 };
+// SPEC.md §11h: the scoring of one sdempc_closed_loop_batch_scored call (host pointers; the target rows are staged per chunk by closed_loop_run when they move).
+// Given only when the call has a score cfg: without one the call is the aged call, launch for launch. With it the per-row outputs of the call may be NULL.
+struct ScoreRun {
+    const sdempc_score_cfg* cfg;
+    const uint32_t* score_in;   // [B][16] or null (the initial row)
+    uint32_t* score_out;        // [B][16]
+};
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
 // One closed-loop call as its entry point describes it. The five entry points are five nested layers (SPEC.md §11, §11a .. §11d): each takes everything the one
 // below it takes, so `layer` says which parts are present; the arguments of an absent part stay null.
@@ -604,14 +613,18 @@ struct LoopCall {
     const sdempc_age_cfg* ac;                   // or NULL: no age (the two pointers must then be NULL)
     const float* xhist_in;
     float* xhist_next;
+    bool scored;                                // sdempc_closed_loop_batch_scored (SPEC.md §11h): the aged call with zc and the two score pointers
+    const sdempc_score_cfg* zc;                 // or NULL: no score (the two pointers must then be NULL, and no per-row output may be)
+    const uint32_t* score_in;
+    uint32_t* score_out;
 };
 int closed_loop_call(sdempc_handle* h, const LoopCall& c);
-int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves);
+int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves, bool rows_optional = false);
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr,
-                         const ObsRun* obs = nullptr);
+                         const ObsRun* obs = nullptr, const ScoreRun* score = nullptr);
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    bool* again);
+                    const ScoreRun* score, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -704,7 +717,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1193,6 +1206,30 @@ int sdempc_closed_loop_batch_aged(sdempc_handle* h, const sdempc_age_cfg* ac, co
     });
 }
 
+int sdempc_closed_loop_batch_scored(sdempc_handle* h, const sdempc_score_cfg* zc, const uint32_t* score_in, const sdempc_age_cfg* ac, const float* xhist_in,
+                                    const sdempc_obs_cfg* oc, const uint32_t* obs_keys, const float* xmeas_in, const sdempc_fault_cfg* fc, const sdempc_rate_cfg* rc_,
+                                    const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc, const void* const* plant_blobs,
+                                    const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T, const float* x0, const float* xref, int32_t xref_solves,
+                                    int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in, const float* u_act_in, float* xs, float* us,
+                                    sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next, float* u_act_next, const float* rate_integ_in,
+                                    const float* rate_tail_in, float* ws, float* rate_integ_next, float* rate_tail_next, float* xsub, float* xmeas, uint32_t* obs_keys_next,
+                                    float* xmeas_next, float* xhist_next, uint32_t* score_out) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    c.observed = true; c.oc = oc; c.obs_keys = obs_keys; c.xmeas_in = xmeas_in; c.xmeas = xmeas; c.obs_keys_next = obs_keys_next; c.xmeas_next = xmeas_next;
+    c.aged = true; c.ac = ac; c.xhist_in = xhist_in; c.xhist_next = xhist_next;
+    c.scored = true; c.zc = zc; c.score_in = score_in; c.score_out = score_out;
+    return closed_loop_call(h, c);
+    });
+}
+
 int sdempc_solve_status(sdempc_handle* h) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1245,8 +1282,8 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
 }
-// The one path behind the eight closed-loop entry points: every check of the call's parts, in one fixed order (age struct, observation struct, fault struct, rate, scenario struct,
-// timing, loop arguments, plant_ticks, plant set, solve_delay, disturbance, fault schedule, observation rows, age rows; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
+// The one path behind the nine closed-loop entry points: every check of the call's parts, in one fixed order (score struct, age struct, observation struct, fault struct, rate, scenario struct,
+// timing, loop arguments, plant_ticks, plant set, solve_delay, disturbance, fault schedule, observation rows, age rows, score target rows; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
 int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     if (!h) return SDEMPC_EINVAL;
     const LoopIo& io = c.io;
@@ -1257,6 +1294,17 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    const sdempc_score_cfg* zc = c.scored ? c.zc : nullptr;
+    if (c.scored) {
+        if (!zc && (c.score_in || c.score_out)) return fail(h, SDEMPC_EINVAL, "score: score_in / score_out must be NULL without a score cfg%s");
+        if (zc) {
+            if (zc->struct_size != (int32_t)sizeof(sdempc_score_cfg)) return fail(h, SDEMPC_EINVAL, "score: struct_size mismatch%s");
+            if (zc->substeps != 0 && zc->substeps != 1) return fail(h, SDEMPC_EINVAL, "score: substeps must be 0 (tick states) or 1 (plant substep states)%s");
+            if (zc->r2_pos != zc->r2_pos || zc->cos_min != zc->cos_min || zc->w2_max != zc->w2_max) return fail(h, SDEMPC_EINVAL, "score: a threshold is NaN%s");
+            if (!zc->score_ref) return fail(h, SDEMPC_EINVAL, "score: score_ref is NULL%s");
+            if (!c.score_out) return fail(h, SDEMPC_EINVAL, "score: score_out is NULL%s");
+        }
+    }
     if (c.aged) {
         if (c.ac && c.ac->struct_size != (int32_t)sizeof(sdempc_age_cfg)) return fail(h, SDEMPC_EINVAL, "age: struct_size mismatch%s");
         if (c.ac && !c.oc) return fail(h, SDEMPC_EINVAL, "age: an age cfg needs an obs cfg%s");
@@ -1285,7 +1333,7 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
                 if (!finite(rc_->mixer[l][a])) return fail(h, SDEMPC_EINVAL, "rate: mixer holds a non-finite entry%s");
         if (!(rc_->motor_weight >= 0.0f) || !(rc_->motor_weight <= 1.0f)) return fail(h, SDEMPC_EINVAL, "rate: motor_weight must be in [0, 1]%s");
         if (rc_->inv_m != 0.0f && !(rc_->inv_m == inv_m)) return fail(h, SDEMPC_EINVAL, "rate: inv_m must be 0 or (float)1 / (float)num_motors%s");
-        if (!c.ws) return fail(h, SDEMPC_EINVAL, "rate: ws is NULL%s");
+        if (!c.ws && !zc) return fail(h, SDEMPC_EINVAL, "rate: ws is NULL%s");
         if (sc && sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg)) return fail(h, SDEMPC_EINVAL, "scenario: struct_size mismatch%s");
     } else if (scenario) {
         if ((!sc && !c.faulted) || (sc && sc->struct_size != (int32_t)sizeof(sdempc_scenario_cfg))) return fail(h, SDEMPC_EINVAL, "scenario: cfg NULL or struct_size mismatch%s");
@@ -1295,7 +1343,7 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
         if (tc->solve_period < 1) return fail(h, SDEMPC_EINVAL, "timing: solve_period must be >= 1%s");
         if (!(tc->lag_alpha >= 0.0f) || !(tc->lag_alpha <= 1.0f)) return fail(h, SDEMPC_EINVAL, "timing: lag_alpha must be 0 (off) or in (0, 1]%s");
     }
-    int rc = check_loop_args(h, io, !timed ? T : (T >= 1 ? loop_solves(T, tc->solve_period) : 1));
+    int rc = check_loop_args(h, io, !timed ? T : (T >= 1 ? loop_solves(T, tc->solve_period) : 1), zc != nullptr);
     if (rc) return rc;
     const int Tp = scenario && sc ? sc->plant_ticks : 1;           // rows of plant_of
     if (Tp != 1 && Tp != T) return fail(h, SDEMPC_EINVAL, "scenario: plant_ticks must be 1 or T%s");
@@ -1354,6 +1402,10 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
         if (ac->renormalise != 0 && ac->renormalise != 1) return fail(h, SDEMPC_EINVAL, "age: renormalise must be 0 or 1%s");
         if (ac->age_max == 0 && (c.xhist_in || c.xhist_next)) return fail(h, SDEMPC_EINVAL, "age: xhist_in / xhist_next must be NULL with age_max 0%s");
     }
+    if (zc) {
+        if (zc->ref_ticks != 1 && zc->ref_ticks != T) return fail(h, SDEMPC_EINVAL, "score: ref_ticks must be 1 or T%s");
+        if (zc->ref_batch != 1 && zc->ref_batch != B) return fail(h, SDEMPC_EINVAL, "score: ref_batch must be 1 or B%s");
+    }
     if ((rc = ensure_device(h))) return rc;
     if (c.layer == LOOP_PLAIN) return closed_loop_attempts(h, io, nullptr, nullptr, nullptr, nullptr);
     const TimedRun run_t{timed ? tc->solve_period : 1, timed ? tc->solve_delay : 0, timed ? tc->lag_alpha : 0.0f, c.u_act_in, c.u_act_next};
@@ -1368,18 +1420,20 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     PlantRun run;
     // (a schedule is staged per chunk by the loop, where stage_plants takes the set itself; the noise of a whole solve period sits beside the set)
     if ((rc = stage_plants(h, *c.pc, c.plant_blobs, scenario ? nullptr : c.plant_of, B, &run, !timed ? 1 : (tc->solve_period < T ? tc->solve_period : T)))) return rc;
+    const ScoreRun run_z{zc, c.score_in, c.score_out};
     return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr, run_f.fault || run_f.xsub ? &run_f : nullptr,
-                                oc ? &run_o : nullptr);
+                                oc ? &run_o : nullptr, zc ? &run_z : nullptr);
 }
 // argument checks every closed-loop entry point shares; no HIP call
-int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves) {
+// rows_optional (SPEC.md §11h, a call with a score cfg): xs / us / info may be NULL
+int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves, bool rows_optional) {
     int rc = check_batch(h, io.B);
     if (rc) return rc;
     if (io.T < 1) return fail(h, SDEMPC_EINVAL, "closed loop: T must be >= 1%s");
     if (io.xref_ticks != 1 && io.xref_ticks != solves)
         return fail(h, SDEMPC_EINVAL, solves == io.T ? "closed loop: xref_ticks must be 1 or T%s" : "closed loop: xref_solves must be 1 or ceil(T / solve_period)%s");
     if (io.xref_batch != 1 && io.xref_batch != io.B) return fail(h, SDEMPC_EINVAL, "closed loop: xref_batch must be 1 or B%s");
-    if (!io.x0 || !io.xref || !io.keys || !io.xs || !io.us || !io.info) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    if (!io.x0 || !io.xref || !io.keys || (!rows_optional && (!io.xs || !io.us || !io.info))) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
     return 0;
 }
 // every check of a plant set (SPEC.md §11a), shared by the four entry points that take one; no HIP call
@@ -1407,10 +1461,10 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt,
-                         const ObsRun* obs) {
+                         const ObsRun* obs, const ScoreRun* score) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -1490,15 +1544,20 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // caller asked for xsub (copied back only if they did): after each plant launch the history is refilled, by device-to-device copies on the stream, from the period's
 // substep rows — and, where it reaches back that far, from the plant state before the launch and from its own newer rows (a partial last period). So it carries over
 // period and chunk boundaries in d_hist alone. The age rows sit behind the valid rows, staged like them.
+// SPEC.md §11h (score, with timed and plant): the score words live in d_score (staged from score_in, or as the initial row, with the other inputs, so that a re-run starts
+// from them again). At the end of every chunk ONE launch of the period's key-schedule kernel in its scoring form walks the chunk's rows — xs, or xsub with substeps = 1,
+// which then exists in the chunk as with age_max > 0 — and its us and info rows. The target rows sit behind the age rows, staged per chunk when they move (one per TICK) and
+// once otherwise. A per-row output the caller passed as NULL is neither copied back nor scattered.
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    bool* again) {
+                    const ScoreRun* score, bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
     const int Ns = loop_solves(T, S);
     const bool seen = obs && timed;
     const int AM = seen ? obs->age_max : 0;                                 // rows of the history (SPEC.md §11g)
-    const bool faulty = flt && flt->fault, subs_out = flt && flt->xsub, subs = subs_out || AM > 0;      // (the history is fed from the chunk's substep rows)
+    const bool scoring = score && timed && plant, score_sub = scoring && score->cfg->substeps == 1;
+    const bool faulty = flt && flt->fault, subs_out = flt && flt->xsub, subs = subs_out || AM > 0 || score_sub;      // (the history is fed from the chunk's substep rows, and so is a substep score)
     const int nsub = plant ? plant->Q.substeps : 1;
     const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m + (rate ? 4 : 0) + (subs ? (size_t)nsub * NX : 0)) + 8 + (seen ? NX : 0);       // floats per reference window / per episode-period of output
     const bool xref_moves = io.xref_ticks > 1;
@@ -1513,9 +1572,11 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     const size_t ORS = (noisy ? OR : 0) + (biased ? OR : 0);
     const bool old = seen && obs->age, age_moves = old && obs->Ta > 1;
     const size_t AR = old ? (size_t)obs->Ba : 0;                                                       // words per solve row of age
+    const bool sref_moves = scoring && score->cfg->ref_ticks > 1;
+    const size_t ZR = scoring ? (size_t)score->cfg->ref_batch * NX : 0;                                // floats per tick row of the score targets (SPEC.md §11h)
     const size_t per_period = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0) +
-                              (fault_moves ? (size_t)S * FR : 0) + (obs_moves ? ORS : 0) + (valid_moves ? VR : 0) + (age_moves ? AR : 0);
-    const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR) + (fault_moves ? 0 : FR) + (obs_moves ? 0 : ORS) + (valid_moves ? 0 : VR) + (age_moves ? 0 : AR);
+                              (fault_moves ? (size_t)S * FR : 0) + (obs_moves ? ORS : 0) + (valid_moves ? VR : 0) + (age_moves ? AR : 0) + (sref_moves ? (size_t)S * ZR : 0);
+    const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR) + (fault_moves ? 0 : FR) + (obs_moves ? 0 : ORS) + (valid_moves ? 0 : VR) + (age_moves ? 0 : AR) + (sref_moves ? 0 : ZR);
     const size_t cap = (h->loop_chunk_bytes < 0 ? LOOP_CHUNK_BYTES : (size_t)h->loop_chunk_bytes) / sizeof(float);
     const size_t fit = cap > fixed ? (cap - fixed) / per_period : 0;
     const int Pc = (int)(fit < 1 ? 1 : (fit < (size_t)Ns ? fit : (size_t)Ns));      // periods per chunk
@@ -1537,6 +1598,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if ((rc = dev_alloc(h, h->d_hist, sizeof(float) * (size_t)AM * h->max_batch * NX, true))) return rc;
     }
     float* d_hist = AM > 0 ? (float*)h->d_hist.p : nullptr;          // [AM][B][13] (SPEC.md §11g)
+    if (scoring && !h->d_score.p && (rc = dev_alloc(h, h->d_score, sizeof(uint32_t) * 16 * (size_t)h->max_batch, true))) return rc;
+    uint32_t* d_score = scoring ? (uint32_t*)h->d_score.p : nullptr; // [B][16] (SPEC.md §11h)
     uint32_t* d_q = (uint32_t*)h->d_obs.p;                           // q [B][2] (SPEC.md §11f)
     float* d_xm = d_q ? (float*)(d_q + 2 * (size_t)h->max_batch) : nullptr;   // xm [B][13]
     float* d_integ = (float*)h->d_rate.p;                            // g [B][3] (SPEC.md §11d)
@@ -1561,10 +1624,12 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* c_beta = c_sigma + (noisy ? (obs_moves ? (size_t)Pc : 1) * OR : 0);        // [Pc or 1][Bo][12]
     int32_t* c_valid = (int32_t*)(c_beta + (biased ? (obs_moves ? (size_t)Pc : 1) * OR : 0));    // [Pc or 1][Bv]
     int32_t* c_age = c_valid + (gated ? (valid_moves ? (size_t)Pc : 1) * VR : 0);                // [Pc or 1][Ba] (SPEC.md §11g)
+    float* c_sref = (float*)(c_age + (old ? (age_moves ? (size_t)Pc : 1) * AR : 0));             // [Tc or 1][Br][13] (SPEC.md §11h)
     float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place (SPEC.md §11f: the plant's; the solve reads d_xm)
     hipStream_t st = h->stream;
     // inputs (host vectors live until the synchronisation at the end of the first chunk)
     std::vector<float> u0, s0, a0, hh;
+    std::vector<uint32_t> z0;
     const float* u_in = io.u_init;
     const float* s_in = io.stepsize_in;
     if (!u_in) {               // sdempc_reset: uref tiled
@@ -1611,6 +1676,20 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 memcpy(&hh[(size_t)i * HR + (size_t)b * NX], obs->xhist_in ? obs->xhist_in + ((size_t)b * AM + i) * NX : io.x0 + (size_t)b * NX, sizeof(float) * NX);
         HIPCHK(h, hipMemcpyAsync(d_hist, hh.data(), sizeof(float) * hh.size(), hipMemcpyHostToDevice, st));
     }
+    if (scoring) {             // the score words start as given, or as the initial row (SPEC.md §11h: counts 0, min c = +inf, first failing row all ones)
+        const uint32_t* z_in = score->score_in;
+        if (!z_in) {
+            const float pinf = INFINITY;
+            uint32_t row0[16] = {0};
+            memcpy(&row0[6], &pinf, sizeof pinf);
+            row0[8] = 0xffffffffu;
+            z0.resize((size_t)B * 16);
+            for (int b = 0; b < B; ++b) memcpy(&z0[(size_t)b * 16], row0, sizeof row0);
+            z_in = z0.data();
+        }
+        HIPCHK(h, hipMemcpyAsync(d_score, z_in, sizeof(uint32_t) * 16 * (size_t)B, hipMemcpyHostToDevice, st));
+        if (!sref_moves) HIPCHK(h, hipMemcpyAsync(c_sref, score->cfg->score_ref, sizeof(float) * ZR, hipMemcpyHostToDevice, st));
+    }
     if (!xref_moves) {
         HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
         if (Bx != B) HIPCHK(h, launch_broadcast_rows(c_xref, (float*)h->d_xref.p, (int)XR, B, st));
@@ -1627,7 +1706,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         }
         HIPCHK(h, hipMemcpyAsync(c_sched, row, sizeof(int32_t) * SR, hipMemcpyHostToDevice, st));
     }
-    for (int b = 0; b < B; ++b) memcpy(io.xs + (size_t)b * (T + 1) * NX, io.x0 + (size_t)b * NX, sizeof(float) * NX);
+    if (io.xs)
+        for (int b = 0; b < B; ++b) memcpy(io.xs + (size_t)b * (T + 1) * NX, io.x0 + (size_t)b * NX, sizeof(float) * NX);
     // the plant launch's arguments: built once, only pointers and `ticks` move from period to period
     LoopAdvance L;
     L.uopt = (const float*)h->d_uopt.p; L.xi = d_xi;
@@ -1638,6 +1718,15 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     LoopRate W{};
     LoopFault V{};
     LoopObserve O{};           // (q null: absent)
+    LoopScore Z{};             // (words null: absent; the period launches never take it)
+    if (scoring) {
+        const sdempc_score_cfg& zc = *score->cfg;
+        Z.words = d_score; Z.rows = score_sub ? c_xsub : c_xs; Z.us = c_us; Z.info = c_info; Z.ref = c_sref;
+        Z.ref_tick_stride = sref_moves ? (int)ZR : 0; Z.ref_ep_stride = zc.ref_batch > 1 ? NX : 0;
+        Z.rows_per_tick = score_sub ? nsub : 1; Z.m = m;
+        Z.r2_pos = zc.r2_pos; Z.cos_min = zc.cos_min; Z.w2_max = zc.w2_max;
+        for (int l = 0; l < 8; ++l) { Z.u_lo[l] = l < m ? h->cfg.u_lo[l] : 0.0f; Z.u_hi[l] = l < m ? h->cfg.u_hi[l] : 0.0f; Z.uref[l] = l < m ? h->cfg.uref[l] : 0.0f; }
+    }
     if (seen) {
         O.q = d_q; O.x = d_x; O.xm = d_xm; O.ep_stride = obs->Bo > 1 ? 12 : 0; O.valid_ep_stride = obs->Bv > 1 ? 1 : 0;
         O.renorm = obs->renorm ? 1 : 0;
@@ -1673,6 +1762,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if (obs_moves && biased) HIPCHK(h, hipMemcpyAsync(c_beta, obs->beta + (size_t)j0 * OR, sizeof(float) * np * OR, hipMemcpyHostToDevice, st));
         if (valid_moves) HIPCHK(h, hipMemcpyAsync(c_valid, obs->valid + (size_t)j0 * VR, sizeof(int32_t) * np * VR, hipMemcpyHostToDevice, st));
         if (age_moves) HIPCHK(h, hipMemcpyAsync(c_age, obs->age + (size_t)j0 * AR, sizeof(int32_t) * np * AR, hipMemcpyHostToDevice, st));
+        if (sref_moves) HIPCHK(h, hipMemcpyAsync(c_sref, score->cfg->score_ref + k0 * ZR, sizeof(float) * nk * ZR, hipMemcpyHostToDevice, st));
         for (int jc = 0; jc < np; ++jc) {
             const int ticks = nk - jc * S < S ? nk - jc * S : S;                    // (the last period of the run may be partial)
             if (seen) {
@@ -1705,7 +1795,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                     C.plant = sched ? c_sched + (sched_moves ? t0 * SR : 0) : nullptr;
                 }
                 if (rate) W.ws = c_ws + t0 * B * 4;
-                if (flt || AM > 0) {
+                if (flt || subs) {
                     V.fault = faulty ? c_fault + (fault_moves ? t0 * FR : 0) : nullptr;
                     V.xsub = subs ? c_xsub + t0 * nsub * B * NX : nullptr;
                 }
@@ -1721,19 +1811,31 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 HIPCHK(h, hipMemcpyAsync(d_hist + (size_t)(AM - d) * HR, d_x, sizeof(float) * HR, hipMemcpyDeviceToDevice, st));
             }
             HIPCHK(h, launch_loop(plant ? plant->k : h->base, L, plant ? &plant->Q : nullptr, timed ? &R : nullptr, scen ? &C : nullptr, rate ? &W : nullptr, st,
-                                  (flt || AM > 0) && timed && scen ? &V : nullptr));
+                                  (flt || subs) && timed && scen ? &V : nullptr));
             if (AM > 0) {
                 const int i0 = AM - d + 1 > 0 ? AM - d + 1 : 0;
                 if (i0 < AM) HIPCHK(h, hipMemcpyAsync(d_hist + (size_t)i0 * HR, V.xsub + (size_t)(d - AM + i0 - 1) * HR, sizeof(float) * (AM - i0) * HR, hipMemcpyDeviceToDevice, st));
             }
         }
-        hx.resize((size_t)nk * B * NX); hu.resize((size_t)nk * B * m); hi.resize((size_t)np * B * 8);
+        if (scoring) {             // SPEC.md §11h: the chunk's rows into the score words, one thread per episode
+            Z.ticks = nk; Z.solves = np;
+            HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, Z));
+        }
         unsigned gave_up = 0;
-        HIPCHK(h, hipMemcpyAsync(hx.data(), c_xs, sizeof(float) * hx.size(), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(hu.data(), c_us, sizeof(float) * hu.size(), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(hi.data(), c_info, sizeof(float) * hi.size(), hipMemcpyDeviceToHost, st));
+        if (io.xs) {
+            hx.resize((size_t)nk * B * NX);
+            HIPCHK(h, hipMemcpyAsync(hx.data(), c_xs, sizeof(float) * hx.size(), hipMemcpyDeviceToHost, st));
+        }
+        if (io.us) {
+            hu.resize((size_t)nk * B * m);
+            HIPCHK(h, hipMemcpyAsync(hu.data(), c_us, sizeof(float) * hu.size(), hipMemcpyDeviceToHost, st));
+        }
+        if (io.info) {
+            hi.resize((size_t)np * B * 8);
+            HIPCHK(h, hipMemcpyAsync(hi.data(), c_info, sizeof(float) * hi.size(), hipMemcpyDeviceToHost, st));
+        }
         HIPCHK(h, hipMemcpyAsync(&gave_up, d_gave_up, sizeof gave_up, hipMemcpyDeviceToHost, st));
-        if (rate) {
+        if (rate && rate->ws) {
             hw.resize((size_t)nk * B * 4);
             HIPCHK(h, hipMemcpyAsync(hw.data(), c_ws, sizeof(float) * hw.size(), hipMemcpyDeviceToHost, st));
         }
@@ -1746,6 +1848,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             HIPCHK(h, hipMemcpyAsync(hm.data(), c_xmeas, sizeof(float) * hm.size(), hipMemcpyDeviceToHost, st));
         }
         if (j0 + np == Ns) {
+            if (scoring) HIPCHK(h, hipMemcpyAsync(score->score_out, d_score, sizeof(uint32_t) * 16 * (size_t)B, hipMemcpyDeviceToHost, st));
             if (AM > 0 && obs->xhist_next) {
                 hn.resize((size_t)AM * HR);
                 HIPCHK(h, hipMemcpyAsync(hn.data(), d_hist, sizeof(float) * hn.size(), hipMemcpyDeviceToHost, st));
@@ -1768,20 +1871,22 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             return 0;
         }
         if (tickets_consistent(h) != 0) { *again = true; return 0; }     // (the mirror is re-synchronised)
-        for (int kc = 0; kc < nk; ++kc)
-            for (int b = 0; b < B; ++b) {
-                const size_t r = (size_t)kc * B + b, k = k0 + kc;
-                memcpy(io.xs + ((size_t)b * (T + 1) + k + 1) * NX, &hx[r * NX], sizeof(float) * NX);
-                memcpy(io.us + ((size_t)b * T + k) * m, &hu[r * m], sizeof(float) * m);
-                if (rate) memcpy(rate->ws + ((size_t)b * T + k) * 4, &hw[r * 4], sizeof(float) * 4);
-            }
+        if (io.xs || io.us || (rate && rate->ws))
+            for (int kc = 0; kc < nk; ++kc)
+                for (int b = 0; b < B; ++b) {
+                    const size_t r = (size_t)kc * B + b, k = k0 + kc;
+                    if (io.xs) memcpy(io.xs + ((size_t)b * (T + 1) + k + 1) * NX, &hx[r * NX], sizeof(float) * NX);
+                    if (io.us) memcpy(io.us + ((size_t)b * T + k) * m, &hu[r * m], sizeof(float) * m);
+                    if (rate && rate->ws) memcpy(rate->ws + ((size_t)b * T + k) * 4, &hw[r * 4], sizeof(float) * 4);
+                }
         if (subs_out)
             for (size_t rr = 0; rr < (size_t)nk * nsub; ++rr)
                 for (int b = 0; b < B; ++b)
                     memcpy(flt->xsub + ((size_t)b * T * nsub + k0 * nsub + rr) * NX, &hs[(rr * B + b) * NX], sizeof(float) * NX);
-        for (int jc = 0; jc < np; ++jc)
-            for (int b = 0; b < B; ++b)
-                memcpy((float*)io.info + ((size_t)b * Ns + j0 + jc) * 8, &hi[((size_t)jc * B + b) * 8], sizeof(float) * 8);
+        if (io.info)
+            for (int jc = 0; jc < np; ++jc)
+                for (int b = 0; b < B; ++b)
+                    memcpy((float*)io.info + ((size_t)b * Ns + j0 + jc) * 8, &hi[((size_t)jc * B + b) * 8], sizeof(float) * 8);
         if (seen && obs->xmeas)
             for (int jc = 0; jc < np; ++jc)
                 for (int b = 0; b < B; ++b)

@@ -247,8 +247,25 @@ struct LoopObserve {
     int age_max;                // rows of hist
     int renorm;                 // 1: renormalise the attitude of xm (wave-uniform); 0: leave the product as it is
 };
+// SPEC.md §11h, scoring episodes on the device: ONE further launch of the period's key-schedule kernel at the end of every chunk, in its scoring form (ticks = 0,
+// an empty LoopObserve, null key buffers: the key words are neither read nor written). Thread b walks the chunk's rows of episode b in time order and updates the
+// episode's 16 score words (include/sdempc.h: the table at sdempc_score_cfg) from words[b] back to words[b]. All row buffers are [row][B][.]: the chunk's own.
+// words null means absent: the period launches pass that, and the kernel then makes no memory access it did not make before.
+struct LoopScore {
+    uint32_t* words;            // [B][16] the score words: in, and out; null: no scoring
+    const float* rows;          // [ticks * rows_per_tick][B][13] the scored rows in time order: the chunk's xs rows (rows_per_tick 1) or xsub rows (the plant's substeps)
+    const float* us;            // [ticks][B][m] the chunk's applied controls
+    const float* info;          // [solves][B][8] the chunk's telemetry rows
+    const float* ref;           // target of chunk tick i, episode b at ref[i * ref_tick_stride + b * ref_ep_stride + 0..12] (position [0..2] and velocity [3..5] are read)
+    int ref_tick_stride;        // floats between two ticks' targets: Br * 13, or 0 (one target for every tick)
+    int ref_ep_stride;          // floats between two episodes' targets: 13, or 0 (one target for every episode)
+    int ticks, rows_per_tick, solves;   // of this chunk
+    int m;
+    float r2_pos, cos_min, w2_max;      // thresholds: squared radius, cosine of the tilt, squared rate (+inf, -inf, +inf: off); never NaN
+    float u_lo[8], u_hi[8], uref[8];    // of motor j < m (wave-uniform kernel arguments, read at constant indices)
+};
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st,
-                                   const LoopObserve& O = LoopObserve{});
+                                   const LoopObserve& O = LoopObserve{}, const LoopScore& Z = LoopScore{});
 // rows_dev[b][0..n) = row_dev[0..n) for b < B
 hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st);
 // canonical [B][P][C] <-> device [B][G][C][32] (to_dev: zero-pads particles >= P)

@@ -161,6 +161,8 @@ DI void split2(uint32_t k0, uint32_t k1, uint32_t* first, uint32_t* second) {
     first[0] = a0; first[1] = c0;
     second[0] = a1; second[1] = c1;
 }
+// SPEC.md §11h: (u32) of a telemetry count — the value itself where 0 <= v < 2^32, else 0 (a NaN among them)
+DI uint32_t score_u32(float v) { return v >= 0.0f && v < 4294967296.0f ? (uint32_t)v : 0u; }
 // one thread per episode: (r', s) = split(r_k), (r_{k+1}, p) = split(r'), xi_k = normal(p, (6,)) (random_bits(p, 6) pairs counter i with
 // i + 3). keys: r_k in, r_{k+1} out; sub: s (the solve's noise key); xi: [B][6]
 __global__ void __launch_bounds__(256) sdempc_loop_keys_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B) {
@@ -214,10 +216,74 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
 // position, velocity and body rates, and the attitude multiplied by (1, e[6..8] / 2) from the right, not renormalised. O.q null: not one access more.
 // SPEC.md §11g (O.age / O.renorm given): the state the measurement is formed from is A = age[b] plant substeps old — row age_max - A of the history (a per-thread
 // gather; A = 0 reads O.x as before) — and the attitude of xm is scaled to unit length with the software rsqrt. O.age null and O.renorm 0: not one access more.
+// SPEC.md §11h (Z.words given; ticks = 0, O empty, keys / sub / xi null and untouched): the SCORING form of the launch, one per chunk. Thread b walks the chunk's rows
+// of its episode in time order — rows, then tick rows, then solve rows; the buffers are [row][B][.], so neighbouring threads read neighbouring rows — and carries
+// the 16 score words of the episode in registers from Z.words[b] back to Z.words[b]. Z.words null (every period launch): not one access more.
 __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int ticks,
-                                                                      int xi_ticks, int n, LoopObserve O) {
+                                                                      int xi_ticks, int n, LoopObserve O, LoopScore Z) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
+    if (Z.words) {                                       // (wave-uniform)
+        uint32_t* w = Z.words + (size_t)b * 16;
+        uint32_t cnt = w[0], imax = w[3], first = w[8], causes = w[9], nbad = w[10];
+        float sdp = __uint_as_float(w[1]), mdp = __uint_as_float(w[2]), ldp = __uint_as_float(w[4]), sdv = __uint_as_float(w[5]);
+        float minc = __uint_as_float(w[6]), mw2 = __uint_as_float(w[7]);
+        for (int i = 0; i < Z.ticks; ++i) {
+            const float* g = Z.ref + (size_t)i * Z.ref_tick_stride + (size_t)b * Z.ref_ep_stride;
+            const float g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3], g4 = g[4], g5 = g[5];
+            for (int jj = 0; jj < Z.rows_per_tick; ++jj) {
+                const float* x = Z.rows + ((size_t)(i * Z.rows_per_tick + jj) * B + b) * 13;
+                bool nf = false;
+#pragma unroll
+                for (int c = 0; c < 13; ++c) nf = nf || !(__builtin_fabsf(x[c]) < __builtin_inff());
+                const float e0 = x[0] - g0, e1 = x[1] - g1, e2 = x[2] - g2;
+                const float dp = FMA(e2, e2, FMA(e1, e1, e0 * e0));
+                const float f0 = x[3] - g3, f1 = x[4] - g4, f2 = x[5] - g5;
+                const float dv = FMA(f2, f2, FMA(f1, f1, f0 * f0));
+                const float c = FMA(-2.0f, x[7] * x[7] + x[8] * x[8], 1.0f);
+                const float w2 = FMA(x[12], x[12], FMA(x[11], x[11], x[10] * x[10]));
+                const uint32_t cause = (!(dp <= Z.r2_pos) ? 1u : 0u) | (!(c >= Z.cos_min) ? 2u : 0u) | (!(w2 <= Z.w2_max) ? 4u : 0u) | (nf ? 8u : 0u);
+                sdp = sdp + dp;
+                if (dp > mdp) { mdp = dp; imax = cnt; }
+                ldp = dp;
+                sdv = sdv + dv;
+                if (c < minc) minc = c;
+                if (w2 > mw2) mw2 = w2;
+                if (cause) {
+                    if (first == 0xffffffffu) first = cnt;
+                    causes |= cause;
+                    nbad += 1u;
+                }
+                cnt += 1u;
+            }
+        }
+        w[0] = cnt; w[1] = __float_as_uint(sdp); w[2] = __float_as_uint(mdp); w[3] = imax; w[4] = __float_as_uint(ldp); w[5] = __float_as_uint(sdv);
+        w[6] = __float_as_uint(minc); w[7] = __float_as_uint(mw2); w[8] = first; w[9] = causes; w[10] = nbad;
+        uint32_t sat = w[11];
+        float sdu = __uint_as_float(w[12]);
+        for (int i = 0; i < Z.ticks; ++i) {
+            const float* u = Z.us + ((size_t)i * B + b) * Z.m;
+            float a = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)                  // (constant indices into the argument: no copy of it in scratch)
+                if (j < Z.m) {
+                    const float uj = u[j], d = uj - Z.uref[j];
+                    if (uj <= Z.u_lo[j] || uj >= Z.u_hi[j]) sat += 1u;
+                    a = FMA(d, d, a);
+                }
+            sdu = sdu + a;
+        }
+        w[11] = sat; w[12] = __float_as_uint(sdu);
+        uint32_t nit = w[13], nls = w[14], flat = w[15];
+        for (int j = 0; j < Z.solves; ++j) {
+            const float* inf = Z.info + ((size_t)j * B + b) * 8;
+            nit += score_u32(inf[2]);
+            nls += score_u32(inf[7]);
+            if (!(inf[6] < inf[5])) flat += 1u;
+        }
+        w[13] = nit; w[14] = nls; w[15] = flat;
+        return;
+    }
     if (O.q) {
         uint32_t q2[2], me[2];
         split2(O.q[2 * b], O.q[2 * b + 1], q2, me);
@@ -283,12 +349,21 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
     keys[2 * b] = r[0]; keys[2 * b + 1] = r[1];
 }
 
-hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st, const LoopObserve& O) {
-    if (B < 1 || substeps < 1 || ticks < 1 || xi_ticks < ticks) return hipErrorInvalidValue;
+hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st, const LoopObserve& O,
+                                   const LoopScore& Z) {
+    if (B < 1 || substeps < 1 || ticks < 0 || xi_ticks < ticks) return hipErrorInvalidValue;
+    // ticks = 0 is the scoring form and nothing else: score words, no observation, no key buffers
+    if ((ticks == 0) != (Z.words != nullptr)) return hipErrorInvalidValue;
+    if (Z.words) {
+        if (O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev) return hipErrorInvalidValue;
+        if (!Z.rows || !Z.us || !Z.info || !Z.ref || Z.ticks < 1 || Z.solves < 1 || Z.solves > Z.ticks || Z.rows_per_tick < 1 || Z.m < 1 || Z.m > 8) return hipErrorInvalidValue;
+        if ((Z.ref_tick_stride != 0 && Z.ref_tick_stride < 13) || (Z.ref_ep_stride != 0 && Z.ref_ep_stride != 13)) return hipErrorInvalidValue;
+        if (Z.r2_pos != Z.r2_pos || Z.cos_min != Z.cos_min || Z.w2_max != Z.w2_max) return hipErrorInvalidValue;
+    } else if (!keys_dev || !sub_dev || !xi_dev) return hipErrorInvalidValue;
     if (O.q && (!O.x || !O.xm || !O.xmeas || (O.ep_stride != 0 && O.ep_stride != 12) || (O.valid_ep_stride != 0 && O.valid_ep_stride != 1))) return hipErrorInvalidValue;
     if ((O.age || O.renorm) && !O.q) return hipErrorInvalidValue;
     if (O.age && (!O.hist || O.age_max < 1 || O.hist_row_stride < B * 13 || (O.age_ep_stride != 0 && O.age_ep_stride != 1))) return hipErrorInvalidValue;
-    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O);
+    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z);
     return hipGetLastError();
 }
 

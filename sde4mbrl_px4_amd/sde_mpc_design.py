@@ -139,7 +139,8 @@ class MpcProblem:
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
                  plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,
-                 fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None, meas_age=None, meas_renorm=False):
+                 fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None, meas_age=None, meas_renorm=False,
+                 score=None, score_ref=None):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -172,7 +173,11 @@ class MpcProblem:
         meas_age / meas_renorm (SPEC.md §11g; each needs one of the three above): meas_age, an int or int[Ns], is the age of the estimate in PLANT SUBSTEPS — a
         valid solve measures the state that many substeps back (before the run the vehicle sat at x; at most min(solve_period, T) * plant_substeps) —, and
         meas_renorm=True scales the measured attitude to unit length. Ages have no frame. With a largest age A > 0 the last A substep states before the run's end,
-        f32[A][13], oldest first, follow the observation key, flipped into the frame of x row by row like xs[1:]; xsub stays the LAST value."""
+        f32[A][13], oldest first, follow the observation key, flipped into the frame of x row by row like xs[1:]; xsub stays the LAST value.
+        score / score_ref (SPEC.md §11h): score is a solver.Score; the episode's 16 score words, formed on the device, are appended behind every value above as a
+        structured array [1] (solver.SCORE_DTYPE; xsub stays the LAST value), and the call is the timed one. score_ref f32[T][13] or f32[13] is the target each scored
+        state of tick k is compared with, GIVEN IN THE FRAME OF x and converted by enu2ned like xs. Its default is the reference at the END of each tick: the loaded
+        trajectory at curr_t + (k + 1) * dt_0 (already in the solver's frame, as every reference window is), else xdes. score_ref without score raises ValueError."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -247,6 +252,22 @@ class MpcProblem:
             hist = int(a.max()) > 0
         if meas_renorm:
             more["meas_renorm"] = True
+        if score is None and score_ref is not None:
+            raise ValueError("MpcProblem.simulate: score_ref needs score=Score(...)")
+        if score is not None:
+            if score_ref is not None:
+                g = np.asarray(score_ref, np.float32)
+                if g.shape not in ((13,), (T, 13)):
+                    raise ValueError(f"MpcProblem.simulate: score_ref must be f32[{T}][13] or f32[13], got {g.shape}")
+                if self.convert_to_enu:
+                    g = enu2ned(g, np)
+            elif self.state_from_traj is not None:
+                dt0 = float(self.cfg.time_steps[0])
+                g = np.asarray(self.state_from_traj(float(curr_t) + (np.arange(T, dtype=np.float64) + 1.0) * dt0), np.float32).reshape(T, 13)
+            else:
+                g = xdes
+            g = np.ascontiguousarray(g, np.float32)
+            more.update(score=score, score_ref=g[None, None] if g.ndim == 1 else g[:, None])
         out = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
             plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag,
@@ -259,6 +280,10 @@ class MpcProblem:
         st = OptState(_arr(u_next[0]), np.float32(i[0]), np.float32(s_next[0]), np.float32(i[2]), np.float32(i[3]), np.float32(i[4]),
                       np.float32(i[5]), np.float32(i[6]), np.float32(i[7]))
         ret = (_arr(xs), _arr(us[0]), _arr(info[0]), st, k_next[0].copy())
+        zrow = None
+        if score is not None:           # the score sits behind every other value, in front of xsub
+            zrow = out[-2] if substep_states else out[-1]
+            out = out[:-2] + out[-1:] if substep_states else out[:-1]
         if observed:
             o = out[:-1] if substep_states else out
             if hist:
@@ -267,6 +292,8 @@ class MpcProblem:
             ret += (_arr(enu2ned(xmeas, np) if self.convert_to_enu else xmeas), q_next.copy())
             if hist:
                 ret += (_arr(enu2ned(xhist, np) if self.convert_to_enu else xhist),)
+        if zrow is not None:
+            ret += (zrow,)
         if substep_states:
             xsub = out[-1][0]
             ret += (_arr(enu2ned(xsub, np) if self.convert_to_enu else xsub),)

@@ -116,6 +116,74 @@ def gauss_markov_bias(Ns, B, std, tau, solve_dt, rng, state=None):
     return out.astype(np.float32), b
 
 
+class Score:
+    """What closed_loop(score=...) scores an episode against (SPEC.md §11h): pos_radius [m] around the tick's target, tilt_max [rad] from the vertical, rate_max
+    [rad/s] on the body-rate vector; substeps=True scores the plant's substep states instead of the tick states. The device compares squares and a cosine, so
+    the three float32 thresholds are formed here: r2_pos = pos_radius^2, cos_min = cos(tilt_max), w2_max = rate_max^2, each computed in float64 and rounded to
+    float32 ONCE (so a squared threshold is not the square of the rounded radius). The defaults (inf, pi, inf) give +inf, -inf, +inf: the criterion is off —
+    tilt_max >= pi maps to -inf, not to cos(pi), since c >= -1 would still fail at c = -1 - ulp. A row fails a criterion when it is not inside it: dp <= r2_pos,
+    c >= cos_min, w2 <= w2_max, and a NaN is never inside."""
+
+    def __init__(self, pos_radius=np.inf, tilt_max=np.pi, rate_max=np.inf, substeps=False):
+        r, t, w = float(pos_radius), float(tilt_max), float(rate_max)
+        if not (r >= 0.0) or not (t >= 0.0) or not (w >= 0.0):
+            raise ValueError("Score: pos_radius, tilt_max and rate_max must be >= 0 (and not NaN)")
+        self.pos_radius, self.tilt_max, self.rate_max, self.substeps = r, t, w, bool(substeps)
+        with np.errstate(over="ignore"):
+            self.r2_pos = np.float32(np.float64(r) * np.float64(r))
+            self.cos_min = np.float32(-np.inf) if t >= np.pi else np.float32(np.cos(np.float64(t)))
+            self.w2_max = np.float32(np.float64(w) * np.float64(w))
+
+    def thresholds(self):
+        """(r2_pos, cos_min, w2_max) as float32."""
+        return self.r2_pos, self.cos_min, self.w2_max
+
+    def __repr__(self):
+        return f"Score(pos_radius={self.pos_radius}, tilt_max={self.tilt_max}, rate_max={self.rate_max}, substeps={self.substeps})"
+
+
+SCORE_DTYPE = np.dtype(_abi.SCORE_FIELDS)          # one episode's 16 score words (SPEC.md §11h), 64 bytes
+SCORE_CAUSES = {"position": 1, "tilt": 2, "rate": 4, "nonfinite": 8}
+
+
+def score_init(B):
+    """The initial score rows of B episodes (what score_in=None means): zeros, min_cos_tilt = +inf, first_fail_row = 0xffffffff."""
+    z = np.zeros(int(B), SCORE_DTYPE)
+    z["min_cos_tilt"] = np.inf
+    z["first_fail_row"] = 0xFFFFFFFF
+    return z
+
+
+def score_summary(score, solves=None):
+    """Host convenience on the structured score array [B] that closed_loop(score=...) returns. A dict of
+        success_rate      fraction of episodes without a failing row (first_fail_row all ones)
+        rms_pos_err       f64[B], sqrt(sum_dp / rows) per episode (NaN for an episode without rows)
+        worst_tilt_deg    the largest tilt of any episode: degrees(acos(min over episodes of min_cos_tilt, clipped to [-1, 1])); NaN if that minimum is
+        mean_steps        optimiser iterations per solve, sum(sum_steps) / (B * solves)
+        mean_ls_trials    line-search trials per solve, sum(sum_ls_trials) / (B * solves)
+    The score words hold no solve count, so the last two need `solves`, the number of solves per episode over everything the score covers (Ns of every call
+    the score was carried through, added up); without it they are None. Reductions across episodes stay on the host: B words per metric."""
+    z = np.asarray(score)
+    if z.dtype != SCORE_DTYPE or z.ndim != 1:
+        raise ValueError(f"score_summary: expected the structured score array [B] of closed_loop(score=...), got dtype {z.dtype} and shape {z.shape}")
+    B = z.shape[0]
+    rows = z["rows"].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rms = np.sqrt(z["sum_dp"].astype(np.float64) / rows)
+        cmin = np.float64(z["min_cos_tilt"].min()) if B else np.float64(np.nan)
+        if np.isnan(z["min_cos_tilt"]).any():
+            cmin = np.float64(np.nan)
+        tilt = np.degrees(np.arccos(np.clip(cmin, -1.0, 1.0)))
+    out = dict(success_rate=float(np.mean(z["first_fail_row"] == 0xFFFFFFFF)) if B else float("nan"), rms_pos_err=rms, worst_tilt_deg=float(tilt),
+               mean_steps=None, mean_ls_trials=None)
+    if solves is not None:
+        if int(solves) < 1:
+            raise ValueError("score_summary: solves must be >= 1")
+        out["mean_steps"] = float(z["sum_steps"].astype(np.float64).sum() / (B * int(solves)))
+        out["mean_ls_trials"] = float(z["sum_ls_trials"].astype(np.float64).sum() / (B * int(solves)))
+    return out
+
+
 class SdeMpcSolver:
     """One solver handle = one (MPC config, model). Single-threaded, like the reference's solver
     objects (one blocking call at a time, sde_control.py:420)."""
@@ -241,7 +309,8 @@ class SdeMpcSolver:
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
                     rate_loop=None, rate_integ_in=None, rate_tail_in=None, fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None,
-                    meas_keys=None, xmeas_in=None, meas_age=None, meas_age_max=None, meas_renorm=False, xhist_in=None):
+                    meas_keys=None, xmeas_in=None, meas_age=None, meas_age_max=None, meas_renorm=False, xhist_in=None, score=None, score_ref=None, score_in=None,
+                    outputs=True):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -313,7 +382,21 @@ class SdeMpcSolver:
         [B][age_max][13] (the last age_max substep states before the run's end) is appended after xmeas_next; xsub stays the LAST value; carried back in as xhist_in
         with the other continuation values it continues the episodes bit for bit when T is a multiple of solve_period. Every age 0 without meas_renorm reproduces
         the paragraph above bit for bit. Coloured estimator noise needs no keyword: gauss_markov_bias draws meas_bias rows of a first-order Gauss-Markov process.
-        With none of the four given nothing of this paragraph is touched."""
+        With none of the four given nothing of this paragraph is touched.
+
+        score / score_ref / score_in / outputs (SPEC.md §11h, sdempc_closed_loop_batch_scored): the evaluator. score is a Score (a position radius, a tilt and a body-rate
+        limit, each off by default; substeps=True scores every plant substep state instead of every tick state); score_ref, required with it, is the target each row
+        is compared with, f32[Tr][Br][13] with Tr in {1, T} (per control TICK: the target of x_{k+1} and of the substep states of tick k is row k) and Br in {1, B}, or
+        [T][13] (shared by all episodes), or [13] (constant), in the solver's frame. The device forms 16 words per episode from rows it already holds — rows scored,
+        sum / max (and where) / last of the squared position error, sum of the squared velocity error, the smallest tilt cosine, the largest squared rate, the first
+        failing row, the causes (SCORE_CAUSES) and the number of failing rows, saturated motor commands, squared control effort, iterations, line-search trials and
+        solves without a decrease — and they come back as ONE more value, a structured array [B] of dtype SCORE_DTYPE (score_summary reduces it), placed behind
+        every value above; xsub, when requested, stays the LAST value. score makes the call the timed one (xref and info per solve, the plant defaulting to the
+        handle's own model; every keyword above still applies). score_in [B] (a score a previous call returned; None: score_init(B)) continues it: word for word the
+        score of the joined run when the first call's T is a multiple of solve_period. outputs=False passes NULL for the per-row outputs — xs, us, info, ws, xmeas and
+        xsub are then neither copied back nor scattered, and None stands in their places in the returned tuple; the continuation values and the score are
+        unchanged. The score depends on nothing but the episode: not on B, the chunking or the outputs requested. score_ref / score_in / outputs=False without score
+        raise ValueError; with none of the four given nothing of this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -418,7 +501,27 @@ class SdeMpcSolver:
                 if age_max == 0:
                     raise ValueError("closed_loop: xhist_in needs meas_age_max > 0")
                 xhist_in = _f32(xhist_in, (B, age_max, 13))
-        faulted = flt is not None or bool(substep_states) or observed
+        scored = score is not None
+        if not scored and (score_ref is not None or score_in is not None or not outputs):
+            raise ValueError("closed_loop: score_ref / score_in / outputs=False need score=Score(...)")
+        if scored:
+            if not isinstance(score, Score):
+                raise ValueError("closed_loop: score must be a Score")
+            if score_ref is None:
+                raise ValueError("closed_loop: score_ref (the target of every tick, f32[Tr][Br][13]) is required with score")
+            sref = _f32(score_ref)
+            if sref.ndim == 1 and sref.shape == (13,):
+                sref = sref[None, None]
+            elif sref.ndim == 2 and sref.shape == (T, 13):
+                sref = sref[:, None]
+            if sref.ndim != 3 or sref.shape[2] != 13 or sref.shape[0] not in (1, T) or sref.shape[1] not in (1, B):
+                raise ValueError(f"closed_loop: score_ref must be f32[Tr][Br][13] with Tr in (1, {T}) and Br in (1, {B}), f32[{T}][13] or f32[13], got {np.shape(score_ref)}")
+            sref = np.ascontiguousarray(sref)
+            if score_in is not None:
+                score_in = np.ascontiguousarray(score_in)
+                if score_in.dtype != SCORE_DTYPE or score_in.shape != (B,):
+                    raise ValueError(f"closed_loop: score_in must be the structured score array [{B}] a previous call returned, got dtype {score_in.dtype} and shape {score_in.shape}")
+        faulted = flt is not None or bool(substep_states) or observed or scored
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
             raise ValueError("closed_loop: rate_integ_in / rate_tail_in need rate_loop=...")
         if rate_loop is not None and not isinstance(rate_loop, RateLoop):
@@ -459,6 +562,8 @@ class SdeMpcSolver:
         common = (B, T, _fp(x0), _fp(xref), int(xref.shape[0]), int(xref.shape[1]), keys.ctypes.data_as(u32p), u_p, s_p)
         outs = (_fp(xs), _fp(us), info.ctypes.data_as(C.POINTER(SdempcInfo)), _fp(u_next), _fp(s_next), k_next.ctypes.data_as(u32p))
         ret = (xs, us, info, u_next, s_next, k_next)
+        if not outputs:             # (scored, checked above) NULL per-row outputs, None in their places
+            outs, ret = (None, None, None) + outs[3:], (None, None, None) + ret[3:]
         if plant is None:
             if plant_of is not None or plant_substeps != 1 or plant_dt is not None or plant_mlp_dtype is not None or plant_math_mode is not None:
                 raise ValueError("closed_loop: plant_of / plant_substeps / plant_dt / plant_mlp_dtype / plant_math_mode need plant=...")
@@ -504,14 +609,16 @@ class SdeMpcSolver:
             g_next = np.zeros((B, 3), np.float32)
             t_next = np.zeros((B, self.H, 3), np.float32)
             lead = [C.byref(rc_)] + (lead if scenario else [None] + lead)       # (no scenario: a NULL scenario cfg)
-            more, ret = more + (g_p, t_p, _fp(ws), _fp(g_next), _fp(t_next)), ret + (ws, g_next, t_next)
+            if not outputs:
+                ws = None
+            more, ret = more + (g_p, t_p, None if ws is None else _fp(ws), _fp(g_next), _fp(t_next)), ret + (ws, g_next, t_next)
         if faulted:                 # the rate entry point's arguments (rate cfg, scenario cfg: NULL where absent) behind the fault cfg, then xsub
             if rate_loop is None:
                 lead, more = [None] + (lead if scenario else [None] + lead), more + (None,) * 5
             fc = None
             if flt is not None:
                 fc = _abi.SdempcFaultCfg(C.sizeof(_abi.SdempcFaultCfg), _fp(flt), flt.shape[0], flt.shape[1])
-            xsub = np.zeros((B, max(T, 0) * int(plant_substeps), 13), np.float32) if substep_states else None
+            xsub = np.zeros((B, max(T, 0) * int(plant_substeps), 13), np.float32) if substep_states and outputs else None
             lead, more = [None if fc is None else C.byref(fc)] + lead, more + (None if xsub is None else _fp(xsub),)
             if observed:            # the fault entry point's arguments behind (obs cfg, obs_keys, xmeas_in), then xmeas, obs_keys_next, xmeas_next
                 rows_ = obs_sigma if obs_sigma is not None else obs_beta
@@ -519,11 +626,13 @@ class SdeMpcSolver:
                                        1 if rows_ is None else rows_.shape[0], 1 if rows_ is None else rows_.shape[1],
                                        None if obs_valid is None else obs_valid.ctypes.data_as(C.POINTER(C.c_int32)),
                                        1 if obs_valid is None else obs_valid.shape[0], 1 if obs_valid is None else obs_valid.shape[1])
-                xmeas = np.zeros((B, max(Ns, 0), 13), np.float32)
+                xmeas = np.zeros((B, max(Ns, 0), 13), np.float32) if outputs else None
                 q_next = np.zeros((B, 2), np.uint32)
                 xm_next = np.zeros((B, 13), np.float32)
                 lead = [C.byref(oc), meas_keys.ctypes.data_as(u32p), None if xmeas_in is None else _fp(xmeas_in)] + lead
-                more, ret = more + (_fp(xmeas), q_next.ctypes.data_as(u32p), _fp(xm_next)), ret + (xmeas, q_next, xm_next)
+                more, ret = more + (None if xmeas is None else _fp(xmeas), q_next.ctypes.data_as(u32p), _fp(xm_next)), ret + (xmeas, q_next, xm_next)
+            elif scored:            # (no observation: a NULL obs cfg and NULL observation pointers)
+                lead, more = [None, None, None] + lead, more + (None, None, None)
             if aged:                # the observed entry point's arguments behind (age cfg, xhist_in), then xhist_next
                 ac = _abi.SdempcAgeCfg(C.sizeof(_abi.SdempcAgeCfg), None if age_rows is None else age_rows.ctypes.data_as(C.POINTER(C.c_int32)),
                                        1 if age_rows is None else age_rows.shape[0], 1 if age_rows is None else age_rows.shape[1], age_max, int(bool(meas_renorm)))
@@ -532,10 +641,20 @@ class SdeMpcSolver:
                 more = more + (None if xh_next is None else _fp(xh_next),)
                 if xh_next is not None:
                     ret = ret + (xh_next,)
+            elif scored:            # (no age: a NULL age cfg and NULL history pointers)
+                lead, more = [None, None] + lead, more + (None,)
+            if scored:              # the aged entry point's arguments behind (score cfg, score_in), then score_out
+                zc = _abi.SdempcScoreCfg(C.sizeof(_abi.SdempcScoreCfg), int(score.substeps), float(score.r2_pos), float(score.cos_min), float(score.w2_max), _fp(sref),
+                                         sref.shape[0], sref.shape[1])
+                z_out = np.zeros(B, SCORE_DTYPE)
+                lead = [C.byref(zc), None if score_in is None else score_in.ctypes.data_as(u32p)] + lead
+                more, ret = more + (z_out.ctypes.data_as(u32p),), ret + (z_out,)
             if substep_states:
                 ret = ret + (xsub,)
         # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
-        if aged:
+        if scored:
+            entry = _abi.scored_entry(self.lib)
+        elif aged:
             entry = _abi.aged_entry(self.lib)
         elif observed:
             entry = _abi.observed_entry(self.lib)

@@ -28,9 +28,14 @@
   9. --age A [--renorm]: with --observe, the estimate of every valid solve is up to A plant substeps old (SPEC.md §11g, sdempc_closed_loop_batch_aged) — an age per
      solve and episode drawn from 0 .. A, a history of A rows — and --renorm scales its attitude to unit length. A <= min(period, T) * substeps. With A > 0 the run
      takes the §11e kernels with a substep region in the chunk.
+ 10. --score [--no-outputs] [--score-substeps]: the same loops scored on the device (SPEC.md §11h, sdempc_closed_loop_batch_scored) — a radius of 1 m, a tilt of 0.6 rad
+     and a rate of 6 rad/s around a hover target per tick and episode (the target rows are staged per chunk), one scoring launch per chunk; --score-substeps scores every
+     plant substep state (a substep region in the chunk); --no-outputs passes NULL for the per-row outputs, so nothing but the continuation values and B x 64 bytes of
+     score come back. Applies to --small-batch and to the C2 loop; it makes the call the timed one. The last run's score_summary is printed.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
                                         [--fault] [--substep-states] [--observe] [--age A] [--renorm]
+                                        [--score] [--no-outputs] [--score-substeps]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -69,9 +74,14 @@ ap.add_argument("--substep-states", action="store_true", help="copy the state af
 ap.add_argument("--observe", action="store_true", help="solve from a measured state: noise, bias and dropouts per solve and episode (SPEC.md §11f)")
 ap.add_argument("--age", type=int, default=-1, metavar="A", help="with --observe: estimates up to A plant substeps old, an age per solve and episode (SPEC.md §11g)")
 ap.add_argument("--renorm", action="store_true", help="with --observe: renormalise the measured attitude (SPEC.md §11g)")
+ap.add_argument("--score", action="store_true", help="score every episode on the device (SPEC.md §11h)")
+ap.add_argument("--no-outputs", action="store_true", help="with --score: NULL per-row outputs, only the continuation values and the score come back")
+ap.add_argument("--score-substeps", action="store_true", help="with --score: score every plant substep state instead of every tick state")
 a = ap.parse_args()
 if (a.age >= 0 or a.renorm) and not a.observe:
     ap.error("--age / --renorm need --observe")
+if (a.no_outputs or a.score_substeps) and not a.score:
+    ap.error("--no-outputs / --score-substeps need --score")
 model = synthetic_iris()
 if a.plant == "own" and a.substeps != 1:
     ap.error("--substeps needs --plant one or per-episode")
@@ -117,6 +127,12 @@ def scenario_kw(kw, B, T):
             kw["meas_age_max"] = a.age
         if a.renorm:
             kw["meas_renorm"] = True
+    if a.score:
+        from sde4mbrl_px4_amd.solver import Score
+        kw["score"] = Score(pos_radius=1.0, tilt_max=0.6, rate_max=6.0, substeps=a.score_substeps)
+        kw["score_ref"] = np.ascontiguousarray(np.broadcast_to(np.asarray(W.HOVER, np.float32), (T, B, 13)))
+        if a.no_outputs:
+            kw["outputs"] = False
     if a.disturbance:
         kw["disturbance"] = np.random.default_rng(2).uniform(-2.0, 2.0, (T, B, 6)).astype(np.float32)
     if a.plant_switch >= 0:
@@ -156,6 +172,18 @@ if a.age >= 0:
     tag += f" age<={a.age}"
 if a.renorm:
     tag += " renorm"
+if a.score:
+    tag += " score" + ("/substeps" if a.score_substeps else "") + (" no-outputs" if a.no_outputs else "")
+
+
+def report_score(out, T):
+    """score_summary of a scored call's result (the score sits behind every other value, in front of xsub)"""
+    if not a.score:
+        return
+    from sde4mbrl_px4_amd.solver import score_summary
+    s = score_summary(out[-2] if a.substep_states else out[-1], solves=-(-T // max(a.period, 1)))
+    print(f"  score: success {s['success_rate']:.3f}, median RMS position error {float(np.median(s['rms_pos_err'])):.3f} m, worst tilt {s['worst_tilt_deg']:.1f} deg, "
+          f"{s['mean_steps']:.2f} iterations and {s['mean_ls_trials']:.2f} trials per solve", flush=True)
 
 if a.small_batch:
     cfg = load_mpc_config(os.path.join(ROOT, "configs", "c1_iris_posctrl_h20_p32.yaml"))
@@ -169,9 +197,10 @@ if a.small_batch:
     kw = scenario_kw(kw, B, T)
     for rep in range(a.repeats):
         t = time.perf_counter()
-        S.closed_loop(x0, hold, keys, T, **kw)
+        out = S.closed_loop(x0, hold, keys, T, **kw)
         dt = time.perf_counter() - t
         print(f"C1 B={B} T={T}{tag}: {T / dt:8.1f} ticks/s ({B * T / dt:9.1f} episode-ticks/s, {dt * 1e3 / T:.3f} ms/tick)", flush=True)
+    report_score(out, T)
     S.close()
     sys.exit(0)
 
@@ -220,8 +249,9 @@ if not a.skip_c2:
     pk = scenario_kw({**plant_kw(B), **timing_kw(cfg, B)}, B, T)
     for rep in range(a.repeats):
         t = time.perf_counter()
-        S.closed_loop(x0, xref, keys, T, u_init=u0, stepsize_in=s0, **pk)
+        out = S.closed_loop(x0, xref, keys, T, u_init=u0, stepsize_in=s0, **pk)
         loop = time.perf_counter() - t
         print(f"C2 f32x3/fast B={B}{tag}: closed_loop {B * T / loop:8.1f} episode-ticks/s ({loop / T:.3f} s/tick, T = {T}); one batch solve_keys "
               f"{B / one:8.1f} solves/s ({one:.3f} s); ratio {(B * T / loop) / (B / one):.3f}", flush=True)
+    report_score(out, T)
     S.close()
