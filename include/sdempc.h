@@ -652,6 +652,58 @@ int sdempc_closed_loop_batch_scored(sdempc_handle* h, const sdempc_score_cfg* sc
                                     float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
                                     float* xhist_next /*[B][age_max][13] or NULL*/, uint32_t* score_out /*[B][16]; NULL without score*/);
 
+/* ---- batched closed loop with gusts and estimator bias drawn on the device (SPEC.md §11i) -------------------
+ * sdempc_closed_loop_batch_scored plus two optional first-order Gauss-Markov processes per episode, stepped on the device from key chains, so that the stochastic
+ * inputs of a campaign are keys and O(B) coefficients instead of [T][B][6] and [Ns][B][12] host arrays. With both cfgs NULL the call IS
+ * sdempc_closed_loop_batch_scored bit for bit, with the same launches; the six new outputs must then be NULL.
+ * A process of width W (dist_proc: W = 6, the disturbance w_v[3], w_omega[3]; bias_proc: W = 12, the estimator bias p, v, theta, omega) holds per episode b a key
+ * chain c_b, a state g_b f32[W] and coefficients rho, scale f32[W] (one row for all episodes, or one per episode). One step, in float32:
+ *   (c, e) = split(c)              the first half continues the chain, the second is the draw key
+ *   xi     = normal(e, (W,))       counter i pairs with i + W / 2
+ *   t_i    = scale_i * xi_i        one rounding; never contracted into the fma
+ *   g_i    = fma(rho_i, g_i, t_i)
+ *   row_i  = g_i, or d_i + g_i when a scheduled input of that kind is given as well (d its row (k or 0, b or 0); one float32 add)
+ * dist_proc takes one step per control tick k = 0 .. T-1, ticks inside a solve period included; row is the disturbance row of tick k and episode b, read by the plant
+ * exactly as a row of scenario->dist is. It makes the run a scenario run, as `dist` does. bias_proc takes one step per solve j, valid or not (a dropout holds the
+ * estimate, the error process keeps running), before the measurement is formed; row is the beta of that solve (e = fma(sigma, normal(me, 12), row), unchanged). It
+ * makes the run an observed one: it needs an obs cfg — whose sigma, beta and valid may all be NULL — and obs_keys, whose chain it does not touch.
+ * dist_rows / bias_rows are per-row outputs (the rows as the plant / the measurement read them): NULL means neither copied back nor scattered. The *_next outputs
+ * continue the processes bit for bit when carried back in as keys / state_in: the disturbance process for any T, the bias process when T is a multiple of
+ * solve_period. Every argument is checked before the first HIP call: SDEMPC_EINVAL for a wrong struct_size, batch not 1 or B, a NULL rho, scale or keys, a non-finite
+ * entry of rho, scale or state_in, rho outside [0, 1], a negative scale, bias_proc without obs_keys, a new output without its cfg, and for everything
+ * sdempc_closed_loop_batch_scored refuses. No ABI version change: detect the entry point by its symbol. */
+typedef struct sdempc_process_cfg {
+    int32_t struct_size;      /* sizeof(sdempc_process_cfg) */
+    int32_t batch;            /* rows of rho / scale: 1 or B */
+    const float* rho;         /* [batch][W], each in [0, 1] */
+    const float* scale;       /* [batch][W], finite, >= 0 */
+    const uint32_t* keys;     /* [B][2] the process chain */
+    const float* state_in;    /* [B][W] or NULL: zeros */
+} sdempc_process_cfg;
+int sdempc_closed_loop_batch_drawn(sdempc_handle* h, const sdempc_process_cfg* dist_proc /*or NULL, W = 6*/, const sdempc_process_cfg* bias_proc /*or NULL, W = 12*/,
+                                   const sdempc_score_cfg* score /*or NULL*/, const uint32_t* score_in /*[B][16] or NULL*/,
+                                   const sdempc_age_cfg* age_cfg /*or NULL*/, const float* xhist_in /*[B][age_max][13] or NULL*/,
+                                   const sdempc_obs_cfg* obs /*or NULL*/, const uint32_t* obs_keys /*[B][2]; NULL without obs*/, const float* xmeas_in /*[B][13] or NULL*/,
+                                   const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*or NULL*/,
+                                   const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                   const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                   const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                   const float* xref, int32_t xref_solves, int32_t xref_batch,
+                                   const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                   const float* u_act_in /*[B][m] or NULL*/,
+                                   float* xs /*[B][T+1][13]; may be NULL with score*/, float* us /*[B][T][m]; may be NULL with score*/,
+                                   sdempc_info* info /*[B][Ns]; may be NULL with score*/,
+                                   float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                   uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                   const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                   float* ws /*[B][T][4]; NULL without rate; may be NULL with score*/, float* rate_integ_next /*[B][3] or NULL*/,
+                                   float* rate_tail_next /*[B][H][3] or NULL*/,
+                                   float* xsub /*[B][T * substeps][13] or NULL*/,
+                                   float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
+                                   float* xhist_next /*[B][age_max][13] or NULL*/, uint32_t* score_out /*[B][16]; NULL without score*/,
+                                   float* dist_rows /*[B][T][6] or NULL*/, uint32_t* dist_keys_next /*[B][2] or NULL*/, float* dist_state_next /*[B][6] or NULL*/,
+                                   float* bias_rows /*[B][Ns][12] or NULL*/, uint32_t* bias_keys_next /*[B][2] or NULL*/, float* bias_state_next /*[B][12] or NULL*/);
+
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so
  * repeating the call runs in the one-workgroup-per-instance layout. Also SDEMPC_EDEVICE when a large throughput launch that hands its

@@ -108,6 +108,13 @@ SCORE_FIELDS = [("rows", "<u4"), ("sum_dp", "<f4"), ("max_dp", "<f4"), ("max_dp_
                 ("max_w2", "<f4"), ("first_fail_row", "<u4"), ("causes", "<u4"), ("fail_rows", "<u4"), ("saturated", "<u4"), ("sum_du2", "<f4"),
                 ("sum_steps", "<u4"), ("sum_ls_trials", "<u4"), ("no_decrease", "<u4")]
 
+class SdempcProcessCfg(C.Structure):
+    """sdempc_process_cfg (SPEC.md §11i): the coefficients, the key chain and the start state of one first-order Gauss-Markov process of
+    sdempc_closed_loop_batch_drawn (width 6: the disturbance, width 12: the estimator bias)."""
+    _fields_ = [("struct_size", C.c_int32), ("batch", C.c_int32), ("rho", C.POINTER(C.c_float)), ("scale", C.POINTER(C.c_float)),
+                ("keys", C.POINTER(C.c_uint32)), ("state_in", C.POINTER(C.c_float))]
+
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -305,6 +312,21 @@ def scored_entry(lib):
     return fn
 
 
+def drawn_entry(lib):
+    """sdempc_closed_loop_batch_drawn (SPEC.md §11i) with its prototype set: the two process cfgs (each may be NULL) in front of the scored entry point's arguments,
+    then rows, keys_next and state_next of the disturbance process and of the bias process. Detected by symbol and only when a call needs it, as scored_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_drawn
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_drawn (SPEC.md §11i): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(scored_entry(lib).argtypes)
+        fp, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        fn.argtypes = [a[0], C.POINTER(SdempcProcessCfg), C.POINTER(SdempcProcessCfg)] + a[1:] + [fp, u32p, fp] * 2
+        fn.restype = C.c_int
+    return fn
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -313,5 +335,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
     "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed", "sdempc_closed_loop_batch_scenario",
     "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault", "sdempc_closed_loop_batch_observed",
-    "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored",
+    "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored", "sdempc_closed_loop_batch_drawn",
 ]

@@ -186,6 +186,9 @@ struct sdempc_handle {
     DevBuf d_hist;
     // closed loop scored on the device (sdempc_closed_loop_batch_scored with a score cfg, allocated on its first use): the score words u32[max_batch][16]
     DevBuf d_score;
+    // closed loop with processes drawn on the device (sdempc_closed_loop_batch_drawn with a process cfg, allocated on its first use), per row of max_batch: the
+    // disturbance chain u32[2] and state f32[6], the bias chain u32[2] and state f32[12], then rho and scale of each (f32[6], f32[6], f32[12], f32[12])
+    DevBuf d_proc;
     DevBuf d_work;            // u64[4] work counters (KArgs::work)
     // cooperative latency path of the solve (allocated on its first use, sized for coop_cap instances)
     DevBuf d_coop_bar, d_coop_pp, d_coop_ck;
@@ -581,6 +584,19 @@ struct ScoreRun {
     const uint32_t* score_in;   // [B][16] or null (the initial row)
     uint32_t* score_out;        // [B][16]
 };
+// SPEC.md §11i: the processes of one sdempc_closed_loop_batch_drawn call (host pointers). Given only when the call has a process cfg: without one the call is the
+// scored call, launch for launch.
+struct ProcRun {
+    const sdempc_process_cfg* dist;     // or null (W = 6, one step per control tick)
+    const sdempc_process_cfg* bias;     // or null (W = 12, one step per solve)
+    float* dist_rows;                   // [B][T][6] or null
+    uint32_t* dist_keys_next;           // [B][2] or null
+    float* dist_state_next;             // [B][6] or null
+    float* bias_rows;                   // [B][Ns][12] or null
+    uint32_t* bias_keys_next;           // [B][2] or null
+    float* bias_state_next;             // [B][12] or null
+};
+constexpr size_t PROC_WORDS = 2 + 6 + 2 + 12 + 2 * 6 + 2 * 12;      // words of d_proc per row of max_batch
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
 // One closed-loop call as its entry point describes it. The five entry points are five nested layers (SPEC.md §11, §11a .. §11d): each takes everything the one
 // below it takes, so `layer` says which parts are present; the arguments of an absent part stay null.
@@ -617,14 +633,16 @@ struct LoopCall {
     const sdempc_score_cfg* zc;                 // or NULL: no score (the two pointers must then be NULL, and no per-row output may be)
     const uint32_t* score_in;
     uint32_t* score_out;
+    bool drawn;                                 // sdempc_closed_loop_batch_drawn (SPEC.md §11i): the scored call with the two process cfgs and their six outputs
+    ProcRun pr;                                 // (a NULL cfg: its three outputs must be NULL)
 };
 int closed_loop_call(sdempc_handle* h, const LoopCall& c);
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves, bool rows_optional = false);
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr,
-                         const ObsRun* obs = nullptr, const ScoreRun* score = nullptr);
+                         const ObsRun* obs = nullptr, const ScoreRun* score = nullptr, const ProcRun* proc = nullptr);
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, bool* again);
+                    const ScoreRun* score, const ProcRun* proc, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -717,7 +735,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1230,6 +1248,32 @@ int sdempc_closed_loop_batch_scored(sdempc_handle* h, const sdempc_score_cfg* zc
     });
 }
 
+int sdempc_closed_loop_batch_drawn(sdempc_handle* h, const sdempc_process_cfg* dist_proc, const sdempc_process_cfg* bias_proc, const sdempc_score_cfg* zc,
+                                   const uint32_t* score_in, const sdempc_age_cfg* ac, const float* xhist_in, const sdempc_obs_cfg* oc, const uint32_t* obs_keys,
+                                   const float* xmeas_in, const sdempc_fault_cfg* fc, const sdempc_rate_cfg* rc_, const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc,
+                                   const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T,
+                                   const float* x0, const float* xref, int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init,
+                                   const float* stepsize_in, const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next, float* stepsize_next,
+                                   uint32_t* keys_next, float* u_act_next, const float* rate_integ_in, const float* rate_tail_in, float* ws, float* rate_integ_next,
+                                   float* rate_tail_next, float* xsub, float* xmeas, uint32_t* obs_keys_next, float* xmeas_next, float* xhist_next, uint32_t* score_out,
+                                   float* dist_rows, uint32_t* dist_keys_next, float* dist_state_next, float* bias_rows, uint32_t* bias_keys_next, float* bias_state_next) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    c.observed = true; c.oc = oc; c.obs_keys = obs_keys; c.xmeas_in = xmeas_in; c.xmeas = xmeas; c.obs_keys_next = obs_keys_next; c.xmeas_next = xmeas_next;
+    c.aged = true; c.ac = ac; c.xhist_in = xhist_in; c.xhist_next = xhist_next;
+    c.scored = true; c.zc = zc; c.score_in = score_in; c.score_out = score_out;
+    c.drawn = true; c.pr = {dist_proc, bias_proc, dist_rows, dist_keys_next, dist_state_next, bias_rows, bias_keys_next, bias_state_next};
+    return closed_loop_call(h, c);
+    });
+}
+
 int sdempc_solve_status(sdempc_handle* h) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1282,7 +1326,7 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
 }
-// The one path behind the nine closed-loop entry points: every check of the call's parts, in one fixed order (score struct, age struct, observation struct, fault struct, rate, scenario struct,
+// The one path behind the ten closed-loop entry points: every check of the call's parts, in one fixed order (process structs and their arrays, score struct, age struct, observation struct, fault struct, rate, scenario struct,
 // timing, loop arguments, plant_ticks, plant set, solve_delay, disturbance, fault schedule, observation rows, age rows, score target rows; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
 int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     if (!h) return SDEMPC_EINVAL;
@@ -1294,6 +1338,30 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    if (c.drawn) {             // SPEC.md §11i: each process cfg with its coefficients, chain and state; an output needs its cfg
+        const ProcRun& pr = c.pr;
+        if (!pr.dist && (pr.dist_rows || pr.dist_keys_next || pr.dist_state_next))
+            return fail(h, SDEMPC_EINVAL, "process: dist_rows / dist_keys_next / dist_state_next must be NULL without dist_proc%s");
+        if (!pr.bias && (pr.bias_rows || pr.bias_keys_next || pr.bias_state_next))
+            return fail(h, SDEMPC_EINVAL, "process: bias_rows / bias_keys_next / bias_state_next must be NULL without bias_proc%s");
+        for (int w = 0; w < 2; ++w) {
+            const sdempc_process_cfg* p = w ? pr.bias : pr.dist;
+            const int W = w ? 12 : SDEMPC_NNOISE;
+            if (!p) continue;
+            if (p->struct_size != (int32_t)sizeof(sdempc_process_cfg)) return fail(h, SDEMPC_EINVAL, "process: struct_size mismatch%s");
+            if (p->batch != 1 && p->batch != B) return fail(h, SDEMPC_EINVAL, "process: batch must be 1 or B%s");
+            if (!p->rho || !p->scale || !p->keys) return fail(h, SDEMPC_EINVAL, "process: rho, scale or keys is NULL%s");
+            if (B < 1) continue;           // (refused below, with the loop arguments)
+            for (size_t e = 0; e < (size_t)p->batch * W; ++e) {
+                if (!(p->rho[e] >= 0.0f) || !(p->rho[e] <= 1.0f)) return fail(h, SDEMPC_EINVAL, "process: rho holds an entry outside [0, 1]%s");
+                if (!finite(p->scale[e]) || p->scale[e] < 0.0f) return fail(h, SDEMPC_EINVAL, "process: scale holds a non-finite or negative entry%s");
+            }
+            for (size_t e = 0; p->state_in && e < (size_t)B * W; ++e)
+                if (!finite(p->state_in[e])) return fail(h, SDEMPC_EINVAL, "process: state_in holds a non-finite entry%s");
+        }
+        if (pr.bias && !c.obs_keys) return fail(h, SDEMPC_EINVAL, "process: bias_proc needs an obs cfg and obs_keys%s");
+    }
+    const ProcRun* proc = c.drawn && (c.pr.dist || c.pr.bias) ? &c.pr : nullptr;
     const sdempc_score_cfg* zc = c.scored ? c.zc : nullptr;
     if (c.scored) {
         if (!zc && (c.score_in || c.score_out)) return fail(h, SDEMPC_EINVAL, "score: score_in / score_out must be NULL without a score cfg%s");
@@ -1422,7 +1490,7 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     if ((rc = stage_plants(h, *c.pc, c.plant_blobs, scenario ? nullptr : c.plant_of, B, &run, !timed ? 1 : (tc->solve_period < T ? tc->solve_period : T)))) return rc;
     const ScoreRun run_z{zc, c.score_in, c.score_out};
     return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr, run_f.fault || run_f.xsub ? &run_f : nullptr,
-                                oc ? &run_o : nullptr, zc ? &run_z : nullptr);
+                                oc ? &run_o : nullptr, zc ? &run_z : nullptr, proc);
 }
 // argument checks every closed-loop entry point shares; no HIP call
 // rows_optional (SPEC.md §11h, a call with a score cfg): xs / us / info may be NULL
@@ -1461,10 +1529,10 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt,
-                         const ObsRun* obs, const ScoreRun* score) {
+                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -1548,8 +1616,13 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // from them again). At the end of every chunk ONE launch of the period's key-schedule kernel in its scoring form walks the chunk's rows — xs, or xsub with substeps = 1,
 // which then exists in the chunk as with age_max > 0 — and its us and info rows. The target rows sit behind the age rows, staged per chunk when they move (one per TICK) and
 // once otherwise. A per-row output the caller passed as NULL is neither copied back nor scattered.
+// SPEC.md §11i (proc, with scen, timed and plant): the process chains, states and coefficients live in d_proc (staged from the cfgs with the other inputs, so that a re-run
+// starts from them again). The period's key-schedule launch takes a LoopProcess: with a disturbance process it writes the period's rows of a [Tc][B][6] region of the chunk,
+// which the plant launch then reads as its disturbance (a scheduled disturbance given as well is staged beside it, as before, and read by the key schedule); with a bias
+// process it writes the solve's row of a [Pc][B][12] region and forms the measurement from it (a scheduled beta likewise). Both regions count in the chunk's bytes and
+// are copied back and scattered only when the caller asked for the rows.
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, bool* again) {
+                    const ScoreRun* score, const ProcRun* proc, bool* again) {
     *again = false;
     const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
@@ -1574,7 +1647,9 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     const size_t AR = old ? (size_t)obs->Ba : 0;                                                       // words per solve row of age
     const bool sref_moves = scoring && score->cfg->ref_ticks > 1;
     const size_t ZR = scoring ? (size_t)score->cfg->ref_batch * NX : 0;                                // floats per tick row of the score targets (SPEC.md §11h)
-    const size_t per_period = (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0) +
+    const bool gproc = proc && proc->dist && scen && timed && plant, bproc = proc && proc->bias && seen;      // (SPEC.md §11i)
+    const int NG = SDEMPC_NNOISE, NB = 12;                                                              // widths of the two processes
+    const size_t per_period = (gproc ? (size_t)S * B * NG : 0) + (bproc ? (size_t)B * NB : 0) + (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0) +
                               (fault_moves ? (size_t)S * FR : 0) + (obs_moves ? ORS : 0) + (valid_moves ? VR : 0) + (age_moves ? AR : 0) + (sref_moves ? (size_t)S * ZR : 0);
     const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR) + (fault_moves ? 0 : FR) + (obs_moves ? 0 : ORS) + (valid_moves ? 0 : VR) + (age_moves ? 0 : AR) + (sref_moves ? 0 : ZR);
     const size_t cap = (h->loop_chunk_bytes < 0 ? LOOP_CHUNK_BYTES : (size_t)h->loop_chunk_bytes) / sizeof(float);
@@ -1600,6 +1675,14 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* d_hist = AM > 0 ? (float*)h->d_hist.p : nullptr;          // [AM][B][13] (SPEC.md §11g)
     if (scoring && !h->d_score.p && (rc = dev_alloc(h, h->d_score, sizeof(uint32_t) * 16 * (size_t)h->max_batch, true))) return rc;
     uint32_t* d_score = scoring ? (uint32_t*)h->d_score.p : nullptr; // [B][16] (SPEC.md §11h)
+    if ((gproc || bproc) && !h->d_proc.p && (rc = dev_alloc(h, h->d_proc, sizeof(uint32_t) * PROC_WORDS * (size_t)h->max_batch, true))) return rc;
+    const size_t MB = (size_t)h->max_batch;
+    uint32_t* p_dchain = (uint32_t*)h->d_proc.p;                     // [B][2] (SPEC.md §11i; the layout is the one stated at d_proc)
+    float* p_dstate = p_dchain ? (float*)(p_dchain + 2 * MB) : nullptr;                  // [B][6]
+    uint32_t* p_bchain = p_dchain ? (uint32_t*)(p_dstate + NG * MB) : nullptr;           // [B][2]
+    float* p_bstate = p_dchain ? (float*)(p_bchain + 2 * MB) : nullptr;                  // [B][12]
+    float* p_drho = p_dchain ? p_bstate + NB * MB : nullptr, *p_dscale = p_dchain ? p_drho + NG * MB : nullptr;
+    float* p_brho = p_dchain ? p_dscale + NG * MB : nullptr, *p_bscale = p_dchain ? p_brho + NB * MB : nullptr;
     uint32_t* d_q = (uint32_t*)h->d_obs.p;                           // q [B][2] (SPEC.md §11f)
     float* d_xm = d_q ? (float*)(d_q + 2 * (size_t)h->max_batch) : nullptr;   // xm [B][13]
     float* d_integ = (float*)h->d_rate.p;                            // g [B][3] (SPEC.md §11d)
@@ -1625,6 +1708,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     int32_t* c_valid = (int32_t*)(c_beta + (biased ? (obs_moves ? (size_t)Pc : 1) * OR : 0));    // [Pc or 1][Bv]
     int32_t* c_age = c_valid + (gated ? (valid_moves ? (size_t)Pc : 1) * VR : 0);                // [Pc or 1][Ba] (SPEC.md §11g)
     float* c_sref = (float*)(c_age + (old ? (age_moves ? (size_t)Pc : 1) * AR : 0));             // [Tc or 1][Br][13] (SPEC.md §11h)
+    float* c_pdist = c_sref + (scoring ? (sref_moves ? Tc : 1) * ZR : 0);                        // [Tc][B][6] (SPEC.md §11i)
+    float* c_pbeta = c_pdist + (gproc ? Tc * B * NG : 0);                                        // [Pc][B][12]
     float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place (SPEC.md §11f: the plant's; the solve reads d_xm)
     hipStream_t st = h->stream;
     // inputs (host vectors live until the synchronisation at the end of the first chunk)
@@ -1690,6 +1775,17 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         HIPCHK(h, hipMemcpyAsync(d_score, z_in, sizeof(uint32_t) * 16 * (size_t)B, hipMemcpyHostToDevice, st));
         if (!sref_moves) HIPCHK(h, hipMemcpyAsync(c_sref, score->cfg->score_ref, sizeof(float) * ZR, hipMemcpyHostToDevice, st));
     }
+    for (int w = 0; w < 2; ++w) {      // the process chains, states (NULL: zeros) and coefficients start as given (SPEC.md §11i)
+        if (!(w ? bproc : gproc)) continue;
+        const sdempc_process_cfg& pc = w ? *proc->bias : *proc->dist;
+        const size_t W = w ? NB : NG;
+        float* state = w ? p_bstate : p_dstate;
+        HIPCHK(h, hipMemcpyAsync(w ? p_bchain : p_dchain, pc.keys, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
+        if (pc.state_in) HIPCHK(h, hipMemcpyAsync(state, pc.state_in, sizeof(float) * B * W, hipMemcpyHostToDevice, st));
+        else HIPCHK(h, hipMemsetAsync(state, 0, sizeof(float) * B * W, st));
+        HIPCHK(h, hipMemcpyAsync(w ? p_brho : p_drho, pc.rho, sizeof(float) * pc.batch * W, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(w ? p_bscale : p_dscale, pc.scale, sizeof(float) * pc.batch * W, hipMemcpyHostToDevice, st));
+    }
     if (!xref_moves) {
         HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
         if (Bx != B) HIPCHK(h, launch_broadcast_rows(c_xref, (float*)h->d_xref.p, (int)XR, B, st));
@@ -1727,6 +1823,15 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         Z.r2_pos = zc.r2_pos; Z.cos_min = zc.cos_min; Z.w2_max = zc.w2_max;
         for (int l = 0; l < 8; ++l) { Z.u_lo[l] = l < m ? h->cfg.u_lo[l] : 0.0f; Z.u_hi[l] = l < m ? h->cfg.u_hi[l] : 0.0f; Z.uref[l] = l < m ? h->cfg.uref[l] : 0.0f; }
     }
+    LoopProcess G{};           // (chains null: absent)
+    if (gproc) {
+        G.dist.chain = p_dchain; G.dist.state = p_dstate; G.dist.rho = p_drho; G.dist.scale = p_dscale; G.dist.par_ep_stride = proc->dist->batch > 1 ? NG : 0;
+        G.dist.sched_tick_stride = dist_moves ? (int)DR : 0; G.dist.sched_ep_stride = gust && scen->Bd > 1 ? NG : 0;
+    }
+    if (bproc) {
+        G.bias.chain = p_bchain; G.bias.state = p_bstate; G.bias.rho = p_brho; G.bias.scale = p_bscale; G.bias.par_ep_stride = proc->bias->batch > 1 ? NB : 0;
+        G.bias.sched_ep_stride = biased && obs->Bo > 1 ? NB : 0;
+    }
     if (seen) {
         O.q = d_q; O.x = d_x; O.xm = d_xm; O.ep_stride = obs->Bo > 1 ? 12 : 0; O.valid_ep_stride = obs->Bv > 1 ? 1 : 0;
         O.renorm = obs->renorm ? 1 : 0;
@@ -1736,6 +1841,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     if (timed) { R.act = d_mot; R.alpha = timed->alpha; R.xi_ticks = S; R.shift = timed->S < H ? timed->S : H; }
     if (scen) {
         C.dist_tick_stride = dist_moves ? (int)DR : 0; C.dist_ep_stride = gust && scen->Bd > 1 ? SDEMPC_NNOISE : 0;
+        if (gproc) { C.dist_tick_stride = B * NG; C.dist_ep_stride = NG; }       // (the plant reads the rows the key schedule wrote)
         C.plant_tick_stride = sched_moves ? B : 0;
         C.dtp = plant->dt;
     }
@@ -1749,7 +1855,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         W.inv_m = rate->inv_m; W.w = rc_.motor_weight;
         W.xevol = (const float*)h->d_xmean.p; W.wt = d_tail; W.g = d_integ;
     }
-    std::vector<float> hx, hu, hi, hw, hs, hm, hn;
+    std::vector<float> hx, hu, hi, hw, hs, hm, hn, hg, hb;
     for (int j0 = 0; j0 < Ns; j0 += Pc) {
         const int np = Ns - j0 < Pc ? Ns - j0 : Pc;                                  // periods of this chunk
         const size_t k0 = (size_t)j0 * S;
@@ -1772,7 +1878,16 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 O.valid = gated ? c_valid + (valid_moves ? (size_t)jc * VR : 0) : nullptr;
                 if (O.hist) O.age = c_age + (age_moves ? (size_t)jc * AR : 0);
             }
-            if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st, O));
+            if (gproc) {               // (the scheduled rows and the written rows of this period's first tick)
+                G.dist.sched = gust ? c_dist + (dist_moves ? (size_t)jc * S * DR : 0) : nullptr;
+                G.dist.dst = c_pdist + (size_t)jc * S * B * NG;
+            }
+            if (bproc) {               // (the scheduled beta goes through the process, which writes the row the measurement reads)
+                G.bias.sched = O.beta;
+                G.bias.dst = c_pbeta + (size_t)jc * B * NB;
+                O.beta = nullptr;
+            }
+            if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st, O, LoopScore{}, G));
             else if (plant) HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st, plant->Q.substeps));
             else HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st));
             HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));
@@ -1791,7 +1906,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 const long long never = (long long)ticks * plant->Q.substeps;       // (a solution that arrives at the period's end is flown by the next period, as its tail)
                 R.ticks = ticks; R.arrive = (int)(timed->D < never ? timed->D : never);
                 if (scen) {
-                    C.dist = gust ? c_dist + (dist_moves ? t0 * DR : 0) : nullptr;
+                    C.dist = gproc ? c_pdist + t0 * B * NG : gust ? c_dist + (dist_moves ? t0 * DR : 0) : nullptr;
                     C.plant = sched ? c_sched + (sched_moves ? t0 * SR : 0) : nullptr;
                 }
                 if (rate) W.ws = c_ws + t0 * B * 4;
@@ -1847,7 +1962,19 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             hm.resize((size_t)np * B * NX);
             HIPCHK(h, hipMemcpyAsync(hm.data(), c_xmeas, sizeof(float) * hm.size(), hipMemcpyDeviceToHost, st));
         }
+        if (gproc && proc->dist_rows) {
+            hg.resize((size_t)nk * B * NG);
+            HIPCHK(h, hipMemcpyAsync(hg.data(), c_pdist, sizeof(float) * hg.size(), hipMemcpyDeviceToHost, st));
+        }
+        if (bproc && proc->bias_rows) {
+            hb.resize((size_t)np * B * NB);
+            HIPCHK(h, hipMemcpyAsync(hb.data(), c_pbeta, sizeof(float) * hb.size(), hipMemcpyDeviceToHost, st));
+        }
         if (j0 + np == Ns) {
+            if (gproc && proc->dist_keys_next) HIPCHK(h, hipMemcpyAsync(proc->dist_keys_next, p_dchain, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
+            if (gproc && proc->dist_state_next) HIPCHK(h, hipMemcpyAsync(proc->dist_state_next, p_dstate, sizeof(float) * B * NG, hipMemcpyDeviceToHost, st));
+            if (bproc && proc->bias_keys_next) HIPCHK(h, hipMemcpyAsync(proc->bias_keys_next, p_bchain, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
+            if (bproc && proc->bias_state_next) HIPCHK(h, hipMemcpyAsync(proc->bias_state_next, p_bstate, sizeof(float) * B * NB, hipMemcpyDeviceToHost, st));
             if (scoring) HIPCHK(h, hipMemcpyAsync(score->score_out, d_score, sizeof(uint32_t) * 16 * (size_t)B, hipMemcpyDeviceToHost, st));
             if (AM > 0 && obs->xhist_next) {
                 hn.resize((size_t)AM * HR);
@@ -1879,6 +2006,14 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                     if (io.us) memcpy(io.us + ((size_t)b * T + k) * m, &hu[r * m], sizeof(float) * m);
                     if (rate && rate->ws) memcpy(rate->ws + ((size_t)b * T + k) * 4, &hw[r * 4], sizeof(float) * 4);
                 }
+        if (gproc && proc->dist_rows)
+            for (int kc = 0; kc < nk; ++kc)
+                for (int b = 0; b < B; ++b)
+                    memcpy(proc->dist_rows + ((size_t)b * T + k0 + kc) * NG, &hg[((size_t)kc * B + b) * NG], sizeof(float) * NG);
+        if (bproc && proc->bias_rows)
+            for (int jc = 0; jc < np; ++jc)
+                for (int b = 0; b < B; ++b)
+                    memcpy(proc->bias_rows + ((size_t)b * Ns + j0 + jc) * NB, &hb[((size_t)jc * B + b) * NB], sizeof(float) * NB);
         if (subs_out)
             for (size_t rr = 0; rr < (size_t)nk * nsub; ++rr)
                 for (int b = 0; b < B; ++b)

@@ -264,8 +264,30 @@ struct LoopScore {
     float r2_pos, cos_min, w2_max;      // thresholds: squared radius, cosine of the tilt, squared rate (+inf, -inf, +inf: off); never NaN
     float u_lo[8], u_hi[8], uref[8];    // of motor j < m (wave-uniform kernel arguments, read at constant indices)
 };
+// SPEC.md §11i, gusts and estimator bias drawn on the device: a first-order Gauss-Markov process per component and episode, stepped by the period's key-schedule
+// thread of episode b beside its schedule. One step: (c, e) = split(c), xi = normal(e, (W,)) (counter i pairs with i + W / 2), t_i = scale_i * xi_i (rounded),
+// g_i = fma(rho_i, g_i, t_i), row_i = g_i, or d_i + g_i when a scheduled input d is given as well. The disturbance half (W = 6) takes one step per control tick of
+// the period and writes row (i, b) of dst, f32[ticks][B][6], which the plant launch then reads as its LoopScenario::dist (tick stride B * 6, episode stride 6); sched
+// addresses the PERIOD's first tick. The bias half (W = 12) takes one step per launch, before the measurement is formed, dropout or not, and writes dst[b], f32[B][12]:
+// the beta of this solve, read back by the same thread in place of LoopObserve::beta (which must then be null; the scheduled rows go to sched, of SOLVE j). chain
+// null means absent: the kernel then makes no memory access it did not make before.
+struct LoopProcessHalf {
+    uint32_t* chain;            // [B][2] the process key chain, advanced in place; null: no process
+    float* state;               // [B][W] g: in, and out
+    const float* rho;           // rho of episode b at rho[b * par_ep_stride + 0..W-1]
+    const float* scale;         // scale, same layout
+    int par_ep_stride;          // floats between two episodes' rows of rho / scale: W, or 0 (one row for every episode)
+    const float* sched;         // the scheduled input d of step i, episode b at sched[i * sched_tick_stride + b * sched_ep_stride + 0..W-1], or null: none
+    int sched_tick_stride;      // floats between two steps' rows: Bd * W, or 0 (one row for every step)
+    int sched_ep_stride;        // floats between two episodes' rows: W, or 0 (one row for every episode)
+    float* dst;                 // the rows written: [ticks][B][6] (disturbance) or [B][12] (bias)
+};
+struct LoopProcess {
+    LoopProcessHalf dist;       // W = 6, one step per control tick
+    LoopProcessHalf bias;       // W = 12, one step per solve; needs LoopObserve::q
+};
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st,
-                                   const LoopObserve& O = LoopObserve{}, const LoopScore& Z = LoopScore{});
+                                   const LoopObserve& O = LoopObserve{}, const LoopScore& Z = LoopScore{}, const LoopProcess& G = LoopProcess{});
 // rows_dev[b][0..n) = row_dev[0..n) for b < B
 hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st);
 // canonical [B][P][C] <-> device [B][G][C][32] (to_dev: zero-pads particles >= P)

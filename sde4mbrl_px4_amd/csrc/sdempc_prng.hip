@@ -219,8 +219,12 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
 // SPEC.md §11h (Z.words given; ticks = 0, O empty, keys / sub / xi null and untouched): the SCORING form of the launch, one per chunk. Thread b walks the chunk's rows
 // of its episode in time order — rows, then tick rows, then solve rows; the buffers are [row][B][.], so neighbouring threads read neighbouring rows — and carries
 // the 16 score words of the episode in registers from Z.words[b] back to Z.words[b]. Z.words null (every period launch): not one access more.
+// SPEC.md §11i (G.bias.chain / G.dist.chain given): the same thread steps the episode's Gauss-Markov processes — the bias process once, in front of the measurement,
+// whose beta is then the row this thread has just written (dropout or not); the disturbance process once per tick, beside the schedule's tick loop, into row (i, b) of
+// the period's disturbance rows. One step is one split, W / 2 blocks, and per component one multiply and one fma (kept apart: -ffp-contract=off). Both null: not one
+// access more.
 __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int ticks,
-                                                                      int xi_ticks, int n, LoopObserve O, LoopScore Z) {
+                                                                      int xi_ticks, int n, LoopObserve O, LoopScore Z, LoopProcess G) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     if (Z.words) {                                       // (wave-uniform)
@@ -284,6 +288,29 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
         w[13] = nit; w[14] = nls; w[15] = flat;
         return;
     }
+    const float* pbeta = nullptr;                    // this solve's beta where the bias process wrote it
+    if (G.bias.chain) {                                  // (wave-uniform)
+        const LoopProcessHalf& Pb = G.bias;
+        uint32_t c2[2], ek[2];
+        split2(Pb.chain[2 * b], Pb.chain[2 * b + 1], c2, ek);
+        Pb.chain[2 * b] = c2[0]; Pb.chain[2 * b + 1] = c2[1];
+        float* g = Pb.state + (size_t)b * 12;
+        const float* rh = Pb.rho + (size_t)b * Pb.par_ep_stride;
+        const float* sc = Pb.scale + (size_t)b * Pb.par_ep_stride;
+        const float* d = Pb.sched ? Pb.sched + (size_t)b * Pb.sched_ep_stride : nullptr;
+        float* row = Pb.dst + (size_t)b * 12;
+#pragma unroll
+        for (uint32_t i = 0; i < 6; ++i) {
+            uint32_t x0 = i, x1 = i + 6u;
+            threefry2x32(ek[0], ek[1], x0, x1);
+            const float t0 = sc[i] * bits_to_normal(x0), t1 = sc[i + 6] * bits_to_normal(x1);
+            const float g0 = FMA(rh[i], g[i], t0), g1 = FMA(rh[i + 6], g[i + 6], t1);
+            g[i] = g0; g[i + 6] = g1;
+            row[i] = d ? d[i] + g0 : g0;
+            row[i + 6] = d ? d[i + 6] + g1 : g1;
+        }
+        pbeta = row;
+    }
     if (O.q) {
         uint32_t q2[2], me[2];
         split2(O.q[2 * b], O.q[2 * b + 1], q2, me);
@@ -296,7 +323,7 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
                 if (A > 0) x = O.hist + (size_t)(O.age_max - A) * O.hist_row_stride + (size_t)b * 13;
             }
             const float* sg = O.sigma ? O.sigma + (size_t)b * O.ep_stride : nullptr;
-            const float* bt = O.beta ? O.beta + (size_t)b * O.ep_stride : nullptr;
+            const float* bt = pbeta ? pbeta : O.beta ? O.beta + (size_t)b * O.ep_stride : nullptr;
             float e[12];
 #pragma unroll
             for (uint32_t i = 0; i < 6; ++i) {
@@ -329,7 +356,34 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
     }
     uint32_t r[2] = {keys[2 * b], keys[2 * b + 1]};
     const uint32_t half = 3u * (uint32_t)n;
+    const LoopProcessHalf& Pd = G.dist;
+    uint32_t dc[2] = {0u, 0u};
+    float dg[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // (constant indices after unrolling: registers)
+    if (Pd.chain) {                                      // (wave-uniform)
+        dc[0] = Pd.chain[2 * b]; dc[1] = Pd.chain[2 * b + 1];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) dg[e] = Pd.state[(size_t)b * 6 + e];
+    }
     for (int i = 0; i < ticks; ++i) {
+        if (Pd.chain) {
+            uint32_t c2[2], ek[2];
+            split2(dc[0], dc[1], c2, ek);
+            dc[0] = c2[0]; dc[1] = c2[1];
+            const float* rh = Pd.rho + (size_t)b * Pd.par_ep_stride;
+            const float* sc = Pd.scale + (size_t)b * Pd.par_ep_stride;
+            const float* d = Pd.sched ? Pd.sched + (size_t)i * Pd.sched_tick_stride + (size_t)b * Pd.sched_ep_stride : nullptr;
+            float* row = Pd.dst + ((size_t)i * B + b) * 6;
+#pragma unroll
+            for (uint32_t e = 0; e < 3; ++e) {
+                uint32_t x0 = e, x1 = e + 3u;
+                threefry2x32(ek[0], ek[1], x0, x1);
+                const float t0 = sc[e] * bits_to_normal(x0), t1 = sc[e + 3] * bits_to_normal(x1);
+                dg[e] = FMA(rh[e], dg[e], t0);
+                dg[e + 3] = FMA(rh[e + 3], dg[e + 3], t1);
+                row[e] = d ? d[e] + dg[e] : dg[e];
+                row[e + 3] = d ? d[e + 3] + dg[e + 3] : dg[e + 3];
+            }
+        }
         uint32_t r2[2], p[2];
         if (i == 0) {
             uint32_t r1[2], s[2];
@@ -347,15 +401,20 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
         }
     }
     keys[2 * b] = r[0]; keys[2 * b + 1] = r[1];
+    if (Pd.chain) {
+        Pd.chain[2 * b] = dc[0]; Pd.chain[2 * b + 1] = dc[1];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) Pd.state[(size_t)b * 6 + e] = dg[e];
+    }
 }
 
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st, const LoopObserve& O,
-                                   const LoopScore& Z) {
+                                   const LoopScore& Z, const LoopProcess& G) {
     if (B < 1 || substeps < 1 || ticks < 0 || xi_ticks < ticks) return hipErrorInvalidValue;
     // ticks = 0 is the scoring form and nothing else: score words, no observation, no key buffers
     if ((ticks == 0) != (Z.words != nullptr)) return hipErrorInvalidValue;
     if (Z.words) {
-        if (O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev) return hipErrorInvalidValue;
+        if (O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev || G.dist.chain || G.bias.chain) return hipErrorInvalidValue;
         if (!Z.rows || !Z.us || !Z.info || !Z.ref || Z.ticks < 1 || Z.solves < 1 || Z.solves > Z.ticks || Z.rows_per_tick < 1 || Z.m < 1 || Z.m > 8) return hipErrorInvalidValue;
         if ((Z.ref_tick_stride != 0 && Z.ref_tick_stride < 13) || (Z.ref_ep_stride != 0 && Z.ref_ep_stride != 13)) return hipErrorInvalidValue;
         if (Z.r2_pos != Z.r2_pos || Z.cos_min != Z.cos_min || Z.w2_max != Z.w2_max) return hipErrorInvalidValue;
@@ -363,7 +422,16 @@ hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float*
     if (O.q && (!O.x || !O.xm || !O.xmeas || (O.ep_stride != 0 && O.ep_stride != 12) || (O.valid_ep_stride != 0 && O.valid_ep_stride != 1))) return hipErrorInvalidValue;
     if ((O.age || O.renorm) && !O.q) return hipErrorInvalidValue;
     if (O.age && (!O.hist || O.age_max < 1 || O.hist_row_stride < B * 13 || (O.age_ep_stride != 0 && O.age_ep_stride != 1))) return hipErrorInvalidValue;
-    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z);
+    // SPEC.md §11i: a present half is complete, its strides are W or 0 (Bd * W or 0 between steps), and the bias half replaces O.beta of an observation
+    for (int w = 0; w < 2; ++w) {
+        const LoopProcessHalf& P = w ? G.bias : G.dist;
+        const int W = w ? 12 : 6;
+        if (!P.chain) continue;
+        if (!P.state || !P.rho || !P.scale || !P.dst || (P.par_ep_stride != 0 && P.par_ep_stride != W)) return hipErrorInvalidValue;
+        if (P.sched && ((P.sched_ep_stride != 0 && P.sched_ep_stride != W) || (P.sched_tick_stride != 0 && P.sched_tick_stride < W))) return hipErrorInvalidValue;
+    }
+    if (G.bias.chain && (!O.q || O.beta)) return hipErrorInvalidValue;
+    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z, G);
     return hipGetLastError();
 }
 

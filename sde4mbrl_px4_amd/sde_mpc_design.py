@@ -140,7 +140,7 @@ class MpcProblem:
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
                  plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,
                  fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None, meas_age=None, meas_renorm=False,
-                 score=None, score_ref=None):
+                 score=None, score_ref=None, dist_process=None, dist_rng=None, dist_state=None, bias_process=None, bias_rng=None, bias_state=None):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -177,7 +177,13 @@ class MpcProblem:
         score / score_ref (SPEC.md §11h): score is a solver.Score; the episode's 16 score words, formed on the device, are appended behind every value above as a
         structured array [1] (solver.SCORE_DTYPE; xsub stays the LAST value), and the call is the timed one. score_ref f32[T][13] or f32[13] is the target each scored
         state of tick k is compared with, GIVEN IN THE FRAME OF x and converted by enu2ned like xs. Its default is the reference at the END of each tick: the loaded
-        trajectory at curr_t + (k + 1) * dt_0 (already in the solver's frame, as every reference window is), else xdes. score_ref without score raises ValueError."""
+        trajectory at curr_t + (k + 1) * dt_0 (already in the solver's frame, as every reference window is), else xdes. score_ref without score raises ValueError.
+        dist_process / dist_rng / dist_state and bias_process / bias_rng / bias_state (SPEC.md §11i): a solver.GaussMarkov drawn on the device — a gust per control
+        tick (width 6, added to `disturbance` when given) or an estimator bias per solve (width 12, added to `meas_bias` when given; the call is then an observed one
+        and needs meas_rng) — with its own key uint32[2] (required) and a start state f32[W] (None: zeros), GIVEN IN THE FRAME OF x. Under convert_to_enu the
+        coefficients rho and scale take the permutation without the sign, as meas_noise does, and the state in, the state out and the returned rows follow the signed
+        vector rules of `disturbance` and `meas_bias`. Behind the score and before xsub come, per process given (disturbance first), its rows f32[T][6] / f32[Ns][12],
+        its key after the run and its state after the run. A key or a state without its process raises ValueError."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -216,10 +222,10 @@ class MpcProblem:
             more["fault"] = f[None, None] if f.ndim == 2 else f[:, None]
         if substep_states:
             more["substep_states"] = True
-        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None
+        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None or bias_process is not None
         if observed:
             if meas_rng is None:
-                raise ValueError("MpcProblem.simulate: meas_rng (uint32[2], the observation key) is required with meas_noise / meas_bias / meas_valid")
+                raise ValueError("MpcProblem.simulate: meas_rng (uint32[2], the observation key) is required with meas_noise / meas_bias / meas_valid / bias_process")
             Ns = -(-T // max(int(solve_period), 1))
             for name, v, signed in (("meas_noise", meas_noise, False), ("meas_bias", meas_bias, True)):
                 if v is None:
@@ -252,6 +258,25 @@ class MpcProblem:
             hist = int(a.max()) > 0
         if meas_renorm:
             more["meas_renorm"] = True
+        drawn = []
+        for name, idx, sgn, proc, pk, ps in (("dist", _PERM6, _SIGN6, dist_process, dist_rng, dist_state), ("bias", _PERM12, _SIGN12, bias_process, bias_rng, bias_state)):
+            if proc is None:
+                if pk is not None or ps is not None:
+                    raise ValueError(f"MpcProblem.simulate: {name}_rng / {name}_state need {name}_process=GaussMarkov(...)")
+                continue
+            if pk is None:
+                raise ValueError(f"MpcProblem.simulate: {name}_rng (uint32[2], the process key) is required with {name}_process")
+            from .solver import GaussMarkov
+            if not isinstance(proc, GaussMarkov):
+                raise ValueError(f"MpcProblem.simulate: {name}_process must be a solver.GaussMarkov")
+            W = len(idx)
+            rho, scale = proc.coeffs(1, W)
+            g0 = None if ps is None else np.asarray(ps, np.float32).reshape(1, W)
+            if self.convert_to_enu:        # (a scale takes the permutation without the sign; a state is a signed vector)
+                rho, scale = rho[:, idx], scale[:, idx]
+                g0 = None if g0 is None else np.ascontiguousarray(g0[:, idx] * sgn)
+            more.update({f"{name}_process": GaussMarkov.from_coeffs(rho, scale), f"{name}_keys": np.asarray(pk, dtype=np.uint32).reshape(1, 2), f"{name}_state_in": g0})
+            drawn.append((idx, sgn))
         if score is None and score_ref is not None:
             raise ValueError("MpcProblem.simulate: score_ref needs score=Score(...)")
         if score is not None:
@@ -280,6 +305,17 @@ class MpcProblem:
         st = OptState(_arr(u_next[0]), np.float32(i[0]), np.float32(s_next[0]), np.float32(i[2]), np.float32(i[3]), np.float32(i[4]),
                       np.float32(i[5]), np.float32(i[6]), np.float32(i[7]))
         ret = (_arr(xs), _arr(us[0]), _arr(info[0]), st, k_next[0].copy())
+        prows = ()
+        if drawn:                       # the processes' values sit behind the score, in front of xsub: rows, key and state of each, back in the frame of x
+            tail = out[-1:] if substep_states else ()
+            body = out[:-1] if substep_states else out
+            vals, body = body[len(body) - 3 * len(drawn):], body[:len(body) - 3 * len(drawn)]
+            for i, (idx, sgn) in enumerate(drawn):
+                rows_, k_, g_ = vals[3 * i][0], vals[3 * i + 1][0], vals[3 * i + 2][0]
+                if self.convert_to_enu:
+                    rows_, g_ = rows_[..., idx] * sgn, g_[..., idx] * sgn
+                prows += (_arr(np.ascontiguousarray(rows_, np.float32)), k_.copy(), _arr(np.ascontiguousarray(g_, np.float32)))
+            out = body + tail
         zrow = None
         if score is not None:           # the score sits behind every other value, in front of xsub
             zrow = out[-2] if substep_states else out[-1]
@@ -294,10 +330,18 @@ class MpcProblem:
                 ret += (_arr(enu2ned(xhist, np) if self.convert_to_enu else xhist),)
         if zrow is not None:
             ret += (zrow,)
+        ret += prows
         if substep_states:
             xsub = out[-1][0]
             ret += (_arr(enu2ned(xsub, np) if self.convert_to_enu else xsub),)
         return ret
+
+# SPEC.md §11c / §11f under convert_to_enu: a world vector (x, y, z) -> (y, x, -z), a body vector (wx, wy, wz) -> (wx, -wy, -wz); each map is its own inverse
+_PERM6 = np.array([1, 0, 2, 3, 4, 5])
+_SIGN6 = np.array([1, 1, -1, 1, -1, -1], np.float32)
+_PERM12 = np.array([1, 0, 2, 4, 3, 5, 6, 7, 8, 9, 10, 11])
+_SIGN12 = np.array([1, 1, -1, 1, 1, -1, 1, -1, -1, 1, -1, -1], np.float32)
+
 
 def _allow_synthetic(flag) -> bool:
     return bool(flag) if flag is not None else os.environ.get("SDEMPC_ALLOW_SYNTHETIC") == "1"

@@ -100,7 +100,8 @@ def gauss_markov_bias(Ns, B, std, tau, solve_dt, rng, state=None):
     so that every b_j has deviation std (the stationary one) and consecutive rows correlate with rho. std and tau are scalars or broadcast against [B][12] (order p, v,
     theta, omega, as meas_bias). `state` f64[B][12] is b_{-1} (the second value a previous call returned, to continue a run); None draws it from the stationary
     distribution. Computed in float64 and cast once. Returns (beta, state): the rows and the last b in float64. This is the answer to "coloured noise": the device
-    loop needs no keyword for it, since meas_bias rows carry any error sequence the caller draws; add white noise on top with meas_noise."""
+    loop needs no keyword for it, since meas_bias rows carry any error sequence the caller draws; add white noise on top with meas_noise.
+    closed_loop(bias_process=GaussMarkov(...), bias_keys=...) draws the same process on the device from keys (SPEC.md §11i), with no host rows at all."""
     Ns, B = int(Ns), int(B)
     std = np.broadcast_to(np.asarray(std, np.float64), (B, 12))
     tau = np.broadcast_to(np.asarray(tau, np.float64), (B, 12))
@@ -114,6 +115,60 @@ def gauss_markov_bias(Ns, B, std, tau, solve_dt, rng, state=None):
         b = rho * b + scale * rng.standard_normal((B, 12))
         out[j] = b
     return out.astype(np.float32), b
+
+
+class GaussMarkov:
+    """A first-order Gauss-Markov process per component and episode, drawn ON THE DEVICE from a key chain (SPEC.md §11i): closed_loop(dist_process=...) steps it once
+    per control tick into the disturbance row (width 6: w_v, w_omega), closed_loop(bias_process=...) once per solve into the estimator bias (width 12: p, v, theta,
+    omega). One step is g <- fma(rho, g, scale * xi), xi a standard normal of the step's key. GaussMarkov(std, tau, dt): std the stationary deviation, tau the
+    correlation time and dt the time between two steps (a control tick or a solve period), both in seconds; rho = exp(-dt / tau) and scale = std * sqrt(1 - rho^2) are
+    computed in float64 and cast to float32 once, as gauss_markov_bias does. std and tau are scalars or broadcast against [B][W]. from_coeffs(rho, scale) takes the
+    two float32 coefficients as they are (rho in [0, 1], scale finite and >= 0)."""
+
+    def __init__(self, std, tau, dt):
+        std, tau = np.asarray(std, np.float64), np.asarray(tau, np.float64)
+        if not (np.isfinite(std).all() and (std >= 0).all()) or not (tau > 0).all() or not float(dt) > 0:
+            raise ValueError("GaussMarkov: std finite and >= 0, tau > 0 and dt > 0 are required")
+        rho = np.exp(-float(dt) / tau)
+        std, rho = np.broadcast_arrays(std, rho)
+        self.std = np.array(std, np.float64)
+        self.rho = np.asarray(rho, np.float64).astype(np.float32)
+        self.scale = (std * np.sqrt(1.0 - rho * rho)).astype(np.float32)
+
+    @classmethod
+    def from_coeffs(cls, rho, scale):
+        rho, scale = np.broadcast_arrays(np.asarray(rho, np.float32), np.asarray(scale, np.float32))
+        if not (np.isfinite(scale).all() and (scale >= 0).all()) or not ((rho >= 0).all() and (rho <= 1).all()):
+            raise ValueError("GaussMarkov.from_coeffs: rho in [0, 1] and scale finite and >= 0 are required")
+        self = cls.__new__(cls)
+        self.rho, self.scale = np.array(rho, np.float32), np.array(scale, np.float32)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = self.rho.astype(np.float64)
+            self.std = np.where(self.scale > 0, self.scale.astype(np.float64) / np.sqrt(1.0 - r * r), 0.0)
+        return self
+
+    def coeffs(self, B, W):
+        """(rho, scale) as contiguous f32[Bp][W], Bp = 1 (one row for all episodes) or B."""
+        out = []
+        for a in (self.rho, self.scale):
+            a = a.reshape((1,) * (2 - a.ndim) + a.shape) if a.ndim < 2 else a
+            if a.ndim != 2 or a.shape[0] not in (1, B) or a.shape[1] not in (1, W):
+                raise ValueError(f"GaussMarkov: std / tau must be scalars or broadcast against [{B}][{W}], got {a.shape}")
+            out.append(np.ascontiguousarray(np.broadcast_to(a, (a.shape[0], W)), np.float32))
+        return out[0], out[1]
+
+    def stationary_state(self, rng, B, W=None):
+        """A start from the stationary distribution: std * N(0, 1) from `rng` (a numpy Generator), f32[B][W]. W defaults to the last axis of std / tau."""
+        if W is None:
+            W = self.std.shape[-1] if self.std.ndim else 0
+        if W not in (6, 12):
+            raise ValueError("GaussMarkov.stationary_state: pass W=6 (disturbance) or W=12 (bias) when std and tau do not carry the component axis")
+        if not np.isfinite(self.std).all():
+            raise ValueError("GaussMarkov.stationary_state: a component with rho = 1 has no stationary distribution")
+        return (np.broadcast_to(self.std, (int(B), W)) * rng.standard_normal((int(B), W))).astype(np.float32)
+
+    def __repr__(self):
+        return f"GaussMarkov.from_coeffs(rho={self.rho.tolist()}, scale={self.scale.tolist()})"
 
 
 class Score:
@@ -310,7 +365,7 @@ class SdeMpcSolver:
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
                     rate_loop=None, rate_integ_in=None, rate_tail_in=None, fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None,
                     meas_keys=None, xmeas_in=None, meas_age=None, meas_age_max=None, meas_renorm=False, xhist_in=None, score=None, score_ref=None, score_in=None,
-                    outputs=True):
+                    outputs=True, dist_process=None, dist_keys=None, dist_state_in=None, bias_process=None, bias_keys=None, bias_state_in=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -396,7 +451,19 @@ class SdeMpcSolver:
         score of the joined run when the first call's T is a multiple of solve_period. outputs=False passes NULL for the per-row outputs — xs, us, info, ws, xmeas and
         xsub are then neither copied back nor scattered, and None stands in their places in the returned tuple; the continuation values and the score are
         unchanged. The score depends on nothing but the episode: not on B, the chunking or the outputs requested. score_ref / score_in / outputs=False without score
-        raise ValueError; with none of the four given nothing of this paragraph is touched."""
+        raise ValueError; with none of the four given nothing of this paragraph is touched.
+
+        dist_process / dist_keys / dist_state_in and bias_process / bias_keys / bias_state_in (SPEC.md §11i, sdempc_closed_loop_batch_drawn): gusts and estimator bias
+        DRAWN ON THE DEVICE, so that a campaign is described by keys and O(B) parameters instead of [T][B][6] and [Ns][B][12] host arrays. Each process is a GaussMarkov
+        (rho and scale per component, shared or per episode) with its own key chain uint32[B][2] (required) and a start state f32[B][W] (None: zeros;
+        GaussMarkov.stationary_state draws a stationary one). dist_process (W = 6) takes one step per control TICK, ticks inside a solve period included, and its state
+        g is the tick's disturbance row (added, in float32, to the row of `disturbance` when that is given as well); it makes the call a scenario run. bias_process
+        (W = 12) takes one step per SOLVE, valid or not — a dropout holds the estimate, the error process keeps running — and g is the solve's beta (added to the row
+        of `meas_bias` when given); it makes the call an observed one and needs meas_keys, whose chain it does not touch. Behind the score and before xsub (which
+        stays LAST) come, with dist_process, dist_rows f32[B][T][6] (the rows the plant read), dist_keys_next and dist_state_next, and with bias_process bias_rows
+        f32[B][Ns][12], bias_keys_next and bias_state_next; the rows are None under outputs=False. Carrying the *_next values back in continues the run bit for bit:
+        the disturbance process for any T, the bias process when T is a multiple of solve_period. A process without its keys, or keys / a state without the process,
+        raises ValueError; with none of the six given nothing of this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -440,12 +507,31 @@ class SdeMpcSolver:
             if not np.isfinite(flt).all():
                 raise ValueError("closed_loop: fault holds a non-finite entry")
             flt = np.ascontiguousarray(flt)
-        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None
+        procs = {}
+        for name, W_, proc, pk, ps in (("dist", 6, dist_process, dist_keys, dist_state_in), ("bias", 12, bias_process, bias_keys, bias_state_in)):
+            if proc is None:
+                if pk is not None or ps is not None:
+                    raise ValueError(f"closed_loop: {name}_keys / {name}_state_in need {name}_process=GaussMarkov(...)")
+                continue
+            if not isinstance(proc, GaussMarkov):
+                raise ValueError(f"closed_loop: {name}_process must be a GaussMarkov")
+            if pk is None:
+                raise ValueError(f"closed_loop: {name}_keys (uint32[B][2], the process chain) is required with {name}_process")
+            rho_, scale_ = proc.coeffs(B, W_)
+            if not (np.isfinite(rho_).all() and (rho_ >= 0).all() and (rho_ <= 1).all() and np.isfinite(scale_).all() and (scale_ >= 0).all()):
+                raise ValueError(f"closed_loop: {name}_process needs rho in [0, 1] and scale finite and >= 0")
+            ps = None if ps is None else _f32(ps, (B, W_))
+            if ps is not None and not np.isfinite(ps).all():
+                raise ValueError(f"closed_loop: {name}_state_in holds a non-finite entry")
+            procs[name] = (W_, rho_, scale_, self._keys(pk, B), ps)
+        drawn = bool(procs)
+        scenario = scenario or "dist" in procs
+        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None or "bias" in procs
         if not observed and (meas_keys is not None or xmeas_in is not None):
-            raise ValueError("closed_loop: meas_keys / xmeas_in need one of meas_noise / meas_bias / meas_valid")
+            raise ValueError("closed_loop: meas_keys / xmeas_in need one of meas_noise / meas_bias / meas_valid / bias_process")
         if observed:
             if meas_keys is None:
-                raise ValueError("closed_loop: meas_keys (uint32[B][2], the observation chain) is required with meas_noise / meas_bias / meas_valid")
+                raise ValueError("closed_loop: meas_keys (uint32[B][2], the observation chain) is required with meas_noise / meas_bias / meas_valid / bias_process")
             meas_keys = self._keys(meas_keys, B)
             Ns_o = -(-max(T, 0) // max(int(solve_period), 1))
 
@@ -521,7 +607,8 @@ class SdeMpcSolver:
                 score_in = np.ascontiguousarray(score_in)
                 if score_in.dtype != SCORE_DTYPE or score_in.shape != (B,):
                     raise ValueError(f"closed_loop: score_in must be the structured score array [{B}] a previous call returned, got dtype {score_in.dtype} and shape {score_in.shape}")
-        faulted = flt is not None or bool(substep_states) or observed or scored
+        faulted = flt is not None or bool(substep_states) or observed or scored or drawn
+        full = scored or drawn          # the entry points from the scored one on take every layer's arguments, NULL where a layer is absent
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
             raise ValueError("closed_loop: rate_integ_in / rate_tail_in need rate_loop=...")
         if rate_loop is not None and not isinstance(rate_loop, RateLoop):
@@ -631,7 +718,7 @@ class SdeMpcSolver:
                 xm_next = np.zeros((B, 13), np.float32)
                 lead = [C.byref(oc), meas_keys.ctypes.data_as(u32p), None if xmeas_in is None else _fp(xmeas_in)] + lead
                 more, ret = more + (None if xmeas is None else _fp(xmeas), q_next.ctypes.data_as(u32p), _fp(xm_next)), ret + (xmeas, q_next, xm_next)
-            elif scored:            # (no observation: a NULL obs cfg and NULL observation pointers)
+            elif full:              # (no observation: a NULL obs cfg and NULL observation pointers)
                 lead, more = [None, None, None] + lead, more + (None, None, None)
             if aged:                # the observed entry point's arguments behind (age cfg, xhist_in), then xhist_next
                 ac = _abi.SdempcAgeCfg(C.sizeof(_abi.SdempcAgeCfg), None if age_rows is None else age_rows.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -641,7 +728,7 @@ class SdeMpcSolver:
                 more = more + (None if xh_next is None else _fp(xh_next),)
                 if xh_next is not None:
                     ret = ret + (xh_next,)
-            elif scored:            # (no age: a NULL age cfg and NULL history pointers)
+            elif full:              # (no age: a NULL age cfg and NULL history pointers)
                 lead, more = [None, None] + lead, more + (None,)
             if scored:              # the aged entry point's arguments behind (score cfg, score_in), then score_out
                 zc = _abi.SdempcScoreCfg(C.sizeof(_abi.SdempcScoreCfg), int(score.substeps), float(score.r2_pos), float(score.cos_min), float(score.w2_max), _fp(sref),
@@ -649,10 +736,30 @@ class SdeMpcSolver:
                 z_out = np.zeros(B, SCORE_DTYPE)
                 lead = [C.byref(zc), None if score_in is None else score_in.ctypes.data_as(u32p)] + lead
                 more, ret = more + (z_out.ctypes.data_as(u32p),), ret + (z_out,)
+            elif drawn:             # (no score: a NULL score cfg and NULL score pointers)
+                lead, more = [None, None] + lead, more + (None,)
+            if drawn:               # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
+                cfgs, keep_p = [], []
+                for name, Nrows in (("dist", max(T, 0)), ("bias", max(Ns, 0))):
+                    if name not in procs:
+                        cfgs.append(None)
+                        more = more + (None, None, None)
+                        continue
+                    W_, rho_, scale_, pk, ps = procs[name]
+                    pcfg = _abi.SdempcProcessCfg(C.sizeof(_abi.SdempcProcessCfg), rho_.shape[0], _fp(rho_), _fp(scale_), pk.ctypes.data_as(u32p), None if ps is None else _fp(ps))
+                    keep_p.append(pcfg)
+                    cfgs.append(C.byref(pcfg))
+                    p_rows = np.zeros((B, Nrows, W_), np.float32) if outputs else None
+                    p_keys, p_state = np.zeros((B, 2), np.uint32), np.zeros((B, W_), np.float32)
+                    more = more + (None if p_rows is None else _fp(p_rows), p_keys.ctypes.data_as(u32p), _fp(p_state))
+                    ret = ret + (p_rows, p_keys, p_state)
+                lead = cfgs + lead
             if substep_states:
                 ret = ret + (xsub,)
         # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
-        if scored:
+        if drawn:
+            entry = _abi.drawn_entry(self.lib)
+        elif scored:
             entry = _abi.scored_entry(self.lib)
         elif aged:
             entry = _abi.aged_entry(self.lib)

@@ -32,10 +32,15 @@
      and a rate of 6 rad/s around a hover target per tick and episode (the target rows are staged per chunk), one scoring launch per chunk; --score-substeps scores every
      plant substep state (a substep region in the chunk); --no-outputs passes NULL for the per-row outputs, so nothing but the continuation values and B x 64 bytes of
      score come back. Applies to --small-batch and to the C2 loop; it makes the call the timed one. The last run's score_summary is printed.
+ 11. --dist-process / --bias-process: gusts and estimator bias drawn on the device from key chains (SPEC.md §11i, sdempc_closed_loop_batch_drawn) instead of host rows — a
+     first-order Gauss-Markov process per component and episode, coefficients per episode: --dist-process one step per control tick (deviations around 1 m/s^2 and
+     1.5 rad/s^2, correlation times around 0.3 s; with --disturbance as well the host rows are the scheduled part the process is added to), --bias-process one step
+     per solve with --observe, whose meas_bias rows it REPLACES (noise and dropouts stay host rows). Apply to --small-batch and to the C2 loop; either makes the call
+     the timed one. So `--disturbance --observe` against `--dist-process --observe --bias-process` is host rows against keys for the same two ingredients.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
                                         [--fault] [--substep-states] [--observe] [--age A] [--renorm]
-                                        [--score] [--no-outputs] [--score-substeps]
+                                        [--score] [--no-outputs] [--score-substeps] [--dist-process] [--bias-process]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -77,12 +82,17 @@ ap.add_argument("--renorm", action="store_true", help="with --observe: renormali
 ap.add_argument("--score", action="store_true", help="score every episode on the device (SPEC.md §11h)")
 ap.add_argument("--no-outputs", action="store_true", help="with --score: NULL per-row outputs, only the continuation values and the score come back")
 ap.add_argument("--score-substeps", action="store_true", help="with --score: score every plant substep state instead of every tick state")
+ap.add_argument("--dist-process", action="store_true", help="gusts drawn on the device, one Gauss-Markov step per control tick (SPEC.md §11i)")
+ap.add_argument("--bias-process", action="store_true", help="with --observe: the estimator bias drawn on the device, one Gauss-Markov step per solve, instead of meas_bias rows (SPEC.md §11i)")
 a = ap.parse_args()
+if a.bias_process and not a.observe:
+    ap.error("--bias-process needs --observe")
 if (a.age >= 0 or a.renorm) and not a.observe:
     ap.error("--age / --renorm need --observe")
 if (a.no_outputs or a.score_substeps) and not a.score:
     ap.error("--no-outputs / --score-substeps need --score")
 model = synthetic_iris()
+DT_TICK = 0.05      # the first step length of the shipped configurations: the time between two control ticks
 if a.plant == "own" and a.substeps != 1:
     ap.error("--substeps needs --plant one or per-episode")
 
@@ -127,6 +137,17 @@ def scenario_kw(kw, B, T):
             kw["meas_age_max"] = a.age
         if a.renorm:
             kw["meas_renorm"] = True
+    if a.dist_process or a.bias_process:
+        from sde4mbrl_px4_amd.solver import GaussMarkov
+        rng = np.random.default_rng(8)
+        if a.dist_process:
+            gm = GaussMarkov(np.array([1.0, 1.0, 0.6, 1.5, 1.5, 1.0]) * rng.uniform(0.5, 1.5, (B, 6)), rng.uniform(0.1, 0.6, (B, 6)), DT_TICK)
+            kw.update(dist_process=gm, dist_keys=np.stack([prng.PRNGKey(20000 + b) for b in range(B)]), dist_state_in=gm.stationary_state(rng, B))
+        if a.bias_process:
+            scale = np.repeat(np.array([0.05, 0.1, 0.02, 0.05]), 3)
+            gm = GaussMarkov(0.3 * scale * rng.uniform(0.5, 1.5, (B, 12)), rng.uniform(0.3, 2.0, (B, 12)), DT_TICK * max(a.period, 1))
+            kw.pop("meas_bias")
+            kw.update(bias_process=gm, bias_keys=np.stack([prng.PRNGKey(30000 + b) for b in range(B)]), bias_state_in=gm.stationary_state(rng, B))
     if a.score:
         from sde4mbrl_px4_amd.solver import Score
         kw["score"] = Score(pos_radius=1.0, tilt_max=0.6, rate_max=6.0, substeps=a.score_substeps)
@@ -172,6 +193,10 @@ if a.age >= 0:
     tag += f" age<={a.age}"
 if a.renorm:
     tag += " renorm"
+if a.dist_process:
+    tag += " dist-process"
+if a.bias_process:
+    tag += " bias-process"
 if a.score:
     tag += " score" + ("/substeps" if a.score_substeps else "") + (" no-outputs" if a.no_outputs else "")
 
@@ -181,7 +206,8 @@ def report_score(out, T):
     if not a.score:
         return
     from sde4mbrl_px4_amd.solver import score_summary
-    s = score_summary(out[-2] if a.substep_states else out[-1], solves=-(-T // max(a.period, 1)))
+    at = -1 - (1 if a.substep_states else 0) - 3 * (int(a.dist_process) + int(a.bias_process))      # the score sits in front of the process values and of xsub
+    s = score_summary(out[at], solves=-(-T // max(a.period, 1)))
     print(f"  score: success {s['success_rate']:.3f}, median RMS position error {float(np.median(s['rms_pos_err'])):.3f} m, worst tilt {s['worst_tilt_deg']:.1f} deg, "
           f"{s['mean_steps']:.2f} iterations and {s['mean_ls_trials']:.2f} trials per solve", flush=True)
 
