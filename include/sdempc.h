@@ -704,6 +704,70 @@ int sdempc_closed_loop_batch_drawn(sdempc_handle* h, const sdempc_process_cfg* d
                                    float* dist_rows /*[B][T][6] or NULL*/, uint32_t* dist_keys_next /*[B][2] or NULL*/, float* dist_state_next /*[B][6] or NULL*/,
                                    float* bias_rows /*[B][Ns][12] or NULL*/, uint32_t* bias_keys_next /*[B][2] or NULL*/, float* bias_state_next /*[B][12] or NULL*/);
 
+/* ---- batched closed loop tracking a trajectory: reference windows and score targets cut on the device (SPEC.md §11j) -------------------
+ * sdempc_closed_loop_batch_drawn plus an optional trajectory set, from which the device forms every solve's reference window (and, if asked, every tick's score
+ * target) where the solve reads it, so that what the controller is asked to fly is a small table and O(B) numbers instead of an [Ns][B][H+1][13] host array. With
+ * `track` NULL the call IS sdempc_closed_loop_batch_drawn bit for bit, with the same launches.
+ * A set holds n_tables piecewise-linear tables, end to end: table j has L = knots[j] >= 1 knots (t strictly increasing and finite; x[L][13] in the solver's frame, taken
+ * as given) and a period (NULL or 0: clamp at the ends; > 0: wrap, and then t[0] = 0 and t[L-1] = period). Episode b flies table table_of[b] (NULL: table 0) with
+ * phase[b] (NULL: 0), rate[b] >= 0 (NULL: 1) and offset[b][3] (NULL: 0). All arithmetic is float32, every multiply and fma as written:
+ *   w[i]   = float32(1 / (float64(t[i+1]) - float64(t[i])))                      formed once by the library
+ *   dt     = time_steps[0];  c[i] = float32(sum_{r<i} float64(time_steps[r])), c[0] = 0;  theta(k) = float32(k) * dt for the GLOBAL tick k = tick0 + tick in the call
+ *   row(u): tau = fma(rate, u, phase);  period > 0: n = floor(tau * float32(1 / float64(period))), tau = fma(-n, period, tau);  tau = min(max(tau, t[0]), t[L-1]);
+ *           i = the largest index in [0, L-2] with t[i] <= tau (bisection from lo = 0, hi = L-1);  a = (tau - t[i]) * w[i];  y_c = fma(a, x[i+1][c] - x[i][c], x[i][c])
+ *           (L = 1: y = x[0]);  y[0..2] += offset;  y[3..5] *= rate;  y[10..12] *= rate;  renorm set: y[6..9] scaled to unit length as sdempc_age_cfg::renormalise does
+ * Row i = 0 .. H of the window of the solve at tick k is row(theta(k) + c[i]); the score target of tick k (of x_{k+1} and of tick k's substep rows) is
+ * row(theta(k + 1)). Nothing else enters, so the chunking, a re-run, the outputs requested and B change no bit, and passing tick0 + T as the next call's tick0
+ * continues the run. With `track` given xref must be NULL and xref_solves 0 (xref_batch is not read); with score_targets set a score cfg must be present and its
+ * score_ref NULL (ref_ticks / ref_batch are not read). Checked before the first HIP call, the track struct first: SDEMPC_EINVAL for a wrong struct_size,
+ * n_tables < 1, a NULL knots, t or x, a knot count below 1, a non-increasing or non-finite t, a non-finite x, a negative or non-finite period, a periodic table
+ * whose t[0] != 0 or t[L-1] != period, table_of outside the set, a non-finite phase or offset, a negative or non-finite rate, renorm or score_targets other than
+ * 0 / 1, tick0 < 0, tick0 + T >= 2^24, xref or score_ref given beside it, and for everything sdempc_closed_loop_batch_drawn refuses. No ABI version change: detect
+ * the entry points by their symbols. */
+typedef struct sdempc_track_cfg {
+    int32_t struct_size;      /* sizeof(sdempc_track_cfg) */
+    int32_t n_tables;         /* >= 1 */
+    const int32_t* knots;     /* [n_tables] L of each table, >= 1 */
+    const float* t;           /* [sum L] knot times, table after table */
+    const float* x;           /* [sum L][13] knot states */
+    const float* period;      /* [n_tables] or NULL: every table clamps */
+    const int32_t* table_of;  /* [B] or NULL: table 0 */
+    const float* phase;       /* [B] or NULL: 0 */
+    const float* rate;        /* [B] or NULL: 1 */
+    const float* offset;      /* [B][3] or NULL: 0 */
+    int32_t tick0;            /* global tick of the call's first tick, >= 0 */
+    int32_t renorm;           /* 1: unit attitude in every row; 0: the interpolated one */
+    int32_t score_targets;    /* 1: the score targets are cut from the set as well (score cfg with score_ref NULL); 0: score_ref as before */
+} sdempc_track_cfg;
+int sdempc_closed_loop_batch_tracked(sdempc_handle* h, const sdempc_track_cfg* track /*or NULL*/,
+                                     const sdempc_process_cfg* dist_proc /*or NULL, W = 6*/, const sdempc_process_cfg* bias_proc /*or NULL, W = 12*/,
+                                     const sdempc_score_cfg* score /*or NULL*/, const uint32_t* score_in /*[B][16] or NULL*/,
+                                     const sdempc_age_cfg* age_cfg /*or NULL*/, const float* xhist_in /*[B][age_max][13] or NULL*/,
+                                     const sdempc_obs_cfg* obs /*or NULL*/, const uint32_t* obs_keys /*[B][2]; NULL without obs*/, const float* xmeas_in /*[B][13] or NULL*/,
+                                     const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*or NULL*/,
+                                     const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                     const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                     const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                     const float* xref /*NULL with track*/, int32_t xref_solves /*0 with track*/, int32_t xref_batch,
+                                     const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                     const float* u_act_in /*[B][m] or NULL*/,
+                                     float* xs /*[B][T+1][13]; may be NULL with score*/, float* us /*[B][T][m]; may be NULL with score*/,
+                                     sdempc_info* info /*[B][Ns]; may be NULL with score*/,
+                                     float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                     uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                     const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                     float* ws /*[B][T][4]; NULL without rate; may be NULL with score*/, float* rate_integ_next /*[B][3] or NULL*/,
+                                     float* rate_tail_next /*[B][H][3] or NULL*/,
+                                     float* xsub /*[B][T * substeps][13] or NULL*/,
+                                     float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
+                                     float* xhist_next /*[B][age_max][13] or NULL*/, uint32_t* score_out /*[B][16]; NULL without score*/,
+                                     float* dist_rows /*[B][T][6] or NULL*/, uint32_t* dist_keys_next /*[B][2] or NULL*/, float* dist_state_next /*[B][6] or NULL*/,
+                                     float* bias_rows /*[B][Ns][12] or NULL*/, uint32_t* bias_keys_next /*[B][2] or NULL*/, float* bias_state_next /*[B][12] or NULL*/);
+/* The same launch with no loop around it: out[g][b] is the reference window f32[H+1][13] of episode b at global tick track->tick0 + ticks[g] (ticks[g] >= 0, the sum
+ * below 2^24), formed on the device and copied back — for callers of sdempc_solve_batch_keys who want device-formed windows, and the direct handle on the device code
+ * of this section. `track` is required and checked as above (score_targets is not read). */
+int sdempc_reference_windows(sdempc_handle* h, const sdempc_track_cfg* track, int32_t B, int32_t n, const int32_t* ticks /*[n]*/, float* out /*[n][B][H+1][13]*/);
+
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so
  * repeating the call runs in the one-workgroup-per-instance layout. Also SDEMPC_EDEVICE when a large throughput launch that hands its

@@ -115,6 +115,14 @@ class SdempcProcessCfg(C.Structure):
                 ("keys", C.POINTER(C.c_uint32)), ("state_in", C.POINTER(C.c_float))]
 
 
+class SdempcTrackCfg(C.Structure):
+    """sdempc_track_cfg (SPEC.md §11j): the trajectory set of sdempc_closed_loop_batch_tracked / sdempc_reference_windows — tables end to end, and per episode the
+    table, phase, rate and offset (each may be NULL)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_tables", C.c_int32), ("knots", C.POINTER(C.c_int32)), ("t", C.POINTER(C.c_float)), ("x", C.POINTER(C.c_float)),
+                ("period", C.POINTER(C.c_float)), ("table_of", C.POINTER(C.c_int32)), ("phase", C.POINTER(C.c_float)), ("rate", C.POINTER(C.c_float)),
+                ("offset", C.POINTER(C.c_float)), ("tick0", C.c_int32), ("renorm", C.c_int32), ("score_targets", C.c_int32)]
+
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -327,6 +335,32 @@ def drawn_entry(lib):
     return fn
 
 
+def tracked_entry(lib):
+    """sdempc_closed_loop_batch_tracked (SPEC.md §11j) with its prototype set: a track cfg (may be NULL) in front of the drawn entry point's arguments; nothing new
+    comes back. Detected by symbol and only when a call needs it, as drawn_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_tracked
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_tracked (SPEC.md §11j): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(drawn_entry(lib).argtypes)
+        fn.argtypes = [a[0], C.POINTER(SdempcTrackCfg)] + a[1:]
+        fn.restype = C.c_int
+    return fn
+
+
+def reference_windows_entry(lib):
+    """sdempc_reference_windows (SPEC.md §11j) with its prototype set. Detected by symbol and only when a call needs it, as tracked_entry is."""
+    try:
+        fn = lib.sdempc_reference_windows
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_reference_windows (SPEC.md §11j): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        fn.argtypes = [C.c_void_p, C.POINTER(SdempcTrackCfg), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        fn.restype = C.c_int
+    return fn
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -336,4 +370,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed", "sdempc_closed_loop_batch_scenario",
     "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault", "sdempc_closed_loop_batch_observed",
     "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored", "sdempc_closed_loop_batch_drawn",
+    "sdempc_closed_loop_batch_tracked", "sdempc_reference_windows",
 ]

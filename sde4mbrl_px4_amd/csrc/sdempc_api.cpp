@@ -189,6 +189,11 @@ struct sdempc_handle {
     // closed loop with processes drawn on the device (sdempc_closed_loop_batch_drawn with a process cfg, allocated on its first use), per row of max_batch: the
     // disturbance chain u32[2] and state f32[6], the bias chain u32[2] and state f32[12], then rho and scale of each (f32[6], f32[6], f32[12], f32[12])
     DevBuf d_proc;
+    // closed loop tracking a trajectory (sdempc_closed_loop_batch_tracked with a track cfg, sdempc_reference_windows; allocated on first use, grown, never shrunk): the set of
+    // the current call — first / knots i32[n_tables], period / inv_period f32[n_tables], t / w f32[sum L], x f32[sum L][13], c f32[H+1], table_of i32[B], phase / rate f32[B],
+    // offset f32[B][3] — in one allocation; track_stage: its host image, alive until the call returns
+    DevBuf d_track;
+    std::vector<char> track_stage;
     DevBuf d_work;            // u64[4] work counters (KArgs::work)
     // cooperative latency path of the solve (allocated on its first use, sized for coop_cap instances)
     DevBuf d_coop_bar, d_coop_pp, d_coop_ck;
@@ -596,6 +601,12 @@ struct ProcRun {
     uint32_t* bias_keys_next;           // [B][2] or null
     float* bias_state_next;             // [B][12] or null
 };
+// SPEC.md §11j: the trajectory set of one sdempc_closed_loop_batch_tracked / sdempc_reference_windows call, staged (stage_track). Given only when the call has a track
+// cfg: without one the call is the drawn call, launch for launch.
+struct TrackRun {
+    LoopTrack K;                // device pointers of the staged set, dt, renorm; tick0 = the cfg's; B / rows / groups are set per launch
+    bool score_targets;
+};
 constexpr size_t PROC_WORDS = 2 + 6 + 2 + 12 + 2 * 6 + 2 * 12;      // words of d_proc per row of max_batch
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
 // One closed-loop call as its entry point describes it. The five entry points are five nested layers (SPEC.md §11, §11a .. §11d): each takes everything the one
@@ -635,14 +646,17 @@ struct LoopCall {
     uint32_t* score_out;
     bool drawn;                                 // sdempc_closed_loop_batch_drawn (SPEC.md §11i): the scored call with the two process cfgs and their six outputs
     ProcRun pr;                                 // (a NULL cfg: its three outputs must be NULL)
+    const sdempc_track_cfg* track;              // sdempc_closed_loop_batch_tracked (SPEC.md §11j): the drawn call with a trajectory set in place of xref; or NULL
 };
 int closed_loop_call(sdempc_handle* h, const LoopCall& c);
-int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves, bool rows_optional = false);
+int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves, bool rows_optional = false, bool tracked = false);
+int check_track(sdempc_handle* h, const sdempc_track_cfg* tk, int B, long long ticks);
+int stage_track(sdempc_handle* h, const sdempc_track_cfg& tk, int B, TrackRun* out);
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr,
-                         const ObsRun* obs = nullptr, const ScoreRun* score = nullptr, const ProcRun* proc = nullptr);
+                         const ObsRun* obs = nullptr, const ScoreRun* score = nullptr, const ProcRun* proc = nullptr, const TrackRun* track = nullptr);
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, bool* again);
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -735,7 +749,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1274,6 +1288,59 @@ int sdempc_closed_loop_batch_drawn(sdempc_handle* h, const sdempc_process_cfg* d
     });
 }
 
+int sdempc_closed_loop_batch_tracked(sdempc_handle* h, const sdempc_track_cfg* track, const sdempc_process_cfg* dist_proc, const sdempc_process_cfg* bias_proc,
+                                     const sdempc_score_cfg* zc, const uint32_t* score_in, const sdempc_age_cfg* ac, const float* xhist_in, const sdempc_obs_cfg* oc,
+                                     const uint32_t* obs_keys, const float* xmeas_in, const sdempc_fault_cfg* fc, const sdempc_rate_cfg* rc_, const sdempc_scenario_cfg* sc,
+                                     const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of,
+                                     int32_t B, int32_t T, const float* x0, const float* xref, int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init,
+                                     const float* stepsize_in, const float* u_act_in, float* xs, float* us, sdempc_info* info, float* u_next, float* stepsize_next,
+                                     uint32_t* keys_next, float* u_act_next, const float* rate_integ_in, const float* rate_tail_in, float* ws, float* rate_integ_next,
+                                     float* rate_tail_next, float* xsub, float* xmeas, uint32_t* obs_keys_next, float* xmeas_next, float* xhist_next, uint32_t* score_out,
+                                     float* dist_rows, uint32_t* dist_keys_next, float* dist_state_next, float* bias_rows, uint32_t* bias_keys_next, float* bias_state_next) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    c.observed = true; c.oc = oc; c.obs_keys = obs_keys; c.xmeas_in = xmeas_in; c.xmeas = xmeas; c.obs_keys_next = obs_keys_next; c.xmeas_next = xmeas_next;
+    c.aged = true; c.ac = ac; c.xhist_in = xhist_in; c.xhist_next = xhist_next;
+    c.scored = true; c.zc = zc; c.score_in = score_in; c.score_out = score_out;
+    c.drawn = true; c.pr = {dist_proc, bias_proc, dist_rows, dist_keys_next, dist_state_next, bias_rows, bias_keys_next, bias_state_next};
+    c.track = track;
+    return closed_loop_call(h, c);
+    });
+}
+
+int sdempc_reference_windows(sdempc_handle* h, const sdempc_track_cfg* track, int32_t B, int32_t n, const int32_t* ticks, float* out) {
+    return guarded(h, [&]() -> int {
+    if (!h) return SDEMPC_EINVAL;
+    if (!track) return fail(h, SDEMPC_EINVAL, "track: cfg is NULL%s");
+    int rc = check_track(h, track, B, 0);
+    if (rc) return rc;
+    if ((rc = check_batch(h, B))) return rc;
+    if (n < 1 || !ticks || !out) return fail(h, SDEMPC_EINVAL, "reference windows: n must be >= 1, ticks and out not NULL%s");
+    for (int g = 0; g < n; ++g)
+        if (ticks[g] < 0 || (long long)track->tick0 + ticks[g] >= (1ll << 24)) return fail(h, SDEMPC_EINVAL, "reference windows: a tick is negative or tick0 + tick >= 2^24%s");
+    if ((rc = ensure_device(h))) return rc;
+    TrackRun run;
+    if ((rc = stage_track(h, *track, B, &run))) return rc;
+    const size_t XR = (size_t)(h->H + 1) * SDEMPC_NX;
+    LoopTrack K = run.K;
+    K.B = B; K.rows = h->H + 1; K.groups = 1;
+    for (int g = 0; g < n; ++g) {
+        K.tick0 = track->tick0 + ticks[g];
+        HIPCHK(h, launch_broadcast_rows(nullptr, (float*)h->d_xref.p, 0, 0, h->stream, K));
+        HIPCHK(h, hipMemcpyAsync(out + (size_t)g * B * XR, h->d_xref.p, sizeof(float) * B * XR, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return SDEMPC_OK;
+    });
+}
+
 int sdempc_solve_status(sdempc_handle* h) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1338,6 +1405,14 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    const sdempc_track_cfg* tk = c.track;
+    if (tk) {                  // SPEC.md §11j: the trajectory set, then what may not be given beside it
+        if (int rc = check_track(h, tk, B, T)) return rc;
+        if (io.xref || io.xref_ticks != 0) return fail(h, SDEMPC_EINVAL, "track: xref must be NULL and xref_solves 0 with a track cfg%s");
+        if (tk->score_targets && !c.zc) return fail(h, SDEMPC_EINVAL, "track: score_targets needs a score cfg%s");
+        if (tk->score_targets && c.zc->struct_size == (int32_t)sizeof(sdempc_score_cfg) && c.zc->score_ref) return fail(h, SDEMPC_EINVAL, "track: score_ref must be NULL with score_targets%s");
+    }
+    const bool targets = tk && tk->score_targets;
     if (c.drawn) {             // SPEC.md §11i: each process cfg with its coefficients, chain and state; an output needs its cfg
         const ProcRun& pr = c.pr;
         if (!pr.dist && (pr.dist_rows || pr.dist_keys_next || pr.dist_state_next))
@@ -1369,7 +1444,7 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
             if (zc->struct_size != (int32_t)sizeof(sdempc_score_cfg)) return fail(h, SDEMPC_EINVAL, "score: struct_size mismatch%s");
             if (zc->substeps != 0 && zc->substeps != 1) return fail(h, SDEMPC_EINVAL, "score: substeps must be 0 (tick states) or 1 (plant substep states)%s");
             if (zc->r2_pos != zc->r2_pos || zc->cos_min != zc->cos_min || zc->w2_max != zc->w2_max) return fail(h, SDEMPC_EINVAL, "score: a threshold is NaN%s");
-            if (!zc->score_ref) return fail(h, SDEMPC_EINVAL, "score: score_ref is NULL%s");
+            if (!zc->score_ref && !targets) return fail(h, SDEMPC_EINVAL, "score: score_ref is NULL%s");
             if (!c.score_out) return fail(h, SDEMPC_EINVAL, "score: score_out is NULL%s");
         }
     }
@@ -1411,7 +1486,7 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
         if (tc->solve_period < 1) return fail(h, SDEMPC_EINVAL, "timing: solve_period must be >= 1%s");
         if (!(tc->lag_alpha >= 0.0f) || !(tc->lag_alpha <= 1.0f)) return fail(h, SDEMPC_EINVAL, "timing: lag_alpha must be 0 (off) or in (0, 1]%s");
     }
-    int rc = check_loop_args(h, io, !timed ? T : (T >= 1 ? loop_solves(T, tc->solve_period) : 1), zc != nullptr);
+    int rc = check_loop_args(h, io, !timed ? T : (T >= 1 ? loop_solves(T, tc->solve_period) : 1), zc != nullptr, tk != nullptr);
     if (rc) return rc;
     const int Tp = scenario && sc ? sc->plant_ticks : 1;           // rows of plant_of
     if (Tp != 1 && Tp != T) return fail(h, SDEMPC_EINVAL, "scenario: plant_ticks must be 1 or T%s");
@@ -1470,7 +1545,7 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
         if (ac->renormalise != 0 && ac->renormalise != 1) return fail(h, SDEMPC_EINVAL, "age: renormalise must be 0 or 1%s");
         if (ac->age_max == 0 && (c.xhist_in || c.xhist_next)) return fail(h, SDEMPC_EINVAL, "age: xhist_in / xhist_next must be NULL with age_max 0%s");
     }
-    if (zc) {
+    if (zc && !targets) {
         if (zc->ref_ticks != 1 && zc->ref_ticks != T) return fail(h, SDEMPC_EINVAL, "score: ref_ticks must be 1 or T%s");
         if (zc->ref_batch != 1 && zc->ref_batch != B) return fail(h, SDEMPC_EINVAL, "score: ref_batch must be 1 or B%s");
     }
@@ -1489,15 +1564,109 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     // (a schedule is staged per chunk by the loop, where stage_plants takes the set itself; the noise of a whole solve period sits beside the set)
     if ((rc = stage_plants(h, *c.pc, c.plant_blobs, scenario ? nullptr : c.plant_of, B, &run, !timed ? 1 : (tc->solve_period < T ? tc->solve_period : T)))) return rc;
     const ScoreRun run_z{zc, c.score_in, c.score_out};
+    TrackRun run_k;
+    if (tk && (rc = stage_track(h, *tk, B, &run_k))) return rc;
     return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr, run_f.fault || run_f.xsub ? &run_f : nullptr,
-                                oc ? &run_o : nullptr, zc ? &run_z : nullptr, proc);
+                                oc ? &run_o : nullptr, zc ? &run_z : nullptr, proc, tk ? &run_k : nullptr);
+}
+// every check of a trajectory set (SPEC.md §11j), shared by the two entry points that take one; no HIP call. ticks: control ticks of the call (tick0 + ticks < 2^24)
+int check_track(sdempc_handle* h, const sdempc_track_cfg* tk, int B, long long ticks) {
+    auto finite = [](float v) { return fabsf(v) < INFINITY; };
+    if (tk->struct_size != (int32_t)sizeof(sdempc_track_cfg)) return fail(h, SDEMPC_EINVAL, "track: struct_size mismatch%s");
+    if (tk->n_tables < 1) return fail(h, SDEMPC_EINVAL, "track: n_tables must be >= 1%s");
+    if (!tk->knots || !tk->t || !tk->x) return fail(h, SDEMPC_EINVAL, "track: knots, t or x is NULL%s");
+    size_t f = 0;
+    for (int j = 0; j < tk->n_tables; ++j) {
+        const int L = tk->knots[j];
+        if (L < 1) return fail(h, SDEMPC_EINVAL, "track: a table has fewer than 1 knot%s");
+        const float* t = tk->t + f;
+        for (int i = 0; i < L; ++i)
+            if (!finite(t[i]) || (i > 0 && !(t[i] > t[i - 1]))) return fail(h, SDEMPC_EINVAL, "track: t must be finite and strictly increasing%s");
+        for (size_t e = 0; e < (size_t)L * SDEMPC_NX; ++e)
+            if (!finite(tk->x[f * SDEMPC_NX + e])) return fail(h, SDEMPC_EINVAL, "track: x holds a non-finite entry%s");
+        const float period = tk->period ? tk->period[j] : 0.0f;
+        if (!finite(period) || period < 0.0f) return fail(h, SDEMPC_EINVAL, "track: period must be finite and >= 0%s");
+        if (period > 0.0f && (t[0] != 0.0f || t[L - 1] != period)) return fail(h, SDEMPC_EINVAL, "track: a periodic table needs t[0] = 0 and t[L-1] = period%s");
+        f += (size_t)L;
+    }
+    for (int b = 0; b < B; ++b) {
+        if (tk->table_of && (tk->table_of[b] < 0 || tk->table_of[b] >= tk->n_tables)) return fail(h, SDEMPC_EINVAL, "track: table_of holds an index outside [0, n_tables)%s");
+        if (tk->phase && !finite(tk->phase[b])) return fail(h, SDEMPC_EINVAL, "track: phase holds a non-finite entry%s");
+        if (tk->rate && (!finite(tk->rate[b]) || tk->rate[b] < 0.0f)) return fail(h, SDEMPC_EINVAL, "track: rate holds a non-finite or negative entry%s");
+        for (int a = 0; tk->offset && a < 3; ++a)
+            if (!finite(tk->offset[(size_t)b * 3 + a])) return fail(h, SDEMPC_EINVAL, "track: offset holds a non-finite entry%s");
+    }
+    if ((tk->renorm != 0 && tk->renorm != 1) || (tk->score_targets != 0 && tk->score_targets != 1)) return fail(h, SDEMPC_EINVAL, "track: renorm and score_targets must be 0 or 1%s");
+    if (tk->tick0 < 0) return fail(h, SDEMPC_EINVAL, "track: tick0 must be >= 0%s");
+    if ((long long)tk->tick0 + ticks >= (1ll << 24)) return fail(h, SDEMPC_EINVAL, "track: tick0 + T must stay below 2^24 (the clock is float32(tick) * dt)%s");
+    return 0;
+}
+// SPEC.md §11j. Forms w, inv_period and c, fills in the defaults of the per-episode numbers (table 0, phase 0, rate 1, offset 0) and stages the set on the device ONCE per
+// call, in one allocation and one copy on the handle's stream. The launches only read it, so a re-run finds it as it was. The arguments were checked by the caller.
+int stage_track(sdempc_handle* h, const sdempc_track_cfg& tk, int B, TrackRun* out) {
+    const int NT = tk.n_tables, H = h->H;
+    size_t SL = 0;
+    for (int j = 0; j < NT; ++j) SL += (size_t)tk.knots[j];
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_first = 0, o_knots = o_first + up16(sizeof(int32_t) * NT), o_period = o_knots + up16(sizeof(int32_t) * NT), o_inv = o_period + up16(sizeof(float) * NT);
+    const size_t o_t = o_inv + up16(sizeof(float) * NT), o_w = o_t + up16(sizeof(float) * SL), o_x = o_w + up16(sizeof(float) * SL), o_c = o_x + up16(sizeof(float) * SL * SDEMPC_NX);
+    const size_t o_of = o_c + up16(sizeof(float) * (H + 1)), o_phase = o_of + up16(sizeof(int32_t) * B), o_rate = o_phase + up16(sizeof(float) * B);
+    const size_t o_off = o_rate + up16(sizeof(float) * B), total = o_off + up16(sizeof(float) * B * 3);
+    std::vector<char>& stg = h->track_stage;
+    stg.assign(total, 0);
+    int32_t* first = (int32_t*)&stg[o_first];
+    float* inv = (float*)&stg[o_inv];
+    float* w = (float*)&stg[o_w];
+    float* cc = (float*)&stg[o_c];
+    size_t f = 0;
+    for (int j = 0; j < NT; ++j) {
+        const int L = tk.knots[j];
+        first[j] = (int32_t)f;
+        for (int i = 0; i + 1 < L; ++i) w[f + i] = (float)(1.0 / ((double)tk.t[f + i + 1] - (double)tk.t[f + i]));
+        const float period = tk.period ? tk.period[j] : 0.0f;
+        inv[j] = period > 0.0f ? (float)(1.0 / (double)period) : 0.0f;
+        f += (size_t)L;
+    }
+    memcpy(&stg[o_knots], tk.knots, sizeof(int32_t) * NT);
+    if (tk.period) memcpy(&stg[o_period], tk.period, sizeof(float) * NT);
+    memcpy(&stg[o_t], tk.t, sizeof(float) * SL);
+    memcpy(&stg[o_x], tk.x, sizeof(float) * SL * SDEMPC_NX);
+    double acc = 0.0;
+    for (int i = 0; i <= H; ++i) { cc[i] = (float)acc; if (i < H) acc += (double)h->time_steps[i]; }
+    if (tk.table_of) memcpy(&stg[o_of], tk.table_of, sizeof(int32_t) * B);
+    if (tk.phase) memcpy(&stg[o_phase], tk.phase, sizeof(float) * B);
+    float* rate = (float*)&stg[o_rate];
+    for (int b = 0; b < B; ++b) rate[b] = tk.rate ? tk.rate[b] : 1.0f;
+    if (tk.offset) memcpy(&stg[o_off], tk.offset, sizeof(float) * B * 3);
+    int rc;
+    if (h->d_track.bytes < total) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        dev_free(h->d_track);
+        if ((rc = dev_alloc(h, h->d_track, total, true))) return rc;      // (every byte a launch reads is copied in below, on the stream, before anything reads it)
+    }
+    char* d = (char*)h->d_track.p;
+    HIPCHK(h, hipMemcpyAsync(d, stg.data(), total, hipMemcpyHostToDevice, h->stream));
+    LoopTrack& K = out->K;
+    K = LoopTrack{};
+    K.t = (const float*)(d + o_t); K.w = (const float*)(d + o_w); K.x = (const float*)(d + o_x);
+    K.first = (const int32_t*)(d + o_first); K.knots = (const int32_t*)(d + o_knots); K.period = (const float*)(d + o_period); K.inv_period = (const float*)(d + o_inv);
+    K.c = (const float*)(d + o_c); K.table_of = (const int32_t*)(d + o_of); K.phase = (const float*)(d + o_phase); K.rate = (const float*)(d + o_rate);
+    K.offset = (const float*)(d + o_off);
+    K.dt = h->time_steps[0]; K.tick0 = tk.tick0; K.B = B; K.renorm = tk.renorm;
+    out->score_targets = tk.score_targets != 0;
+    return 0;
 }
 // argument checks every closed-loop entry point shares; no HIP call
 // rows_optional (SPEC.md §11h, a call with a score cfg): xs / us / info may be NULL
-int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves, bool rows_optional) {
+// tracked (SPEC.md §11j, a call with a track cfg): xref is NULL and its two counts are not read
+int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves, bool rows_optional, bool tracked) {
     int rc = check_batch(h, io.B);
     if (rc) return rc;
     if (io.T < 1) return fail(h, SDEMPC_EINVAL, "closed loop: T must be >= 1%s");
+    if (tracked) {
+        if (!io.x0 || !io.keys || (!rows_optional && (!io.xs || !io.us || !io.info))) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+        return 0;
+    }
     if (io.xref_ticks != 1 && io.xref_ticks != solves)
         return fail(h, SDEMPC_EINVAL, solves == io.T ? "closed loop: xref_ticks must be 1 or T%s" : "closed loop: xref_solves must be 1 or ceil(T / solve_period)%s");
     if (io.xref_batch != 1 && io.xref_batch != io.B) return fail(h, SDEMPC_EINVAL, "closed loop: xref_batch must be 1 or B%s");
@@ -1529,10 +1698,10 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt,
-                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc) {
+                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc, const TrackRun* track) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, track, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -1621,10 +1790,14 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // which the plant launch then reads as its disturbance (a scheduled disturbance given as well is staged beside it, as before, and read by the key schedule); with a bias
 // process it writes the solve's row of a [Pc][B][12] region and forms the measurement from it (a scheduled beta likewise). Both regions count in the chunk's bytes and
 // are copied back and scattered only when the caller asked for the rows.
+// SPEC.md §11j (track, with timed and plant): the trajectory set lives in d_track (staged once per call by stage_track). In front of every solve ONE launch of the row-filling
+// kernel in its tracking form writes the B windows of the period's first tick into d_xref, where a shared window was broadcast to before; the chunk has no xref region and
+// takes no xref copy. With score targets, one more launch per chunk writes the chunk's [Tc][B][13] target rows in front of the scoring launch, in place of their copy.
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, bool* again) {
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, bool* again) {
     *again = false;
-    const int B = io.B, T = io.T, Bx = io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
+    const bool tracked = track && timed && plant;                          // (SPEC.md §11j)
+    const int B = io.B, T = io.T, Bx = tracked ? 0 : io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
     const int Ns = loop_solves(T, S);
     const bool seen = obs && timed;
@@ -1633,7 +1806,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     const bool faulty = flt && flt->fault, subs_out = flt && flt->xsub, subs = subs_out || AM > 0 || score_sub;      // (the history is fed from the chunk's substep rows, and so is a substep score)
     const int nsub = plant ? plant->Q.substeps : 1;
     const size_t XR = (size_t)(H + 1) * NX, OUT = (size_t)S * (NX + m + (rate ? 4 : 0) + (subs ? (size_t)nsub * NX : 0)) + 8 + (seen ? NX : 0);       // floats per reference window / per episode-period of output
-    const bool xref_moves = io.xref_ticks > 1;
+    const bool xref_moves = !tracked && io.xref_ticks > 1;
     const bool gust = scen && scen->dist, sched = scen && plant && plant->Q.models;        // (one shared plant: nothing to schedule)
     const bool dist_moves = gust && scen->Td > 1, sched_moves = sched && scen->Tp > 1;
     const size_t DR = gust ? (size_t)scen->Bd * SDEMPC_NNOISE : 0, SR = sched ? (size_t)B : 0;       // floats per tick row of the disturbance / words of the schedule
@@ -1645,8 +1818,9 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     const size_t ORS = (noisy ? OR : 0) + (biased ? OR : 0);
     const bool old = seen && obs->age, age_moves = old && obs->Ta > 1;
     const size_t AR = old ? (size_t)obs->Ba : 0;                                                       // words per solve row of age
-    const bool sref_moves = scoring && score->cfg->ref_ticks > 1;
-    const size_t ZR = scoring ? (size_t)score->cfg->ref_batch * NX : 0;                                // floats per tick row of the score targets (SPEC.md §11h)
+    const bool targets = tracked && scoring && track->score_targets;                                   // (the target rows are formed on the device, one per tick and episode)
+    const bool sref_moves = scoring && (targets || score->cfg->ref_ticks > 1);
+    const size_t ZR = scoring ? (size_t)(targets ? B : score->cfg->ref_batch) * NX : 0;                                // floats per tick row of the score targets (SPEC.md §11h)
     const bool gproc = proc && proc->dist && scen && timed && plant, bproc = proc && proc->bias && seen;      // (SPEC.md §11i)
     const int NG = SDEMPC_NNOISE, NB = 12;                                                              // widths of the two processes
     const size_t per_period = (gproc ? (size_t)S * B * NG : 0) + (bproc ? (size_t)B * NB : 0) + (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0) +
@@ -1773,7 +1947,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             z_in = z0.data();
         }
         HIPCHK(h, hipMemcpyAsync(d_score, z_in, sizeof(uint32_t) * 16 * (size_t)B, hipMemcpyHostToDevice, st));
-        if (!sref_moves) HIPCHK(h, hipMemcpyAsync(c_sref, score->cfg->score_ref, sizeof(float) * ZR, hipMemcpyHostToDevice, st));
+        if (!sref_moves) HIPCHK(h, hipMemcpyAsync(c_sref, score->cfg->score_ref, sizeof(float) * ZR, hipMemcpyHostToDevice, st));      // (targets: they move)
     }
     for (int w = 0; w < 2; ++w) {      // the process chains, states (NULL: zeros) and coefficients start as given (SPEC.md §11i)
         if (!(w ? bproc : gproc)) continue;
@@ -1786,7 +1960,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         HIPCHK(h, hipMemcpyAsync(w ? p_brho : p_drho, pc.rho, sizeof(float) * pc.batch * W, hipMemcpyHostToDevice, st));
         HIPCHK(h, hipMemcpyAsync(w ? p_bscale : p_dscale, pc.scale, sizeof(float) * pc.batch * W, hipMemcpyHostToDevice, st));
     }
-    if (!xref_moves) {
+    if (!tracked && !xref_moves) {
         HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
         if (Bx != B) HIPCHK(h, launch_broadcast_rows(c_xref, (float*)h->d_xref.p, (int)XR, B, st));
     }
@@ -1818,11 +1992,13 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     if (scoring) {
         const sdempc_score_cfg& zc = *score->cfg;
         Z.words = d_score; Z.rows = score_sub ? c_xsub : c_xs; Z.us = c_us; Z.info = c_info; Z.ref = c_sref;
-        Z.ref_tick_stride = sref_moves ? (int)ZR : 0; Z.ref_ep_stride = zc.ref_batch > 1 ? NX : 0;
+        Z.ref_tick_stride = sref_moves ? (int)ZR : 0; Z.ref_ep_stride = targets || zc.ref_batch > 1 ? NX : 0;
         Z.rows_per_tick = score_sub ? nsub : 1; Z.m = m;
         Z.r2_pos = zc.r2_pos; Z.cos_min = zc.cos_min; Z.w2_max = zc.w2_max;
         for (int l = 0; l < 8; ++l) { Z.u_lo[l] = l < m ? h->cfg.u_lo[l] : 0.0f; Z.u_hi[l] = l < m ? h->cfg.u_hi[l] : 0.0f; Z.uref[l] = l < m ? h->cfg.uref[l] : 0.0f; }
     }
+    LoopTrack K{};             // (t null: absent)
+    if (tracked) K = track->K;
     LoopProcess G{};           // (chains null: absent)
     if (gproc) {
         G.dist.chain = p_dchain; G.dist.state = p_dstate; G.dist.rho = p_drho; G.dist.scale = p_dscale; G.dist.par_ep_stride = proc->dist->batch > 1 ? NG : 0;
@@ -1868,7 +2044,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         if (obs_moves && biased) HIPCHK(h, hipMemcpyAsync(c_beta, obs->beta + (size_t)j0 * OR, sizeof(float) * np * OR, hipMemcpyHostToDevice, st));
         if (valid_moves) HIPCHK(h, hipMemcpyAsync(c_valid, obs->valid + (size_t)j0 * VR, sizeof(int32_t) * np * VR, hipMemcpyHostToDevice, st));
         if (age_moves) HIPCHK(h, hipMemcpyAsync(c_age, obs->age + (size_t)j0 * AR, sizeof(int32_t) * np * AR, hipMemcpyHostToDevice, st));
-        if (sref_moves) HIPCHK(h, hipMemcpyAsync(c_sref, score->cfg->score_ref + k0 * ZR, sizeof(float) * nk * ZR, hipMemcpyHostToDevice, st));
+        if (sref_moves && !targets) HIPCHK(h, hipMemcpyAsync(c_sref, score->cfg->score_ref + k0 * ZR, sizeof(float) * nk * ZR, hipMemcpyHostToDevice, st));
         for (int jc = 0; jc < np; ++jc) {
             const int ticks = nk - jc * S < S ? nk - jc * S : S;                    // (the last period of the run may be partial)
             if (seen) {
@@ -1893,7 +2069,11 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));
             const float* win = c_xref + (xref_moves ? (size_t)jc * Bx * XR : 0);
             const float* xr = win;
-            if (Bx != B) {
+            if (tracked) {             // the windows of this solve's tick, cut where the solve reads them
+                K.tick0 = track->K.tick0 + (int)(k0 + (size_t)jc * S); K.B = B; K.rows = H + 1; K.groups = 1;
+                HIPCHK(h, launch_broadcast_rows(nullptr, (float*)h->d_xref.p, 0, 0, st, K));
+                xr = (const float*)h->d_xref.p;
+            } else if (Bx != B) {
                 if (xref_moves) HIPCHK(h, launch_broadcast_rows(win, (float*)h->d_xref.p, (int)XR, B, st));
                 xr = (const float*)h->d_xref.p;
             }
@@ -1934,6 +2114,10 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         }
         if (scoring) {             // SPEC.md §11h: the chunk's rows into the score words, one thread per episode
             Z.ticks = nk; Z.solves = np;
+            if (targets) {         // SPEC.md §11j: the target of chunk tick i is the row at theta(k0 + i + 1)
+                K.tick0 = track->K.tick0 + (int)k0 + 1; K.B = B; K.rows = 1; K.groups = nk;
+                HIPCHK(h, launch_broadcast_rows(nullptr, c_sref, 0, 0, st, K));
+            }
             HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, Z));
         }
         unsigned gave_up = 0;

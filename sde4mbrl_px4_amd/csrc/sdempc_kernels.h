@@ -288,8 +288,32 @@ struct LoopProcess {
 };
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st,
                                    const LoopObserve& O = LoopObserve{}, const LoopScore& Z = LoopScore{}, const LoopProcess& G = LoopProcess{});
-// rows_dev[b][0..n) = row_dev[0..n) for b < B
-hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st);
+// SPEC.md §11j, reference windows and score targets cut from a trajectory on the device: the row-filling launch below in its TRACKING form. The tables of a set lie
+// end to end: table j owns knots first[j] .. first[j] + knots[j] - 1 of t / w / x (w[i] = float32(1 / (t[i+1] - t[i])) formed by the library in float64; the last w of
+// a table is not read). Thread i of the launch writes one whole row of 13 floats, row i of out f32[groups][B][rows][13]: group g is tick tick0 + g, its clock value
+// theta = float32(tick) * dt, and row r of episode b is the trajectory of table_of[b] at u = theta + c[r], through (phase, rate, offset) of b. A reference window is
+// rows = H + 1 of ONE group; the score targets of a chunk are rows = 1 (c[0] = 0) of one group per tick, tick0 the chunk's first tick + 1.
+// t null means absent: the launch then copies rows as it always did and makes no memory access it did not make before.
+struct LoopTrack {
+    const float* t;             // [sum L] knot times, table after table; null: no trajectory
+    const float* w;             // [sum L] reciprocal segment lengths
+    const float* x;             // [sum L][13] knot states, in the solver's frame
+    const int32_t* first;       // [n_tables] index of each table's first knot
+    const int32_t* knots;       // [n_tables] L >= 1 of each table
+    const float* period;        // [n_tables] 0: clamp at the ends; > 0: wrap (t[0] = 0 and t[L-1] = period)
+    const float* inv_period;    // [n_tables] float32(1 / float64(period)), 0 where the period is 0
+    const float* c;             // [rows] clock offsets of the rows: c[0] = 0, c[i] = float32(float64 sum of time_steps[0 .. i-1])
+    const int32_t* table_of;    // [B] table of each episode
+    const float* phase;         // [B]
+    const float* rate;          // [B] >= 0
+    const float* offset;        // [B][3]
+    float dt;                   // float32(time_steps[0])
+    int tick0;                  // global tick of group 0 (tick0 + groups - 1 < 2^24)
+    int B, rows, groups;
+    int renorm;                 // 1: scale the attitude of every row to unit length, software rsqrt (wave-uniform)
+};
+// rows_dev[b][0..n) = row_dev[0..n) for b < B; or, with K.t given (row_dev, n and B are then not read): rows_dev[g][b][r][0..13) from the trajectory set K
+hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st, const LoopTrack& K = LoopTrack{});
 // canonical [B][P][C] <-> device [B][G][C][32] (to_dev: zero-pads particles >= P)
 hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int P, int G, int C, hipStream_t st);
 // SPEC.md §7: noise of B instances from their threefry keys (device u32[B][2]) straight into the device layout [B][G][H][6][32]

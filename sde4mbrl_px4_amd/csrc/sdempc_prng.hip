@@ -435,16 +435,86 @@ hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float*
     return hipGetLastError();
 }
 
+// SPEC.md §11j: one row of episode b's trajectory at clock value u, into y[13] (constant indices after unrolling: registers). Every multiply and fma is the one
+// written (-ffp-contract=off). The segment search is this thread's own: it may diverge inside a wave. Whatever tau is (a NaN among it: an overflowing rate), the
+// segment index stays inside the table.
+DI void track_row(const LoopTrack& K, int b, float u, float* y) {
+    const int tb = K.table_of[b];
+    const int f = K.first[tb], L = K.knots[tb];
+    const float* t = K.t + f;
+    const float* x0 = K.x + (size_t)f * 13;
+    const float rate = K.rate[b];
+    if (L == 1) {
+#pragma unroll
+        for (int c = 0; c < 13; ++c) y[c] = x0[c];
+    } else {
+        float tau = FMA(rate, u, K.phase[b]);
+        const float period = K.period[tb];
+        if (period > 0.0f) {
+            const float n = __builtin_floorf(tau * K.inv_period[tb]);
+            tau = FMA(-n, period, tau);
+        }
+        const float ta = t[0], tz = t[L - 1];
+        tau = tau > ta ? tau : ta;
+        tau = tau < tz ? tau : tz;
+        int lo = 0, hi = L - 1;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (t[mid] <= tau) lo = mid; else hi = mid;
+        }
+        const float a = (tau - t[lo]) * K.w[f + lo];
+        const float* xa = x0 + (size_t)lo * 13;
+#pragma unroll
+        for (int c = 0; c < 13; ++c) y[c] = FMA(a, xa[13 + c] - xa[c], xa[c]);
+    }
+    const float* off = K.offset + (size_t)b * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        y[c] = y[c] + off[c];
+        y[3 + c] = y[3 + c] * rate;
+        y[10 + c] = y[10 + c] * rate;
+    }
+    if (K.renorm) {                                      // (wave-uniform)
+        const float q0 = y[6], q1 = y[7], q2 = y[8], q3 = y[9];
+        const float r = rsqrt_spec(FMA(q3, q3, FMA(q2, q2, FMA(q1, q1, q0 * q0))));
+        y[6] = q0 * r; y[7] = q1 * r; y[8] = q2 * r; y[9] = q3 * r;
+    }
+}
+
 // rows[b] = row for b < B (one reference window shared by every episode of a closed-loop batch), n floats per row
-__global__ void __launch_bounds__(256) sdempc_broadcast_rows_kernel(const float* __restrict__ row, float* __restrict__ rows, int n, long long total) {
+// SPEC.md §11j (K.t given; row, n and total are then not read): the TRACKING form of the launch. Thread i forms row i of rows f32[groups][B][K.rows][13] from the
+// trajectory set and stores its 13 floats, so neighbouring threads write neighbouring rows. K.t null (every launch before §11j): not one access more.
+__global__ void __launch_bounds__(256) sdempc_broadcast_rows_kernel(const float* __restrict__ row, float* __restrict__ rows, int n, long long total, LoopTrack K) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (K.t) {                                           // (wave-uniform)
+        const long long per_group = (long long)K.B * K.rows;
+        if (i >= per_group * K.groups) return;
+        const int g = (int)(i / per_group);
+        const int e = (int)(i - (long long)g * per_group);
+        const int b = e / K.rows, r = e - b * K.rows;
+        const float theta = (float)(K.tick0 + g) * K.dt;
+        float y[13];
+        track_row(K, b, theta + K.c[r], y);
+        float* o = rows + i * 13;
+#pragma unroll
+        for (int c = 0; c < 13; ++c) o[c] = y[c];
+        return;
+    }
     if (i < total) rows[i] = row[i % n];
 }
 
-hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st) {
+hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st, const LoopTrack& K) {
+    if (K.t) {      // SPEC.md §11j: a present set is complete, and its clock stays exact in float32
+        if (!rows_dev || !K.w || !K.x || !K.first || !K.knots || !K.period || !K.inv_period || !K.c || !K.table_of || !K.phase || !K.rate || !K.offset) return hipErrorInvalidValue;
+        if (K.B < 1 || K.rows < 1 || K.groups < 1 || K.tick0 < 0 || (long long)K.tick0 + K.groups > (1ll << 24) || (K.renorm != 0 && K.renorm != 1)) return hipErrorInvalidValue;
+        const long long threads = (long long)K.B * K.rows * K.groups;
+        if (threads > (1ll << 31) - 256) return hipErrorInvalidValue;
+        sdempc_broadcast_rows_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(nullptr, rows_dev, 0, 0, K);
+        return hipGetLastError();
+    }
     if (B < 1 || n < 1) return hipErrorInvalidValue;
     const long long total = (long long)n * B;
-    sdempc_broadcast_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(row_dev, rows_dev, n, total);
+    sdempc_broadcast_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(row_dev, rows_dev, n, total, K);
     return hipGetLastError();
 }
 

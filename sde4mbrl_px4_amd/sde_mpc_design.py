@@ -103,6 +103,14 @@ class MpcProblem:
             return workload.reference_window(float(curr_t), self.cfg.time_steps, self.state_from_traj)
         return workload.constant_reference(np.asarray(xdes, np.float32), self.cfg.horizon)
 
+    def trajectory(self, t0: float, t1: float, n: int, period: float = 0.0):
+        """The loaded state_from_traj sampled at n knots over [t0, t1] as a solver.Trajectory (SPEC.md §11j): what simulate(track=...) and
+        SdeMpcSolver.closed_loop(track=...) take. state_from_traj returns solver-frame states, as every reference window is; trajectory time 0 is t0."""
+        if self.state_from_traj is None:
+            raise ValueError("MpcProblem.trajectory: no trajectory is loaded (a position-control configuration)")
+        from .solver import Trajectory
+        return Trajectory.from_function(self.state_from_traj, t0, t1, n, period)
+
     # ---- the two callables ------------------------------------------------------------------------
     def m_reset(self, x=None, rng=None, xdes=None) -> OptState:
         H, m = self.cfg.horizon, self.cfg.num_motors
@@ -140,7 +148,8 @@ class MpcProblem:
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
                  plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,
                  fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None, meas_age=None, meas_renorm=False,
-                 score=None, score_ref=None, dist_process=None, dist_rng=None, dist_state=None, bias_process=None, bias_rng=None, bias_state=None):
+                 score=None, score_ref=None, dist_process=None, dist_rng=None, dist_state=None, bias_process=None, bias_rng=None, bias_state=None,
+                 track=None, track_phase=None, track_rate=None):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -183,14 +192,24 @@ class MpcProblem:
         and needs meas_rng) — with its own key uint32[2] (required) and a start state f32[W] (None: zeros), GIVEN IN THE FRAME OF x. Under convert_to_enu the
         coefficients rho and scale take the permutation without the sign, as meas_noise does, and the state in, the state out and the returned rows follow the signed
         vector rules of `disturbance` and `meas_bias`. Behind the score and before xsub come, per process given (disturbance first), its rows f32[T][6] / f32[Ns][12],
-        its key after the run and its state after the run. A key or a state without its process raises ValueError."""
+        its key after the run and its state after the run. A key or a state without its process raises ValueError.
+        track / track_phase / track_rate (SPEC.md §11j): a solver.Trajectory IN THE SOLVER'S FRAME (self.trajectory samples the loaded state_from_traj into one),
+        passed through: the device cuts the window of every solve and, with a score and no score_ref, the target of every tick from the table, entered at
+        track_phase and flown at track_rate times its speed; the global tick of the run's first tick is round(curr_t / dt_0). This is a DIFFERENT arithmetic
+        from the state_from_traj route above, which stays as it is, float64 and all: float32 interpolation between the knots, the same trajectory to a few
+        ulps of a linear interpolant and no further. xdes is then not read; the returned values are the same. track_phase / track_rate without track raise
+        ValueError."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
         x = np.asarray(x, np.float32).reshape(13)
         xs0 = enu2ned(x, np) if self.convert_to_enu else x
         xdes = xs0 if xdes is None else np.asarray(xdes, np.float32).reshape(13)
-        if self.state_from_traj is not None:
+        if track is None and (track_phase is not None or track_rate is not None):
+            raise ValueError("MpcProblem.simulate: track_phase / track_rate need track=Trajectory(...)")
+        if track is not None:
+            xref = None
+        elif self.state_from_traj is not None:
             dt0 = float(self.cfg.time_steps[0])
             S = int(solve_period)
             xref = np.stack([self.xref(float(curr_t) + j * S * dt0, xdes) for j in range(-(-T // max(S, 1)))])[:, None]
@@ -214,6 +233,8 @@ class MpcProblem:
                 raise ValueError(f"MpcProblem.simulate: plant_of must be int[{T}] (one episode: the plant of every tick), got {plant_of.shape}")
             plant_of = plant_of[:, None]
         more = {} if rate_loop is None else {"rate_loop": rate_loop}
+        if track is not None:
+            more.update(track=track, track_phase=track_phase, track_rate=track_rate, track_tick0=int(round(float(curr_t) / float(self.cfg.time_steps[0]))))
         if fault is not None:
             f = np.asarray(fault, np.float32)
             m = self.cfg.num_motors
@@ -286,13 +307,18 @@ class MpcProblem:
                     raise ValueError(f"MpcProblem.simulate: score_ref must be f32[{T}][13] or f32[13], got {g.shape}")
                 if self.convert_to_enu:
                     g = enu2ned(g, np)
+            elif track is not None:
+                g = None
             elif self.state_from_traj is not None:
                 dt0 = float(self.cfg.time_steps[0])
                 g = np.asarray(self.state_from_traj(float(curr_t) + (np.arange(T, dtype=np.float64) + 1.0) * dt0), np.float32).reshape(T, 13)
             else:
                 g = xdes
-            g = np.ascontiguousarray(g, np.float32)
-            more.update(score=score, score_ref=g[None, None] if g.ndim == 1 else g[:, None])
+            if g is None:
+                more.update(score=score, score_ref="track")
+            else:
+                g = np.ascontiguousarray(g, np.float32)
+                more.update(score=score, score_ref=g[None, None] if g.ndim == 1 else g[:, None])
         out = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
             plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag,

@@ -197,6 +197,141 @@ class Score:
         return f"Score(pos_radius={self.pos_radius}, tilt_max={self.tilt_max}, rate_max={self.rate_max}, substeps={self.substeps})"
 
 
+# Host arithmetic of Trajectory.rows only (a restatement for users: planning, plots). The AUTHORITATIVE statement of these two functions is oracle/sde_mpc_numpy.py
+# (fma, rsqrt; SPEC.md §3), which the device is tested against; the package may import neither oracle/ nor tests/, so they are restated here, and
+# tests/test_track_loop_cpu.py holds Trajectory.windows bit for bit to tests/track_loop_ref.py, which is written with the oracle's. Change the oracle's first.
+def _fma32(a, b, c):
+    """float32 fma(a, b, c) with ONE rounding: the product is exact in float64, the sum is corrected to round-to-odd there, then cast."""
+    a, b, c = np.asarray(a, np.float32), np.asarray(b, np.float32), np.asarray(c, np.float32)
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c64 = c.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = np.asarray(p + c64)
+        t = s - p
+        e = (p - (s - t)) + (c64 - t)
+        fix = np.isfinite(s) & np.isfinite(e) & (e != 0.0) & ((s.view(np.uint64) & np.uint64(1)) == 0)
+        s = np.where(fix, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+
+def _rsqrt32(a):
+    """The software reciprocal square root of SPEC.md §3.2, in float32."""
+    a = np.asarray(a, np.float32)
+    y = (np.uint32(0x5F3759DF) - (a.view(np.uint32) >> np.uint32(1))).view(np.float32)
+    h = np.float32(0.5) * a
+    for _ in range(3):
+        y = y * _fma32(-h, y * y, np.float32(1.5))
+    return y
+
+
+class Trajectory:
+    """A piecewise-linear trajectory table for closed_loop(track=...) and reference_windows (SPEC.md §11j): L >= 1 knots, times t f32[L] (finite, strictly
+    increasing) and states x f32[L][13] IN THE SOLVER'S FRAME, as every reference window is. period = 0 clamps at the ends; period > 0 wraps the trajectory time
+    (then t[0] = 0 and t[L-1] = period are required, and the last knot should repeat the first). The device cuts every solve's window and every tick's score target
+    from the table, per episode through a phase, a rate >= 0 and a position offset: row(u) is the table at tau = fma(rate, u, phase), linearly interpolated in
+    float32, position + offset, velocity and body rates times rate, the attitude (interpolated component by component) scaled to unit length when asked. The
+    constructors flip knot quaternion signs (an exact negation) so that consecutive knots have a non-negative dot product; nothing else is touched. This is a
+    different arithmetic from a float64 state_from_traj evaluated on the host: the same trajectory to a few float32 ulps of a linear interpolant, not bit for bit."""
+
+    def __init__(self, t, x, period=0.0):
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1)
+        x = np.array(x, dtype=np.float32, order="C")
+        L = t.shape[0]
+        if L < 1 or x.shape != (L, 13):
+            raise ValueError(f"Trajectory: t must be f32[L] with L >= 1 and x f32[L][13], got {t.shape} and {x.shape}")
+        if not np.isfinite(t).all() or (L > 1 and not (np.diff(t) > 0).all()):
+            raise ValueError("Trajectory: t must be finite and strictly increasing (in float32)")
+        if not np.isfinite(x).all():
+            raise ValueError("Trajectory: x holds a non-finite entry")
+        period = np.float32(period)
+        if not np.isfinite(period) or period < 0:
+            raise ValueError("Trajectory: period must be finite and >= 0")
+        if period > 0 and (t[0] != 0 or t[-1] != period):
+            raise ValueError("Trajectory: a periodic table needs t[0] = 0 and t[L-1] = period (in float32)")
+        for i in range(1, L):          # (sequential: each knot against the one before it, as already flipped)
+            if np.dot(x[i - 1, 6:10].astype(np.float64), x[i, 6:10].astype(np.float64)) < 0:
+                x[i, 6:10] = -x[i, 6:10]
+        self.t, self.x, self.period = t, x, period
+
+    @classmethod
+    def from_knots(cls, t, x, period=0.0):
+        return cls(t, x, period)
+
+    @classmethod
+    def from_function(cls, state_fn, t0, t1, n, period=0.0):
+        """n >= 1 knots of state_fn (t f64[n] -> [n][13], e.g. a loaded state_from_traj or workload.lemniscate_state) at equal spacing over [t0, t1]. The knot times
+        become the table's times MINUS t0, so that trajectory time 0 is t0. period > 0 makes the table periodic and must then be the sampled span: float32(period) ==
+        float32(t1 - t0), the last knot's time (ValueError otherwise)."""
+        n = int(n)
+        if n < 1 or not float(t1) >= float(t0):
+            raise ValueError("Trajectory.from_function: n >= 1 and t1 >= t0 are required")
+        ts = np.linspace(float(t0), float(t1), n) if n > 1 else np.array([float(t0)])
+        x = np.asarray(state_fn(ts), np.float32).reshape(n, 13)
+        t = (ts - float(t0)).astype(np.float32)
+        if float(period) > 0 and np.float32(period) != t[-1]:
+            raise ValueError(f"Trajectory.from_function: a periodic table spans one period: period = {float(period)} but t1 - t0 = {float(t[-1])} (in float32)")
+        return cls(t, x, period)
+
+    @classmethod
+    def from_csv(cls, csv, n=None, period=0.0):
+        """From a utils.TrajectoryCSV (its own samples as knots, times from its first sample; n given: n equally spaced samples of its interpolant). The CSV's
+        state() forms the yaw quaternion and, for a file in NED, the frame flip: the table holds what state() returns."""
+        if n is None:
+            ts = np.asarray(csv.t, np.float64)
+            return cls((ts - ts[0]).astype(np.float32), np.asarray(csv.state(ts), np.float32), period)
+        return cls.from_function(csv.state, float(csv.t[0]), float(csv.t[-1]), n, period)
+
+    def rows(self, u, phase=0.0, rate=1.0, offset=(0.0, 0.0, 0.0), renorm=True):
+        """row(u) of SPEC.md §11j for clock values u f32[...] and ONE episode's (phase, rate, offset): f32[...][13], in the device's arithmetic."""
+        F = np.float32
+        u = np.asarray(u, F)
+        rate, phase, offset = F(rate), F(phase), np.asarray(offset, F).reshape(3)
+        t, x, L = self.t, self.x, self.t.shape[0]
+        if L == 1:
+            y = np.broadcast_to(x[0], u.shape + (13,)).copy()
+        else:
+            with np.errstate(invalid="ignore", over="ignore"):
+                tau = _fma32(rate, u, phase)
+                if self.period > 0:
+                    inv = F(1.0 / np.float64(self.period))
+                    n = np.floor(tau * inv).astype(F)
+                    tau = _fma32(-n, self.period, tau)
+                tau = np.where(tau > t[0], tau, t[0]).astype(F)
+                tau = np.where(tau < t[-1], tau, t[-1]).astype(F)
+            i = np.clip(np.searchsorted(t, tau, side="right") - 1, 0, L - 2)       # the largest index in [0, L-2] with t[i] <= tau
+            w = (1.0 / (t[1:].astype(np.float64) - t[:-1].astype(np.float64))).astype(F)
+            a = ((tau - t[i]).astype(F) * w[i]).astype(F)
+            y = _fma32(a[..., None], (x[i + 1] - x[i]).astype(F), x[i])
+        y[..., 0:3] = y[..., 0:3] + offset
+        y[..., 3:6] = y[..., 3:6] * rate
+        y[..., 10:13] = y[..., 10:13] * rate
+        if renorm:
+            q0, q1, q2, q3 = y[..., 6], y[..., 7], y[..., 8], y[..., 9]
+            r = _rsqrt32(_fma32(q3, q3, _fma32(q2, q2, _fma32(q1, q1, (q0 * q0).astype(F)))))
+            y[..., 6:10] = y[..., 6:10] * r[..., None]
+        return y
+
+    def windows(self, time_steps, ticks, phase=0.0, rate=1.0, offset=(0.0, 0.0, 0.0), renorm=True):
+        """Host restatement of what the device cuts for ONE episode: the reference windows f32[n][H+1][13] of the solves at the global ticks `ticks` int[n]
+        (row i at u = float32(k) * float32(time_steps[0]) + c[i], c the float64 cumulative sum of time_steps cast once), for planning and plotting."""
+        F = np.float32
+        ts = np.asarray(time_steps, F)
+        k = np.asarray(ticks, np.int64).reshape(-1)
+        if k.size and (k.min() < 0 or k.max() >= 1 << 24):
+            raise ValueError("Trajectory.windows: ticks must be in [0, 2^24)")
+        c = np.concatenate([[0.0], np.cumsum(ts.astype(np.float64))]).astype(F)
+        theta = (k.astype(F) * F(ts[0])).astype(F)
+        return self.rows((theta[:, None] + c[None, :]).astype(F), phase, rate, offset, renorm)
+
+    def targets(self, time_steps, ticks, phase=0.0, rate=1.0, offset=(0.0, 0.0, 0.0), renorm=True):
+        """The score targets f32[n][13] of the ticks `ticks`: the row at u = float32(k + 1) * float32(time_steps[0])."""
+        k = np.asarray(ticks, np.int64).reshape(-1) + 1
+        return self.rows((k.astype(np.float32) * np.asarray(time_steps, np.float32)[0]).astype(np.float32), phase, rate, offset, renorm)
+
+    def __repr__(self):
+        return f"Trajectory(L={self.t.shape[0]}, t=[{float(self.t[0])}, {float(self.t[-1])}], period={float(self.period)})"
+
+
 SCORE_DTYPE = np.dtype(_abi.SCORE_FIELDS)          # one episode's 16 score words (SPEC.md §11h), 64 bytes
 SCORE_CAUSES = {"position": 1, "tilt": 2, "rate": 4, "nonfinite": 8}
 
@@ -365,7 +500,8 @@ class SdeMpcSolver:
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
                     rate_loop=None, rate_integ_in=None, rate_tail_in=None, fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None,
                     meas_keys=None, xmeas_in=None, meas_age=None, meas_age_max=None, meas_renorm=False, xhist_in=None, score=None, score_ref=None, score_in=None,
-                    outputs=True, dist_process=None, dist_keys=None, dist_state_in=None, bias_process=None, bias_keys=None, bias_state_in=None):
+                    outputs=True, dist_process=None, dist_keys=None, dist_state_in=None, bias_process=None, bias_keys=None, bias_state_in=None,
+                    track=None, track_of=None, track_phase=None, track_rate=None, track_offset=None, track_tick0=None, track_renorm=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -463,11 +599,39 @@ class SdeMpcSolver:
         stays LAST) come, with dist_process, dist_rows f32[B][T][6] (the rows the plant read), dist_keys_next and dist_state_next, and with bias_process bias_rows
         f32[B][Ns][12], bias_keys_next and bias_state_next; the rows are None under outputs=False. Carrying the *_next values back in continues the run bit for bit:
         the disturbance process for any T, the bias process when T is a multiple of solve_period. A process without its keys, or keys / a state without the process,
-        raises ValueError; with none of the six given nothing of this paragraph is touched."""
+        raises ValueError; with none of the six given nothing of this paragraph is touched.
+
+        track / track_of / track_phase / track_rate / track_offset / track_tick0 / track_renorm (SPEC.md §11j, sdempc_closed_loop_batch_tracked): TRAJECTORY TRACKING
+        with the reference windows CUT ON THE DEVICE, so that what the controller is asked to fly is a small table and O(B) numbers instead of an [Ns][B][H+1][13] host
+        array. track is a Trajectory or a sequence of them (track_of int[B] then names each episode's table; None: table 0), and xref must be None. Episode b flies its
+        table from track_phase[b] (f32[B] or a scalar; None: 0) at track_rate[b] >= 0 times its speed (None: 1; 0 holds the point at the phase) shifted by
+        track_offset[b] (f32[B][3] or f32[3]; None: 0): row i of the window of the solve at global tick k = track_tick0 + tick is the table at
+        tau = fma(rate, float32(k) * dt_0 + c_i, phase), c the cumulative time_steps — wrapped into a periodic table, clamped to a clamped one —, with the velocity and
+        body rates scaled by the rate and, unless track_renorm=False, the interpolated attitude scaled to unit length. score_ref="track" cuts the score targets from
+        the same tables (the target of x_{k+1} is the row at float32(k + 1) * dt_0). The call is the timed one (info per solve, the plant defaulting to the handle's
+        own model; every keyword above still applies) and the returned tuple is unchanged: nothing new comes back. Windows and targets depend on the global tick
+        alone, so passing track_tick0 + T as the next call's track_tick0 with the other continuation values continues the run bit for bit, under the conditions
+        stated above for them. xref together with track, a track_* keyword or score_ref="track" without track, raise ValueError; with none of the seven given
+        nothing of this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
         keys = self._keys(keys, B)
+        tracked = track is not None
+        score_track = isinstance(score_ref, str) and score_ref == "track"
+        if not tracked and (track_of is not None or track_phase is not None or track_rate is not None or track_offset is not None or track_tick0 is not None or
+                            track_renorm is not None or score_track):
+            raise ValueError('closed_loop: track_of / track_phase / track_rate / track_offset / track_tick0 / track_renorm / score_ref="track" need track=Trajectory(...)')
+        if tracked:
+            if xref is not None:
+                raise ValueError("closed_loop: xref must be None with track=... (an array and a trajectory for the same thing cannot both be meant)")
+            tick0_ = 0 if track_tick0 is None else int(track_tick0)
+            if tick0_ < 0 or tick0_ + max(T, 0) >= 1 << 24:
+                raise ValueError("closed_loop: track_tick0 must be >= 0 and track_tick0 + T below 2^24")
+            tkc, keep_track = self._track_cfg(track, B, track_of, track_phase, track_rate, track_offset, tick0_, True if track_renorm is None else track_renorm, score_track)
+            if score_track:
+                score_ref = None
+            xref = np.zeros((0, 1, self.H + 1, 13), np.float32)        # (NULL and 0 solves at the entry point)
         xref = _f32(xref)
         if xref.ndim == 2:
             xref = xref[None, None]
@@ -593,9 +757,9 @@ class SdeMpcSolver:
         if scored:
             if not isinstance(score, Score):
                 raise ValueError("closed_loop: score must be a Score")
-            if score_ref is None:
+            if score_ref is None and not score_track:
                 raise ValueError("closed_loop: score_ref (the target of every tick, f32[Tr][Br][13]) is required with score")
-            sref = _f32(score_ref)
+            sref = np.zeros((1, 1, 13), np.float32) if score_track else _f32(score_ref)
             if sref.ndim == 1 and sref.shape == (13,):
                 sref = sref[None, None]
             elif sref.ndim == 2 and sref.shape == (T, 13):
@@ -607,8 +771,10 @@ class SdeMpcSolver:
                 score_in = np.ascontiguousarray(score_in)
                 if score_in.dtype != SCORE_DTYPE or score_in.shape != (B,):
                     raise ValueError(f"closed_loop: score_in must be the structured score array [{B}] a previous call returned, got dtype {score_in.dtype} and shape {score_in.shape}")
-        faulted = flt is not None or bool(substep_states) or observed or scored or drawn
-        full = scored or drawn          # the entry points from the scored one on take every layer's arguments, NULL where a layer is absent
+        if score_track and not scored:
+            raise ValueError('closed_loop: score_ref="track" needs score=Score(...)')
+        faulted = flt is not None or bool(substep_states) or observed or scored or drawn or tracked
+        full = scored or drawn or tracked          # the entry points from the scored one on take every layer's arguments, NULL where a layer is absent
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
             raise ValueError("closed_loop: rate_integ_in / rate_tail_in need rate_loop=...")
         if rate_loop is not None and not isinstance(rate_loop, RateLoop):
@@ -646,7 +812,7 @@ class SdeMpcSolver:
         s_next = np.zeros(B, np.float32)
         k_next = np.zeros((B, 2), np.uint32)
         u32p = C.POINTER(C.c_uint32)
-        common = (B, T, _fp(x0), _fp(xref), int(xref.shape[0]), int(xref.shape[1]), keys.ctypes.data_as(u32p), u_p, s_p)
+        common = (B, T, _fp(x0), None if tracked else _fp(xref), int(xref.shape[0]), int(xref.shape[1]), keys.ctypes.data_as(u32p), u_p, s_p)
         outs = (_fp(xs), _fp(us), info.ctypes.data_as(C.POINTER(SdempcInfo)), _fp(u_next), _fp(s_next), k_next.ctypes.data_as(u32p))
         ret = (xs, us, info, u_next, s_next, k_next)
         if not outputs:             # (scored, checked above) NULL per-row outputs, None in their places
@@ -731,14 +897,14 @@ class SdeMpcSolver:
             elif full:              # (no age: a NULL age cfg and NULL history pointers)
                 lead, more = [None, None] + lead, more + (None,)
             if scored:              # the aged entry point's arguments behind (score cfg, score_in), then score_out
-                zc = _abi.SdempcScoreCfg(C.sizeof(_abi.SdempcScoreCfg), int(score.substeps), float(score.r2_pos), float(score.cos_min), float(score.w2_max), _fp(sref),
+                zc = _abi.SdempcScoreCfg(C.sizeof(_abi.SdempcScoreCfg), int(score.substeps), float(score.r2_pos), float(score.cos_min), float(score.w2_max), None if score_track else _fp(sref),
                                          sref.shape[0], sref.shape[1])
                 z_out = np.zeros(B, SCORE_DTYPE)
                 lead = [C.byref(zc), None if score_in is None else score_in.ctypes.data_as(u32p)] + lead
                 more, ret = more + (z_out.ctypes.data_as(u32p),), ret + (z_out,)
-            elif drawn:             # (no score: a NULL score cfg and NULL score pointers)
+            elif drawn or tracked:  # (no score: a NULL score cfg and NULL score pointers)
                 lead, more = [None, None] + lead, more + (None,)
-            if drawn:               # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
+            if drawn or tracked:               # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
                 cfgs, keep_p = [], []
                 for name, Nrows in (("dist", max(T, 0)), ("bias", max(Ns, 0))):
                     if name not in procs:
@@ -754,10 +920,14 @@ class SdeMpcSolver:
                     more = more + (None if p_rows is None else _fp(p_rows), p_keys.ctypes.data_as(u32p), _fp(p_state))
                     ret = ret + (p_rows, p_keys, p_state)
                 lead = cfgs + lead
+            if tracked:             # the drawn entry point's arguments behind the track cfg; nothing new comes back
+                lead = [C.byref(tkc)] + lead
             if substep_states:
                 ret = ret + (xsub,)
         # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
-        if drawn:
+        if tracked:
+            entry = _abi.tracked_entry(self.lib)
+        elif drawn:
             entry = _abi.drawn_entry(self.lib)
         elif scored:
             entry = _abi.scored_entry(self.lib)
@@ -777,6 +947,63 @@ class SdeMpcSolver:
             entry = self.lib.sdempc_closed_loop_batch_plant
         self._check(entry(self._h, *lead, C.cast(bufs, C.POINTER(C.c_void_p)), sizes, of_p, *common, *u_act, *outs, *more))
         return ret
+
+    def _track_cfg(self, track, B, track_of, phase, rate, offset, tick0, renorm, score_targets):
+        """sdempc_track_cfg of one Trajectory or a sequence of them for B episodes, and what must stay alive while it is in use."""
+        tables = [track] if isinstance(track, Trajectory) else list(track)
+        if not tables or not all(isinstance(t, Trajectory) for t in tables):
+            raise ValueError("closed_loop: track must be a Trajectory or a non-empty sequence of them")
+        knots = np.array([t.t.shape[0] for t in tables], np.int32)
+        t_all = np.ascontiguousarray(np.concatenate([t.t for t in tables]), np.float32)
+        x_all = np.ascontiguousarray(np.concatenate([t.x for t in tables]), np.float32)
+        period = np.array([t.period for t in tables], np.float32)
+        keep = [knots, t_all, x_all, period]
+        i32p = C.POINTER(C.c_int32)
+
+        def per_episode(v, tail, what, dtype=np.float32):
+            if v is None:
+                return None
+            a = np.asarray(v, dtype)
+            if a.shape == tail:
+                a = np.broadcast_to(a, (B,) + tail)
+            if a.shape != (B,) + tail:
+                raise ValueError(f"closed_loop: {what} must have shape {(B,) + tail}" + (f" or {tail}" if tail else " or be a scalar") + f", got {np.shape(v)}")
+            a = np.ascontiguousarray(a, dtype)
+            keep.append(a)
+            return a
+        of = None
+        if track_of is not None:
+            of = np.asarray(track_of)
+            if of.dtype.kind not in "iu" or of.shape != (B,) or of.min() < 0 or of.max() >= len(tables):
+                raise ValueError(f"closed_loop: track_of must be int[{B}] with entries in [0, {len(tables)})")
+            of = np.ascontiguousarray(of, np.int32)
+            keep.append(of)
+        ph, rt, off = per_episode(phase, (), "track_phase"), per_episode(rate, (), "track_rate"), per_episode(offset, (3,), "track_offset")
+        if (ph is not None and not np.isfinite(ph).all()) or (off is not None and not np.isfinite(off).all()):
+            raise ValueError("closed_loop: track_phase / track_offset hold a non-finite entry")
+        if rt is not None and not (np.isfinite(rt).all() and (rt >= 0).all()):
+            raise ValueError("closed_loop: track_rate must be finite and >= 0")
+        cfg = _abi.SdempcTrackCfg(C.sizeof(_abi.SdempcTrackCfg), len(tables), knots.ctypes.data_as(i32p), _fp(t_all), _fp(x_all), _fp(period),
+                                  None if of is None else of.ctypes.data_as(i32p), None if ph is None else _fp(ph), None if rt is None else _fp(rt),
+                                  None if off is None else _fp(off), int(tick0), int(bool(renorm)), int(bool(score_targets)))
+        return cfg, keep
+
+    def reference_windows(self, track, ticks, B, track_of=None, track_phase=None, track_rate=None, track_offset=None, track_tick0=0, track_renorm=True):
+        """The reference windows f32[n][B][H+1][13] the device cuts from `track` for B episodes at the global ticks track_tick0 + ticks[g] (SPEC.md §11j,
+        sdempc_reference_windows): the launch closed_loop(track=...) makes in front of every solve, with no loop around it — for callers of solve_keys who want
+        device-formed windows. The track_* keywords are closed_loop's."""
+        k = np.ascontiguousarray(np.asarray(ticks, np.int64).reshape(-1))
+        if k.size < 1 or k.min() < 0 or int(track_tick0) < 0 or k.max() + int(track_tick0) >= 1 << 24:
+            raise ValueError("reference_windows: ticks must be a non-empty int array with 0 <= track_tick0 + tick < 2^24")
+        k = np.ascontiguousarray(k, np.int32)
+        B = int(B)
+        if B < 1:
+            raise ValueError("reference_windows: B must be >= 1")
+        cfg, keep = self._track_cfg(track, B, track_of, track_phase, track_rate, track_offset, int(track_tick0), track_renorm, False)
+        out = np.zeros((k.shape[0], B, self.H + 1, 13), np.float32)
+        self._check(_abi.reference_windows_entry(self.lib)(self._h, C.byref(cfg), B, k.shape[0], k.ctypes.data_as(C.POINTER(C.c_int32)), _fp(out)))
+        del keep
+        return out
 
     def _rate_cfg(self, rate_loop, plant_substeps, plant_dt):
         """sdempc_rate_cfg of a RateLoop for this handle: ki_dt = float32(ki) * float32(dt_plant), the default mixer from the controller's rotor tables (as

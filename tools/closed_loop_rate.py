@@ -37,10 +37,14 @@
      1.5 rad/s^2, correlation times around 0.3 s; with --disturbance as well the host rows are the scheduled part the process is added to), --bias-process one step
      per solve with --observe, whose meas_bias rows it REPLACES (noise and dropouts stay host rows). Apply to --small-batch and to the C2 loop; either makes the call
      the timed one. So `--disturbance --observe` against `--dist-process --observe --bias-process` is host rows against keys for the same two ingredients.
+ 12. --track: the reference windows cut on the device from a trajectory table (SPEC.md §11j, sdempc_closed_loop_batch_tracked) instead of a host xref array — the
+     lemniscate as a periodic table of 161 knots, every episode entering it at its own phase and flying it at its own rate (0.8 .. 1.2); with --score the targets are cut
+     from the table as well. It makes the call the timed one. --per-episode-xref gives --small-batch the route it replaces: a host array with a window per solve and
+     episode on the same lemniscate (the C2 loop always stages one). So `--timed --per-episode-xref` against `--track` is the array route against the table.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
                                         [--fault] [--substep-states] [--observe] [--age A] [--renorm]
-                                        [--score] [--no-outputs] [--score-substeps] [--dist-process] [--bias-process]
+                                        [--score] [--no-outputs] [--score-substeps] [--dist-process] [--bias-process] [--track] [--per-episode-xref]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -84,7 +88,11 @@ ap.add_argument("--no-outputs", action="store_true", help="with --score: NULL pe
 ap.add_argument("--score-substeps", action="store_true", help="with --score: score every plant substep state instead of every tick state")
 ap.add_argument("--dist-process", action="store_true", help="gusts drawn on the device, one Gauss-Markov step per control tick (SPEC.md §11i)")
 ap.add_argument("--bias-process", action="store_true", help="with --observe: the estimator bias drawn on the device, one Gauss-Markov step per solve, instead of meas_bias rows (SPEC.md §11i)")
+ap.add_argument("--track", action="store_true", help="reference windows (and score targets) cut on the device from a trajectory table, per-episode phase and rate (SPEC.md §11j)")
+ap.add_argument("--per-episode-xref", action="store_true", help="--small-batch: a host xref array with a lemniscate window per solve and episode instead of one hold window")
 a = ap.parse_args()
+if a.track and a.per_episode_xref:
+    ap.error("--track replaces the xref array: not with --per-episode-xref")
 if a.bias_process and not a.observe:
     ap.error("--bias-process needs --observe")
 if (a.age >= 0 or a.renorm) and not a.observe:
@@ -151,9 +159,11 @@ def scenario_kw(kw, B, T):
     if a.score:
         from sde4mbrl_px4_amd.solver import Score
         kw["score"] = Score(pos_radius=1.0, tilt_max=0.6, rate_max=6.0, substeps=a.score_substeps)
-        kw["score_ref"] = np.ascontiguousarray(np.broadcast_to(np.asarray(W.HOVER, np.float32), (T, B, 13)))
+        kw["score_ref"] = "track" if a.track else np.ascontiguousarray(np.broadcast_to(np.asarray(W.HOVER, np.float32), (T, B, 13)))
         if a.no_outputs:
             kw["outputs"] = False
+    if a.track:
+        kw.update(track_kw(B))
     if a.disturbance:
         kw["disturbance"] = np.random.default_rng(2).uniform(-2.0, 2.0, (T, B, 6)).astype(np.float32)
     if a.plant_switch >= 0:
@@ -166,6 +176,19 @@ def scenario_kw(kw, B, T):
             before, after = np.zeros(B), np.ones(B)
         kw["plant_of"] = np.stack([before if k < a.plant_switch else after for k in range(T)]).astype(np.int32)
     return kw
+
+
+def track_kw(B):
+    """keyword arguments of closed_loop for --track: the lemniscate as a periodic table, per-episode phase and rate"""
+    from sde4mbrl_px4_amd.solver import Trajectory
+    rng = np.random.default_rng(11)
+    return dict(track=Trajectory.from_function(W.lemniscate_state, 0.0, 8.0, 161, period=8.0), track_phase=(0.05 * (np.arange(B) % 160)).astype(np.float32),
+                track_rate=rng.uniform(0.8, 1.2, B).astype(np.float32))
+
+
+def lemniscate_windows(cfg, B, T):
+    """xref f32[Ns][B][H+1][13]: a moving window per episode and solve, the largest staging the loop does"""
+    return np.stack([np.stack([W.reference_window(0.05 * (b % 160) + k * float(cfg.time_steps[0]), cfg.time_steps) for b in range(B)]) for k in range(0, T, a.period)])
 
 
 def timing_kw(cfg, B):
@@ -197,6 +220,10 @@ if a.dist_process:
     tag += " dist-process"
 if a.bias_process:
     tag += " bias-process"
+if a.track:
+    tag += " track"
+if a.per_episode_xref:
+    tag += " per-episode-xref"
 if a.score:
     tag += " score" + ("/substeps" if a.score_substeps else "") + (" no-outputs" if a.no_outputs else "")
 
@@ -219,11 +246,13 @@ if a.small_batch:
     keys = prng.split(prng.PRNGKey(10), B)
     S = SdeMpcSolver(cfg, model, max_batch=B)
     kw = {**plant_kw(B), **timing_kw(cfg, B)}
-    S.closed_loop(x0, hold, keys, 2 * a.period, **scenario_kw(kw, B, 2 * a.period))       # warm-up: device buffers, workspaces
+    window = lambda n: None if a.track else lemniscate_windows(cfg, B, n) if a.per_episode_xref else hold      # noqa: E731
+    S.closed_loop(x0, window(2 * a.period), keys, 2 * a.period, **scenario_kw(kw, B, 2 * a.period))       # warm-up: device buffers, workspaces
     kw = scenario_kw(kw, B, T)
+    xr = window(T)
     for rep in range(a.repeats):
         t = time.perf_counter()
-        out = S.closed_loop(x0, hold, keys, T, **kw)
+        out = S.closed_loop(x0, xr, keys, T, **kw)
         dt = time.perf_counter() - t
         print(f"C1 B={B} T={T}{tag}: {T / dt:8.1f} ticks/s ({B * T / dt:9.1f} episode-ticks/s, {dt * 1e3 / T:.3f} ms/tick)", flush=True)
     report_score(out, T)
@@ -261,8 +290,7 @@ if not a.skip_c2:
     cfg = load_mpc_config(os.path.join(ROOT, "configs", "c2_iris_traj_h50_p128.yaml")).replace(mlp_dtype="f32x3", math_mode="fast")
     B, T = 12288, a.c2_ticks
     x0 = W.random_initial_states(B, 3)
-    xref = np.stack([np.stack([W.reference_window(0.05 * (b % 160) + k * float(cfg.time_steps[0]), cfg.time_steps) for b in range(B)])
-                     for k in range(0, T, a.period)])       # a moving window per episode and solve: the largest staging the loop does
+    xref = lemniscate_windows(cfg, B, 1 if a.track else T)   # (--track: one window per episode for the batch solve; the loop cuts its own)
     keys = prng.split(prng.PRNGKey(10), B)
     S = SdeMpcSolver(cfg, model, max_batch=B)
     yk, i0 = S.reset()
@@ -275,7 +303,7 @@ if not a.skip_c2:
     pk = scenario_kw({**plant_kw(B), **timing_kw(cfg, B)}, B, T)
     for rep in range(a.repeats):
         t = time.perf_counter()
-        out = S.closed_loop(x0, xref, keys, T, u_init=u0, stepsize_in=s0, **pk)
+        out = S.closed_loop(x0, None if a.track else xref, keys, T, u_init=u0, stepsize_in=s0, **pk)
         loop = time.perf_counter() - t
         print(f"C2 f32x3/fast B={B}{tag}: closed_loop {B * T / loop:8.1f} episode-ticks/s ({loop / T:.3f} s/tick, T = {T}); one batch solve_keys "
               f"{B / one:8.1f} solves/s ({one:.3f} s); ratio {(B * T / loop) / (B / one):.3f}", flush=True)
