@@ -7,8 +7,9 @@
 // ≈22 % of the adjoint step's vector instructions — is computed twice, identically, by both lane halves.
 // Here a wave owns a PAIR of groups: lanes 0..31 carry the particles of group gA = 2 gp, lanes 32..63 those of gB = 2 gp + 1. The per-
 // particle work runs once on 64 distinct particles; the MLPs run as two passes in the unchanged MFMA accumulator layout (pass A on group
-// A's inputs broadcast to both halves, then pass B), and v_permlane32_swap both broadcasts the six inputs of a pass and, in one swap +
-// one add per value, folds the per-half partial sums of both passes so that every lane ends up with ITS particle's total:
+// A's inputs, then pass B), and v_permlane32_swap both forms the layer-1 operands of the two passes from the six inputs (duo_pair_inputs:
+// three swaps; the fp16-operand layer 1 broadcasts them with half_split) and, in one swap + one add per value, folds the per-half partial
+// sums of both passes so that every lane ends up with ITS particle's total:
 //     swap(PA, PB) = {PA.lo, PB.lo}, {PA.hi, PB.hi};  sum: lanes < 32 -> PA.lo + PA.hi, lanes >= 32 -> PB.lo + PB.hi   ( = (P0 + P1), SPEC.md §4 )
 // Every value is produced by the same operations in the same order as in the plain layout: results are bit-identical (same tests).
 // Teams: two waves own an instance of up to four groups (C2: P = 128 -> 128-thread workgroups, six per CU), four waves otherwise.
@@ -21,6 +22,32 @@ DI void half_split(float v, float& a_both, float& b_both) {
     auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
     const unsigned r0 = r[0], r1 = r[1];
     a_both = __builtin_bit_cast(float, r0); b_both = __builtin_bit_cast(float, r1);
+}
+// The six MLP inputs of the wave's two groups as the layer-1 B operands of both passes, ready to use: k-step s of a pass multiplies input 2 s in the lower lane
+// half and input 2 s + 1 in the upper one, and swap(z[2 s], z[2 s + 1]) = {z[2 s].lo, z[2 s + 1].lo}, {z[2 s].hi, z[2 s + 1].hi} is exactly that for group A
+// (first result) and group B (second result): three swaps instead of six broadcasts (half_split) and a per-half select per k-step, tile and pass
+DI void duo_pair_inputs(const float* z, float* bA, float* bB) {
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, z[2 * s]), __builtin_bit_cast(unsigned, z[2 * s + 1]), false, false);
+        const unsigned r0 = r[0], r1 = r[1];
+        bA[s] = __builtin_bit_cast(float, r0); bB[s] = __builtin_bit_cast(float, r1);
+    }
+}
+// The fp16-operand layer 1 (mlp_dtype f16) takes all six inputs of a group from the lower lane half (k slots 0..5 of one MFMA): it keeps the broadcast form.
+// The kernels without noise staging rows (!NZS: long horizons, the next step's noise held in registers) keep it too, and the one-value-per-register
+// particle sums of the adjoint: with the paired forms one of the 24 such kernels spilled a prefetched noise row synchronously where the build before had no
+// such spill, and moving the change around only moved the spill to another of them (profiles/duo_lane_plumbing.txt §2); their code is what it was.
+// zA / zB: the first DUO_NB elements are a pass's inputs in the form its layer 1 takes (fwd_mlp_partials / layer1_tile, PAIRED)
+template <int F16, bool NZS> constexpr bool DUO_PAIRED = F16 != 1 && NZS;
+template <int F16, bool NZS> constexpr int DUO_NB = DUO_PAIRED<F16, NZS> ? 3 : NN;
+template <bool PAIRED>
+DI void duo_split_inputs(const float* z, float* zA, float* zB) {
+    if constexpr (PAIRED) duo_pair_inputs(z, zA, zB);
+    else {
+#pragma unroll
+        for (int k = 0; k < NN; ++k) half_split(z[k], zA[k], zB[k]);
+    }
 }
 // per-half partial sums of pass A (pa) and pass B (pb) -> this lane's particle total: lanes < 32: pa.lo + pa.hi, lanes >= 32: pb.lo + pb.hi
 DI float half_join_sum(float pa, float pb) {
@@ -128,11 +155,10 @@ DI void duo_step_fwd(const KArgs& a, const Smem& sm, const WaveW& ww, int t, int
     const float* ust = sm.ust + t * UST;
     float z[NN], zA[NN], zB[NN];
     fwd_head(x, A.Rm, z);
-#pragma unroll
-    for (int k = 0; k < NN; ++k) half_split(z[k], zA[k], zB[k]);
+    duo_split_inputs<DUO_PAIRED<F16, NZS>>(z, zA, zB);
     SCHED_PHASE();
     float PA[7], PB[7];
-    fwd_mlp_partials<F16, false, CKPT ? 4 : 7>(a, sm, ww, ust, h, lane, zA, A, PA);
+    fwd_mlp_partials<F16, false, CKPT ? 4 : 7, DUO_PAIRED<F16, NZS>>(a, sm, ww, ust, h, lane, zA, A, PA);
     if constexpr (CKPT) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -140,7 +166,7 @@ DI void duo_step_fwd(const KArgs& a, const Smem& sm, const WaveW& ww, int t, int
     }
     SCHED_PHASE();
     if (hasB) {
-        fwd_mlp_partials<F16, false, CKPT ? 4 : 7>(a, sm, ww, ust, h, lane, zB, A, PB);
+        fwd_mlp_partials<F16, false, CKPT ? 4 : 7, DUO_PAIRED<F16, NZS>>(a, sm, ww, ust, h, lane, zB, A, PB);
         if constexpr (CKPT) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -401,8 +427,7 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
             const float* ust = sm.ust + t * UST;
             float z[NN], zA[NN], zB[NN];
             fwd_head(xt, A.Rm, z);
-#pragma unroll
-            for (int k = 0; k < NN; ++k) half_split(z[k], zA[k], zB[k]);
+            duo_split_inputs<DUO_PAIRED<F16, NZS>>(z, zA, zB);
             A.eta = ns4.x; A.Fb[0] = ns4.y; A.Fb[1] = ns4.z; A.Fb[2] = ns4.w; A.rn = nrn;
 #pragma unroll
             for (int i = 0; i < 3; ++i) A.Jom[i] = a.M.J[i] * xt[10 + i];
@@ -440,19 +465,20 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
                 // (only AdjRegs<M>::N registers of a pass's result tile hold existing rows)
                 constexpr int NR = AdjRegs<M>::N;
                 float rA[NR], rB[NR];
-                // (pass B's six broadcast inputs wait in this wave's noise staging rows — idle during the adjoint sweep — while pass A runs)
+                // (pass B's layer-1 operands wait in this wave's noise staging rows — idle during the adjoint sweep — while pass A runs; with three
+                // operands instead of six, keeping them in registers measured the same to 0.03 %: profiles/duo_lane_plumbing.txt)
                 if constexpr (NZS) {
 #pragma unroll
-                    for (int k = 0; k < NN; ++k) sm.nzs[k * 64 + lane] = zB[k];
+                    for (int k = 0; k < DUO_NB<F16, NZS>; ++k) sm.nzs[k * 64 + lane] = zB[k];
                 }
-                adj_mlp_pass_mp<NR, false, F16>(sm, ww, ust, h, lane, zA, hA, eA, OA, rA, []() {});
+                adj_mlp_pass_mp<NR, false, F16, DUO_PAIRED<F16, NZS>>(sm, ww, ust, h, lane, zA, hA, eA, OA, rA, []() {});
                 SCHED_PHASE();
                 if constexpr (NZS) {
 #pragma unroll
-                    for (int k = 0; k < NN; ++k) zB[k] = sm.nzs[k * 64 + lane];
+                    for (int k = 0; k < DUO_NB<F16, NZS>; ++k) zB[k] = sm.nzs[k * 64 + lane];
                 }
                 // (parking pass A's result rows there in turn while pass B runs was tried: the allocator answered with MORE spills in three of four kernels)
-                if (pr.hasB) adj_mlp_pass_mp<NR, true, F16>(sm, ww, ust, h, lane, zB, hB, eB, OB, rB, [&]() {
+                if (pr.hasB) adj_mlp_pass_mp<NR, true, F16, DUO_PAIRED<F16, NZS>>(sm, ww, ust, h, lane, zB, hB, eB, OB, rB, [&]() {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) hB[q] = *reinterpret_cast<const float4*>(apB + (q * 64 + lane) * 4);       // (touched at the top of the step: an L2 hit)
                 });
@@ -477,7 +503,7 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
             } else {
             float PzA[NN], PuA[M], PzB[NN], PuB[M];
             // per pass: layer 1 recomputed tile by tile (6 MFMAs, 32 tanh), layer 2 from the checkpoint (adj_mlp_pass)
-            adj_mlp_pass<M, F16>(sm, ww, ust, h, lane, zA, hA, eA, obA, PzA, PuA);
+            adj_mlp_pass<M, F16, DUO_PAIRED<F16, NZS>>(sm, ww, ust, h, lane, zA, hA, eA, obA, PzA, PuA);
             SCHED_PHASE();
             if (pr.hasB) {
                 // pass B's second-layer checkpoint: touched at the top of the step, loaded here (until round 5 it was requested before pass A and held in registers
@@ -485,7 +511,7 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
 #pragma unroll
                 for (int q = 0; q < 4; ++q) hB[q] = *reinterpret_cast<const float4*>(apB + (q * 64 + lane) * 4);
                 SCHED_PHASE();
-                adj_mlp_pass<M, F16>(sm, ww, ust, h, lane, zB, hB, eB, obB, PzB, PuB);
+                adj_mlp_pass<M, F16, DUO_PAIRED<F16, NZS>>(sm, ww, ust, h, lane, zB, hB, eB, obB, PzB, PuB);
             } else {
 #pragma unroll
                 for (int k = 0; k < NN; ++k) PzB[k] = PzA[k];
@@ -503,11 +529,19 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
             vjp_tail(sm, t, xt, A, lam, T, zb, lamn);
 #pragma unroll
             for (int i = 0; i < NX; ++i) { lam[i] = lamn[i]; x[i] = xt[i]; }
-            // particle sums of the nq per-step adjoint outputs: each lane half reduces its own group (halves never mix below xor 32)
+            // particle sums of the nq per-step adjoint outputs: each lane half reduces its own group (halves never mix below xor 32), two values per register
+            if constexpr (NZS) {
+                float gs[nq];
 #pragma unroll
-            for (int k = 0; k < nq; ++k) {
-                const float s = group_bfly32(valid ? gq[k] : 0.0f);
-                if (j == 0 && pr.own) Sq[t * 12 + k] = s;
+                for (int k = 0; k < nq; ++k) gs[k] = valid ? gq[k] : 0.0f;
+                group_bfly32_pairs<nq>(gs);
+                group_pair_store<nq>(gs, Sq + t * 12, j, pr.own);
+            } else {
+#pragma unroll
+                for (int k = 0; k < nq; ++k) {
+                    const float s = group_bfly32(valid ? gq[k] : 0.0f);
+                    if (j == 0 && pr.own) Sq[t * 12 + k] = s;
+                }
             }
         }
         CLK_END(5, t_adj);

@@ -407,6 +407,36 @@ DI float group_bfly32(float v) {
     v = v + dpp_f<0xB1>(v);   // quad_perm [1,0,3,2]
     return v;
 }
+// group_bfly32 of N values, two per register. v_permlane16_swap(a, b) of two DIFFERENT values leaves {a.r0, b.r0, a.r2, b.r2} and {a.r1, b.r1, a.r3, b.r3}:
+// their sum is the xor-16 stage of both at once — a.r0 + a.r1 in the even rows, b.r0 + b.r1 in the odd rows, the operand pairs of xor16_sum — without the
+// copy, and the four DPP stages, which stay inside a 16-lane row, then serve two values each. v[2 i] receives the pair (v[2 i], v[2 i + 1]): group total of
+// v[2 i] in lanes j < 16 of each group (j = lane & 31), of v[2 i + 1] in lanes j >= 16; group_pair_store writes them from j == 0 and j == 16. v[2 i + 1] is
+// consumed. An odd N leaves v[N - 1] to a plain group_bfly32 (its total in every lane). Every addition has the operands it has in group_bfly32: the same bits.
+template <int N>
+DI void group_bfly32_pairs(float* v) {
+#pragma unroll
+    for (int i = 0; i + 1 < N; i += 2) {
+        auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, v[i]), __builtin_bit_cast(unsigned, v[i + 1]), false, false);
+        const unsigned r0 = r[0], r1 = r[1];
+        float s = __builtin_bit_cast(float, r0) + __builtin_bit_cast(float, r1);
+        s = s + dpp_f<0x128>(s);  // row_ror:8
+        s = s + dpp_f<0x124>(s);  // row_ror:4
+        s = s + dpp_f<0x4E>(s);   // quad_perm [2,3,0,1]
+        s = s + dpp_f<0xB1>(s);   // quad_perm [1,0,3,2]
+        v[i] = s;
+    }
+    if constexpr (N & 1) v[N - 1] = group_bfly32(v[N - 1]);
+}
+// dst[k] = group total of value k, from what group_bfly32_pairs<N> left in v: one store per register from lanes j == 0 (value 2 i) and j == 16 (value 2 i + 1)
+// of the lane halves for which own holds
+template <int N>
+DI void group_pair_store(const float* v, float* dst, int j, bool own) {
+    float* d = dst + (j >> 4);
+    const bool wr = own && (j & 15) == 0;
+#pragma unroll
+    for (int i = 0; i + 1 < N; i += 2) { if (wr) d[i] = v[i]; }
+    if constexpr (N & 1) { if (wr && j == 0) dst[N - 1] = v[N - 1]; }
+}
 DI float wave_bfly64(float v) { return group_bfly32(xor32_sum(v)); }
 // SPEC.md §6.2 dot256: virtual lane i < 256 chains e = i, i+256, ...; butterflies inside each 64-lane virtual wave;
 // ((w0+w1)+w2)+w3. A team of NT threads walks the 256 virtual lanes in 256/NT passes.

@@ -252,11 +252,14 @@ DI void load_l1_c(const Smem& sm, const float* ust, int h, f32x16& accD, f32x16&
         accN[4 * q] = n4.x; accN[4 * q + 1] = n4.y; accN[4 * q + 2] = n4.z; accN[4 * q + 3] = n4.w;
     }
 }
-template <int F16, bool PK, int OB = 7>
+// PAIRED (duo layout, duo_pair_inputs): z holds the three ready B operands of this pass's layer-1 k-steps — each lane half already carries ITS input of the
+// step — instead of the six inputs in both halves: the per-half select below falls away, the MFMAs read the same bits
+template <int F16, bool PK, int OB = 7, bool PAIRED = false>
 DI void fwd_mlp_partials(const KArgs& a, const Smem& sm, const WaveW& ww, const float* ust, int h, int lane, const float* z, StepAux& A, float* Po) {
     // layer 1: C operand = per-step offsets (drift) / bias (density); K = 6 -> 3 MFMAs per tile
     f32x16 accD, accN;
     load_l1_c(sm, ust, h, accD, accN);
+    static_assert(!(PAIRED && F16 == 1), "the fp16-operand layer 1 reads all six inputs from the lower lane half");
     if constexpr (F16 == 1) {
         // fp16 operands (round toward zero), f32 accumulate: one v_mfma_f32_32x32x16_f16 per tile, k slots 0..5 live in lanes 0..31
         half8 bv;
@@ -271,7 +274,7 @@ DI void fwd_mlp_partials(const KArgs& a, const Smem& sm, const WaveW& ww, const 
     } else {
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
-            float b = h ? z[2 * s + 1] : z[2 * s];
+            float b = PAIRED ? z[s] : (h ? z[2 * s + 1] : z[2 * s]);
             accD = __builtin_amdgcn_mfma_f32_32x32x2f32(ww.w1d[s], b, accD, 0, 0, 0);
             accN = __builtin_amdgcn_mfma_f32_32x32x2f32(ww.w1n[s], b, accN, 0, 0, 0);
         }
@@ -673,14 +676,15 @@ DI void vjp_mlp_partials(const Smem& sm, int h, int lane, const StepAux& A, floa
     }
 }
 // One layer-1 tile (3 f32 MFMAs, or one fp16 MFMA) on top of its C operand, then tanh: the drift tile (DRIFT: C = per-step control
-// terms c_t, A = W1z rows 0..31) or the density tile (C = b1 rows 32..63, A = W1z rows 32..63)
-template <int F16, bool DRIFT>
+// terms c_t, A = W1z rows 0..31) or the density tile (C = b1 rows 32..63, A = W1z rows 32..63). PAIRED: z = the pass's three ready B operands (see fwd_mlp_partials)
+template <int F16, bool DRIFT, bool PAIRED = false>
 DI void layer1_tile(const Smem& sm, const WaveW& ww, const float* ust, int h, const float* z, f32x16& acc) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         float4 c4 = *reinterpret_cast<const float4*>((DRIFT ? ust : sm.b1n) + 8 * q + 4 * h);
         acc[4 * q] = c4.x; acc[4 * q + 1] = c4.y; acc[4 * q + 2] = c4.z; acc[4 * q + 3] = c4.w;
     }
+    static_assert(!(PAIRED && F16 == 1), "the fp16-operand layer 1 reads all six inputs from the lower lane half");
     if constexpr (F16 == 1) {
         half8 bv;
 #pragma unroll
@@ -693,7 +697,7 @@ DI void layer1_tile(const Smem& sm, const WaveW& ww, const float* ust, int h, co
     } else {
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
-            float bb = h ? z[2 * s + 1] : z[2 * s];
+            float bb = PAIRED ? z[s] : (h ? z[2 * s + 1] : z[2 * s]);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(DRIFT ? ww.w1d[s] : ww.w1n[s], bb, acc, 0, 0, 0);
         }
     }
@@ -708,14 +712,14 @@ DI void layer1_tile(const Smem& sm, const WaveW& ww, const float* ust, int h, co
 // that live for one phase only: its lines were touched (one dword each) at the top of the step, a pass and a half earlier, so the load is an L2 hit. Holding the tile in
 // registers from before pass A, as the f32 / three-limb forms do, leaves the allocator the choice of what to spill, and it chooses the checkpoint itself: a synchronous
 // HBM round trip per spilled quad and step — 0 to 2 of them, changing with every source line (profiles/r5_ab.txt §2 – §3).
-template <int NR, bool DENS_FIRST, int F16, class Hook>
+template <int NR, bool DENS_FIRST, int F16, bool PAIRED = false, class Hook>
 DI void adj_mlp_pass_mp(const Smem& sm, const WaveW& ww, const float* ust, int h, int lane, const float* z, const float4* h2c, float ebraw, const ObLimbs& O, float* rows, const Hook& load_ckpt) {
     float rn[4];
     if constexpr (DENS_FIRST) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) rn[r] = 0.0f;
         f32x16 hn;
-        layer1_tile<F16, false>(sm, ww, ust, h, z, hn);
+        layer1_tile<F16, false, PAIRED>(sm, ww, ust, h, z, hn);
         adj_mp_density<F16>(sm, h, lane, hn, ebraw, rn);
         SCHED_PHASE();
     }
@@ -726,7 +730,7 @@ DI void adj_mlp_pass_mp(const Smem& sm, const WaveW& ww, const float* ust, int h
     SCHED_PHASE();
     {
         f32x16 hd;
-        layer1_tile<F16, true>(sm, ww, ust, h, z, hd);
+        layer1_tile<F16, true, PAIRED>(sm, ww, ust, h, z, hd);
         adj_mp_drift<NR, F16>(sm, lane, hd, accB, rows);
     }
     if constexpr (DENS_FIRST) {
@@ -735,7 +739,7 @@ DI void adj_mlp_pass_mp(const Smem& sm, const WaveW& ww, const float* ust, int h
     } else {
         SCHED_PHASE();
         f32x16 hn;
-        layer1_tile<F16, false>(sm, ww, ust, h, z, hn);
+        layer1_tile<F16, false, PAIRED>(sm, ww, ust, h, z, hn);
         adj_mp_density<F16>(sm, h, lane, hn, ebraw, rows);
     }
 }
@@ -744,7 +748,7 @@ DI void adj_mlp_pass_mp(const Smem& sm, const WaveW& ww, const float* ust, int h
 // consumed, then abar2 from the checkpointed second layer (h2c: this lane's four float4 of the tile), W2^T abar2 by MFMA, and only
 // then the drift layer-1 tile recomputed and consumed. Same operations and the same chain order per value as step_fwd's layer 1 +
 // vjp_mlp_partials (density tile first, then the drift tile: SPEC.md §5.4), hence the same bits; peak 32 tile registers instead of 64.
-template <int M, int F16>
+template <int M, int F16, bool PAIRED = false>
 DI void adj_mlp_pass(const Smem& sm, const WaveW& ww, const float* ust, int h, int lane, const float* z, const float4* h2c,
                      float ebraw_in, const float* ob_in, float* Pz, float* Pu) {
     float ob[6];       // (math_mode fast: -2 onto the output adjoints, see vjp_mlp_partials)
@@ -757,7 +761,7 @@ DI void adj_mlp_pass(const Smem& sm, const WaveW& ww, const float* ust, int h, i
     for (int jj = 0; jj < M; ++jj) Pu[jj] = 0.0f;
     {   // density net: abar1n = (w3n * etaraw_bar) * (1 - h1n^2); zbar += W1z[32:64]^T abar1n
         f32x16 hn;
-        layer1_tile<F16, false>(sm, ww, ust, h, z, hn);
+        layer1_tile<F16, false, PAIRED>(sm, ww, ust, h, z, hn);
         // (weight quads of a quarter are requested from LDS together, then consumed: one exposed LDS round trip per quarter, see fwd_mlp_partials)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -827,7 +831,7 @@ DI void adj_mlp_pass(const Smem& sm, const WaveW& ww, const float* ust, int h, i
     }
     {   // drift net, first layer: recomputed only now
         f32x16 hd;
-        layer1_tile<F16, true>(sm, ww, ust, h, z, hd);
+        layer1_tile<F16, true, PAIRED>(sm, ww, ust, h, z, hd);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             float ad0 = accB[4 * q] * dact(hd[4 * q]);
