@@ -114,6 +114,37 @@ DI void duo_rotate_priority() {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Per-step streams of the sweeps (trajectory rows, noise rows, step scalars). A pair's rows of one step lie at (uniform base of the pair) +
+// (step) * (rows per step) * 32 + (row) * 32 + (this lane's group and column). Indexed as base[lane + (unsigned)((t * ROWS + i) * 32)] the 32-bit
+// sum may wrap, so every access got an address of its own: v_add_u32, a zeroed high word and v_lshl_add_u64. In the IMM form the pair's base stays
+// in its SGPR pair, the step and the lane make ONE 32-bit BYTE offset per stream and step (a v_add_u32), and the row is the instruction's
+// immediate offset (row * 128 bytes <= 1,536, inside the 13-bit field): global_load/store_dword v, v_ofs, s[base:base+1] offset:row * 128.
+// (An offset in elements keeps one v_lshl_add_u64 per access: the shift by two must be done in 64 bits. A per-step base on the SALU plus a
+// loop-invariant lane offset is no better: the compiler extends the lane offset to 64 bits once, in front of the loop, holds it in a VGPR
+// pair per stream and adds the step's base to it with a 64-bit vector instruction.)
+// Horizons end at 4,096: the largest offset, two groups' H x ACT_STRIDE floats, is 42 MB.
+// The kernels without noise staging rows (!NZS) keep the indexed form: with the IMM form two of the 24 spilled more loads synchronously than
+// before, and keeping the indexed form for their noise prefetch alone only moved the spill (profiles/duo_stream_addressing.txt §2).
+// Their code objects are the ones they had: the indexed expressions below are, term for term, those of the build before.
+// ------------------------------------------------------------------------------------------------
+// row `row0 + i` of a stream of 32-float rows: row0 = (step) x (rows per step) selects the step, i the row within it (the immediate offset)
+template <bool IMM, class T>
+DI T& stream_row(T* pair_base, unsigned lane, int row0, int i) {
+    if constexpr (IMM) {
+        using Byte = std::conditional_t<std::is_const_v<T>, const char, char>;
+        return reinterpret_cast<T*>(reinterpret_cast<Byte*>(pair_base) + (lane * 4u + (unsigned)row0 * 128u))[i * 32];
+    } else return pair_base[lane + (unsigned)((row0 + i) * 32)];
+}
+// element k of a step's record that begins `step` elements into the stream (the step scalars)
+template <bool IMM, class T>
+DI T& stream_el(T* pair_base, unsigned lane, int step, int k) {
+    if constexpr (IMM) {
+        using Byte = std::conditional_t<std::is_const_v<T>, const char, char>;
+        return reinterpret_cast<T*>(reinterpret_cast<Byte*>(pair_base) + (lane * 4u + (unsigned)step * 4u))[k];
+    } else return pair_base[lane + (unsigned)step + k];
+}
+
+// ------------------------------------------------------------------------------------------------
 // Noise staging of the forward sweeps. The six noise rows of step t are used once, by the Euler-Maruyama update at the END of step t.
 // Held in registers from a request early enough to cover HBM latency they are live across both MLP passes, and the compiler spilled
 // them: load -> s_waitcnt -> scratch store, six synchronous HBM round trips per step. They travel by LDS-DMA instead
@@ -232,11 +263,11 @@ DI float duo_rollout(const KArgs& a, const Smem& sm, const WaveW& ww, const floa
             for (int i = 0; i < NX; ++i) asm volatile("" : "+v"(x[i]));
         } else {
 #pragma unroll
-            for (int i = 0; i < NN; ++i) xi[i] = nzb[nzo + (unsigned)(i * 32)];
+            for (int i = 0; i < NN; ++i) xi[i] = stream_row<NZS>(nzb, nzo, 0, i);
         }
         if (store_traj && pr.own) {
 #pragma unroll
-            for (int i = 0; i < NX; ++i) tjb[tjo + (unsigned)(i * 32)] = x[i];
+            for (int i = 0; i < NX; ++i) stream_row<NZS>(tjb, tjo, 0, i) = x[i];
         }
         if (want_mean) {
 #pragma unroll
@@ -253,7 +284,7 @@ DI float duo_rollout(const KArgs& a, const Smem& sm, const WaveW& ww, const floa
             if constexpr (!NZS) {
                 if (t + 1 < H) {
 #pragma unroll
-                    for (int i = 0; i < NN; ++i) xin[i] = nzb[nzo + (unsigned)(((t + 1) * NN + i) * 32)];
+                    for (int i = 0; i < NN; ++i) xin[i] = stream_row<NZS>(nzb, nzo, (t + 1) * NN, i);
                 }
             }
             duo_step_fwd<F16, false, NZS>(a, sm, ww, t, h, lane, pr.hasB, x, xi, xn, A, nullptr, nullptr);
@@ -271,7 +302,7 @@ DI float duo_rollout(const KArgs& a, const Smem& sm, const WaveW& ww, const floa
             }
             if (store_traj && pr.own) {
 #pragma unroll
-                for (int i = 0; i < NX; ++i) tjb[tjo + (unsigned)(((t + 1) * NX + i) * 32)] = x[i];
+                for (int i = 0; i < NX; ++i) stream_row<NZS>(tjb, tjo, (t + 1) * NX, i) = x[i];
             }
             if (want_mean) {
 #pragma unroll
@@ -332,7 +363,7 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
         for (int i = 0; i < NX; ++i) x[i] = a.x0[b * NX + i];      // (read here, per pair: nothing of it stays live across the pair loop)
         if (pr.own) {
 #pragma unroll
-            for (int i = 0; i < NX; ++i) tjb[tjo + (unsigned)(i * 32)] = x[i];
+            for (int i = 0; i < NX; ++i) stream_row<NZS>(tjb, tjo, 0, i) = x[i];
         }
         if constexpr (NZS) {
             duo_noise_request(nzb, nzo, 0, sm.nzs);
@@ -340,7 +371,7 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
             for (int i = 0; i < NX; ++i) asm volatile("" : "+v"(x[i]));      // (as in duo_rollout: no wait for the initial state inside the loop)
         } else {
 #pragma unroll
-            for (int i = 0; i < NN; ++i) xi[i] = nzb[nzo + (unsigned)(i * 32)];
+            for (int i = 0; i < NN; ++i) xi[i] = stream_row<NZS>(nzb, nzo, 0, i);
         }
         float J = 0.0f;
         for (int t = 0; t < H; ++t) {
@@ -349,15 +380,14 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
             if constexpr (!NZS) {
                 if (t + 1 < H) {
 #pragma unroll
-                    for (int i = 0; i < NN; ++i) xin[i] = nzb[nzo + (unsigned)(((t + 1) * NN + i) * 32)];
+                    for (int i = 0; i < NN; ++i) xin[i] = stream_row<NZS>(nzb, nzo, (t + 1) * NN, i);
                 }
             }
             duo_step_fwd<F16, true, NZS>(a, sm, ww, t, h, lane, pr.hasB, x, xi, xn, A, acA + (size_t)t * ACT_STRIDE, acB + (size_t)t * ACT_STRIDE);
             if constexpr (NZS) { if (t + 1 < H) duo_noise_request(nzb, nzo, t + 1, sm.nzs); }   // before this step's scalar / trajectory stores: older than they are
             if (pr.own) {
-                const unsigned so = aso + (unsigned)(t * ACT_STRIDE);
-                *reinterpret_cast<float4*>(acA + so) = make_float4(A.eta, A.Fb[0], A.Fb[1], A.Fb[2]);
-                acA[so + 4] = A.rn;
+                *reinterpret_cast<float4*>(&stream_el<NZS>(acA, aso, t * ACT_STRIDE, 0)) = make_float4(A.eta, A.Fb[0], A.Fb[1], A.Fb[2]);
+                stream_el<NZS>(acA, aso, t * ACT_STRIDE, 4) = A.rn;
             }
             float l = stage_cost<false>(a, xn, sm.xref + (t + 1) * NX, nullptr);
             l = FMA(a.C.res_mult * A.eta, A.eta, l);
@@ -372,7 +402,7 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
             }
             if (pr.own) {
 #pragma unroll
-                for (int i = 0; i < NX; ++i) tjb[tjo + (unsigned)(((t + 1) * NX + i) * 32)] = x[i];
+                for (int i = 0; i < NX; ++i) stream_row<NZS>(tjb, tjo, (t + 1) * NX, i) = x[i];
             }
         }
         { const float T = group_bfly32(valid ? J : 0.0f); if (j == 0 && pr.own) Sq[PS - 1] = T; }
@@ -406,14 +436,13 @@ DI float duo_cost_grad(const KArgs& a, const Smem& sm, const WaveW& ww, const fl
                     asm volatile("global_load_dword %0, %1, off" : "=v"(touched) : "v"(tp) : "memory");
                 }
             }
-            const unsigned so = aso + (unsigned)(t * ACT_STRIDE);
-            const float4 ns4 = *reinterpret_cast<const float4*>(acA + so);
-            const float nrn = acA[so + 4];
+            const float4 ns4 = *reinterpret_cast<const float4*>(&stream_el<NZS>(acA, aso, t * ACT_STRIDE, 0));
+            const float nrn = stream_el<NZS>(acA, aso, t * ACT_STRIDE, 4);
             {
 #pragma unroll
-                for (int i = 0; i < NX; ++i) xt[i] = tjb[tjo + (unsigned)((t * NX + i) * 32)];
+                for (int i = 0; i < NX; ++i) xt[i] = stream_row<NZS>(tjb, tjo, t * NX, i);
 #pragma unroll
-                for (int i = 0; i < NN; ++i) xi[i] = nzb[nzo + (unsigned)((t * NN + i) * 32)];
+                for (int i = 0; i < NN; ++i) xi[i] = stream_row<NZS>(nzb, nzo, t * NN, i);
             }
             // x = x_{t+1}: fold the stage-cost gradient into the incoming adjoint
             const float dsc = sm.disc[t];
