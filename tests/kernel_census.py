@@ -6,6 +6,11 @@ launch_rollout) pick exactly that instantiation, at the smallest shape at which 
     rollout kernel, in both math modes. tests/test_gpu_kernel_census.py runs each row, requires the reported name to EQUAL the row's and compares
     every output with the CPU oracle bit for bit; tests/test_kernel_census_cpu.py proves on the CPU that the table names exactly the kernels of
     the build and that every row's problem moves (iterations, an accepted step, a gradient in every motor column).
+  * ALL_ROWS: one Row per kernel that only the all-variants build carries (`make allvariants`, csrc/allvariants/libsdempc.so: the generic 8-slot
+    instantiation in the duo, six-team, cooperative, speculative and global-control-table layouts; the packed-tanh latency kernels), and two rows on
+    the two sides of the batch size at which that build's dispatcher stops taking a packed-tanh kernel. tests/test_gpu_kernel_census_all.py runs them
+    in a child process that has that library loaded. The stated limit of this census: the kernels common to both builds get no second set of rows;
+    of the second library's own copies of them only the one behind the threshold row is run.
   * ELSEWHERE: the kernels whose choice is route and arithmetic alone and whose names cannot be read back (the closed loop's plant steps: launch_loop
     does not call note_kernel; the PRNG kernels; the layout conversions): the existing GPU test that runs each.
   * UNREACHED: kernels that are built but that no input can dispatch, with the dispatcher's own words for why.
@@ -17,7 +22,7 @@ restatement of the one in sdempc_kernels.hip) makes the pick, and the row's note
 force the layout (5 for the one-wave teams: a second workgroup with one of its four teams in use); a function of the device's CU count where the
 batch size is what selects the kernel. The oracle runs on a sample of instances: the first, the last and one across a workgroup boundary.
 
-`python tests/kernel_census.py` rewrites tests/KERNELS.md."""
+`python tests/kernel_census.py` rewrites tests/KERNELS.md and tests/KERNELS_ALL.md."""
 import dataclasses
 import functools
 import os
@@ -29,7 +34,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "sde4mbrl_px4_amd", "csrc")
+AV_DIR = os.path.join(CSRC, "allvariants")          # `make allvariants`: the all-variants build, objects and library
 KERNELS_MD = os.path.join(ROOT, "tests", "KERNELS.md")
+KERNELS_ALL_MD = os.path.join(ROOT, "tests", "KERNELS_ALL.md")
 CUS = 256                       # compute units of an MI355X: what the CPU-side checks and KERNELS.md evaluate the batch expressions for
 F16_OF = {"f32": 0, "f16": 1, "f32x3": 2}
 MLP_OF = {v: k for k, v in F16_OF.items()}
@@ -57,13 +64,13 @@ def normalise(name):
     return s.strip(), mode
 
 
-def built_kernels():
-    """{(kernel, mode)} of what is built, from the symbol table (one __device_stub__ per kernel): of libsdempc.so, else of the objects beside it.
-    None when nothing is built or nm is missing."""
-    if not shutil.which("nm"):
+def built_kernels(where=CSRC):
+    """{(kernel, mode)} of what is built in the directory `where`, from the symbol table (one __device_stub__ per kernel): of libsdempc.so, else of the
+    objects beside it. None when nothing is built or nm is missing."""
+    if not shutil.which("nm") or not os.path.isdir(where):
         return None
-    so = os.path.join(CSRC, "libsdempc.so")
-    files = [so] if os.path.exists(so) else sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".o"))
+    so = os.path.join(where, "libsdempc.so")
+    files = [so] if os.path.exists(so) else sorted(os.path.join(where, f) for f in os.listdir(where) if f.endswith(".o"))
     if not files:
         return None
     out = set()
@@ -152,10 +159,11 @@ class Row:
     options: tuple              # handle options, ((name, value), ...)
     note: str = ""
     stepsize: float = 0.01      # stepsize_in of the solve
+    tag: str = ""               # tells apart the rows of a kernel that has more than one (ALL_ROWS: the packed-tanh threshold)
 
     @property
     def id(self):
-        return f"{self.mode}-{self.kernel}".replace(" ", "")
+        return f"{self.mode}-{self.kernel}".replace(" ", "") + (f"-{self.tag}" if self.tag else "")
 
     @property
     def vehicle(self):
@@ -266,6 +274,72 @@ def _rows():
 
 ROWS = _rows()
 
+
+def _all_rows():
+    """The kernels that only the all-variants build carries. Options and shapes are those of the matching M = 4 / M = 6 rows of _rows(), with one
+    addition: takes_pk, on auto, sends every f32 / exact launch of at most `cus` workgroups to a packed-tanh kernel in that build, so the f32 / exact
+    rows of B = 3 that are about another kernel carry pk = 0 (the cooperative and speculative layouts are chosen before takes_pk is asked)."""
+    rows = []
+    opt = lambda **kw: tuple(sorted(kw.items()))
+    m = GENERIC_M
+    for mode in MODES:
+        add = lambda kernel, kind, M, f, P, H, batch, options, note="", **kw: rows.append(
+            Row(kernel, mode, kind, m if M == 8 else M, MLP_OF[f], P, H, str(batch), options, note, **kw))
+        for f in (0, 1, 2):
+            pk0 = dict(pk=0) if f == 0 and mode == "exact" else {}
+            Hg = shortest_h(lambda H: global_table(H, m))
+            add(f"sdempc_solve_kernel<TeamBlock, 8, {f}, false, 0, true>", "solve", 8, f, 33, Hg, 3, opt(coop=0, **pk0),
+                f"use_global_ust: H = {Hg} is the shortest horizon with smem_bytes(H, {m}, 1) = {smem_bytes(Hg, m)} > 156 KiB / 3 = {LDS_CAP // 3} "
+                f">= {smem_bytes(Hg, m, 1, False, False)} without the table: three workgroups per CU instead of two", stepsize=1e-4)
+            # two-wave teams in pairs: one row picked by the batch (noise drawn on the device), the others forced at B = 3
+            if f == 2 and mode == "exact":
+                add(f"sdempc_solve_kernel<TeamPairT<2>, 8, {f}, false, 3, false>", "solve_keys", 8, f, 70, 8, "3 * cus + 1", opt(),
+                    "takes_duo on auto: B > 3 workgroups per CU x CUs (one_group_per_wave_batch), B < 6 x CUs (no six-team workgroups)")
+            else:
+                add(f"sdempc_solve_kernel<TeamPairT<2>, 8, {f}, false, 3, false>", "solve", 8, f, 70, 8, 3, opt(coop=0, duo=1, **pk0))
+            add(f"sdempc_solve_kernel<TeamPairT<6>, 8, {f}, false, 3, false>", "solve_keys", 8, f, 70, 8, "6 * cus", opt(),
+                "launch_duo_small: B >= 6 x CUs fills every team slot")
+            Hp = shortest_h(lambda H: not pair_fits(H, m))
+            assert duo_pick(Hp, m, 2, 0) == 0
+            add(f"sdempc_solve_kernel<TeamBlock2, 8, {f}, false, 3, false>", "solve", 8, f, 70, Hp, 3, opt(coop=0, duo=1, ustg=0, **pk0),
+                f"launch_duo_small: H = {Hp} is the shortest horizon at which 3 x smem_bytes(H, {m}, 2, nz_waves = 4) = 3 x {smem_bytes(Hp, m, 2, False, True, 4)} "
+                f"> 156 KiB = {LDS_CAP}: no TeamPair; ustg = 0 pins launch_duo_m's pick 0", stepsize=1e-3)
+            add(f"sdempc_solve_kernel<TeamBlock2, 8, {f}, false, 3, true>", "solve", 8, f, 70, 8, 3, opt(coop=0, duo=1, ustg=1, **pk0))
+            H4 = shortest_h(lambda H: not pair_fits(H, m) and duo_pick(H, m, 2) == 2)
+            add(f"sdempc_solve_kernel<TeamBlock2, 8, {f}, false, 4, true>", "solve", 8, f, 70, H4, 3, opt(coop=0, duo=1, **pk0),
+                f"launch_duo_m, ustg on auto: H = {H4} is the shortest horizon at which the pair does not fit and dropping the staging rows as well buys a "
+                f"workgroup per CU: {LDS_CAP} // {smem_bytes(H4, m, 1, False, False, 0)} > {LDS_CAP} // {smem_bytes(H4, m, 1, False, False, 2)} "
+                f"(table in LDS: {smem_bytes(H4, m, 1, False, True, 2)})", stepsize=1e-4)
+            add(f"sdempc_solve_kernel<TeamBlock, 8, {f}, false, 3, false>", "solve", 8, f, 130, 8, 3, opt(coop=0, **pk0))
+            add(f"sdempc_solve_kernel<TeamBlock, 8, {f}, false, 3, true>", "solve", 8, f, 130, 8, 3, opt(coop=0, ustg=1, **pk0))
+            H4b = shortest_h(lambda H: duo_pick(H, m, 4) == 2)
+            add(f"sdempc_solve_kernel<TeamBlock, 8, {f}, false, 4, true>", "solve", 8, f, 130, H4b, 3, opt(coop=0, **pk0),
+                f"launch_duo_m, ustg on auto: H = {H4b} is the shortest horizon at which only the carve without table and staging rows keeps the most "
+                f"workgroups per CU: {LDS_CAP} // {smem_bytes(H4b, m, 1, False, False, 0)} > {LDS_CAP} // {smem_bytes(H4b, m, 1, False, False, 4)} "
+                f"(table in LDS: {smem_bytes(H4b, m, 1, False, True, 4)})", stepsize=1e-4)
+        # f32 contractions only: the cooperative and speculative layouts, as at M = 4 / 6
+        add("sdempc_solve_kernel<TeamBlock, 8, 0, true, 2, false>", "solve", 8, 0, 33, 8, 3, opt(spec=0))
+        add("sdempc_solve_kernel<TeamBlock, 8, 0, false, 2, false>", "solve", 8, 0, 33, 8, "cus // 9 + 1", opt(spec=0),
+            "launch_coop_m: B x coop_nwg(33) = B x 9 > CUs, B <= coop_max_instances = (2 CUs - 16) / 9")
+        add("sdempc_solve_spec_kernel<8, false>", "solve", 8, 0, 33, 8, 3, opt())
+        add("sdempc_solve_spec_kernel<8, true>", "solve", 8, 0, 1, 8, 3, opt())
+        if mode == "exact":
+            # packed tanh: pk on auto takes every f32 / exact launch of at most `cus` workgroups; shapes of the one-group-per-wave rows
+            for M in (4, 6, 8):
+                add(f"sdempc_solve_kernel<TeamWave, {M}, 0, true, 0, false>", "solve", M, 0, 32, 8, 5, opt(coop=0))
+                add(f"sdempc_solve_kernel<TeamBlock, {M}, 0, true, 0, false>", "solve", M, 0, 33, 8, 3, opt(coop=0, duo=0))
+                add(f"sdempc_solve_kernel<TeamBlock8, {M}, 0, true, 0, false>", "solve", M, 0, 130, 8, 3, opt(coop=0),
+                    "launch_solve_team: more than four groups, so the packed-tanh launch takes the eight-wave team")
+            # the two sides of takes_pk's threshold; the second runs a kernel common to both builds from this library's own code object
+            add("sdempc_solve_kernel<TeamBlock, 4, 0, true, 0, false>", "solve", 4, 0, 33, 8, "cus", opt(coop=0, duo=0),
+                "takes_pk on auto: B = CUs workgroups is the largest packed-tanh launch", tag="threshold")
+            add("sdempc_solve_kernel<TeamBlock, 4, 0, false, 0, false>", "solve", 4, 0, 33, 8, "cus + 1", opt(coop=0, duo=0),
+                "takes_pk on auto: one workgroup more than CUs", tag="threshold")
+    return rows
+
+
+ALL_ROWS = _all_rows()
+
 # ---- kernels whose names cannot be read back: the existing GPU test that runs each ------------------------------------------------------------
 ARITH = [(d, mth) for d in ("f32", "f16", "f32x3") for mth in MODES]      # tests/loop_cases.py
 LOOP_ROUTES = {     # launch_loop's if-chain, top to bottom -> (kernel, test); the plant's math mode picks the namespace, its mlp_dtype F16
@@ -309,6 +383,11 @@ UNREACHED = {
 
 def table_names():
     return {(r.kernel, r.mode) for r in ROWS} | set(ELSEWHERE) | set(UNREACHED)
+
+
+def all_names():
+    """what the all-variants build carries beyond table_names()"""
+    return {(r.kernel, r.mode) for r in ALL_ROWS} - table_names()
 
 
 # ---- a row's problem and its oracle results -----------------------------------------------------------------------------------------------------
@@ -384,6 +463,23 @@ def kernels_markdown():
     return "\n".join(L)
 
 
+def kernels_all_markdown():
+    L = ["# Kernels that only the all-variants build carries and what runs each", "",
+         "Generated by `tests/kernel_census.py` (`python tests/kernel_census.py` rewrites it; `tests/test_kernel_census_cpu.py` fails when it is stale, and",
+         "when the names below together with those of `tests/KERNELS.md` are not exactly the kernels in the symbol table of `csrc/allvariants/libsdempc.so`).", "",
+         f"{len(ALL_ROWS)} rows of `tests/test_gpu_kernel_census_all.py`: {len(all_names())} kernels and {sum(bool(r.tag) for r in ALL_ROWS)} rows on the two sides of the "
+         "packed-tanh threshold. The kernels common to both builds are run from the default library only (`tests/KERNELS.md`). `cus`: the device's compute "
+         "units (256 on an MI355X).", "",
+         "| mode | kernel | call | vehicle | mlp | P | H | B | options | why this shape |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for r in ALL_ROWS:
+        L.append(f"| {r.mode} | `{r.kernel}` | {r.kind} | `{r.vehicle}` | {r.mlp} | {r.P} | {r.H} | `{r.batch}` | "
+                 f"{' '.join(f'{k}={v}' for k, v in r.options) or '-'} | {r.note or '-'} |")
+    L.append("")
+    return "\n".join(L)
+
+
 if __name__ == "__main__":
     with open(KERNELS_MD, "w") as f:
         f.write(kernels_markdown())
+    with open(KERNELS_ALL_MD, "w") as f:
+        f.write(kernels_all_markdown())

@@ -2,9 +2,10 @@
 the oracle alone (a row whose solve does not move, or whose gradient has a dead motor column, could not tell a wrong kernel from a right one), the
 unreachable kernels, and the committed matrix tests/KERNELS.md. No GPU.
 
-The census is of the DEFAULT build. An all-variants build (make EXTRA=-DSDEMPC_ALL_VARIANTS=1; sdempc_build_flags() & 1) carries more kernels (the
-generic motor count in every layout, the packed-tanh latency instantiations): there every name of the table must still be built, the extra kernels
-are printed and not failed, and a census of them is out of scope."""
+Two builds, two tables. The default build (csrc/libsdempc.so) carries exactly table_names(). The all-variants build (make allvariants:
+csrc/allvariants/libsdempc.so; sdempc_build_flags() & 1) carries those and the kernels of ALL_ROWS (the generic motor count in every layout, the
+packed-tanh latency instantiations), again exactly, in both directions; so does a library at the default path that was itself built with
+EXTRA=-DSDEMPC_ALL_VARIANTS=1. The new rows' problems are held to the same conditions as the default ones."""
 import numpy as np
 import pytest
 
@@ -14,10 +15,10 @@ import orc
 EV = orc.EVENT_FIELDS
 
 
-def _built():
-    built = kc.built_kernels()
+def _built(where=kc.CSRC):
+    built = kc.built_kernels(where)
     if built is None:
-        pytest.skip("libsdempc.so / its objects are not built here, or nm is missing")
+        pytest.skip(f"libsdempc.so / its objects are not built in {where}, or nm is missing")
     return built
 
 
@@ -40,11 +41,20 @@ def test_table_names_exactly_the_kernels_of_the_build():
     print(f"built: {len(built)} kernels ({per_mode}); table: {len(kc.ROWS)} rows + {len(kc.ELSEWHERE)} mapped to existing tests + {len(kc.UNREACHED)} unreachable")
     missing = sorted(table - built)
     assert not missing, f"in the table but not built: {missing}"
-    extra = sorted(built - table)
+    extra = set(built - table)
     if _abi.load_library().sdempc_build_flags() & 1:
-        print(f"all-variants build: {len(extra)} kernels beyond the census:", *extra, sep="\n  ")
+        print(f"all-variants build at the default path: {len(extra)} kernels beyond the default table")
+        assert extra == kc.all_names(), f"in no row of ALL_ROWS: {sorted(extra - kc.all_names())}; in ALL_ROWS but not built: {sorted(kc.all_names() - extra)}"
     else:
-        assert not extra, f"built but in no row, no existing test and not declared unreachable: {extra}"
+        assert not extra, f"built but in no row, no existing test and not declared unreachable: {sorted(extra)}"
+
+
+def test_both_tables_name_exactly_the_kernels_of_the_all_variants_build():
+    """csrc/allvariants: the default table's names and ALL_ROWS' names, both directions."""
+    built, table = _built(kc.AV_DIR), kc.table_names() | kc.all_names()
+    print(f"built: {len(built)} kernels; tables: {len(kc.table_names())} + {len(kc.all_names())}")
+    assert not sorted(table - built), f"in the tables but not built: {sorted(table - built)}"
+    assert not sorted(built - table), f"built but in no row, no existing test and not declared unreachable: {sorted(built - table)}"
 
 
 def test_table_is_one_entry_per_kernel():
@@ -52,7 +62,15 @@ def test_table_is_one_entry_per_kernel():
     assert len(set(rows)) == len(rows) and len({r.id for r in kc.ROWS}) == len(rows)
     assert not (set(rows) & set(kc.ELSEWHERE)) and not (set(rows) & set(kc.UNREACHED)) and not (set(kc.ELSEWHERE) & set(kc.UNREACHED))
     assert len(kc.UNREACHED) <= 4 and all(why for why in kc.UNREACHED.values())
-    for r in kc.ROWS:
+    # the all-variants rows: one untagged row per kernel, none of them a kernel of the default table; ids unique across both tables
+    plain = [(r.kernel, r.mode) for r in kc.ALL_ROWS if not r.tag]
+    assert len(set(plain)) == len(plain) == len(kc.all_names()) == 71 and not (set(plain) & kc.table_names())
+    tagged = [r for r in kc.ALL_ROWS if r.tag]
+    assert [(r.kernel, r.batch) for r in tagged] == [("sdempc_solve_kernel<TeamBlock, 4, 0, true, 0, false>", "cus"),
+                                                     ("sdempc_solve_kernel<TeamBlock, 4, 0, false, 0, false>", "cus + 1")]
+    assert len({r.id for r in kc.ROWS + kc.ALL_ROWS}) == len(kc.ROWS) + len(kc.ALL_ROWS)
+    assert all(r.m == kc.GENERIC_M for r in kc.ALL_ROWS if ", 8, " in r.kernel or "<8, " in r.kernel)
+    for r in kc.ROWS + kc.ALL_ROWS:
         assert r.mode in kc.MODES and r.kind in ("solve", "solve_keys", "grad", "rollout") and r.mlp in kc.F16_OF
         assert "test_absent_wg" not in dict(r.options), r.id
         assert 1 <= r.B(256) and sorted(r.sample(256))[-1] == r.B(256) - 1 and len(r.sample(256)) <= 4
@@ -61,9 +79,9 @@ def test_table_is_one_entry_per_kernel():
 
 def test_rows_chosen_by_the_lds_budget_sit_on_the_threshold():
     """The shortest horizon of each derived row: one step shorter and the dispatcher's arithmetic picks another instantiation."""
-    for r in kc.ROWS:
-        if r.H <= 12:
-            continue
+    derived = [r for r in kc.ROWS + kc.ALL_ROWS if r.H > 12]
+    assert len(derived) == 48 + 24
+    for r in derived:
         M = r.m
         if "TeamBlock, " in r.kernel and r.kernel.endswith("false, 0, true>"):
             assert kc.global_table(r.H, M) and not kc.global_table(r.H - 1, M), r.id
@@ -96,7 +114,7 @@ def test_existing_tests_named_for_the_unnamed_kernels_exist():
     assert len(loop) == 42 and sum(m == "fast" for _, m in loop) == 21
 
 
-@pytest.mark.parametrize("row", [r for r in kc.ROWS if r.kind in ("solve", "solve_keys")], ids=lambda r: r.id)
+@pytest.mark.parametrize("row", [r for r in kc.ROWS + kc.ALL_ROWS if r.kind in ("solve", "solve_keys")], ids=lambda r: r.id)
 def test_every_solve_row_can_fail(row):
     """The oracle alone, on the sampled instances: at least two iterations, at least one accepted step (uopt differs from the warm start in some
     word), all outputs finite."""
@@ -125,3 +143,5 @@ def test_every_gradient_and_rollout_row_can_fail(row):
 def test_committed_matrix_is_current():
     with open(kc.KERNELS_MD) as f:
         assert f.read() == kc.kernels_markdown(), "tests/KERNELS.md is stale: run python tests/kernel_census.py"
+    with open(kc.KERNELS_ALL_MD) as f:
+        assert f.read() == kc.kernels_all_markdown(), "tests/KERNELS_ALL.md is stale: run python tests/kernel_census.py"
