@@ -175,7 +175,8 @@ int sdempc_device_ready(const sdempc_handle* h);
  *                                                                                          no kernel may read a word of these buffers that the same call has not written.
  *                                                                                          Filled: the workspaces (particle x horizon tensor, activation checkpoint,
  *                                                                                          partial sums, control table), the cooperative layouts' per-particle outputs and
- *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs,
+ *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs (the tube planes of
+ *                                                                                          sdempc_tube_batch, d_tube, among them),
  *                                                                                          the closed loop's key / chunk / plant / rate-state / observation / history buffers (the chunk buffer includes the
  *                                                                                          staged disturbance rows and plant-schedule rows of a scenario). (The particle x horizon tensor is
  *                                                                                          zeroed at allocation otherwise; nothing depends on that.) Keep their initial value:
@@ -280,6 +281,33 @@ int sdempc_noise_from_keys(sdempc_handle* h, int32_t B, const uint32_t* keys, fl
 int sdempc_solve_batch_keys(sdempc_handle* h, int32_t B, const float* x0, const float* xref, const uint32_t* keys,
                             const float* u_init /*[B][H][m]*/, const float* stepsize_in /*[B]*/,
                             float* uopt /*[B][H][m]*/, float* xevol /*[B][H+1][13]*/, sdempc_info* info /*[B]*/);
+
+/* ---- predicted tube (SPEC.md §12) --------------------------------------------------------------
+ * The solve rolls out P particles per instance and returns their mean (xevol). These entry points reduce the same particle x horizon tensor where it lies
+ * on the device to five planes per instance, each [H+1][13] (column c = t * 13 + i), over the valid particles p < P:
+ *   mean     the particle mean — bit for bit the xmean of the same rollout;
+ *   var      the population variance about that rounded mean (P = 1: exactly 0);
+ *   min, max the extrema (NaN operands ignored; +inf / -inf where every particle is NaN);
+ *   outside  uint32: how many particles have !(x >= lo[i] && x <= hi[i]) — a NaN counts — the empirical chance-constraint estimate per step and component
+ *            (divide by P on the host). -inf / +inf in lo / hi: no bound on that component.
+ * Each plane pointer may be NULL (not computed, not written); at least one must be given, and outside needs cfg. cfg may be NULL otherwise; a NaN bound or a
+ * wrong struct_size is SDEMPC_EINVAL. Every argument is checked before the first HIP call. */
+typedef struct sdempc_tube_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_tube_cfg) */
+    float lo[SDEMPC_NX], hi[SDEMPC_NX];
+} sdempc_tube_cfg;
+/* Reduces the tensor that the last sdempc_rollout_batch_dev(store_traj=1) of at least B instances left in the handle; device pointers, f32[B][H+1][13]
+ * (outside_dev: u32). Refused like sdempc_traj_to_canonical_dev when the workspace holds fewer instances: after a gradient evaluation, a solve, a smaller
+ * rollout or a workspace reallocation. Enqueue it on the stream of that rollout. */
+int sdempc_tube_batch_dev(sdempc_handle* h, const sdempc_tube_cfg* cfg /*or NULL*/, int32_t B, void* mean_dev, void* var_dev, void* min_dev, void* max_dev,
+                          void* outside_dev, void* stream);
+/* Host pointers: one rollout of u (as sdempc_rollout_batch; cost [B] may be NULL) with the tensor kept, the reduction, the requested planes copied back. */
+int sdempc_tube_batch(sdempc_handle* h, const sdempc_tube_cfg* cfg /*or NULL*/, int32_t B, const float* x0, const float* u, const float* xref,
+                      const float* noise, float* cost /*[B] or NULL*/, float* mean, float* var, float* min, float* max, uint32_t* outside);
+/* The same with the noise of instance b drawn on the device as normal(keys[b], (P, H, 6)) (keys: host u32[B][2]), as sdempc_solve_batch_keys does: with the
+ * uopt and the keys of a solve, mean is that solve's xevol bit for bit. */
+int sdempc_tube_batch_keys(sdempc_handle* h, const sdempc_tube_cfg* cfg /*or NULL*/, int32_t B, const float* x0, const float* u, const float* xref,
+                           const uint32_t* keys, float* cost /*[B] or NULL*/, float* mean, float* var, float* min, float* max, uint32_t* outside);
 
 /* ---- batched closed loop (SPEC.md §11) ---------------------------------------------------------
  * B independent episodes of T control ticks, entirely on the device: per tick, the solve of sdempc_solve_batch_keys on the episode's

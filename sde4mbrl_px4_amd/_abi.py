@@ -123,6 +123,11 @@ class SdempcTrackCfg(C.Structure):
                 ("offset", C.POINTER(C.c_float)), ("tick0", C.c_int32), ("renorm", C.c_int32), ("score_targets", C.c_int32)]
 
 
+class SdempcTubeCfg(C.Structure):
+    """sdempc_tube_cfg (SPEC.md §12): the per-component bounds the tube's `outside` plane counts against (-inf / +inf: none)."""
+    _fields_ = [("struct_size", C.c_int32), ("lo", C.c_float * NX), ("hi", C.c_float * NX)]
+
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -144,12 +149,14 @@ def lib_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libsdempc.so")
 
 
-def load_library():
-    """Load csrc/libsdempc.so. Fails loudly: there is no CPU fallback for the product path."""
+def load_library(path=None):
+    """Load csrc/libsdempc.so. Fails loudly: there is no CPU fallback for the product path. With `path`: that build of the library instead, beside the
+    package's own and not remembered (A/B runs of two builds in one process: SdeMpcSolver(..., lib_path=))."""
     global _LIB
-    if _LIB is not None:
+    if path is None and _LIB is not None:
         return _LIB
-    path = lib_path()
+    explicit = path is not None
+    path = os.path.abspath(path) if explicit else lib_path()
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()' "
@@ -213,7 +220,8 @@ def load_library():
                  "sdempc_noise_from_keys_dev", "sdempc_noise_from_keys", "sdempc_solve_batch_keys", "sdempc_closed_loop_batch",
                  "sdempc_closed_loop_batch_plant"):
         getattr(lib, name).restype = C.c_int
-    _LIB = lib
+    if not explicit:
+        _LIB = lib
     return lib
 
 
@@ -361,6 +369,24 @@ def reference_windows_entry(lib):
     return fn
 
 
+def tube_entries(lib):
+    """sdempc_tube_batch, sdempc_tube_batch_keys and sdempc_tube_batch_dev (SPEC.md §12) with their prototypes set. Detected by symbol and only when a call
+    needs them, as the closed-loop entry points are (no ABI version change)."""
+    try:
+        fns = lib.sdempc_tube_batch, lib.sdempc_tube_batch_keys, lib.sdempc_tube_batch_dev
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_tube_batch (SPEC.md §12): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fns[0].argtypes is None:
+        vp, i32, fp, u32p = C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        cfgp = C.POINTER(SdempcTubeCfg)
+        fns[0].argtypes = [vp, cfgp, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, u32p]
+        fns[1].argtypes = [vp, cfgp, i32, fp, fp, fp, u32p, fp, fp, fp, fp, fp, u32p]
+        fns[2].argtypes = [vp, cfgp, i32, vp, vp, vp, vp, vp, vp]
+        for f in fns:
+            f.restype = C.c_int
+    return fns
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -371,4 +397,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault", "sdempc_closed_loop_batch_observed",
     "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored", "sdempc_closed_loop_batch_drawn",
     "sdempc_closed_loop_batch_tracked", "sdempc_reference_windows",
+    "sdempc_tube_batch", "sdempc_tube_batch_keys", "sdempc_tube_batch_dev",
 ]

@@ -170,6 +170,8 @@ struct sdempc_handle {
     DevBuf d_part, d_act, d_traj, d_x0, d_u, d_xref, d_noise, d_step, d_cost, d_grad, d_xmean, d_uopt, d_info;
     // canonical-layout staging of the host-pointer entry points (allocated on their first use)
     DevBuf d_noise_canon, d_traj_canon, d_keys;
+    // predicted tube (sdempc_tube_batch / _keys, allocated on their first use): the five planes mean, var, min, max f32 and outside u32, each [max_batch][(H+1)*13]
+    DevBuf d_tube;
     // closed loop (sdempc_closed_loop_batch, allocated on its first use): d_loop = keys u32[max_batch][2], solve keys u32[max_batch][2], plant noise
     // f32[max_batch][6], one flag word; d_loop_chunk = the per-tick outputs of one chunk of ticks and the reference windows it reads (grown, never shrunk)
     DevBuf d_loop, d_loop_chunk;
@@ -429,6 +431,26 @@ int check_batch(sdempc_handle* h, int B) {
     if (!h) return SDEMPC_EINVAL;
     if (B < 1) return fail(h, SDEMPC_EINVAL, "batch must be >= 1%s");
     if (B > h->max_batch) return fail(h, SDEMPC_ECAPACITY, "batch exceeds max_batch given to sdempc_create%s");
+    return 0;
+}
+
+// does the trajectory workspace hold the particle x horizon tensor of at least B instances? (sdempc_traj_to_canonical_dev, sdempc_tube_batch_dev)
+int check_traj_held(sdempc_handle* h, int B) {
+    if (B > h->traj_batch)
+        return fail(h, SDEMPC_EINVAL, h->traj_batch ? "the trajectory workspace holds fewer instances than asked for (last rollout with store_traj was smaller)%s"
+                                                     : "the trajectory workspace holds no rollout: run a rollout with store_traj first (a gradient evaluation, a solve or a "
+                                                       "workspace reallocation since then has overwritten it)%s");
+    return 0;
+}
+
+// every check of a tube request (SPEC.md §12) that needs no device; no HIP call
+int check_tube(sdempc_handle* h, const sdempc_tube_cfg* cfg, const void* mean, const void* var, const void* mn, const void* mx, const void* outside) {
+    if (cfg && cfg->struct_size != (int32_t)sizeof(sdempc_tube_cfg)) return fail(h, SDEMPC_EINVAL, "sdempc_tube_cfg.struct_size mismatch%s");
+    if (!mean && !var && !mn && !mx && !outside) return fail(h, SDEMPC_EINVAL, "no output plane asked for: mean, var, min, max and outside are all NULL%s");
+    if (outside && !cfg) return fail(h, SDEMPC_EINVAL, "outside needs a sdempc_tube_cfg (the bounds it counts against)%s");
+    if (cfg)
+        for (int i = 0; i < SDEMPC_NX; ++i)
+            if (cfg->lo[i] != cfg->lo[i] || cfg->hi[i] != cfg->hi[i]) return fail(h, SDEMPC_EINVAL, "a bound of sdempc_tube_cfg is NaN (use -inf / +inf for no bound)%s");
     return 0;
 }
 
@@ -749,7 +771,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -880,10 +902,7 @@ int sdempc_traj_to_canonical_dev(sdempc_handle* h, int32_t B, void* traj_out_dev
     if (rc) return rc;
     if (!traj_out_dev) return fail(h, SDEMPC_EINVAL, "NULL device pointer%s");
     if ((rc = ensure_device(h))) return rc;
-    if (B > h->traj_batch)
-        return fail(h, SDEMPC_EINVAL, h->traj_batch ? "the trajectory workspace holds fewer instances than asked for (last rollout with store_traj was smaller)%s"
-                                                     : "the trajectory workspace holds no rollout: run a rollout with store_traj first (a gradient evaluation, a solve or a "
-                                                       "workspace reallocation since then has overwritten it)%s");
+    if ((rc = check_traj_held(h, B))) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     HIPCHK(h, launch_relayout(false, (const float*)h->d_traj.p, (float*)traj_out_dev, B, h->P, h->G, (h->H + 1) * SDEMPC_NX, st));
     return SDEMPC_OK;
@@ -1100,6 +1119,77 @@ int sdempc_solve_batch_keys(sdempc_handle* h, int32_t B, const float* x0, const 
     HIPCHK(h, hipMemcpyAsync(h->d_step.p, stepsize_in, sizeof(float) * B, hipMemcpyHostToDevice, h->stream));
     if ((rc = noise_from_keys(h, B, keys, (float*)h->d_noise.p, h->stream))) return rc;
     return solve_staged(h, B, uopt, xevol, info);
+    });
+}
+
+int sdempc_tube_batch_dev(sdempc_handle* h, const sdempc_tube_cfg* cfg, int32_t B, void* mean_dev, void* var_dev, void* min_dev, void* max_dev, void* outside_dev,
+                          void* stream) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if ((rc = check_tube(h, cfg, mean_dev, var_dev, min_dev, max_dev, outside_dev))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    if ((rc = check_traj_held(h, B))) return rc;
+    TubeArgs T{};
+    T.traj = (const float*)h->d_traj.p;
+    T.mean = (float*)mean_dev; T.var = (float*)var_dev; T.mn = (float*)min_dev; T.mx = (float*)max_dev; T.outside = (uint32_t*)outside_dev;
+    if (cfg)
+        for (int i = 0; i < SDEMPC_NX; ++i) { T.lo[i] = cfg->lo[i]; T.hi[i] = cfg->hi[i]; }
+    T.invP = h->base.invP;
+    T.C = (h->H + 1) * SDEMPC_NX;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    HIPCHK(h, launch_tube(T, B, h->P, h->G, h->H, st));
+    return SDEMPC_OK;
+    });
+}
+
+namespace {
+// the staged inputs (d_x0, d_u, d_xref, d_noise on the handle's stream) -> one store_traj rollout, the reducer, the planes asked for back on the host
+int tube_staged(sdempc_handle* h, const sdempc_tube_cfg* cfg, int32_t B, float* cost, float* mean, float* var, float* mn, float* mx, uint32_t* outside) {
+    int rc = sdempc_rollout_batch_dev(h, B, h->d_x0.p, h->d_u.p, h->d_xref.p, h->d_noise.p, h->d_cost.p, nullptr, 1, h->stream);
+    if (rc) return rc;
+    const size_t n = (size_t)(h->H + 1) * SDEMPC_NX, plane = sizeof(float) * (size_t)h->max_batch * n;
+    if (!h->d_tube.p && (rc = dev_alloc(h, h->d_tube, 5 * plane, true))) return rc;
+    char* d = (char*)h->d_tube.p;
+    void* host[5] = {mean, var, mn, mx, outside};
+    void* dev[5];
+    for (int k = 0; k < 5; ++k) dev[k] = host[k] ? d + k * plane : nullptr;
+    if ((rc = sdempc_tube_batch_dev(h, cfg, B, dev[0], dev[1], dev[2], dev[3], dev[4], h->stream))) return rc;
+    if (cost) HIPCHK(h, hipMemcpyAsync(cost, h->d_cost.p, sizeof(float) * B, hipMemcpyDeviceToHost, h->stream));
+    for (int k = 0; k < 5; ++k)
+        if (host[k]) HIPCHK(h, hipMemcpyAsync(host[k], dev[k], sizeof(float) * B * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return SDEMPC_OK;
+}
+}  // namespace
+
+int sdempc_tube_batch(sdempc_handle* h, const sdempc_tube_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const float* noise, float* cost,
+                      float* mean, float* var, float* min, float* max, uint32_t* outside) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if (!x0 || !u || !xref || !noise) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    if ((rc = check_tube(h, cfg, mean, var, min, max, outside))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    if ((rc = stage_common(h, B, x0, u, xref, noise))) return rc;
+    return tube_staged(h, cfg, B, cost, mean, var, min, max, outside);
+    });
+}
+
+int sdempc_tube_batch_keys(sdempc_handle* h, const sdempc_tube_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const uint32_t* keys, float* cost,
+                           float* mean, float* var, float* min, float* max, uint32_t* outside) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if (!x0 || !u || !xref || !keys) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    if ((rc = check_tube(h, cfg, mean, var, min, max, outside))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    const int H = h->H, m = h->m;
+    HIPCHK(h, hipMemcpyAsync(h->d_x0.p, x0, sizeof(float) * B * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_u.p, u, sizeof(float) * B * H * m, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_xref.p, xref, sizeof(float) * B * (H + 1) * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
+    if ((rc = noise_from_keys(h, B, keys, (float*)h->d_noise.p, h->stream))) return rc;
+    return tube_staged(h, cfg, B, cost, mean, var, min, max, outside);
     });
 }
 

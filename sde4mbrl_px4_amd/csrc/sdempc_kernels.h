@@ -318,5 +318,20 @@ hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, i
 hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int P, int G, int C, hipStream_t st);
 // SPEC.md §7: noise of B instances from their threefry keys (device u32[B][2]) straight into the device layout [B][G][H][6][32]
 hipError_t launch_noise_from_keys(const uint32_t* keys_dev, float* out, int B, int P, int G, int H, hipStream_t st);
+// SPEC.md §12, the predicted tube: the noise kernel in its TUBE form (sdempc_tube.inc.h). It reduces the particle x horizon tensor f32[B][G][C][32], C = (H+1)*13, over
+// the valid particles of every (instance, column): mean, population variance, extrema and the number of particles outside [lo_i, hi_i] (i = c mod 13), each plane
+// [B][C] and each optional. traj null means absent: every noise launch passes that, and the kernel then makes no memory access it did not make before.
+struct TubeArgs {
+    const float* traj;          // [B][G][C][32] the tensor a store_traj rollout left (KArgs::traj); null: the noise mode
+    float* mean;                // [B][C] or null
+    float* var;                 // [B][C] or null
+    float* mn;                  // [B][C] or null
+    float* mx;                  // [B][C] or null
+    uint32_t* outside;          // [B][C] or null: no bounds (lo / hi are then not read)
+    float lo[13], hi[13];       // bounds per state component, -inf / +inf: none (wave-uniform kernel arguments, read at constant indices)
+    float invP;                 // float32(1) / float32(P), as KArgs::invP
+    int C;                      // columns per instance
+};
+hipError_t launch_tube(const TubeArgs& T, int B, int P, int G, int H, hipStream_t st);
 
 }  // namespace sdempc

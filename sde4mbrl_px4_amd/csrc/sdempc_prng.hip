@@ -116,9 +116,19 @@ DI float bits_to_normal(uint32_t bits) {
     return 1.41421354f * erfinv_spec(u);
 }
 
+}  // namespace sdempc
+#include "sdempc_tube.inc.h"
+namespace sdempc {
+
 // grid: x = chunks of 256 threads over [pg][r][lane] (pg < ceil(ceil(P/2)/32), r < H*6), y = instance
-__global__ void __launch_bounds__(256) sdempc_noise_kernel(const uint32_t* __restrict__ keys, float* __restrict__ out, int P, int G, int HC, int b0) {
+// SPEC.md §12 (T.traj given; keys, out and HC are then not read): the TUBE form of the launch — x = tiles of 32 columns of the particle x horizon tensor, y = instance
+// (sdempc_tube.inc.h). T.traj null (every noise launch): not one access more.
+__global__ void __launch_bounds__(256) sdempc_noise_kernel(const uint32_t* __restrict__ keys, float* __restrict__ out, int P, int G, int HC, int b0, TubeArgs T) {
     const int b = b0 + blockIdx.y;
+    if (T.traj) {                                        // (wave-uniform)
+        tube_reduce(T, P, G, b);
+        return;
+    }
     const uint32_t k0 = keys[2 * b], k1 = keys[2 * b + 1];
     const unsigned N = (unsigned)P * (unsigned)HC, half = N / 2;          // N is even (HC = 6H)
     const unsigned k = blockIdx.x * 256u + threadIdx.x;
@@ -146,7 +156,19 @@ hipError_t launch_noise_from_keys(const uint32_t* keys_dev, float* out, int B, i
     const unsigned gx = (unsigned)((threads + 255) / 256);
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(keys_dev, out, P, G, HC, b0);
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(keys_dev, out, P, G, HC, b0, TubeArgs{});
+    }
+    return hipGetLastError();
+}
+
+// SPEC.md §12: one workgroup per (tile of 32 columns, instance); every word of every plane given is written
+hipError_t launch_tube(const TubeArgs& T, int B, int P, int G, int H, hipStream_t st) {
+    if (B < 1 || P < 1 || H < 1 || G != (P + 31) / 32 || !T.traj || T.C != (H + 1) * 13) return hipErrorInvalidValue;
+    if (!T.mean && !T.var && !T.mn && !T.mx && !T.outside) return hipErrorInvalidValue;
+    const unsigned gx = (unsigned)((T.C + 31) / 32);
+    for (int b0 = 0; b0 < B; b0 += 65535) {
+        const int nb = B - b0 < 65535 ? B - b0 : 65535;
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, T);
     }
     return hipGetLastError();
 }

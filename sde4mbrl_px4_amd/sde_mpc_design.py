@@ -144,6 +144,22 @@ class MpcProblem:
                       np.float32(i[5]), np.float32(i[6]), np.float32(i[7]))
         return _arr(uo), st, new_rng, _arr(xevol[0])
 
+    def m_tube(self, x, rng, uopt, curr_t=0.0, xdes=None, lo=None, hi=None):
+        """The predicted tube (SPEC.md §12) of the plan `uopt` on the noise m_mpc(x, rng, ...) solved on: the same key rule (SPEC.md §7.3, `sub` of
+        split(rng, 2)), the same reference window, one rollout, its particle x horizon tensor reduced on the device. Returns a solver.Tube whose planes are
+        [H+1][13] (cost a scalar array) IN THE SOLVER'S FRAME — variance, extrema and counts per component do not survive the attitude part of the frame flip —
+        and so are lo / hi. With the uopt m_mpc returned, `mean` is that call's xevol bit for bit (through enu2ned when convert_to_enu is set). rng is not
+        consumed: pass the key that went INTO m_mpc."""
+        from .solver import Tube
+        x = np.asarray(x, np.float32).reshape(13)
+        xs = enu2ned(x, np) if self.convert_to_enu else x
+        xdes = xs if xdes is None else np.asarray(xdes, np.float32).reshape(13)
+        _, sub = _next_key(rng)
+        xref = self.xref(float(curr_t), xdes)[None]
+        u = np.asarray(uopt, np.float32).reshape(1, self.cfg.horizon, self.cfg.num_motors)
+        t = self.solver().tube_keys(xs[None], u, xref, sub[None], lo=lo, hi=hi)
+        return Tube.of(t.P, *(a[0] for a in t))
+
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
                  plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,

@@ -6,6 +6,7 @@ callables, sde_control.py:681-721); all hot-path arithmetic happens in csrc/libs
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -374,12 +375,52 @@ def score_summary(score, solves=None):
     return out
 
 
+class _TubeFields(NamedTuple):
+    cost: np.ndarray
+    mean: np.ndarray
+    var: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    outside: np.ndarray
+
+
+class Tube(_TubeFields):
+    """The predicted tube of a rollout (SPEC.md §12), a named tuple (cost, mean, var, min, max, outside): per step t and state component i, over the P
+    particles. cost is f32[B]; mean, var, min, max are f32[B][H+1][13]; outside is uint32[B][H+1][13], the number of particles outside [lo_i, hi_i] (a NaN
+    counts). The particle count rides along as the attribute P (not a field): Tube.of(P, ...) sets it, and a Tube made any other way (the constructor,
+    _replace, _make) has none — p_outside then refuses instead of dividing by a guess."""
+    P = None
+
+    @classmethod
+    def of(cls, P, *planes):
+        t = cls(*planes)
+        t.P = int(P)
+        return t
+
+    def _replace(self, **kw):
+        t = super()._replace(**kw)
+        t.P = self.P                      # (the particle count of the tube the planes came from)
+        return t
+
+    @property
+    def std(self):
+        """sqrt of the population variance, float32"""
+        return np.sqrt(self.var, dtype=np.float32)
+
+    @property
+    def p_outside(self):
+        """outside / P: the empirical probability of leaving the bounds, per step and component"""
+        if self.P is None:
+            raise ValueError("Tube.p_outside: this Tube carries no particle count (build it with Tube.of(P, ...))")
+        return self.outside / self.P
+
+
 class SdeMpcSolver:
     """One solver handle = one (MPC config, model). Single-threaded, like the reference's solver
     objects (one blocking call at a time, sde_control.py:420)."""
 
-    def __init__(self, mpc_cfg, model, max_batch: int = 1, device: int = 0, options=None):
-        self.lib = _abi.load_library()
+    def __init__(self, mpc_cfg, model, max_batch: int = 1, device: int = 0, options=None, lib_path=None):
+        self.lib = _abi.load_library(lib_path)          # lib_path: another build of libsdempc.so for this handle alone (A/B runs in one process)
         self.cfg_py = mpc_cfg
         self.cfg, self._keep = mpc_cfg.to_cfg()
         blob = model.to_blob() if hasattr(model, "to_blob") else bytes(model)
@@ -495,6 +536,48 @@ class SdeMpcSolver:
         self._check(self.lib.sdempc_solve_batch_keys(self._h, B, _fp(x0), _fp(xref), keys.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                      _fp(u_init), _fp(stepsize_in), _fp(uopt), _fp(xevol), info))
         return uopt, xevol, np.frombuffer(info, dtype=np.float32).reshape(B, 8).copy()
+
+    # ---- predicted tube (SPEC.md §12): per-step particle spread and bound exceedance, reduced on the device ----
+    @staticmethod
+    def _tube_cfg(lo, hi):
+        """lo / hi: 13 values each, None: no bound on any component (-inf / +inf)"""
+        cfg = _abi.SdempcTubeCfg()
+        cfg.struct_size = C.sizeof(_abi.SdempcTubeCfg)
+        lo = _f32(np.full(13, -np.inf) if lo is None else lo, (13,))
+        hi = _f32(np.full(13, np.inf) if hi is None else hi, (13,))
+        for i in range(13):
+            cfg.lo[i], cfg.hi[i] = float(lo[i]), float(hi[i])
+        return cfg
+
+    def _tube_call(self, fn, x0, u, xref, draw, lo, hi):
+        B = x0.shape[0]
+        x0, u, xref = _f32(x0, (B, 13)), _f32(u, (B, self.H, self.m)), _f32(xref, (B, self.H + 1, 13))
+        cfg = self._tube_cfg(lo, hi)
+        cost = np.zeros(B, np.float32)
+        mean, var, mn, mx = (np.zeros((B, self.H + 1, 13), np.float32) for _ in range(4))
+        outside = np.zeros((B, self.H + 1, 13), np.uint32)
+        self._check(fn(self._h, C.byref(cfg), B, _fp(x0), _fp(u), _fp(xref), draw, _fp(cost), _fp(mean), _fp(var), _fp(mn), _fp(mx),
+                       outside.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return Tube.of(self.P, cost, mean, var, mn, mx, outside)
+
+    def tube(self, x0, u, xref, noise, lo=None, hi=None) -> Tube:
+        """One rollout of u per instance with its particle x horizon tensor reduced on the device: Tube(cost, mean, var, min, max, outside). mean is the
+        rollout's xmean bit for bit; outside counts the particles outside [lo_i, hi_i] (13 values each, default: no bound — then only NaNs count)."""
+        x0 = _f32(x0)
+        noise = _f32(noise, (x0.shape[0], self.P, self.H, 6))
+        return self._tube_call(_abi.tube_entries(self.lib)[0], x0, u, xref, _fp(noise), lo, hi)
+
+    def tube_keys(self, x0, u, xref, keys, lo=None, hi=None) -> Tube:
+        """tube() with the noise of instance b drawn on the device as normal(keys[b], (P, H, 6)), as solve_keys draws it."""
+        x0 = _f32(x0)
+        keys = self._keys(keys, x0.shape[0])
+        return self._tube_call(_abi.tube_entries(self.lib)[1], x0, u, xref, keys.ctypes.data_as(C.POINTER(C.c_uint32)), lo, hi)
+
+    def tube_dev(self, B, mean, var, min, max, outside=None, lo=None, hi=None, stream=0):
+        """Device pointers (each may be None): reduces the tensor the last rollout_dev(store_traj=True) of at least B instances left in the handle into
+        f32[B][H+1][13] planes (outside: uint32). Refused after a grad_dev, a solve_dev or a smaller rollout, as traj_to_canonical_dev is."""
+        cfg = self._tube_cfg(lo, hi) if (outside is not None or lo is not None or hi is not None) else None
+        self._check(_abi.tube_entries(self.lib)[2](self._h, C.byref(cfg) if cfg is not None else None, B, mean, var, min, max, outside, C.c_void_p(stream)))
 
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
