@@ -809,7 +809,10 @@ int32_t sdempc_layout_fallbacks(const sdempc_handle* h);
 
 /* Work the solve launches of this handle have actually done since creation (or the last reset), summed over instances:
  * out[0] solves, out[1] gradient evaluations (forward + adjoint sweep), out[2] forward-only rollouts (line-search trials, the
- * initial-cost and the final mean-trajectory rollout), out[3] reserved. An iteration whose extrapolation point did not move re-uses
+ * initial-cost and the final mean-trajectory rollout; every trial is counted, so out[2] is sum(info[7]) + 2 per solve), out[3] the
+ * number of those trials that were settled without a rollout: with every cost weight of the handle >= 0 a cost cannot be negative, so a
+ * trial whose Armijo bound fma(ls_coef, g.d, c_y) is negative is rejected unevaluated unless it is the last trial of its line search
+ * (SPEC.md §8; results are unchanged). The rollouts actually run are out[2] - out[3]. An iteration whose extrapolation point did not move re-uses
  * its gradient instead of evaluating it again, so out[1] can be below the sum of the iteration counts. Counted by the
  * one-team-per-instance and plain cooperative layouts (the speculative latency layout evaluates extra, discarded rollouts and is
  * not counted). Call after the stream of the last solve has been synchronised. Roofline accounting of bench.py. */

@@ -749,6 +749,13 @@ int sdempc_create(const sdempc_cfg* cfg, const void* model_blob, size_t blob_byt
         a.C.ulo[j] = cfg->u_lo[j]; a.C.uhi[j] = cfg->u_hi[j];
     }
     a.C.sc_n = 0; a.C.sc_tab = nullptr;       // the table goes to the device with the other tables (ensure_device)
+    // KArgs::nonneg: every weight a cost term is multiplied by is >= 0 (a NaN compares false). Each term is then fma(w * e, e, l) or d * c with
+    // non-negative operands, rounding is monotone, and so no stage, control or total cost is negative (SPEC.md §8, implementation note).
+    bool nonneg = cfg->res_mult >= 0.0f && cfg->uerr >= 0.0f && cfg->u_slew_coeff >= 0.0f && cfg->u_slew_constr_coeff >= 0.0f;
+    for (int i = 0; i < 3; ++i) nonneg = nonneg && cfg->perr[i] >= 0.0f && cfg->verr[i] >= 0.0f && cfg->qerr[i] >= 0.0f && cfg->werr[i] >= 0.0f;
+    for (int k = 0; k < cfg->num_state_constr; ++k) nonneg = nonneg && cfg->state_w[k] >= 0.0f;
+    for (int t = 0; t <= h->H; ++t) nonneg = nonneg && h->h_disc[t] >= 0.0f;
+    a.nonneg = nonneg ? 1 : 0;
     a.A.max_iter = cfg->max_iter; a.A.max_noimp = cfg->max_no_improvement_iter; a.A.maxls = cfg->ls_maxls;
     a.A.reset_inc = cfg->ls_reset_option == 1;
     a.A.atol = cfg->atol; a.A.rtol = cfg->rtol; a.A.stepsize = cfg->stepsize; a.A.smax = cfg->ls_max_stepsize;

@@ -98,13 +98,16 @@ struct KArgs {
     unsigned coop_spin;        // time one grid barrier may wait before it gives up, in ticks of the 100 MHz s_memrealtime clock (10 ns)
     float* coop_pp;            // [B][2][part_stride(H)][G*32]
     float* coop_ck;            // [B][P][H+1][160]
-    unsigned long long* work;  // [4] cumulative work of sdempc_solve_kernel launches: solves, gradient evaluations, forward-only rollouts, spare;
+    unsigned long long* work;  // [4] cumulative work of sdempc_solve_kernel launches: solves, gradient evaluations, forward-only rollouts (every line-search
+                               // trial counted), and how many of those trials were settled without a rollout (nonneg below);
                                // [4] (as unsigned) the instance ticket word of the persistent launches (see ticket_base)
     int tickets;               // persistent launches: 1 = instances beyond the grid's first ones are handed out by the ticket word (set by the launcher)
     unsigned ticket_base;      // value of the ticket word when this launch starts (set by the launcher from *ticket_host)
     unsigned* ticket_host;     // HOST memory, owned by the handle: running total of the ticket word (it is never reset: every ticketed launch of B
                                // instances advances it by exactly B — B - S successful draws and one failing draw by each of the S teams)
     int fast;                  // SPEC.md §10: hardware transcendentals (selects the fastm translation unit; host-side switch)
+    int nonneg;                // 1: every weight that enters a cost (C.perr .. C.slew_cc, the state-bound weights, disc[]) is >= 0 and not NaN, so no cost is
+                               // negative and a line-search trial whose Armijo bound is negative is rejected without its rollout (SPEC.md §8; set at create)
     LaunchOpts opt;
 };
 

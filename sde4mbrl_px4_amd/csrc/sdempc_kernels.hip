@@ -913,6 +913,14 @@ DI void solve_instance(const KArgs& a, const Smem& sm, const WaveW& ww, const La
     // lower the cost — every iteration of a cold start until the line search has shrunk the step far enough) the next iteration would
     // recompute the same bits, so they are kept instead. g lives in LDS and is written by the gradient evaluation only.
     int yk_unchanged = 0, ngrad = 0;
+    // A line-search trial settled without a rollout (below) is counted in work[3] at once: a count carried to the end of the solve is one more value
+    // live across every sweep. Some 20 of 375 trials per C2 solve.
+#if SDEMPC_VAR_PHASE_CLK
+    int nskip = 0;                                   // (work[3] holds a clock in the diagnostic build: reported per instance in the telemetry instead)
+    auto settled = [&]() { nskip += 1; };
+#else
+    auto settled = [&]() { if (a.work && tid == 0) __hip_atomic_fetch_add(a.work + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+#endif
     float c_y = 0.0f;
     for (int k = 0; k < a.A.max_iter; ++k) {
         c_x = uni_f(c_x); s = uni_f(s); sum_ls = uni_f(sum_ls); sum_s = uni_f(sum_s); c_y = uni_f(c_y); gsq = uni_f(gsq);
@@ -934,10 +942,22 @@ DI void solve_instance(const KArgs& a, const Smem& sm, const WaveW& ww, const La
                     float v = clampf(FMA(-s, g[e], yk[e]), a.C.ulo[jj], a.C.uhi[jj]);
                     xn[e] = v; d1[e] = v - yk[e];
                 }
-                c_n = uni_f(team_rollout<Team, F16, PK, MODE>(a, sm, ww, LW, CC, xn, b, tid, false, nullptr));
-                float gd = uni_f(block_dot<Team>(sm, g, d1, N, tid));
                 nls = jl + 1;
-                if (c_n <= FMA(a.A.coef, gd, c_y)) break;
+                // The Armijo bound needs no rollout: g and d1 are in LDS already. With non-negative cost weights (KArgs::nonneg) a cost is
+                // never negative, so a trial whose bound is negative is rejected whatever its rollout would return; unless it is the
+                // line search's last trial (whose cost is read below) the rollout is not run (SPEC.md §8, implementation note). A NaN
+                // bound compares false: nothing is skipped. Team-uniform: formed from uni_f values and kernel arguments only.
+                if constexpr (MODE == 2) {   // cooperative layout: every trial is rolled out (its rollouts carry the grid-wide hand-offs)
+                    c_n = uni_f(team_rollout<Team, F16, PK, MODE>(a, sm, ww, LW, CC, xn, b, tid, false, nullptr));
+                    float gd = uni_f(block_dot<Team>(sm, g, d1, N, tid));
+                    if (c_n <= FMA(a.A.coef, gd, c_y)) break;
+                } else {
+                    const float gd = uni_f(block_dot<Team>(sm, g, d1, N, tid));
+                    const float thr = uni_f(FMA(a.A.coef, gd, c_y));
+                    if (a.nonneg && jl < a.A.maxls - 1 && thr < 0.0f) { settled(); s = s * a.A.dec; continue; }
+                    c_n = uni_f(team_rollout<Team, F16, PK, MODE>(a, sm, ww, LW, CC, xn, b, tid, false, nullptr));
+                    if (c_n <= thr) break;
+                }
                 if (jl < a.A.maxls - 1) s = s * a.A.dec;
             }
         } else {
@@ -996,7 +1016,8 @@ DI void solve_instance(const KArgs& a, const Smem& sm, const WaveW& ww, const La
             __hip_atomic_fetch_add(a.work + 1, (unsigned long long)ngrad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_fetch_add(a.work + 2, (unsigned long long)(nls_tot + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-#if SDEMPC_VAR_PHASE_CLK    // diagnostic build: where and when this instance was solved, in place of three telemetry words
+#if SDEMPC_VAR_PHASE_CLK    // diagnostic build: where and when this instance was solved and how many of its trials ran no rollout (work[3] holds a clock here), in place of five telemetry words
+        inf[5] = (float)nskip;
         inf[0] = __uint_as_float(__builtin_amdgcn_s_getreg(63492));                       // HW_REG_HW_ID
         inf[1] = __uint_as_float(__builtin_amdgcn_s_getreg(63508));                       // HW_REG_XCC_ID
         inf[3] = (float)(unsigned)(t_solve & 0x3FFFFFFFull) * 1e-5f;                      // start, ms (wraps at 10.7 s)

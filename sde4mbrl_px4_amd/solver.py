@@ -1164,9 +1164,18 @@ class SdeMpcSolver:
 
     def work_counters(self, reset: bool = False):
         """(solves, gradient evaluations, forward-only rollouts) done by this handle's solve launches so far (sdempc_work_counters)."""
+        return self.work_counters_full(reset)[:3]
+
+    def work_counters_full(self, reset: bool = False):
+        """work_counters() plus a fourth word: how many of the counted line-search trials were settled without a rollout (a negative
+        Armijo bound under non-negative cost weights, SPEC.md §8). The rollouts actually run are [2] - [3]."""
         out = (C.c_uint64 * 4)()
         self._check(self.lib.sdempc_work_counters(self._h, out, int(reset)))
-        return int(out[0]), int(out[1]), int(out[2])
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def settled_trials(self) -> int:
+        """Line-search trials this handle's solve launches have settled without a rollout so far (work_counters_full()[3])."""
+        return self.work_counters_full()[3]
 
     def last_kernel_name(self) -> str:
         """Kernel instantiation the last *_dev launch started, as rocprofv3 prints it (sdempc_last_kernel_name)."""

@@ -12,9 +12,11 @@ from sde4mbrl_px4_amd.solver import SdeMpcSolver
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="configs/c2_iris_traj_h50_p128.yaml")
 ap.add_argument("--batch", type=int, default=3072)
+ap.add_argument("--mlp-dtype", default="f32", choices=["f32", "f16", "f32x3"])
+ap.add_argument("--math-mode", default="exact", choices=["exact", "fast"], help="fast: the variant must be built with FAST=1 (tools/build_variant.sh)")
 a = ap.parse_args()
 torch.cuda.init()
-cfg = load_mpc_config(a.config)
+cfg = load_mpc_config(a.config).replace(mlp_dtype=a.mlp_dtype, math_mode=a.math_mode)
 m, B, H, P = cfg.num_motors, a.batch, cfg.horizon, cfg.num_particles
 S = SdeMpcSolver(cfg, (synthetic_iris() if m == 4 else synthetic_hexa()).to_blob(), max_batch=B, device=0)
 x0 = W.random_initial_states(B, 0)
@@ -34,8 +36,9 @@ t_solve, t_roll, ngrad, t_fwd, t_adj, t_sync = hi(w[0]), lo(w[0]), w[1], hi(w[2]
 nwaves = w[3] & 0xFFFFFFFF
 ms = S.last_kernel_ms()
 G = (P + 31) // 32; pairs = (G + 1) // 2
-nfwd = float((info[:, 7] + 2).sum())                 # cost rollouts: line-search trials + initial + final
-print(f"{S.last_kernel_name()}\nkernel {ms:.1f} ms; {B} solves on {nwaves} wave-solves; {ngrad / B:.1f} gradient evaluations and {nfwd / B:.1f} cost rollouts per solve")
+nset = float(info[:, 5].sum())                       # trials settled without a rollout (the diagnostic build reports them per instance in info[5])
+nfwd = float((info[:, 7] + 2).sum()) - nset          # cost rollouts actually run: line-search trials + initial + final, less the settled ones
+print(f"{S.last_kernel_name()}\nkernel {ms:.1f} ms; {B} solves on {nwaves} wave-solves; {ngrad / B:.1f} gradient evaluations and {nfwd / B:.1f} cost rollouts per solve ({nset / B:.2f} further trials settled without one)")
 for name, v in [("cost rollouts (whole call)", t_roll), ("gradient evaluations: forward sweeps", t_fwd), ("gradient evaluations: adjoint sweeps", t_adj),
                 ("everything else (optimiser, reductions, gradient assembly)", t_solve - t_roll - t_fwd - t_adj), ("team barriers (inside all of the above)", t_sync)]:
     print(f"{name:60s} {v / t_solve:6.1%}")

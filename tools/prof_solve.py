@@ -43,8 +43,9 @@ for r in range(a.reps):
     extra = ""
     if a.mode == "solve":
         ih = info.cpu().numpy(); extra = f" N_it {ih[:,2].mean():.1f} N_ls {ih[:,7].mean():.1f} -> {B/ms*1e3:.1f} solves/s"
-        wc = S.work_counters(reset=True)
-        extra += f"  work: {wc[1]/B:.1f} gradients + {wc[2]/B:.1f} rollouts per solve -> {(2*wc[1]+wc[2])*H*P/ms*1e3/1e9:.2f} G particle-steps/s"
+        wc = S.work_counters_full(reset=True)
+        run = wc[2] - wc[3]             # rollouts actually run: trials settled without one (negative Armijo bound) are counted in wc[2]
+        extra += f"  work: {wc[1]/B:.1f} gradients + {run/B:.1f} rollouts per solve ({wc[3]/B:.2f} further trials settled without one, {wc[3]/max(wc[2],1):.4f} of the counted rollouts) -> {(2*wc[1]+run)*H*P/ms*1e3/1e9:.2f} G particle-steps/s"
         if wc[0] != B: extra += f"  [work counters: {wc[0]} solves for a batch of {B}]"
     else:
         extra = f" -> {B*H*P/ms*1e3/1e9:.3f} G particle-steps/s"
