@@ -176,7 +176,7 @@ int sdempc_device_ready(const sdempc_handle* h);
  *                                                                                          Filled: the workspaces (particle x horizon tensor, activation checkpoint,
  *                                                                                          partial sums, control table), the cooperative layouts' per-particle outputs and
  *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs (the tube planes of
- *                                                                                          sdempc_tube_batch, d_tube, among them),
+ *                                                                                          sdempc_tube_batch, d_tube, and the risk rows of sdempc_risk_batch, d_risk, among them),
  *                                                                                          the closed loop's key / chunk / plant / rate-state / observation / history buffers (the chunk buffer includes the
  *                                                                                          staged disturbance rows and plant-schedule rows of a scenario). (The particle x horizon tensor is
  *                                                                                          zeroed at allocation otherwise; nothing depends on that.) Keep their initial value:
@@ -308,6 +308,45 @@ int sdempc_tube_batch(sdempc_handle* h, const sdempc_tube_cfg* cfg /*or NULL*/, 
  * uopt and the keys of a solve, mean is that solve's xevol bit for bit. */
 int sdempc_tube_batch_keys(sdempc_handle* h, const sdempc_tube_cfg* cfg /*or NULL*/, int32_t B, const float* x0, const float* u, const float* xref,
                            const uint32_t* keys, float* cost /*[B] or NULL*/, float* mean, float* var, float* min, float* max, uint32_t* outside);
+
+/* ---- predicted risk (SPEC.md §12a) --------------------------------------------------------------
+ * Trajectory-level statistics of the same particle x horizon tensor, reduced where it lies on the device. Per instance b the caller gives a box lo[b][13],
+ * hi[b][13] (-inf / +inf: no bound on that component; a NaN bound in host memory is SDEMPC_EINVAL) around a per-step centre row c[b][t][13] chosen by
+ * cfg->centre_mode: 0 none (the box is absolute), 1 the caller's rows centre[B][H+1][13], 2 the call's xref, 3 the tensor's own particle mean (the mean plane of
+ * sdempc_tube_batch, formed first). Particle p is outside at step t iff !(e >= lo_i && e <= hi_i) for some i, e = x - c one float32 subtraction: a NaN is
+ * outside, a particle ON a bound inside. Outputs, each optional (NULL: not computed, not written), at least one:
+ *   exit        u32[B][P]     first t in 0..H at which p is outside, H+1: never
+ *   jx          f32[B][P]     tracking cost Jx_p = sum_t disc[t] * l_x(x_{t+1}^p, xref_{t+1}): the state-error part of the cost (SPEC.md §5.3, state bounds included)
+ *   first_exit  u32[B][H+2]   histogram of exit over the particles; bin H+1: never (P(ever leaves) = 1 - first_exit[H+1] / P)
+ *   outside_any u32[B][H+1]   particles outside at step t (re-entries make it differ from the cumulative histogram)
+ *   jstat       f32[B][4]     mean, population variance about the rounded mean, min, max of jx
+ *   jq          f32[B][n_ranks]  jx of rank cfg->ranks[q] (0: smallest) in the total order: numbers by value, a NaN above every number, ties by particle index
+ *   jtail       f32[B]        mean of the cfg->tail_k largest jx in that order (CVaR)
+ * exit, first_exit and outside_any need lo and hi; jq needs 1 <= n_ranks <= 8 and 0 <= ranks[q] < P; jtail needs 1 <= tail_k <= P; jq and jtail are refused
+ * for P > 4096 (the selection stage counts P particles per particle), and every output when 4 (2 H + 29 + 37 ceil(P / 32)) bytes exceed 64 KiB of workgroup
+ * memory. Every argument is checked before the first HIP call. */
+typedef struct sdempc_risk_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_risk_cfg) */
+    int32_t centre_mode;   /* 0 none, 1 centre rows, 2 xref, 3 particle mean */
+    int32_t tail_k;        /* jtail: number of worst particles */
+    int32_t n_ranks;       /* jq: number of ranks */
+    int32_t ranks[8];
+} sdempc_risk_cfg;
+/* Reduces the tensor that the last sdempc_rollout_batch_dev(store_traj=1) of at least B instances left in the handle; device pointers. lo_dev / hi_dev
+ * f32[B][13] (NULL: no exit outputs), centre_dev f32[B][H+1][13] (centre_mode 1), xref_dev f32[B][H+1][13] (needed for jx, jstat, jq, jtail and centre_mode 2).
+ * Bounds in device memory cannot be inspected: a NaN bound there puts every particle outside. Refused like sdempc_tube_batch_dev when the workspace holds
+ * fewer instances. Enqueue it on the stream of that rollout. */
+int sdempc_risk_batch_dev(sdempc_handle* h, const sdempc_risk_cfg* cfg, int32_t B, const void* lo_dev, const void* hi_dev, const void* centre_dev, const void* xref_dev,
+                          void* exit_dev, void* jx_dev, void* first_exit_dev, void* outside_any_dev, void* jstat_dev, void* jq_dev, void* jtail_dev, void* stream);
+/* Host pointers: ONE rollout of u (as sdempc_rollout_batch; cost [B] may be NULL) with the tensor kept, the reduction, the requested outputs copied back.
+ * lo / hi [B][13] or both NULL; centre [B][H+1][13] (centre_mode 1) or NULL. */
+int sdempc_risk_batch(sdempc_handle* h, const sdempc_risk_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const float* noise, const float* lo,
+                      const float* hi, const float* centre, float* cost /*[B] or NULL*/, uint32_t* exit, float* jx, uint32_t* first_exit, uint32_t* outside_any,
+                      float* jstat, float* jq, float* jtail);
+/* The same with the noise of instance b drawn on the device as normal(keys[b], (P, H, 6)), as sdempc_solve_batch_keys does. */
+int sdempc_risk_batch_keys(sdempc_handle* h, const sdempc_risk_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const uint32_t* keys,
+                           const float* lo, const float* hi, const float* centre, float* cost /*[B] or NULL*/, uint32_t* exit, float* jx, uint32_t* first_exit,
+                           uint32_t* outside_any, float* jstat, float* jq, float* jtail);
 
 /* ---- batched closed loop (SPEC.md §11) ---------------------------------------------------------
  * B independent episodes of T control ticks, entirely on the device: per tick, the solve of sdempc_solve_batch_keys on the episode's

@@ -128,6 +128,15 @@ class SdempcTubeCfg(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("lo", C.c_float * NX), ("hi", C.c_float * NX)]
 
 
+class SdempcRiskCfg(C.Structure):
+    """sdempc_risk_cfg (SPEC.md §12a): where the exit box sits (centre_mode 0 none, 1 caller's rows, 2 xref, 3 particle mean), the tail size of jtail and the
+    ranks of jq."""
+    _fields_ = [("struct_size", C.c_int32), ("centre_mode", C.c_int32), ("tail_k", C.c_int32), ("n_ranks", C.c_int32), ("ranks", C.c_int32 * 8)]
+
+
+RISK_MAX_RANKS = 8        # sdempc_risk_cfg.ranks
+RISK_RANK_MAX_P = 4096    # jq / jtail are refused above this particle count
+
 PLANT_MAX_SUBSTEPS = 64  # include/sdempc.h: SDEMPC_PLANT_MAX_SUBSTEPS
 
 INFO_FIELDS = [f[0] for f in SdempcInfo._fields_]
@@ -387,6 +396,24 @@ def tube_entries(lib):
     return fns
 
 
+def risk_entries(lib):
+    """sdempc_risk_batch, sdempc_risk_batch_keys and sdempc_risk_batch_dev (SPEC.md §12a) with their prototypes set; detected by symbol, as tube_entries does."""
+    try:
+        fns = lib.sdempc_risk_batch, lib.sdempc_risk_batch_keys, lib.sdempc_risk_batch_dev
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_risk_batch (SPEC.md §12a): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fns[0].argtypes is None:
+        vp, i32, fp, u32p = C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        cfgp = C.POINTER(SdempcRiskCfg)
+        outs = [fp, u32p, fp, u32p, u32p, fp, fp, fp]          # cost, exit, jx, first_exit, outside_any, jstat, jq, jtail
+        fns[0].argtypes = [vp, cfgp, i32, fp, fp, fp, fp, fp, fp, fp] + outs
+        fns[1].argtypes = [vp, cfgp, i32, fp, fp, fp, u32p, fp, fp, fp] + outs
+        fns[2].argtypes = [vp, cfgp, i32] + [vp] * 12
+        for f in fns:
+            f.restype = C.c_int
+    return fns
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -398,4 +425,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored", "sdempc_closed_loop_batch_drawn",
     "sdempc_closed_loop_batch_tracked", "sdempc_reference_windows",
     "sdempc_tube_batch", "sdempc_tube_batch_keys", "sdempc_tube_batch_dev",
+    "sdempc_risk_batch", "sdempc_risk_batch_keys", "sdempc_risk_batch_dev",
 ]

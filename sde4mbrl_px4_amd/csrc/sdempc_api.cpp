@@ -172,6 +172,9 @@ struct sdempc_handle {
     DevBuf d_noise_canon, d_traj_canon, d_keys;
     // predicted tube (sdempc_tube_batch / _keys, allocated on their first use): the five planes mean, var, min, max f32 and outside u32, each [max_batch][(H+1)*13]
     DevBuf d_tube;
+    // predicted risk (sdempc_risk_batch / _keys / _dev, allocated on their first use; risk_regions): staged bounds and centre rows (the particle mean of
+    // centre_mode 3 among them) and the staging copies of the seven outputs
+    DevBuf d_risk;
     // closed loop (sdempc_closed_loop_batch, allocated on its first use): d_loop = keys u32[max_batch][2], solve keys u32[max_batch][2], plant noise
     // f32[max_batch][6], one flag word; d_loop_chunk = the per-tick outputs of one chunk of ticks and the reference windows it reads (grown, never shrunk)
     DevBuf d_loop, d_loop_chunk;
@@ -778,7 +781,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_risk, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1197,6 +1200,181 @@ int sdempc_tube_batch_keys(sdempc_handle* h, const sdempc_tube_cfg* cfg, int32_t
     HIPCHK(h, hipMemcpyAsync(h->d_xref.p, xref, sizeof(float) * B * (H + 1) * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
     if ((rc = noise_from_keys(h, B, keys, (float*)h->d_noise.p, h->stream))) return rc;
     return tube_staged(h, cfg, B, cost, mean, var, min, max, outside);
+    });
+}
+
+// ---- predicted risk (SPEC.md §12a) ----
+namespace {
+struct RiskOut { void *exit, *jx, *first_exit, *outside_any, *jstat, *jq, *jtail; };
+constexpr int RISK_REGIONS = 10;     // lo, hi, centre, then the seven outputs in RiskOut's order
+
+// byte offsets of d_risk's regions, each sized for max_batch instances; off[RISK_REGIONS] = total
+void risk_regions(const sdempc_handle* h, size_t* off, size_t* per_instance) {
+    const size_t C = (size_t)(h->H + 1) * SDEMPC_NX;
+    const size_t words[RISK_REGIONS] = {SDEMPC_NX, SDEMPC_NX, C, (size_t)h->P, (size_t)h->P, (size_t)h->H + 2, (size_t)h->H + 1, 4, RISK_MAX_RANKS, 1};
+    size_t o = 0;
+    for (int k = 0; k < RISK_REGIONS; ++k) {
+        off[k] = o;
+        if (per_instance) per_instance[k] = sizeof(float) * words[k];
+        o += (sizeof(float) * words[k] * (size_t)h->max_batch + 255) & ~(size_t)255;
+    }
+    off[RISK_REGIONS] = o;
+}
+
+int ensure_risk_buf(sdempc_handle* h) {
+    if (h->d_risk.p) return 0;
+    size_t off[RISK_REGIONS + 1];
+    risk_regions(h, off, nullptr);
+    return dev_alloc(h, h->d_risk, off[RISK_REGIONS], true);
+}
+
+// every check of a risk request (SPEC.md §12a) that needs no device; no HIP call. have_*: whether the caller gave that input.
+int check_risk(sdempc_handle* h, const sdempc_risk_cfg* cfg, bool have_lo, bool have_hi, bool have_centre, bool have_xref, const RiskOut& O) {
+    if (!cfg) return fail(h, SDEMPC_EINVAL, "NULL sdempc_risk_cfg%s");
+    if (cfg->struct_size != (int32_t)sizeof(sdempc_risk_cfg)) return fail(h, SDEMPC_EINVAL, "sdempc_risk_cfg.struct_size mismatch%s");
+    const bool want_x = O.exit || O.first_exit || O.outside_any, want_j = O.jx || O.jstat || O.jq || O.jtail;
+    if (!want_x && !want_j) return fail(h, SDEMPC_EINVAL, "no output asked for: exit, jx, first_exit, outside_any, jstat, jq and jtail are all NULL%s");
+    if (cfg->centre_mode < 0 || cfg->centre_mode > 3) return fail(h, SDEMPC_EINVAL, "sdempc_risk_cfg.centre_mode out of range (0 none, 1 caller's rows, 2 xref, 3 particle mean)%s");
+    if (have_lo != have_hi) return fail(h, SDEMPC_EINVAL, "lo and hi come together%s");
+    if (want_x && !have_lo) return fail(h, SDEMPC_EINVAL, "exit, first_exit and outside_any need bounds (lo, hi)%s");
+    if (want_x && cfg->centre_mode == 1 && !have_centre) return fail(h, SDEMPC_EINVAL, "centre_mode 1 needs the caller's centre rows%s");
+    if ((want_j || (want_x && cfg->centre_mode == 2)) && !have_xref) return fail(h, SDEMPC_EINVAL, "jx, jstat, jq, jtail and centre_mode 2 need xref%s");
+    if (O.jq) {
+        if (cfg->n_ranks < 1 || cfg->n_ranks > RISK_MAX_RANKS) return fail(h, SDEMPC_EINVAL, "jq needs 1 <= sdempc_risk_cfg.n_ranks <= 8%s");
+        for (int k = 0; k < cfg->n_ranks; ++k)
+            if (cfg->ranks[k] < 0 || cfg->ranks[k] >= h->P) return fail(h, SDEMPC_EINVAL, "a rank of sdempc_risk_cfg.ranks is outside 0 .. P-1%s");
+    }
+    if (O.jtail && (cfg->tail_k < 1 || cfg->tail_k > h->P)) return fail(h, SDEMPC_EINVAL, "jtail needs 1 <= sdempc_risk_cfg.tail_k <= P%s");
+    if ((O.jq || O.jtail) && h->P > RISK_RANK_MAX_P) return fail(h, SDEMPC_EINVAL, "jq and jtail are limited to 4096 particles (the selection stage); the other outputs are not%s");
+    if (sizeof(uint32_t) * risk_lds_words_host(h->H, h->G) > RISK_MAX_LDS)
+        return fail(h, SDEMPC_EINVAL, "horizon and particle count too large for the risk reducer's workgroup memory (4 (2 H + 29 + 37 ceil(P / 32)) bytes > 64 KiB)%s");
+    return 0;
+}
+
+int check_risk_bounds(sdempc_handle* h, int B, const float* lo, const float* hi) {
+    if (lo && hi)
+        for (size_t i = 0; i < (size_t)B * SDEMPC_NX; ++i)
+            if (lo[i] != lo[i] || hi[i] != hi[i]) return fail(h, SDEMPC_EINVAL, "a risk bound is NaN (use -inf / +inf for no bound)%s");
+    return 0;
+}
+}  // namespace
+
+int sdempc_risk_batch_dev(sdempc_handle* h, const sdempc_risk_cfg* cfg, int32_t B, const void* lo_dev, const void* hi_dev, const void* centre_dev, const void* xref_dev,
+                          void* exit_dev, void* jx_dev, void* first_exit_dev, void* outside_any_dev, void* jstat_dev, void* jq_dev, void* jtail_dev, void* stream) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    const RiskOut O{exit_dev, jx_dev, first_exit_dev, outside_any_dev, jstat_dev, jq_dev, jtail_dev};
+    if ((rc = check_risk(h, cfg, lo_dev != nullptr, hi_dev != nullptr, centre_dev != nullptr, xref_dev != nullptr, O))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    if ((rc = check_traj_held(h, B))) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const bool want_x = exit_dev || first_exit_dev || outside_any_dev;
+    RiskArgs R{};
+    R.traj = (const float*)h->d_traj.p;
+    R.xref = (const float*)xref_dev;
+    R.disc = h->base.disc;
+    if (want_x) {
+        R.lo = (const float*)lo_dev; R.hi = (const float*)hi_dev;
+        if (cfg->centre_mode == 1) R.centre = (const float*)centre_dev;
+        else if (cfg->centre_mode == 2) R.centre = (const float*)xref_dev;
+        else if (cfg->centre_mode == 3) {                // the §12 mean plane first, into the handle's own rows
+            if ((rc = ensure_risk_buf(h))) return rc;
+            size_t off[RISK_REGIONS + 1];
+            risk_regions(h, off, nullptr);
+            TubeArgs T{};
+            T.traj = R.traj;
+            T.mean = (float*)((char*)h->d_risk.p + off[2]);
+            T.invP = h->base.invP;
+            T.C = (h->H + 1) * SDEMPC_NX;
+            HIPCHK(h, launch_tube(T, B, h->P, h->G, h->H, st));
+            R.centre = T.mean;
+        }
+    }
+    R.sc_n = h->base.C.sc_n; R.sc_tab = h->base.C.sc_tab;
+    R.exit = (uint32_t*)exit_dev; R.jx = (float*)jx_dev; R.first_exit = (uint32_t*)first_exit_dev; R.outside_any = (uint32_t*)outside_any_dev;
+    R.jstat = (float*)jstat_dev; R.jq = (float*)jq_dev; R.jtail = (float*)jtail_dev;
+    for (int i = 0; i < 3; ++i) { R.perr[i] = h->base.C.perr[i]; R.verr[i] = h->base.C.verr[i]; R.qerr[i] = h->base.C.qerr[i]; R.werr[i] = h->base.C.werr[i]; }
+    R.invP = h->base.invP;
+    R.H = h->H;
+    if (jtail_dev) { R.tail_k = cfg->tail_k; R.inv_tail = 1.0f / (float)cfg->tail_k; }
+    if (jq_dev) {
+        R.n_ranks = cfg->n_ranks;
+        for (int k = 0; k < cfg->n_ranks; ++k) R.ranks[k] = cfg->ranks[k];
+    }
+    HIPCHK(h, launch_risk(R, B, h->P, h->G, st));
+    return SDEMPC_OK;
+    });
+}
+
+namespace {
+// the staged inputs (d_x0, d_u, d_xref, d_noise on the handle's stream) -> one store_traj rollout, the reducer, the outputs asked for back on the host
+int risk_staged(sdempc_handle* h, const sdempc_risk_cfg* cfg_in, int32_t B, const float* lo, const float* hi, const float* centre, float* cost, const RiskOut& O) {
+    int rc = ensure_risk_buf(h);
+    if (rc) return rc;
+    size_t off[RISK_REGIONS + 1], per[RISK_REGIONS];
+    risk_regions(h, off, per);
+    char* d = (char*)h->d_risk.p;
+    // centre_mode 3: the rollout's own mean trajectory IS the §12 mean plane (SPEC.md §6.3), so the rollout writes the centre rows and the reducer takes them as
+    // caller's rows — the tensor is not read a second time for them
+    sdempc_risk_cfg staged = *cfg_in;
+    const bool own_mean = staged.centre_mode == 3 && (O.exit || O.first_exit || O.outside_any);
+    if (own_mean) staged.centre_mode = 1;
+    const sdempc_risk_cfg* cfg = &staged;
+    if ((rc = sdempc_rollout_batch_dev(h, B, h->d_x0.p, h->d_u.p, h->d_xref.p, h->d_noise.p, h->d_cost.p, own_mean ? d + off[2] : nullptr, 1, h->stream))) return rc;
+    const void* in[3] = {lo, hi, cfg_in->centre_mode == 1 ? centre : nullptr};
+    void* in_dev[3];
+    for (int k = 0; k < 3; ++k) {
+        in_dev[k] = in[k] ? d + off[k] : nullptr;
+        if (in[k]) HIPCHK(h, hipMemcpyAsync(in_dev[k], in[k], per[k] * B, hipMemcpyHostToDevice, h->stream));
+    }
+    void* host[7] = {O.exit, O.jx, O.first_exit, O.outside_any, O.jstat, O.jq, O.jtail};
+    void* dev[7];
+    for (int k = 0; k < 7; ++k) dev[k] = host[k] ? d + off[3 + k] : nullptr;
+    per[3 + 5] = sizeof(float) * (size_t)(O.jq ? cfg->n_ranks : 0);      // jq is [B][n_ranks]
+    if (own_mean) in_dev[2] = d + off[2];
+    if ((rc = sdempc_risk_batch_dev(h, cfg, B, in_dev[0], in_dev[1], in_dev[2], h->d_xref.p, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], h->stream))) return rc;
+    if (cost) HIPCHK(h, hipMemcpyAsync(cost, h->d_cost.p, sizeof(float) * B, hipMemcpyDeviceToHost, h->stream));
+    for (int k = 0; k < 7; ++k)
+        if (host[k]) HIPCHK(h, hipMemcpyAsync(host[k], dev[k], per[3 + k] * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return SDEMPC_OK;
+}
+}  // namespace
+
+int sdempc_risk_batch(sdempc_handle* h, const sdempc_risk_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const float* noise, const float* lo,
+                      const float* hi, const float* centre, float* cost, uint32_t* exit, float* jx, uint32_t* first_exit, uint32_t* outside_any, float* jstat, float* jq,
+                      float* jtail) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if (!x0 || !u || !xref || !noise) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    const RiskOut O{exit, jx, first_exit, outside_any, jstat, jq, jtail};
+    if ((rc = check_risk(h, cfg, lo != nullptr, hi != nullptr, centre != nullptr, true, O))) return rc;
+    if ((rc = check_risk_bounds(h, B, lo, hi))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    if ((rc = stage_common(h, B, x0, u, xref, noise))) return rc;
+    return risk_staged(h, cfg, B, lo, hi, centre, cost, O);
+    });
+}
+
+int sdempc_risk_batch_keys(sdempc_handle* h, const sdempc_risk_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const uint32_t* keys,
+                           const float* lo, const float* hi, const float* centre, float* cost, uint32_t* exit, float* jx, uint32_t* first_exit, uint32_t* outside_any,
+                           float* jstat, float* jq, float* jtail) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if (!x0 || !u || !xref || !keys) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    const RiskOut O{exit, jx, first_exit, outside_any, jstat, jq, jtail};
+    if ((rc = check_risk(h, cfg, lo != nullptr, hi != nullptr, centre != nullptr, true, O))) return rc;
+    if ((rc = check_risk_bounds(h, B, lo, hi))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    const int H = h->H, m = h->m;
+    HIPCHK(h, hipMemcpyAsync(h->d_x0.p, x0, sizeof(float) * B * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_u.p, u, sizeof(float) * B * H * m, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_xref.p, xref, sizeof(float) * B * (H + 1) * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
+    if ((rc = noise_from_keys(h, B, keys, (float*)h->d_noise.p, h->stream))) return rc;
+    return risk_staged(h, cfg, B, lo, hi, centre, cost, O);
     });
 }
 

@@ -336,5 +336,35 @@ struct TubeArgs {
     int C;                      // columns per instance
 };
 hipError_t launch_tube(const TubeArgs& T, int B, int P, int G, int H, hipStream_t st);
+// SPEC.md §12a, predicted risk: the noise kernel in its RISK form (sdempc_risk.inc.h), one workgroup per instance. It walks the same tensor particle by particle:
+// first exit from the per-instance box [lo, hi] around the centre rows, the tracking cost Jx_p, and per instance the exit histogram, the per-step outside count,
+// mean / variance / extrema, order statistics and the tail mean of Jx. Every output is optional. traj null means absent: every noise and tube launch passes that,
+// and the kernel then makes no memory access it did not make before.
+constexpr int RISK_MAX_RANKS = 8;
+constexpr int RISK_RANK_MAX_P = 4096;   // the selection stage counts P particles per particle: the rank outputs (jq, jtail) are refused above this
+constexpr size_t RISK_MAX_LDS = 64 * 1024;
+// 4-byte words of workgroup memory of the risk form: any[H+1] hist[H+2] jx[G*32], five group arrays [G] and the instance's box [26] (sdempc_risk.inc.h)
+inline size_t risk_lds_words_host(int H, int G) { return (size_t)(2 * H + 3) + (size_t)G * 37 + 26; }
+struct RiskArgs {
+    const float* traj;          // [B][G][C][32], C = (H+1)*13 (KArgs::traj); null: not the risk mode
+    const float* xref;          // [B][H+1][13]; needed for Jx
+    const float* centre;        // [B][H+1][13] or null: e = x
+    const float* lo;            // [B][13] or null: no exit outputs (hi is then not read)
+    const float* hi;            // [B][13]
+    const float* disc;          // [H+1] (KArgs::disc)
+    const CostK::StateBound* sc_tab;
+    uint32_t* exit;             // [B][P] or null
+    float* jx;                  // [B][P] or null
+    uint32_t* first_exit;       // [B][H+2] or null
+    uint32_t* outside_any;      // [B][H+1] or null
+    float* jstat;               // [B][4] or null
+    float* jq;                  // [B][n_ranks] or null
+    float* jtail;               // [B] or null
+    float perr[3], verr[3], qerr[3], werr[3];   // CostK's
+    float invP, inv_tail;       // float32(1) / float32(P), float32(1) / float32(tail_k)
+    int H, sc_n, tail_k, n_ranks;
+    int ranks[RISK_MAX_RANKS];
+};
+hipError_t launch_risk(const RiskArgs& R, int B, int P, int G, hipStream_t st);
 
 }  // namespace sdempc

@@ -118,15 +118,23 @@ DI float bits_to_normal(uint32_t bits) {
 
 }  // namespace sdempc
 #include "sdempc_tube.inc.h"
+#include "sdempc_risk.inc.h"
 namespace sdempc {
 
 // grid: x = chunks of 256 threads over [pg][r][lane] (pg < ceil(ceil(P/2)/32), r < H*6), y = instance
 // SPEC.md §12 (T.traj given; keys, out and HC are then not read): the TUBE form of the launch — x = tiles of 32 columns of the particle x horizon tensor, y = instance
 // (sdempc_tube.inc.h). T.traj null (every noise launch): not one access more.
-__global__ void __launch_bounds__(256) sdempc_noise_kernel(const uint32_t* __restrict__ keys, float* __restrict__ out, int P, int G, int HC, int b0, TubeArgs T) {
+// SPEC.md §12a (R.traj given; keys, out, HC and T are then not read): the RISK form — x = 1, y = instance, dynamic LDS of risk_lds_words_host words.
+// R.traj null (every noise and tube launch): not one access more. The second launch bound asks for the 8 waves / SIMD the kernel had before this form: its scalar
+// registers stay below 96 (the risk form's later-phase arguments are spilled to lanes of a vector register outside its loops), scratch stays 0.
+__global__ void __launch_bounds__(256, 8) sdempc_noise_kernel(const uint32_t* __restrict__ keys, float* __restrict__ out, int P, int G, int HC, int b0, TubeArgs T,
+                                                           RiskArgs R) {
     const int b = b0 + blockIdx.y;
-    if (T.traj) {                                        // (wave-uniform)
-        tube_reduce(T, P, G, b);
+    // (wave-uniform; ONE test of both mode pointers, so that the noise form waits for one batch of scalar loads and takes one branch, as it did with one mode —
+    // its workgroups are short, and a second dependent load in front of `keys` showed in its time)
+    if (__builtin_expect((reinterpret_cast<uintptr_t>(T.traj) | reinterpret_cast<uintptr_t>(R.traj)) != 0, 0)) {
+        if (R.traj) risk_reduce(R, P, G, b);
+        else tube_reduce(T, P, G, b);
         return;
     }
     const uint32_t k0 = keys[2 * b], k1 = keys[2 * b + 1];
@@ -156,7 +164,7 @@ hipError_t launch_noise_from_keys(const uint32_t* keys_dev, float* out, int B, i
     const unsigned gx = (unsigned)((threads + 255) / 256);
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(keys_dev, out, P, G, HC, b0, TubeArgs{});
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(keys_dev, out, P, G, HC, b0, TubeArgs{}, RiskArgs{});
     }
     return hipGetLastError();
 }
@@ -168,7 +176,27 @@ hipError_t launch_tube(const TubeArgs& T, int B, int P, int G, int H, hipStream_
     const unsigned gx = (unsigned)((T.C + 31) / 32);
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, T);
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, T, RiskArgs{});
+    }
+    return hipGetLastError();
+}
+
+// SPEC.md §12a: one workgroup per instance; every word of every output given is written
+hipError_t launch_risk(const RiskArgs& R, int B, int P, int G, hipStream_t st) {
+    if (B < 1 || P < 1 || R.H < 1 || G != (P + 31) / 32 || !R.traj) return hipErrorInvalidValue;
+    const bool want_x = R.exit || R.first_exit || R.outside_any, want_j = R.jx || R.jstat || R.jq || R.jtail;
+    if (!want_x && !want_j) return hipErrorInvalidValue;
+    if ((want_x && (!R.lo || !R.hi)) || (!want_x && R.lo) || (want_j && (!R.xref || !R.disc)) || (R.sc_n && !R.sc_tab)) return hipErrorInvalidValue;
+    if (R.jq && (R.n_ranks < 1 || R.n_ranks > RISK_MAX_RANKS)) return hipErrorInvalidValue;
+    for (int k = 0; R.jq && k < R.n_ranks; ++k)
+        if (R.ranks[k] < 0 || R.ranks[k] >= P) return hipErrorInvalidValue;
+    if (R.jtail && (R.tail_k < 1 || R.tail_k > P)) return hipErrorInvalidValue;
+    if ((R.jq || R.jtail) && P > RISK_RANK_MAX_P) return hipErrorInvalidValue;
+    const size_t lds = sizeof(uint32_t) * risk_lds_words_host(R.H, G);
+    if (lds > RISK_MAX_LDS) return hipErrorInvalidValue;
+    for (int b0 = 0; b0 < B; b0 += 65535) {
+        const int nb = B - b0 < 65535 ? B - b0 : 65535;
+        sdempc_noise_kernel<<<dim3(1, nb), 256, lds, st>>>(nullptr, nullptr, P, G, 0, b0, TubeArgs{}, R);
     }
     return hipGetLastError();
 }

@@ -160,6 +160,22 @@ class MpcProblem:
         t = self.solver().tube_keys(xs[None], u, xref, sub[None], lo=lo, hi=hi)
         return Tube.of(t.P, *(a[0] for a in t))
 
+    def m_risk(self, x, rng, uopt, curr_t=0.0, xdes=None, lo=None, hi=None, centre=None, tail=None, quantiles=None, want_particles=False):
+        """Predicted risk (SPEC.md §12a) of the plan `uopt` on the noise m_mpc(x, rng, ...) solved on: the key rule of m_tube (SPEC.md §7.3), the same reference
+        window, one rollout, its tensor reduced on the device. Returns a solver.Risk without the batch axis, IN THE SOLVER'S FRAME, as lo / hi / centre rows are.
+        rng is not consumed: pass the key that went INTO m_mpc."""
+        from .solver import Risk
+        x = np.asarray(x, np.float32).reshape(13)
+        xs = enu2ned(x, np) if self.convert_to_enu else x
+        xdes = xs if xdes is None else np.asarray(xdes, np.float32).reshape(13)
+        _, sub = _next_key(rng)
+        xref = self.xref(float(curr_t), xdes)[None]
+        u = np.asarray(uopt, np.float32).reshape(1, self.cfg.horizon, self.cfg.num_motors)
+        if centre is not None and not isinstance(centre, str):
+            centre = np.asarray(centre, np.float32)[None]
+        r = self.solver().risk_keys(xs[None], u, xref, sub[None], lo=lo, hi=hi, centre=centre, tail=tail, quantiles=quantiles, want_particles=want_particles)
+        return Risk.of(r.P, *(None if a is None else a[0] for a in r))
+
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
                  plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,

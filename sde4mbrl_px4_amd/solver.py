@@ -415,6 +415,69 @@ class Tube(_TubeFields):
         return self.outside / self.P
 
 
+class _RiskFields(NamedTuple):
+    cost: np.ndarray
+    exit: object
+    jx: object
+    first_exit: object
+    outside_any: object
+    jstat: np.ndarray
+    jq: object
+    jtail: object
+
+
+class Risk(_RiskFields):
+    """Predicted risk of a rollout (SPEC.md §12a), a named tuple (cost, exit, jx, first_exit, outside_any, jstat, jq, jtail). cost f32[B] is the rollout's
+    expected cost. exit uint32[B][P] (first step outside the box, H+1: never) and jx f32[B][P] (tracking cost per particle) are None unless asked for
+    (want_particles). first_exit uint32[B][H+2] is the histogram of exit (bin H+1: never), outside_any uint32[B][H+1] the particles outside at each step — both None
+    without bounds. jstat f32[B][4]: mean, population variance, min, max of jx. jq f32[B][Q]: the quantiles asked for; jtail f32[B]: the mean of the tail (CVaR);
+    None when not asked for. The particle count rides along as the attribute P (Risk.of sets it), as on Tube."""
+    P = None
+
+    @classmethod
+    def of(cls, P, *fields):
+        r = cls(*fields)
+        r.P = int(P)
+        return r
+
+    def _replace(self, **kw):
+        r = super()._replace(**kw)
+        r.P = self.P
+        return r
+
+    def _need(self, what):
+        if self.P is None:
+            raise ValueError(f"Risk.{what}: this Risk carries no particle count (build it with Risk.of(P, ...))")
+        if self.first_exit is None:
+            raise ValueError(f"Risk.{what}: no bounds were given, so there is no exit histogram")
+
+    @property
+    def p_ever(self):
+        """1 - first_exit[..., H+1] / P: the empirical probability that a particle EVER leaves the box within the horizon"""
+        self._need("p_ever")
+        return 1.0 - self.first_exit[..., -1] / self.P
+
+    @property
+    def survival(self):
+        """[..., H+1]: the fraction of particles that have not left the box up to and including step t"""
+        self._need("survival")
+        return 1.0 - np.cumsum(self.first_exit[..., :-1], axis=-1) / self.P
+
+
+def quantile_ranks(quantiles, P):
+    """SPEC.md §12a: quantile q -> rank ceil(q P) - 1, clamped to [0, P-1] (rank 0: the smallest)"""
+    import math
+    return [min(P - 1, max(0, math.ceil(float(q) * P) - 1)) for q in quantiles]
+
+
+def tail_count(tail, P):
+    """SPEC.md §12a: a fraction alpha -> max(1, ceil(alpha P)); an integer is the count itself"""
+    import math
+    if isinstance(tail, (int, np.integer)) and not isinstance(tail, bool):
+        return int(tail)
+    return max(1, math.ceil(float(tail) * P))
+
+
 class SdeMpcSolver:
     """One solver handle = one (MPC config, model). Single-threaded, like the reference's solver
     objects (one blocking call at a time, sde_control.py:420)."""
@@ -578,6 +641,86 @@ class SdeMpcSolver:
         f32[B][H+1][13] planes (outside: uint32). Refused after a grad_dev, a solve_dev or a smaller rollout, as traj_to_canonical_dev is."""
         cfg = self._tube_cfg(lo, hi) if (outside is not None or lo is not None or hi is not None) else None
         self._check(_abi.tube_entries(self.lib)[2](self._h, C.byref(cfg) if cfg is not None else None, B, mean, var, min, max, outside, C.c_void_p(stream)))
+
+    # ---- predicted risk (SPEC.md §12a): joint exit probability and tracking-cost tail, reduced on the device ----
+    def _risk_cfg(self, centre, tail, quantiles):
+        """-> (cfg, centre rows or None). centre: None (absolute box), "xref", "mean", or rows [B][H+1][13]"""
+        cfg = _abi.SdempcRiskCfg()
+        cfg.struct_size = C.sizeof(_abi.SdempcRiskCfg)
+        rows = None
+        if centre is None:
+            cfg.centre_mode = 0
+        elif isinstance(centre, str):
+            if centre not in ("xref", "mean"):
+                raise ValueError('centre: None, "xref", "mean" or an array [B][H+1][13]')
+            cfg.centre_mode = 2 if centre == "xref" else 3
+        else:
+            cfg.centre_mode, rows = 1, centre
+        if tail is not None:
+            cfg.tail_k = tail_count(tail, self.P)
+        if quantiles is not None:
+            ranks = quantile_ranks(quantiles, self.P)
+            if not 1 <= len(ranks) <= _abi.RISK_MAX_RANKS:
+                raise ValueError(f"quantiles: 1 to {_abi.RISK_MAX_RANKS} values")
+            cfg.n_ranks = len(ranks)
+            for k, r in enumerate(ranks):
+                cfg.ranks[k] = r
+        return cfg, rows
+
+    @staticmethod
+    def _bounds(b, B, fill):
+        """a bound: None (none on any component), [13] (broadcast over the batch) or [B][13]"""
+        a = np.full(13, fill, np.float32) if b is None else np.asarray(b, np.float32)
+        return np.ascontiguousarray(np.broadcast_to(a, (B, 13)), np.float32)
+
+    def _risk_call(self, fn, x0, u, xref, draw, lo, hi, centre, tail, quantiles, want_particles):
+        B = x0.shape[0]
+        H, P = self.H, self.P
+        x0, u, xref = _f32(x0, (B, 13)), _f32(u, (B, H, self.m)), _f32(xref, (B, H + 1, 13))
+        cfg, rows = self._risk_cfg(centre, tail, quantiles)
+        bounded = lo is not None or hi is not None
+        lo_a, hi_a = (self._bounds(lo, B, -np.inf), self._bounds(hi, B, np.inf)) if bounded else (None, None)
+        rows = _f32(rows, (B, H + 1, 13)) if rows is not None else None
+        u32p = C.POINTER(C.c_uint32)
+        cost = np.zeros(B, np.float32)
+        ex = np.zeros((B, P), np.uint32) if want_particles and bounded else None
+        jx = np.zeros((B, P), np.float32) if want_particles else None
+        first = np.zeros((B, H + 2), np.uint32) if bounded else None
+        anyo = np.zeros((B, H + 1), np.uint32) if bounded else None
+        jstat = np.zeros((B, 4), np.float32)
+        jq = np.zeros((B, cfg.n_ranks), np.float32) if cfg.n_ranks else None
+        jtail = np.zeros(B, np.float32) if tail is not None else None
+        f = lambda a: _fp(a) if a is not None else None
+        w = lambda a: a.ctypes.data_as(u32p) if a is not None else None
+        self._check(fn(self._h, C.byref(cfg), B, _fp(x0), _fp(u), _fp(xref), draw, f(lo_a), f(hi_a), f(rows), _fp(cost), w(ex), f(jx), w(first), w(anyo),
+                       _fp(jstat), f(jq), f(jtail)))
+        return Risk.of(P, cost, ex, jx, first, anyo, jstat, jq, jtail)
+
+    def risk(self, x0, u, xref, noise, lo=None, hi=None, centre=None, tail=None, quantiles=None, want_particles=False) -> Risk:
+        """One rollout of u per instance with its particle x horizon tensor reduced on the device to trajectory-level statistics (SPEC.md §12a): Risk(cost, exit,
+        jx, first_exit, outside_any, jstat, jq, jtail). lo / hi: the box, [13] (broadcast) or [B][13], around `centre`: None (absolute), "xref", "mean" (the
+        particle mean) or rows [B][H+1][13]. tail: a fraction alpha (k = max(1, ceil(alpha P))) or an integer k of worst particles; quantiles: up to 8 values
+        in [0, 1] (rank ceil(q P) - 1). want_particles: also the per-particle planes exit and jx."""
+        x0 = _f32(x0)
+        noise = _f32(noise, (x0.shape[0], self.P, self.H, 6))
+        return self._risk_call(_abi.risk_entries(self.lib)[0], x0, u, xref, _fp(noise), lo, hi, centre, tail, quantiles, want_particles)
+
+    def risk_keys(self, x0, u, xref, keys, lo=None, hi=None, centre=None, tail=None, quantiles=None, want_particles=False) -> Risk:
+        """risk() with the noise of instance b drawn on the device as normal(keys[b], (P, H, 6)), as solve_keys draws it."""
+        x0 = _f32(x0)
+        keys = self._keys(keys, x0.shape[0])
+        return self._risk_call(_abi.risk_entries(self.lib)[1], x0, u, xref, keys.ctypes.data_as(C.POINTER(C.c_uint32)), lo, hi, centre, tail, quantiles,
+                               want_particles)
+
+    def risk_dev(self, B, xref=None, lo=None, hi=None, centre=None, tail=None, quantiles=None, exit=None, jx=None, first_exit=None, outside_any=None, jstat=None,
+                 jq=None, jtail=None, stream=0):
+        """Device pointers (each may be None): reduces the tensor the last rollout_dev(store_traj=True) of at least B instances left in the handle. lo / hi:
+        pointers to f32[B][13]; centre: None, "xref", "mean" or a pointer to f32[B][H+1][13]; xref: pointer to f32[B][H+1][13] (for jx, jstat, jq, jtail and
+        centre="xref"). Outputs: exit u32[B][P], jx f32[B][P], first_exit u32[B][H+2], outside_any u32[B][H+1], jstat f32[B][4], jq f32[B][len(quantiles)],
+        jtail f32[B]. Refused after a grad_dev, a solve_dev or a smaller rollout, as tube_dev is."""
+        cfg, rows = self._risk_cfg(centre, tail, quantiles)
+        self._check(_abi.risk_entries(self.lib)[2](self._h, C.byref(cfg), B, lo, hi, rows, xref, exit, jx, first_exit, outside_any, jstat, jq, jtail,
+                                                   C.c_void_p(stream)))
 
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
