@@ -176,7 +176,7 @@ int sdempc_device_ready(const sdempc_handle* h);
  *                                                                                          Filled: the workspaces (particle x horizon tensor, activation checkpoint,
  *                                                                                          partial sums, control table), the cooperative layouts' per-particle outputs and
  *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs (the tube planes of
- *                                                                                          sdempc_tube_batch, d_tube, and the risk rows of sdempc_risk_batch, d_risk, among them),
+ *                                                                                          sdempc_tube_batch, d_tube, the band planes of sdempc_bands_batch, d_band, and the risk rows of sdempc_risk_batch, d_risk, among them),
  *                                                                                          the closed loop's key / chunk / plant / rate-state / observation / history buffers (the chunk buffer includes the
  *                                                                                          staged disturbance rows and plant-schedule rows of a scenario). (The particle x horizon tensor is
  *                                                                                          zeroed at allocation otherwise; nothing depends on that.) Keep their initial value:
@@ -347,6 +347,34 @@ int sdempc_risk_batch(sdempc_handle* h, const sdempc_risk_cfg* cfg, int32_t B, c
 int sdempc_risk_batch_keys(sdempc_handle* h, const sdempc_risk_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const uint32_t* keys,
                            const float* lo, const float* hi, const float* centre, float* cost /*[B] or NULL*/, uint32_t* exit, float* jx, uint32_t* first_exit,
                            uint32_t* outside_any, float* jstat, float* jq, float* jtail);
+
+/* ---- predicted bands (SPEC.md §12b) --------------------------------------------------------------
+ * Per-step quantiles across the particles and the rank of an observed state in the predicted distribution, from the same particle x horizon tensor, reduced
+ * where it lies on the device. Every word v is ordered by its key: u = bits(v); key = 0xFFFFFFFF for a NaN, else u ^ 0xFFFFFFFF where the sign bit is set,
+ * else u ^ 0x80000000 — so -inf < ... < -0 < +0 < ... < +inf < NaN, all NaNs equal, and equal keys are identical words (no tie-break exists). Per
+ * instance and column c = t * 13 + i, over the valid particles p < P, each output optional (NULL: not computed, not written), at least one:
+ *   q      f32[B][n_ranks][H+1][13]  plane k: the value with the cfg->ranks[k]-th smallest key (0-based; ranks neither sorted nor distinct). No arithmetic
+ *                                    touches it: bit for bit one particle's word, -0 / +0 kept apart; a selected NaN is 0x7FC00000.
+ *   below  u32[B][H+1][13]           particles with key < key(obs[c])
+ *   at     u32[B][H+1][13]           particles with key == key(obs[c])
+ * obs f32[B][H+1][13] are the observed rows. A NaN there is not refused: below = the non-NaN particles, at = the NaN ones; use it for rows the caller does
+ * not have and mask them. q needs cfg with 1 <= n_ranks <= 8 and 0 <= ranks[k] < P; below / at need obs; a wrong struct_size is SDEMPC_EINVAL. No particle
+ * limit. Every argument is checked before the first HIP call. */
+typedef struct sdempc_bands_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_bands_cfg) */
+    int32_t n_ranks;       /* q: number of planes */
+    int32_t ranks[8];
+} sdempc_bands_cfg;
+/* Reduces the tensor that the last sdempc_rollout_batch_dev(store_traj=1) of at least B instances left in the handle; device pointers. Refused like
+ * sdempc_tube_batch_dev when the workspace holds fewer instances. Enqueue it on the stream of that rollout. */
+int sdempc_bands_batch_dev(sdempc_handle* h, const sdempc_bands_cfg* cfg /*or NULL without q*/, int32_t B, const void* obs_dev /*or NULL*/, void* q_dev, void* below_dev,
+                           void* at_dev, void* stream);
+/* Host pointers: ONE rollout of u (as sdempc_rollout_batch; cost [B] may be NULL) with the tensor kept, the reduction, the requested outputs copied back. */
+int sdempc_bands_batch(sdempc_handle* h, const sdempc_bands_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const float* noise,
+                       const float* obs /*[B][H+1][13] or NULL*/, float* cost /*[B] or NULL*/, float* q, uint32_t* below, uint32_t* at);
+/* The same with the noise of instance b drawn on the device as normal(keys[b], (P, H, 6)), as sdempc_solve_batch_keys does. */
+int sdempc_bands_batch_keys(sdempc_handle* h, const sdempc_bands_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const uint32_t* keys,
+                            const float* obs /*[B][H+1][13] or NULL*/, float* cost /*[B] or NULL*/, float* q, uint32_t* below, uint32_t* at);
 
 /* ---- batched closed loop (SPEC.md §11) ---------------------------------------------------------
  * B independent episodes of T control ticks, entirely on the device: per tick, the solve of sdempc_solve_batch_keys on the episode's

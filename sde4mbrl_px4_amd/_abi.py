@@ -134,6 +134,12 @@ class SdempcRiskCfg(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("centre_mode", C.c_int32), ("tail_k", C.c_int32), ("n_ranks", C.c_int32), ("ranks", C.c_int32 * 8)]
 
 
+class SdempcBandsCfg(C.Structure):
+    """sdempc_bands_cfg (SPEC.md §12b): the ranks (0-based, in the key order over the valid particles) whose values fill the planes of q."""
+    _fields_ = [("struct_size", C.c_int32), ("n_ranks", C.c_int32), ("ranks", C.c_int32 * 8)]
+
+
+BANDS_MAX_RANKS = 8       # sdempc_bands_cfg.ranks
 RISK_MAX_RANKS = 8        # sdempc_risk_cfg.ranks
 RISK_RANK_MAX_P = 4096    # jq / jtail are refused above this particle count
 
@@ -414,6 +420,23 @@ def risk_entries(lib):
     return fns
 
 
+def bands_entries(lib):
+    """sdempc_bands_batch, sdempc_bands_batch_keys and sdempc_bands_batch_dev (SPEC.md §12b) with their prototypes set; detected by symbol, as tube_entries does."""
+    try:
+        fns = lib.sdempc_bands_batch, lib.sdempc_bands_batch_keys, lib.sdempc_bands_batch_dev
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_bands_batch (SPEC.md §12b): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fns[0].argtypes is None:
+        vp, i32, fp, u32p = C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        cfgp = C.POINTER(SdempcBandsCfg)
+        fns[0].argtypes = [vp, cfgp, i32, fp, fp, fp, fp, fp, fp, fp, u32p, u32p]      # x0, u, xref, noise, obs, cost, q, below, at
+        fns[1].argtypes = [vp, cfgp, i32, fp, fp, fp, u32p, fp, fp, fp, u32p, u32p]
+        fns[2].argtypes = [vp, cfgp, i32, vp, vp, vp, vp, vp]
+        for f in fns:
+            f.restype = C.c_int
+    return fns
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -426,4 +449,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_closed_loop_batch_tracked", "sdempc_reference_windows",
     "sdempc_tube_batch", "sdempc_tube_batch_keys", "sdempc_tube_batch_dev",
     "sdempc_risk_batch", "sdempc_risk_batch_keys", "sdempc_risk_batch_dev",
+    "sdempc_bands_batch", "sdempc_bands_batch_keys", "sdempc_bands_batch_dev",
 ]

@@ -172,6 +172,8 @@ struct sdempc_handle {
     DevBuf d_noise_canon, d_traj_canon, d_keys;
     // predicted tube (sdempc_tube_batch / _keys, allocated on their first use): the five planes mean, var, min, max f32 and outside u32, each [max_batch][(H+1)*13]
     DevBuf d_tube;
+    // predicted bands (sdempc_bands_batch / _keys, allocated on their first use): obs f32, q f32[8 planes], below u32, at u32 — eleven planes, each [max_batch][(H+1)*13]
+    DevBuf d_band;
     // predicted risk (sdempc_risk_batch / _keys / _dev, allocated on their first use; risk_regions): staged bounds and centre rows (the particle mean of
     // centre_mode 3 among them) and the staging copies of the seven outputs
     DevBuf d_risk;
@@ -781,7 +783,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_risk, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1375,6 +1377,96 @@ int sdempc_risk_batch_keys(sdempc_handle* h, const sdempc_risk_cfg* cfg, int32_t
     HIPCHK(h, hipMemcpyAsync(h->d_xref.p, xref, sizeof(float) * B * (H + 1) * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
     if ((rc = noise_from_keys(h, B, keys, (float*)h->d_noise.p, h->stream))) return rc;
     return risk_staged(h, cfg, B, lo, hi, centre, cost, O);
+    });
+}
+
+// ---- predicted bands (SPEC.md §12b) ----
+namespace {
+// every check of a bands request (SPEC.md §12b) that needs no device; no HIP call
+int check_bands(sdempc_handle* h, const sdempc_bands_cfg* cfg, bool have_obs, const void* q, const void* below, const void* at) {
+    if (cfg && cfg->struct_size != (int32_t)sizeof(sdempc_bands_cfg)) return fail(h, SDEMPC_EINVAL, "sdempc_bands_cfg.struct_size mismatch%s");
+    if (!q && !below && !at) return fail(h, SDEMPC_EINVAL, "no output asked for: q, below and at are all NULL%s");
+    if ((below || at) && !have_obs) return fail(h, SDEMPC_EINVAL, "below and at need the observed rows (obs)%s");
+    if (q) {
+        if (!cfg) return fail(h, SDEMPC_EINVAL, "q needs a sdempc_bands_cfg (the ranks it selects)%s");
+        if (cfg->n_ranks < 1 || cfg->n_ranks > BAND_MAX_RANKS) return fail(h, SDEMPC_EINVAL, "q needs 1 <= sdempc_bands_cfg.n_ranks <= 8%s");
+        for (int k = 0; k < cfg->n_ranks; ++k)
+            if (cfg->ranks[k] < 0 || cfg->ranks[k] >= h->P) return fail(h, SDEMPC_EINVAL, "a rank of sdempc_bands_cfg.ranks is outside 0 .. P-1%s");
+    }
+    return 0;
+}
+}  // namespace
+
+int sdempc_bands_batch_dev(sdempc_handle* h, const sdempc_bands_cfg* cfg, int32_t B, const void* obs_dev, void* q_dev, void* below_dev, void* at_dev, void* stream) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if ((rc = check_bands(h, cfg, obs_dev != nullptr, q_dev, below_dev, at_dev))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    if ((rc = check_traj_held(h, B))) return rc;
+    BandArgs N{};
+    N.traj = (const float*)h->d_traj.p;
+    if (below_dev || at_dev) { N.obs = (const float*)obs_dev; N.below = (uint32_t*)below_dev; N.at = (uint32_t*)at_dev; }
+    if (q_dev) {
+        N.q = (float*)q_dev;
+        N.n_ranks = cfg->n_ranks;
+        for (int k = 0; k < cfg->n_ranks; ++k) N.ranks[k] = cfg->ranks[k];
+    }
+    N.C = (h->H + 1) * SDEMPC_NX;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    HIPCHK(h, launch_bands(N, B, h->P, h->G, h->H, st));
+    return SDEMPC_OK;
+    });
+}
+
+namespace {
+// the staged inputs (d_x0, d_u, d_xref, d_noise on the handle's stream) -> obs staged, one store_traj rollout, the reducer, the outputs asked for back on the host
+int bands_staged(sdempc_handle* h, const sdempc_bands_cfg* cfg, int32_t B, const float* obs, float* cost, float* q, uint32_t* below, uint32_t* at) {
+    int rc;
+    const size_t n = (size_t)(h->H + 1) * SDEMPC_NX, plane = sizeof(float) * (size_t)h->max_batch * n;
+    if (!h->d_band.p && (rc = dev_alloc(h, h->d_band, (3 + BAND_MAX_RANKS) * plane, true))) return rc;
+    char* d = (char*)h->d_band.p;
+    void* d_obs = d, *d_below = d + plane, *d_at = d + 2 * plane, *d_q = d + 3 * plane;
+    const bool want_obs = below || at;
+    if (want_obs) HIPCHK(h, hipMemcpyAsync(d_obs, obs, sizeof(float) * B * n, hipMemcpyHostToDevice, h->stream));
+    if ((rc = sdempc_rollout_batch_dev(h, B, h->d_x0.p, h->d_u.p, h->d_xref.p, h->d_noise.p, h->d_cost.p, nullptr, 1, h->stream))) return rc;
+    if ((rc = sdempc_bands_batch_dev(h, cfg, B, want_obs ? d_obs : nullptr, q ? d_q : nullptr, below ? d_below : nullptr, at ? d_at : nullptr, h->stream))) return rc;
+    if (cost) HIPCHK(h, hipMemcpyAsync(cost, h->d_cost.p, sizeof(float) * B, hipMemcpyDeviceToHost, h->stream));
+    if (q) HIPCHK(h, hipMemcpyAsync(q, d_q, sizeof(float) * B * n * cfg->n_ranks, hipMemcpyDeviceToHost, h->stream));
+    if (below) HIPCHK(h, hipMemcpyAsync(below, d_below, sizeof(uint32_t) * B * n, hipMemcpyDeviceToHost, h->stream));
+    if (at) HIPCHK(h, hipMemcpyAsync(at, d_at, sizeof(uint32_t) * B * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return SDEMPC_OK;
+}
+}  // namespace
+
+int sdempc_bands_batch(sdempc_handle* h, const sdempc_bands_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const float* noise, const float* obs,
+                       float* cost, float* q, uint32_t* below, uint32_t* at) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if (!x0 || !u || !xref || !noise) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    if ((rc = check_bands(h, cfg, obs != nullptr, q, below, at))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    if ((rc = stage_common(h, B, x0, u, xref, noise))) return rc;
+    return bands_staged(h, cfg, B, obs, cost, q, below, at);
+    });
+}
+
+int sdempc_bands_batch_keys(sdempc_handle* h, const sdempc_bands_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const uint32_t* keys,
+                            const float* obs, float* cost, float* q, uint32_t* below, uint32_t* at) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if (!x0 || !u || !xref || !keys) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    if ((rc = check_bands(h, cfg, obs != nullptr, q, below, at))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    const int H = h->H, m = h->m;
+    HIPCHK(h, hipMemcpyAsync(h->d_x0.p, x0, sizeof(float) * B * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_u.p, u, sizeof(float) * B * H * m, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_xref.p, xref, sizeof(float) * B * (H + 1) * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
+    if ((rc = noise_from_keys(h, B, keys, (float*)h->d_noise.p, h->stream))) return rc;
+    return bands_staged(h, cfg, B, obs, cost, q, below, at);
     });
 }
 

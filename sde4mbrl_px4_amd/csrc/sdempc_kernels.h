@@ -366,5 +366,21 @@ struct RiskArgs {
     int ranks[RISK_MAX_RANKS];
 };
 hipError_t launch_risk(const RiskArgs& R, int B, int P, int G, hipStream_t st);
+// SPEC.md §12b, predicted bands: the noise kernel in its BANDS form (sdempc_band.inc.h), on the tube's grid. Per (instance, column) of the same tensor, over the valid
+// particles in the total key order: the values at n_ranks requested ranks (q, plane k = rank ranks[k]) and the number of particles below / at the observed word of
+// that column. Every output is optional. traj null means absent: every noise, tube and risk launch passes that, and the kernel then makes no memory access it did
+// not make before.
+constexpr int BAND_MAX_RANKS = 8;
+struct BandArgs {
+    const float* traj;          // [B][G][C][32], C = (H+1)*13 (KArgs::traj); null: not the bands mode
+    const float* obs;           // [B][C] observed rows, or null: below / at are then not written
+    float* q;                   // [B][n_ranks][C] or null (n_ranks / ranks are then not read)
+    uint32_t* below;            // [B][C] or null
+    uint32_t* at;               // [B][C] or null
+    int C;                      // columns per instance
+    int n_ranks;                // 1 .. BAND_MAX_RANKS
+    int ranks[BAND_MAX_RANKS];  // each in [0, P); neither sorted nor distinct (wave-uniform kernel arguments, read at constant indices)
+};
+hipError_t launch_bands(const BandArgs& N, int B, int P, int G, int H, hipStream_t st);
 
 }  // namespace sdempc

@@ -119,6 +119,7 @@ DI float bits_to_normal(uint32_t bits) {
 }  // namespace sdempc
 #include "sdempc_tube.inc.h"
 #include "sdempc_risk.inc.h"
+#include "sdempc_band.inc.h"
 namespace sdempc {
 
 // grid: x = chunks of 256 threads over [pg][r][lane] (pg < ceil(ceil(P/2)/32), r < H*6), y = instance
@@ -127,13 +128,16 @@ namespace sdempc {
 // SPEC.md §12a (R.traj given; keys, out, HC and T are then not read): the RISK form — x = 1, y = instance, dynamic LDS of risk_lds_words_host words.
 // R.traj null (every noise and tube launch): not one access more. The second launch bound asks for the 8 waves / SIMD the kernel had before this form: its scalar
 // registers stay below 96 (the risk form's later-phase arguments are spilled to lanes of a vector register outside its loops), scratch stays 0.
+// SPEC.md §12b (Q.traj given; keys, out, HC, T and R are then not read): the BANDS form — the tube's grid, x = tiles of 32 columns, y = instance (sdempc_band.inc.h).
+// Q.traj null (every noise, tube and risk launch): not one access more.
 __global__ void __launch_bounds__(256, 8) sdempc_noise_kernel(const uint32_t* __restrict__ keys, float* __restrict__ out, int P, int G, int HC, int b0, TubeArgs T,
-                                                           RiskArgs R) {
+                                                           RiskArgs R, BandArgs Q) {
     const int b = b0 + blockIdx.y;
-    // (wave-uniform; ONE test of both mode pointers, so that the noise form waits for one batch of scalar loads and takes one branch, as it did with one mode —
+    // (wave-uniform; ONE test of all mode pointers, so that the noise form waits for one batch of scalar loads and takes one branch, as it did with one mode —
     // its workgroups are short, and a second dependent load in front of `keys` showed in its time)
-    if (__builtin_expect((reinterpret_cast<uintptr_t>(T.traj) | reinterpret_cast<uintptr_t>(R.traj)) != 0, 0)) {
-        if (R.traj) risk_reduce(R, P, G, b);
+    if (__builtin_expect((reinterpret_cast<uintptr_t>(T.traj) | reinterpret_cast<uintptr_t>(R.traj) | reinterpret_cast<uintptr_t>(Q.traj)) != 0, 0)) {
+        if (Q.traj) band_reduce(Q, P, G, b);
+        else if (R.traj) risk_reduce(R, P, G, b);
         else tube_reduce(T, P, G, b);
         return;
     }
@@ -164,7 +168,7 @@ hipError_t launch_noise_from_keys(const uint32_t* keys_dev, float* out, int B, i
     const unsigned gx = (unsigned)((threads + 255) / 256);
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(keys_dev, out, P, G, HC, b0, TubeArgs{}, RiskArgs{});
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(keys_dev, out, P, G, HC, b0, TubeArgs{}, RiskArgs{}, BandArgs{});
     }
     return hipGetLastError();
 }
@@ -176,7 +180,7 @@ hipError_t launch_tube(const TubeArgs& T, int B, int P, int G, int H, hipStream_
     const unsigned gx = (unsigned)((T.C + 31) / 32);
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, T, RiskArgs{});
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, T, RiskArgs{}, BandArgs{});
     }
     return hipGetLastError();
 }
@@ -196,7 +200,23 @@ hipError_t launch_risk(const RiskArgs& R, int B, int P, int G, hipStream_t st) {
     if (lds > RISK_MAX_LDS) return hipErrorInvalidValue;
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(1, nb), 256, lds, st>>>(nullptr, nullptr, P, G, 0, b0, TubeArgs{}, R);
+        sdempc_noise_kernel<<<dim3(1, nb), 256, lds, st>>>(nullptr, nullptr, P, G, 0, b0, TubeArgs{}, R, BandArgs{});
+    }
+    return hipGetLastError();
+}
+
+// SPEC.md §12b: the tube's grid; every word of every output given is written
+hipError_t launch_bands(const BandArgs& N, int B, int P, int G, int H, hipStream_t st) {
+    if (B < 1 || P < 1 || H < 1 || G != (P + 31) / 32 || !N.traj || N.C != (H + 1) * 13) return hipErrorInvalidValue;
+    if (!N.q && !N.below && !N.at) return hipErrorInvalidValue;
+    if ((N.below || N.at) && !N.obs) return hipErrorInvalidValue;
+    if (N.q && (N.n_ranks < 1 || N.n_ranks > BAND_MAX_RANKS)) return hipErrorInvalidValue;
+    for (int k = 0; N.q && k < N.n_ranks; ++k)
+        if (N.ranks[k] < 0 || N.ranks[k] >= P) return hipErrorInvalidValue;
+    const unsigned gx = (unsigned)((N.C + 31) / 32);
+    for (int b0 = 0; b0 < B; b0 += 65535) {
+        const int nb = B - b0 < 65535 ? B - b0 : 65535;
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, TubeArgs{}, RiskArgs{}, N);
     }
     return hipGetLastError();
 }

@@ -470,6 +470,97 @@ def quantile_ranks(quantiles, P):
     return [min(P - 1, max(0, math.ceil(float(q) * P) - 1)) for q in quantiles]
 
 
+def band_keys(v):
+    """SPEC.md §12b: the uint32 key of every float32 word of v — -inf < ... < -0 < +0 < ... < +inf < NaN as unsigned integers, all NaNs one key"""
+    v = np.ascontiguousarray(v, np.float32)
+    u = v.view(np.uint32)
+    k = np.where(u & np.uint32(0x80000000), ~u, u ^ np.uint32(0x80000000)).astype(np.uint32)
+    return np.where(np.isnan(v), np.uint32(0xFFFFFFFF), k).astype(np.uint32)
+
+
+class _BandsFields(NamedTuple):
+    cost: np.ndarray
+    q: object
+    below: object
+    at: object
+
+
+class Bands(_BandsFields):
+    """Predicted bands of a rollout (SPEC.md §12b), a named tuple (cost, q, below, at). cost f32[B] is the rollout's expected cost. q f32[B][Q][H+1][13]:
+    plane k is, per step and state component, the value at rank ranks[k] of the key order over the P particles (None when no rank was asked for). below, at
+    uint32[B][H+1][13]: how many particles lie below / at the observed value (None without `observed`). The particle count P, the ranks, the quantiles they
+    came from (None when ranks were given directly) and the observed rows ride along as attributes: Bands.of sets them."""
+    P = None
+    ranks = None
+    quantiles = None
+    observed = None
+
+    @classmethod
+    def of(cls, P, ranks, quantiles, observed, *fields):
+        r = cls(*fields)
+        r.P, r.ranks, r.quantiles, r.observed = int(P), (None if ranks is None else tuple(int(k) for k in ranks)), (None if quantiles is None else tuple(quantiles)), observed
+        return r
+
+    def _replace(self, **kw):
+        r = super()._replace(**kw)
+        r.P, r.ranks, r.quantiles, r.observed = self.P, self.ranks, self.quantiles, self.observed
+        return r
+
+    def band(self, k):
+        """plane k of q: [..., H+1, 13]"""
+        if self.q is None:
+            raise ValueError("Bands.band: no rank was asked for")
+        return self.q[..., k, :, :]
+
+    @property
+    def median(self):
+        """the plane of quantile 0.5; only when 0.5 was among the quantiles asked for"""
+        if self.quantiles is None or 0.5 not in self.quantiles:
+            raise ValueError("Bands.median: 0.5 was not among the quantiles asked for")
+        return self.band(self.quantiles.index(0.5))
+
+    def _need_obs(self, what):
+        if self.below is None or self.at is None or self.observed is None or self.P is None:
+            raise ValueError(f"Bands.{what}: no observed rows were given (or this Bands was not built with Bands.of)")
+
+    @property
+    def pit(self):
+        """(below + at / 2) / P in float64: the mid-rank of the observed value in the predicted distribution (the PIT value); NaN where the observation was NaN"""
+        self._need_obs("pit")
+        v = (self.below.astype(np.float64) + 0.5 * self.at.astype(np.float64)) / self.P
+        return np.where(np.isnan(self.observed), np.nan, v)
+
+    def inside(self, k_lo, k_hi):
+        """boolean plane: key(q[k_lo]) <= key(observed) <= key(q[k_hi]); False where the observation was NaN"""
+        self._need_obs("inside")
+        ko = band_keys(self.observed)
+        ok = (band_keys(self.band(k_lo)) <= ko) & (ko <= band_keys(self.band(k_hi)))
+        return ok & ~np.isnan(self.observed)
+
+
+def calibration(bands, bins=10, levels=(0.5, 0.9)):
+    """Calibration table from one Bands or a list of them (every instance of every one is a sample; all of one horizon). Per horizon step and component:
+    `hist` int64[H+1][13][bins], the histogram of the PIT values over the samples (bin j: j / bins <= pit < (j + 1) / bins, pit = 1 in the last);
+    `n` int64[H+1][13], the samples counted — columns whose observation was NaN are left out; `coverage` float64[len(levels)][H+1][13], the fraction of samples
+    with |pit - 1/2| <= level / 2 (the central interval of that nominal level; NaN where n = 0); `levels` as given. A calibrated model has a flat histogram and
+    coverage equal to the level; coverage above it says the model's sigma is too wide."""
+    if isinstance(bands, Bands):
+        bands = [bands]
+    pit = np.concatenate([np.asarray(b.pit, np.float64).reshape((-1,) + b.pit.shape[-2:]) for b in bands], axis=0)
+    ok = ~np.isnan(pit)
+    n = ok.sum(axis=0).astype(np.int64)
+    idx = np.clip(np.floor(np.where(ok, pit, 0.0) * bins).astype(np.int64), 0, bins - 1)
+    hist = np.zeros(pit.shape[1:] + (bins,), np.int64)
+    for j in range(bins):
+        hist[..., j] = ((idx == j) & ok).sum(axis=0)
+    cov = np.full((len(levels),) + pit.shape[1:], np.nan, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i, lv in enumerate(levels):
+            hit = (np.abs(np.where(ok, pit, np.inf) - 0.5) <= 0.5 * float(lv)).sum(axis=0)
+            cov[i] = np.where(n > 0, hit / np.maximum(n, 1), np.nan)
+    return {"hist": hist, "n": n, "coverage": cov, "levels": tuple(float(v) for v in levels), "bins": int(bins)}
+
+
 def tail_count(tail, P):
     """SPEC.md §12a: a fraction alpha -> max(1, ceil(alpha P)); an integer is the count itself"""
     import math
@@ -721,6 +812,63 @@ class SdeMpcSolver:
         cfg, rows = self._risk_cfg(centre, tail, quantiles)
         self._check(_abi.risk_entries(self.lib)[2](self._h, C.byref(cfg), B, lo, hi, rows, xref, exit, jx, first_exit, outside_any, jstat, jq, jtail,
                                                    C.c_void_p(stream)))
+
+    # ---- predicted bands (SPEC.md §12b): per-step particle quantiles and observation ranks, reduced on the device ----
+    def _bands_cfg(self, quantiles, ranks):
+        """-> (cfg or None, ranks or None, quantiles or None). ranks given: they are used as they are and quantiles is ignored."""
+        if ranks is None and quantiles is None:
+            return None, None, None
+        if ranks is None:
+            quantiles = tuple(float(q) for q in quantiles)
+            ranks = quantile_ranks(quantiles, self.P)
+        else:
+            quantiles, ranks = None, [int(r) for r in ranks]
+        if not 1 <= len(ranks) <= _abi.BANDS_MAX_RANKS:
+            raise ValueError(f"quantiles / ranks: 1 to {_abi.BANDS_MAX_RANKS} values")
+        cfg = _abi.SdempcBandsCfg()
+        cfg.struct_size = C.sizeof(_abi.SdempcBandsCfg)
+        cfg.n_ranks = len(ranks)
+        for k, r in enumerate(ranks):
+            cfg.ranks[k] = r
+        return cfg, ranks, quantiles
+
+    def _bands_call(self, fn, x0, u, xref, draw, quantiles, ranks, observed):
+        B = x0.shape[0]
+        H = self.H
+        x0, u, xref = _f32(x0, (B, 13)), _f32(u, (B, H, self.m)), _f32(xref, (B, H + 1, 13))
+        cfg, ranks, quantiles = self._bands_cfg(quantiles, ranks)
+        obs = _f32(observed, (B, H + 1, 13)) if observed is not None else None
+        u32p = C.POINTER(C.c_uint32)
+        cost = np.zeros(B, np.float32)
+        q = np.zeros((B, cfg.n_ranks, H + 1, 13), np.float32) if cfg is not None else None
+        below = np.zeros((B, H + 1, 13), np.uint32) if obs is not None else None
+        at = np.zeros((B, H + 1, 13), np.uint32) if obs is not None else None
+        f = lambda a: _fp(a) if a is not None else None
+        w = lambda a: a.ctypes.data_as(u32p) if a is not None else None
+        self._check(fn(self._h, C.byref(cfg) if cfg is not None else None, B, _fp(x0), _fp(u), _fp(xref), draw, f(obs), _fp(cost), f(q), w(below), w(at)))
+        return Bands.of(self.P, ranks, quantiles, obs, cost, q, below, at)
+
+    def bands(self, x0, u, xref, noise, quantiles=(0.05, 0.5, 0.95), ranks=None, observed=None) -> Bands:
+        """One rollout of u per instance with its particle x horizon tensor reduced on the device to per-step quantiles across the particles (SPEC.md §12b):
+        Bands(cost, q, below, at). quantiles: up to 8 values in [0, 1], each the rank ceil(q P) - 1 of the key order (quantile_ranks); ranks: the 0-based ranks
+        themselves instead. observed f32[B][H+1][13]: rows to rank in the predicted distribution (NaN where there is none) — below / at count the particles
+        below / at them; None: neither is computed. quantiles=None and ranks=None: no q."""
+        x0 = _f32(x0)
+        noise = _f32(noise, (x0.shape[0], self.P, self.H, 6))
+        return self._bands_call(_abi.bands_entries(self.lib)[0], x0, u, xref, _fp(noise), quantiles, ranks, observed)
+
+    def bands_keys(self, x0, u, xref, keys, quantiles=(0.05, 0.5, 0.95), ranks=None, observed=None) -> Bands:
+        """bands() with the noise of instance b drawn on the device as normal(keys[b], (P, H, 6)), as solve_keys draws it."""
+        x0 = _f32(x0)
+        keys = self._keys(keys, x0.shape[0])
+        return self._bands_call(_abi.bands_entries(self.lib)[1], x0, u, xref, keys.ctypes.data_as(C.POINTER(C.c_uint32)), quantiles, ranks, observed)
+
+    def bands_dev(self, B, quantiles=None, ranks=None, observed=None, q=None, below=None, at=None, stream=0):
+        """Device pointers (each may be None): reduces the tensor the last rollout_dev(store_traj=True) of at least B instances left in the handle. observed:
+        pointer to f32[B][H+1][13]; q f32[B][Q][H+1][13] (Q = len(quantiles) or len(ranks)), below / at uint32[B][H+1][13]. Refused after a grad_dev, a
+        solve_dev or a smaller rollout, as tube_dev is."""
+        cfg, _, _ = self._bands_cfg(quantiles, ranks)
+        self._check(_abi.bands_entries(self.lib)[2](self._h, C.byref(cfg) if cfg is not None else None, B, observed, q, below, at, C.c_void_p(stream)))
 
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
