@@ -176,7 +176,7 @@ int sdempc_device_ready(const sdempc_handle* h);
  *                                                                                          Filled: the workspaces (particle x horizon tensor, activation checkpoint,
  *                                                                                          partial sums, control table), the cooperative layouts' per-particle outputs and
  *                                                                                          checkpoint rows, the noise buffers, the staging copies of inputs and outputs (the tube planes of
- *                                                                                          sdempc_tube_batch, d_tube, the band planes of sdempc_bands_batch, d_band, and the risk rows of sdempc_risk_batch, d_risk, among them),
+ *                                                                                          sdempc_tube_batch, d_tube, the band planes of sdempc_bands_batch, d_band, the risk rows of sdempc_risk_batch, d_risk, and the outcome rows of sdempc_outcome_batch, d_outcome, among them),
  *                                                                                          the closed loop's key / chunk / plant / rate-state / observation / history buffers (the chunk buffer includes the
  *                                                                                          staged disturbance rows and plant-schedule rows of a scenario). (The particle x horizon tensor is
  *                                                                                          zeroed at allocation otherwise; nothing depends on that.) Keep their initial value:
@@ -375,6 +375,52 @@ int sdempc_bands_batch(sdempc_handle* h, const sdempc_bands_cfg* cfg, int32_t B,
 /* The same with the noise of instance b drawn on the device as normal(keys[b], (P, H, 6)), as sdempc_solve_batch_keys does. */
 int sdempc_bands_batch_keys(sdempc_handle* h, const sdempc_bands_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const uint32_t* keys,
                             const float* obs /*[B][H+1][13] or NULL*/, float* cost /*[B] or NULL*/, float* q, uint32_t* below, uint32_t* at);
+
+/* ---- predicted outcome (SPEC.md §12c) --------------------------------------------------------------
+ * The failure criteria of the episode score (SPEC.md §11h) asked of the prediction: every particle of the same particle x horizon tensor is scored as if it
+ * were an episode, where the tensor lies on the device. Scored rows are x_t, t = 1 .. H (row index r = t - 1); the target of row t is row t of the call's xref
+ * (target_mode 0) or of the caller's rows target f32[tgt_batch][tgt_steps][13] (target_mode 1; tgt_steps 1 or H+1, tgt_batch 1 or B; an index into a size-1
+ * axis is 0). Per row and particle: dp, dv, c, w2, nf and the cause bits 1 radius, 2 tilt, 4 rate, 8 non-finite, exactly as §11h forms them against r2_pos,
+ * cos_min, w2_max (+inf / -inf / +inf: criterion off; a NaN threshold is SDEMPC_EINVAL). Outputs over the valid particles, each optional (NULL: not
+ * computed, not written), at least one:
+ *   words      u32[B][P][11]        words 0 .. 10 of the §11h score table of particle p over its H rows, from the initial row
+ *   fail_step  u32[B][H][5]         particles whose row r carries cause bit k = 0 .. 3; slot 4: any cause
+ *   first_fail u32[B][H+1]          histogram of word 8 (first failing row); slot H: never failed. The sum is P.
+ *   cause_ever u32[B][4]            particles whose word 9 has bit k
+ *   chan_stat  f32[B][H][4][3]      per row and channel (dp, dv, c, w2): mean (the particle sum of SPEC.md §6.1 times float32 1/P), min, max (NaN ignored)
+ *   chan_q     f32[B][H][4][n_ranks]  per row and channel the value of rank cfg->ranks[k] in the key order of the bands (-0 < +0, NaN above +inf)
+ *   agg_stat   f32[B][4][3]         the same three statistics over the particles' words 1 (sum dp), 2 (max dp), 6 (min c), 7 (max w2)
+ *   agg_q      f32[B][4][n_ranks]   the same order statistics over those four words
+ * chan_q and agg_q need 1 <= n_ranks <= 8 and 0 <= ranks[k] < P and are refused for P > 128 (the selection sorts four particle groups in registers); every
+ * output is refused when 4 (6 H + 5 + 140 ceil(P / 32)) bytes exceed 64 KiB of workgroup memory. Refusals, in this order, before the first HIP call: a wrong
+ * struct_size; a NaN threshold; all outputs NULL; n_ranks or a rank out of range, then P > 128, where chan_q or agg_q is given; target_mode outside {0, 1};
+ * in target_mode 1 tgt_steps or tgt_batch outside their sets, then target NULL; in target_mode 0 a NULL xref_dev. */
+typedef struct sdempc_outcome_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_outcome_cfg) */
+    float r2_pos;          /* radius^2 [m^2] around the target position */
+    float cos_min;         /* cosine of the largest tilt */
+    float w2_max;          /* |body rate|^2 [rad^2/s^2] */
+    int32_t target_mode;   /* 0 the call's xref, 1 the caller's rows */
+    int32_t tgt_steps;     /* target_mode 1: 1 or H+1 */
+    int32_t tgt_batch;     /* target_mode 1: 1 or B */
+    int32_t n_ranks;       /* chan_q, agg_q: number of ranks */
+    int32_t ranks[8];
+} sdempc_outcome_cfg;
+/* Reduces the tensor that the last sdempc_rollout_batch_dev(store_traj=1) of at least B instances left in the handle; device pointers. target_dev
+ * f32[tgt_batch][tgt_steps][13] (target_mode 1), xref_dev f32[B][H+1][13] (target_mode 0). Refused like sdempc_tube_batch_dev when the workspace holds fewer
+ * instances. Enqueue it on the stream of that rollout. */
+int sdempc_outcome_batch_dev(sdempc_handle* h, const sdempc_outcome_cfg* cfg, int32_t B, const void* target_dev, const void* xref_dev, void* words_dev,
+                             void* fail_step_dev, void* first_fail_dev, void* cause_ever_dev, void* chan_stat_dev, void* chan_q_dev, void* agg_stat_dev,
+                             void* agg_q_dev, void* stream);
+/* Host pointers: ONE rollout of u (as sdempc_rollout_batch; cost [B] may be NULL) with the tensor kept, the reduction, the requested outputs copied back.
+ * target [tgt_batch][tgt_steps][13] (target_mode 1) or NULL. */
+int sdempc_outcome_batch(sdempc_handle* h, const sdempc_outcome_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const float* noise,
+                         const float* target, float* cost /*[B] or NULL*/, uint32_t* words, uint32_t* fail_step, uint32_t* first_fail, uint32_t* cause_ever,
+                         float* chan_stat, float* chan_q, float* agg_stat, float* agg_q);
+/* The same with the noise of instance b drawn on the device as normal(keys[b], (P, H, 6)), as sdempc_solve_batch_keys does. */
+int sdempc_outcome_batch_keys(sdempc_handle* h, const sdempc_outcome_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const uint32_t* keys,
+                              const float* target, float* cost /*[B] or NULL*/, uint32_t* words, uint32_t* fail_step, uint32_t* first_fail,
+                              uint32_t* cause_ever, float* chan_stat, float* chan_q, float* agg_stat, float* agg_q);
 
 /* ---- batched closed loop (SPEC.md §11) ---------------------------------------------------------
  * B independent episodes of T control ticks, entirely on the device: per tick, the solve of sdempc_solve_batch_keys on the episode's

@@ -139,7 +139,17 @@ class SdempcBandsCfg(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_ranks", C.c_int32), ("ranks", C.c_int32 * 8)]
 
 
+class SdempcOutcomeCfg(C.Structure):
+    """sdempc_outcome_cfg (SPEC.md §12c): the three thresholds of the episode score (§11h), where the target rows come from (target_mode 0 the call's xref, 1 the
+    caller's rows [tgt_batch][tgt_steps][13]) and the ranks of chan_q / agg_q."""
+    _fields_ = [("struct_size", C.c_int32), ("r2_pos", C.c_float), ("cos_min", C.c_float), ("w2_max", C.c_float), ("target_mode", C.c_int32),
+                ("tgt_steps", C.c_int32), ("tgt_batch", C.c_int32), ("n_ranks", C.c_int32), ("ranks", C.c_int32 * 8)]
+
+
 BANDS_MAX_RANKS = 8       # sdempc_bands_cfg.ranks
+OUTCOME_MAX_RANKS = 8     # sdempc_outcome_cfg.ranks
+OUTCOME_RANK_MAX_P = 128  # chan_q / agg_q are refused above this particle count
+OUTCOME_WORDS = 11        # words 0 .. 10 of the score table (SCORE_FIELDS) per particle
 RISK_MAX_RANKS = 8        # sdempc_risk_cfg.ranks
 RISK_RANK_MAX_P = 4096    # jq / jtail are refused above this particle count
 
@@ -437,6 +447,24 @@ def bands_entries(lib):
     return fns
 
 
+def outcome_entries(lib):
+    """sdempc_outcome_batch, sdempc_outcome_batch_keys and sdempc_outcome_batch_dev (SPEC.md §12c) with their prototypes set; detected by symbol, as tube_entries does."""
+    try:
+        fns = lib.sdempc_outcome_batch, lib.sdempc_outcome_batch_keys, lib.sdempc_outcome_batch_dev
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_outcome_batch (SPEC.md §12c): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fns[0].argtypes is None:
+        vp, i32, fp, u32p = C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        cfgp = C.POINTER(SdempcOutcomeCfg)
+        outs = [fp, u32p, u32p, u32p, u32p, fp, fp, fp, fp]    # cost, words, fail_step, first_fail, cause_ever, chan_stat, chan_q, agg_stat, agg_q
+        fns[0].argtypes = [vp, cfgp, i32, fp, fp, fp, fp, fp] + outs       # x0, u, xref, noise, target
+        fns[1].argtypes = [vp, cfgp, i32, fp, fp, fp, u32p, fp] + outs
+        fns[2].argtypes = [vp, cfgp, i32] + [vp] * 11
+        for f in fns:
+            f.restype = C.c_int
+    return fns
+
+
 EXPORTED_SYMBOLS = [
     "sdempc_create", "sdempc_destroy", "sdempc_last_error", "sdempc_abi_version", "sdempc_build_flags", "sdempc_set_device", "sdempc_device_ready", "sdempc_set_option", "sdempc_get_option", "sdempc_reset",
     "sdempc_rollout_batch", "sdempc_grad_batch", "sdempc_solve_batch", "sdempc_noise_dev_floats",
@@ -450,4 +478,5 @@ EXPORTED_SYMBOLS = [
     "sdempc_tube_batch", "sdempc_tube_batch_keys", "sdempc_tube_batch_dev",
     "sdempc_risk_batch", "sdempc_risk_batch_keys", "sdempc_risk_batch_dev",
     "sdempc_bands_batch", "sdempc_bands_batch_keys", "sdempc_bands_batch_dev",
+    "sdempc_outcome_batch", "sdempc_outcome_batch_keys", "sdempc_outcome_batch_dev",
 ]

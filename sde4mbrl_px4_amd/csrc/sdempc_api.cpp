@@ -177,6 +177,9 @@ struct sdempc_handle {
     // predicted risk (sdempc_risk_batch / _keys / _dev, allocated on their first use; risk_regions): staged bounds and centre rows (the particle mean of
     // centre_mode 3 among them) and the staging copies of the seven outputs
     DevBuf d_risk;
+    // predicted outcome (sdempc_outcome_batch / _keys, allocated on their first use; outcome_regions): the staged target rows and the staging copies of the
+    // eight outputs
+    DevBuf d_outcome;
     // closed loop (sdempc_closed_loop_batch, allocated on its first use): d_loop = keys u32[max_batch][2], solve keys u32[max_batch][2], plant noise
     // f32[max_batch][6], one flag word; d_loop_chunk = the per-tick outputs of one chunk of ticks and the reference windows it reads (grown, never shrunk)
     DevBuf d_loop, d_loop_chunk;
@@ -783,7 +786,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_outcome, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1467,6 +1470,150 @@ int sdempc_bands_batch_keys(sdempc_handle* h, const sdempc_bands_cfg* cfg, int32
     HIPCHK(h, hipMemcpyAsync(h->d_xref.p, xref, sizeof(float) * B * (H + 1) * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
     if ((rc = noise_from_keys(h, B, keys, (float*)h->d_noise.p, h->stream))) return rc;
     return bands_staged(h, cfg, B, obs, cost, q, below, at);
+    });
+}
+
+// ---- predicted outcome (SPEC.md §12c) ----
+namespace {
+struct OutcomeOut { void *words, *fail_step, *first_fail, *cause_ever, *chan_stat, *chan_q, *agg_stat, *agg_q; };
+constexpr int OUTCOME_REGIONS = 9;   // target rows, then the eight outputs in OutcomeOut's order
+
+// byte offsets of d_outcome's regions, each sized for max_batch instances; off[OUTCOME_REGIONS] = total
+void outcome_regions(const sdempc_handle* h, size_t* off, size_t* per_instance) {
+    const size_t H = (size_t)h->H;
+    const size_t words[OUTCOME_REGIONS] = {(H + 1) * SDEMPC_NX, (size_t)h->P * OUTCOME_WORDS, H * 5, H + 1, 4, H * 12, H * 4 * OUTCOME_MAX_RANKS, 12, 4 * OUTCOME_MAX_RANKS};
+    size_t o = 0;
+    for (int k = 0; k < OUTCOME_REGIONS; ++k) {
+        off[k] = o;
+        if (per_instance) per_instance[k] = sizeof(float) * words[k];
+        o += (sizeof(float) * words[k] * (size_t)h->max_batch + 255) & ~(size_t)255;
+    }
+    off[OUTCOME_REGIONS] = o;
+}
+
+// every check of an outcome request (SPEC.md §12c) that needs no device, in the documented order; no HIP call. have_*: whether the caller gave that input.
+int check_outcome(sdempc_handle* h, const sdempc_outcome_cfg* cfg, int B, bool have_target, bool have_xref, const OutcomeOut& O) {
+    if (!cfg) return fail(h, SDEMPC_EINVAL, "NULL sdempc_outcome_cfg%s");
+    if (cfg->struct_size != (int32_t)sizeof(sdempc_outcome_cfg)) return fail(h, SDEMPC_EINVAL, "sdempc_outcome_cfg.struct_size mismatch%s");
+    if (cfg->r2_pos != cfg->r2_pos || cfg->cos_min != cfg->cos_min || cfg->w2_max != cfg->w2_max)
+        return fail(h, SDEMPC_EINVAL, "a threshold of sdempc_outcome_cfg is NaN (use +inf / -inf / +inf to switch a criterion off)%s");
+    if (!O.words && !O.fail_step && !O.first_fail && !O.cause_ever && !O.chan_stat && !O.chan_q && !O.agg_stat && !O.agg_q)
+        return fail(h, SDEMPC_EINVAL, "no output asked for: words, fail_step, first_fail, cause_ever, chan_stat, chan_q, agg_stat and agg_q are all NULL%s");
+    if (O.chan_q || O.agg_q) {
+        if (cfg->n_ranks < 1 || cfg->n_ranks > OUTCOME_MAX_RANKS) return fail(h, SDEMPC_EINVAL, "chan_q and agg_q need 1 <= sdempc_outcome_cfg.n_ranks <= 8%s");
+        for (int k = 0; k < cfg->n_ranks; ++k)
+            if (cfg->ranks[k] < 0 || cfg->ranks[k] >= h->P) return fail(h, SDEMPC_EINVAL, "a rank of sdempc_outcome_cfg.ranks is outside 0 .. P-1%s");
+        if (h->P > OUTCOME_RANK_MAX_P)
+            return fail(h, SDEMPC_EINVAL, "chan_q and agg_q are limited to 128 particles (the selection sorts four particle groups in registers); the other outputs are not%s");
+    }
+    if (cfg->target_mode < 0 || cfg->target_mode > 1) return fail(h, SDEMPC_EINVAL, "sdempc_outcome_cfg.target_mode out of range (0 xref, 1 caller's rows)%s");
+    if (cfg->target_mode == 1) {
+        if (cfg->tgt_steps != 1 && cfg->tgt_steps != h->H + 1) return fail(h, SDEMPC_EINVAL, "sdempc_outcome_cfg.tgt_steps must be 1 or H+1%s");
+        if (cfg->tgt_batch != 1 && cfg->tgt_batch != B) return fail(h, SDEMPC_EINVAL, "sdempc_outcome_cfg.tgt_batch must be 1 or B%s");
+        if (!have_target) return fail(h, SDEMPC_EINVAL, "target_mode 1 needs the caller's target rows%s");
+    } else if (!have_xref) return fail(h, SDEMPC_EINVAL, "target_mode 0 needs xref%s");
+    if (sizeof(uint32_t) * outcome_lds_words_host(h->H, h->G) > RISK_MAX_LDS)
+        return fail(h, SDEMPC_EINVAL, "horizon and particle count too large for the outcome reducer's workgroup memory (4 (6 H + 5 + 140 ceil(P / 32)) bytes > 64 KiB)%s");
+    return 0;
+}
+}  // namespace
+
+int sdempc_outcome_batch_dev(sdempc_handle* h, const sdempc_outcome_cfg* cfg, int32_t B, const void* target_dev, const void* xref_dev, void* words_dev,
+                             void* fail_step_dev, void* first_fail_dev, void* cause_ever_dev, void* chan_stat_dev, void* chan_q_dev, void* agg_stat_dev,
+                             void* agg_q_dev, void* stream) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    const OutcomeOut O{words_dev, fail_step_dev, first_fail_dev, cause_ever_dev, chan_stat_dev, chan_q_dev, agg_stat_dev, agg_q_dev};
+    if ((rc = check_outcome(h, cfg, B, target_dev != nullptr, xref_dev != nullptr, O))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    if ((rc = check_traj_held(h, B))) return rc;
+    OutcomeArgs W{};
+    W.traj = (const float*)h->d_traj.p;
+    if (cfg->target_mode == 1) {
+        W.tgt = (const float*)target_dev;
+        W.tgt_tstride = cfg->tgt_steps > 1 ? SDEMPC_NX : 0;
+        W.tgt_bstride = cfg->tgt_batch > 1 ? cfg->tgt_steps * SDEMPC_NX : 0;
+    } else {
+        W.tgt = (const float*)xref_dev;
+        W.tgt_tstride = SDEMPC_NX;
+        W.tgt_bstride = (h->H + 1) * SDEMPC_NX;
+    }
+    W.words = (uint32_t*)words_dev; W.fail_step = (uint32_t*)fail_step_dev; W.first_fail = (uint32_t*)first_fail_dev; W.cause_ever = (uint32_t*)cause_ever_dev;
+    W.chan_stat = (float*)chan_stat_dev; W.chan_q = (float*)chan_q_dev; W.agg_stat = (float*)agg_stat_dev; W.agg_q = (float*)agg_q_dev;
+    W.r2_pos = cfg->r2_pos; W.cos_min = cfg->cos_min; W.w2_max = cfg->w2_max;
+    W.invP = h->base.invP;
+    W.H = h->H;
+    if (chan_q_dev || agg_q_dev) {
+        W.n_ranks = cfg->n_ranks;
+        for (int k = 0; k < cfg->n_ranks; ++k) W.ranks[k] = cfg->ranks[k];
+    }
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    HIPCHK(h, launch_outcome(W, B, h->P, h->G, st));
+    return SDEMPC_OK;
+    });
+}
+
+namespace {
+// the staged inputs (d_x0, d_u, d_xref, d_noise on the handle's stream) -> the target rows staged, one store_traj rollout, the reducer, the outputs asked for
+// back on the host
+int outcome_staged(sdempc_handle* h, const sdempc_outcome_cfg* cfg, int32_t B, const float* target, float* cost, const OutcomeOut& O) {
+    int rc;
+    size_t off[OUTCOME_REGIONS + 1], per[OUTCOME_REGIONS];
+    outcome_regions(h, off, per);
+    if (!h->d_outcome.p && (rc = dev_alloc(h, h->d_outcome, off[OUTCOME_REGIONS], true))) return rc;
+    char* d = (char*)h->d_outcome.p;
+    void* d_target = nullptr;
+    if (cfg->target_mode == 1) {
+        d_target = d + off[0];
+        HIPCHK(h, hipMemcpyAsync(d_target, target, sizeof(float) * (size_t)cfg->tgt_batch * cfg->tgt_steps * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
+    }
+    if ((rc = sdempc_rollout_batch_dev(h, B, h->d_x0.p, h->d_u.p, h->d_xref.p, h->d_noise.p, h->d_cost.p, nullptr, 1, h->stream))) return rc;
+    void* host[8] = {O.words, O.fail_step, O.first_fail, O.cause_ever, O.chan_stat, O.chan_q, O.agg_stat, O.agg_q};
+    void* dev[8];
+    for (int k = 0; k < 8; ++k) dev[k] = host[k] ? d + off[1 + k] : nullptr;
+    per[1 + 5] = sizeof(float) * (size_t)h->H * 4 * (size_t)(O.chan_q ? cfg->n_ranks : 0);      // chan_q is [B][H][4][n_ranks]
+    per[1 + 7] = sizeof(float) * 4 * (size_t)(O.agg_q ? cfg->n_ranks : 0);                      // agg_q is [B][4][n_ranks]
+    if ((rc = sdempc_outcome_batch_dev(h, cfg, B, d_target, h->d_xref.p, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], h->stream))) return rc;
+    if (cost) HIPCHK(h, hipMemcpyAsync(cost, h->d_cost.p, sizeof(float) * B, hipMemcpyDeviceToHost, h->stream));
+    for (int k = 0; k < 8; ++k)
+        if (host[k]) HIPCHK(h, hipMemcpyAsync(host[k], dev[k], per[1 + k] * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return SDEMPC_OK;
+}
+}  // namespace
+
+int sdempc_outcome_batch(sdempc_handle* h, const sdempc_outcome_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const float* noise,
+                         const float* target, float* cost, uint32_t* words, uint32_t* fail_step, uint32_t* first_fail, uint32_t* cause_ever, float* chan_stat,
+                         float* chan_q, float* agg_stat, float* agg_q) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if (!x0 || !u || !xref || !noise) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    const OutcomeOut O{words, fail_step, first_fail, cause_ever, chan_stat, chan_q, agg_stat, agg_q};
+    if ((rc = check_outcome(h, cfg, B, target != nullptr, true, O))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    if ((rc = stage_common(h, B, x0, u, xref, noise))) return rc;
+    return outcome_staged(h, cfg, B, target, cost, O);
+    });
+}
+
+int sdempc_outcome_batch_keys(sdempc_handle* h, const sdempc_outcome_cfg* cfg, int32_t B, const float* x0, const float* u, const float* xref, const uint32_t* keys,
+                              const float* target, float* cost, uint32_t* words, uint32_t* fail_step, uint32_t* first_fail, uint32_t* cause_ever,
+                              float* chan_stat, float* chan_q, float* agg_stat, float* agg_q) {
+    return guarded(h, [&]() -> int {
+    int rc = check_batch(h, B);
+    if (rc) return rc;
+    if (!x0 || !u || !xref || !keys) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    const OutcomeOut O{words, fail_step, first_fail, cause_ever, chan_stat, chan_q, agg_stat, agg_q};
+    if ((rc = check_outcome(h, cfg, B, target != nullptr, true, O))) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    const int H = h->H, m = h->m;
+    HIPCHK(h, hipMemcpyAsync(h->d_x0.p, x0, sizeof(float) * B * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_u.p, u, sizeof(float) * B * H * m, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_xref.p, xref, sizeof(float) * B * (H + 1) * SDEMPC_NX, hipMemcpyHostToDevice, h->stream));
+    if ((rc = noise_from_keys(h, B, keys, (float*)h->d_noise.p, h->stream))) return rc;
+    return outcome_staged(h, cfg, B, target, cost, O);
     });
 }
 

@@ -382,5 +382,32 @@ struct BandArgs {
     int ranks[BAND_MAX_RANKS];  // each in [0, P); neither sorted nor distinct (wave-uniform kernel arguments, read at constant indices)
 };
 hipError_t launch_bands(const BandArgs& N, int B, int P, int G, int H, hipStream_t st);
+// SPEC.md §12c, predicted outcome: the noise kernel in its OUTCOME form (sdempc_outcome.inc.h), one workgroup per instance. Every particle of the same tensor is
+// scored as §11h scores an episode — rows x_1 .. x_H against the target rows, the channels dp, dv, c, w2, the cause bits — and the words and channels are reduced
+// over the valid particles. Every output is optional. traj null means absent: every noise, tube, risk and bands launch passes that, and the kernel then makes no
+// memory access it did not make before.
+constexpr int OUTCOME_MAX_RANKS = 8;
+constexpr int OUTCOME_WORDS = 11;        // words 0 .. 10 of the §11h table
+constexpr int OUTCOME_RANK_MAX_P = 128;  // the selection is the in-register sort over four groups: the order statistics (chan_q, agg_q) are refused above this
+// 4-byte words of workgroup memory of the outcome form: fail[5 H] hist[H+1] cause[4] gs[G][12] val[G*32][4] (sdempc_outcome.inc.h); capped by RISK_MAX_LDS
+inline size_t outcome_lds_words_host(int H, int G) { return (size_t)(6 * H + 5) + (size_t)G * 140; }
+struct OutcomeArgs {
+    const float* traj;          // [B][G][C][32], C = (H+1)*13 (KArgs::traj); null: not the outcome mode
+    const float* tgt;           // target rows: row t of instance b is tgt + b * tgt_bstride + t * tgt_tstride (13 floats; 6 are read)
+    uint32_t* words;            // [B][P][11] or null
+    uint32_t* fail_step;        // [B][H][5] or null
+    uint32_t* first_fail;       // [B][H+1] or null
+    uint32_t* cause_ever;       // [B][4] or null
+    float* chan_stat;           // [B][H][4][3] or null
+    float* chan_q;              // [B][H][4][n_ranks] or null
+    float* agg_stat;            // [B][4][3] or null
+    float* agg_q;               // [B][4][n_ranks] or null
+    float r2_pos, cos_min, w2_max, invP;
+    int tgt_bstride, tgt_tstride;   // floats; 0 on a size-1 axis
+    int H;
+    int n_ranks;                // 1 .. OUTCOME_MAX_RANKS where chan_q or agg_q is given
+    int ranks[OUTCOME_MAX_RANKS];   // each in [0, P); neither sorted nor distinct
+};
+hipError_t launch_outcome(const OutcomeArgs& W, int B, int P, int G, hipStream_t st);
 
 }  // namespace sdempc

@@ -120,6 +120,7 @@ DI float bits_to_normal(uint32_t bits) {
 #include "sdempc_tube.inc.h"
 #include "sdempc_risk.inc.h"
 #include "sdempc_band.inc.h"
+#include "sdempc_outcome.inc.h"
 namespace sdempc {
 
 // grid: x = chunks of 256 threads over [pg][r][lane] (pg < ceil(ceil(P/2)/32), r < H*6), y = instance
@@ -130,15 +131,20 @@ namespace sdempc {
 // registers stay below 96 (the risk form's later-phase arguments are spilled to lanes of a vector register outside its loops), scratch stays 0.
 // SPEC.md §12b (Q.traj given; keys, out, HC, T and R are then not read): the BANDS form — the tube's grid, x = tiles of 32 columns, y = instance (sdempc_band.inc.h).
 // Q.traj null (every noise, tube and risk launch): not one access more.
+// SPEC.md §12c (W.traj given; keys, out, HC, T, R and Q are then not read): the OUTCOME form — x = 1, y = instance, dynamic LDS of outcome_lds_words_host words
+// (sdempc_outcome.inc.h). W.traj null (every noise, tube, risk and bands launch): not one access more.
 __global__ void __launch_bounds__(256, 8) sdempc_noise_kernel(const uint32_t* __restrict__ keys, float* __restrict__ out, int P, int G, int HC, int b0, TubeArgs T,
-                                                           RiskArgs R, BandArgs Q) {
+                                                           RiskArgs R, BandArgs Q, OutcomeArgs W) {
     const int b = b0 + blockIdx.y;
     // (wave-uniform; ONE test of all mode pointers, so that the noise form waits for one batch of scalar loads and takes one branch, as it did with one mode —
     // its workgroups are short, and a second dependent load in front of `keys` showed in its time)
-    if (__builtin_expect((reinterpret_cast<uintptr_t>(T.traj) | reinterpret_cast<uintptr_t>(R.traj) | reinterpret_cast<uintptr_t>(Q.traj)) != 0, 0)) {
+    if (__builtin_expect((reinterpret_cast<uintptr_t>(T.traj) | reinterpret_cast<uintptr_t>(R.traj) | reinterpret_cast<uintptr_t>(Q.traj) |
+                          reinterpret_cast<uintptr_t>(W.traj)) != 0, 0)) {
+        // (the outcome form LAST, and read in place, not from W: in front of the others it cost the bands form a second register of spilled scalars — profiles/outcome_resources.txt)
         if (Q.traj) band_reduce(Q, P, G, b);
         else if (R.traj) risk_reduce(R, P, G, b);
-        else tube_reduce(T, P, G, b);
+        else if (T.traj) tube_reduce(T, P, G, b);
+        else outcome_reduce(P, G, b);
         return;
     }
     const uint32_t k0 = keys[2 * b], k1 = keys[2 * b + 1];
@@ -168,7 +174,7 @@ hipError_t launch_noise_from_keys(const uint32_t* keys_dev, float* out, int B, i
     const unsigned gx = (unsigned)((threads + 255) / 256);
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(keys_dev, out, P, G, HC, b0, TubeArgs{}, RiskArgs{}, BandArgs{});
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(keys_dev, out, P, G, HC, b0, TubeArgs{}, RiskArgs{}, BandArgs{}, OutcomeArgs{});
     }
     return hipGetLastError();
 }
@@ -180,7 +186,7 @@ hipError_t launch_tube(const TubeArgs& T, int B, int P, int G, int H, hipStream_
     const unsigned gx = (unsigned)((T.C + 31) / 32);
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, T, RiskArgs{}, BandArgs{});
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, T, RiskArgs{}, BandArgs{}, OutcomeArgs{});
     }
     return hipGetLastError();
 }
@@ -200,7 +206,7 @@ hipError_t launch_risk(const RiskArgs& R, int B, int P, int G, hipStream_t st) {
     if (lds > RISK_MAX_LDS) return hipErrorInvalidValue;
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(1, nb), 256, lds, st>>>(nullptr, nullptr, P, G, 0, b0, TubeArgs{}, R, BandArgs{});
+        sdempc_noise_kernel<<<dim3(1, nb), 256, lds, st>>>(nullptr, nullptr, P, G, 0, b0, TubeArgs{}, R, BandArgs{}, OutcomeArgs{});
     }
     return hipGetLastError();
 }
@@ -216,7 +222,27 @@ hipError_t launch_bands(const BandArgs& N, int B, int P, int G, int H, hipStream
     const unsigned gx = (unsigned)((N.C + 31) / 32);
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
-        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, TubeArgs{}, RiskArgs{}, N);
+        sdempc_noise_kernel<<<dim3(gx, nb), 256, 0, st>>>(nullptr, nullptr, P, G, 0, b0, TubeArgs{}, RiskArgs{}, N, OutcomeArgs{});
+    }
+    return hipGetLastError();
+}
+
+// SPEC.md §12c: one workgroup per instance; every word of every output given is written
+hipError_t launch_outcome(const OutcomeArgs& W, int B, int P, int G, hipStream_t st) {
+    if (B < 1 || P < 1 || W.H < 1 || G != (P + 31) / 32 || !W.traj || !W.tgt) return hipErrorInvalidValue;
+    if (!W.words && !W.fail_step && !W.first_fail && !W.cause_ever && !W.chan_stat && !W.chan_q && !W.agg_stat && !W.agg_q) return hipErrorInvalidValue;
+    if (W.r2_pos != W.r2_pos || W.cos_min != W.cos_min || W.w2_max != W.w2_max) return hipErrorInvalidValue;
+    if ((W.tgt_tstride != 0 && W.tgt_tstride != 13) || (W.tgt_bstride != 0 && W.tgt_bstride != 13 && W.tgt_bstride != (W.H + 1) * 13)) return hipErrorInvalidValue;
+    const bool want_q = W.chan_q || W.agg_q;
+    if (want_q ? (W.n_ranks < 1 || W.n_ranks > OUTCOME_MAX_RANKS) : W.n_ranks != 0) return hipErrorInvalidValue;
+    for (int k = 0; k < W.n_ranks; ++k)
+        if (W.ranks[k] < 0 || W.ranks[k] >= P) return hipErrorInvalidValue;
+    if (want_q && P > OUTCOME_RANK_MAX_P) return hipErrorInvalidValue;
+    const size_t lds = sizeof(uint32_t) * outcome_lds_words_host(W.H, G);
+    if (lds > RISK_MAX_LDS) return hipErrorInvalidValue;
+    for (int b0 = 0; b0 < B; b0 += 65535) {
+        const int nb = B - b0 < 65535 ? B - b0 : 65535;
+        sdempc_noise_kernel<<<dim3(1, nb), 256, lds, st>>>(nullptr, nullptr, P, G, 0, b0, TubeArgs{}, RiskArgs{}, BandArgs{}, W);
     }
     return hipGetLastError();
 }

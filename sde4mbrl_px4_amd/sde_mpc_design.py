@@ -192,6 +192,23 @@ class MpcProblem:
         r = self.solver().bands_keys(xs[None], u, xref, sub[None], quantiles=quantiles, ranks=ranks, observed=observed)
         return Bands.of(r.P, r.ranks, r.quantiles, None if r.observed is None else r.observed[0], *(None if a is None else a[0] for a in r))
 
+    def m_outcome(self, x, rng, uopt, curr_t=0.0, xdes=None, score=None, target=None, ranks=None, quantiles=(0.5, 0.95), want_particles=False):
+        """Predicted outcome (SPEC.md §12c) of the plan `uopt` on the noise m_mpc(x, rng, ...) solved on: the key rule of m_tube (SPEC.md §7.3), the same
+        reference window, one rollout, every particle scored on the device with the criteria of `score` (a solver.Score, the one a simulate(score=...) campaign
+        uses). Returns a solver.Outcome without the batch axis. target: None (the reference window) or rows [H+1][13] / [13] IN THE SOLVER'S FRAME, as m_risk's
+        centre rows are. rng is not consumed: pass the key that went INTO m_mpc."""
+        from .solver import Outcome
+        x = np.asarray(x, np.float32).reshape(13)
+        xs = enu2ned(x, np) if self.convert_to_enu else x
+        xdes = xs if xdes is None else np.asarray(xdes, np.float32).reshape(13)
+        _, sub = _next_key(rng)
+        xref = self.xref(float(curr_t), xdes)[None]
+        u = np.asarray(uopt, np.float32).reshape(1, self.cfg.horizon, self.cfg.num_motors)
+        if target is not None:
+            target = np.asarray(target, np.float32).reshape(1, -1, 13)
+        r = self.solver().outcome_keys(xs[None], u, xref, sub[None], score=score, target=target, ranks=ranks, quantiles=quantiles, want_particles=want_particles)
+        return Outcome.of(r.P, r.ranks, r.quantiles, *(None if a is None else a[0] for a in r))
+
 
     def simulate(self, x, rng, T, curr_t=0.0, xdes=None, opt_state: Optional[OptState] = None, plant=None, plant_substeps=1, plant_dt=None,
                  plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,

@@ -561,6 +561,83 @@ def calibration(bands, bins=10, levels=(0.5, 0.9)):
     return {"hist": hist, "n": n, "coverage": cov, "levels": tuple(float(v) for v in levels), "bins": int(bins)}
 
 
+class _OutcomeFields(NamedTuple):
+    cost: np.ndarray
+    words: object
+    fail_step: np.ndarray
+    first_fail: np.ndarray
+    cause_ever: np.ndarray
+    chan_stat: np.ndarray
+    chan_q: object
+    agg_stat: np.ndarray
+    agg_q: object
+
+
+OUTCOME_CHANNELS = ("dp", "dv", "c", "w2")                # chan_stat / chan_q: squared position error, squared velocity error, tilt cosine, squared body rate
+OUTCOME_AGGREGATES = ("sum_dp", "max_dp", "min_c", "max_w2")      # agg_stat / agg_q: score words 1, 2, 6, 7 of each particle
+
+
+class Outcome(_OutcomeFields):
+    """Predicted outcome of a rollout (SPEC.md §12c): every particle scored as closed_loop(score=...) scores an episode (§11h), a named tuple (cost, words,
+    fail_step, first_fail, cause_ever, chan_stat, chan_q, agg_stat, agg_q). cost f32[B] is the rollout's expected cost. words uint32[B][P][11] (words 0 .. 10
+    of the score table per particle) is None unless asked for (want_particles). fail_step uint32[B][H][5]: particles failing at row r = t - 1 by cause
+    (radius, tilt, rate, non-finite) and by any; first_fail uint32[B][H+1]: histogram of the first failing row, slot H: never; cause_ever uint32[B][4].
+    chan_stat f32[B][H][4][3]: mean, min, max per row of the channels OUTCOME_CHANNELS; agg_stat f32[B][4][3] the same over OUTCOME_AGGREGATES. chan_q
+    f32[B][H][4][K], agg_q f32[B][4][K]: the order statistics at `ranks` (None when none were asked for). The particle count, the ranks and the quantiles
+    they came from ride along as attributes (Outcome.of sets them)."""
+    P = None
+    ranks = None
+    quantiles = None
+
+    @classmethod
+    def of(cls, P, ranks, quantiles, *fields):
+        r = cls(*fields)
+        r.P, r.ranks, r.quantiles = int(P), None if ranks is None else tuple(ranks), None if quantiles is None else tuple(quantiles)
+        return r
+
+    def _replace(self, **kw):
+        r = super()._replace(**kw)
+        r.P, r.ranks, r.quantiles = self.P, self.ranks, self.quantiles
+        return r
+
+    def _need(self, what, field="first_fail"):
+        if self.P is None:
+            raise ValueError(f"Outcome.{what}: this Outcome carries no particle count (build it with Outcome.of(P, ...))")
+        if getattr(self, field) is None:
+            raise ValueError(f"Outcome.{what}: {field} was not computed")
+
+    @property
+    def p_fail(self):
+        """1 - first_fail[..., H] / P: the predicted probability that the score's criteria fail somewhere within the horizon"""
+        self._need("p_fail")
+        return 1.0 - self.first_fail[..., -1] / self.P
+
+    @property
+    def survival(self):
+        """[..., H]: the fraction of particles that have not failed up to and including row r (state x_{r+1})"""
+        self._need("survival")
+        return 1.0 - np.cumsum(self.first_fail[..., :-1], axis=-1) / self.P
+
+    @property
+    def p_cause(self):
+        """[..., 4]: the fraction of particles that ever fail by radius, tilt, rate, non-finite (SCORE_CAUSES); they overlap"""
+        self._need("p_cause", "cause_ever")
+        return self.cause_ever / self.P
+
+    def pos_err(self, k):
+        """[..., H]: sqrt of order statistic k of dp per row — the position error [m] at rank ranks[k] (sqrt is increasing: the rank carries over)"""
+        self._need("pos_err", "chan_q")
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(self.chan_q[..., 0, k].astype(np.float64))
+
+    def tilt_deg(self, k):
+        """[..., H]: the tilt [deg] of order statistic k of the tilt cosine c per row. arccos is DEcreasing: rank ranks[k] of c is rank P - 1 - ranks[k] of the
+        tilt, so the 95 % tilt comes from the 5 % quantile of c."""
+        self._need("tilt_deg", "chan_q")
+        with np.errstate(invalid="ignore"):
+            return np.degrees(np.arccos(np.clip(self.chan_q[..., 2, k].astype(np.float64), -1.0, 1.0)))
+
+
 def tail_count(tail, P):
     """SPEC.md §12a: a fraction alpha -> max(1, ceil(alpha P)); an integer is the count itself"""
     import math
@@ -869,6 +946,92 @@ class SdeMpcSolver:
         solve_dev or a smaller rollout, as tube_dev is."""
         cfg, _, _ = self._bands_cfg(quantiles, ranks)
         self._check(_abi.bands_entries(self.lib)[2](self._h, C.byref(cfg) if cfg is not None else None, B, observed, q, below, at, C.c_void_p(stream)))
+
+    # ---- predicted outcome (SPEC.md §12c): the score's failure criteria over the particles, reduced on the device ----
+    def _outcome_cfg(self, score, target, ranks, quantiles, B):
+        """-> (cfg, target rows or None, ranks or None, quantiles or None). score: a Score (its substeps flag plays no part: a rollout has none); target: None
+        (the call's xref) or rows [Bt][Ht][13] / [Ht][13] / [13] with Ht in {1, H+1}, Bt in {1, B}; ranks given: used as they are and quantiles is ignored."""
+        score = Score() if score is None else score
+        cfg = _abi.SdempcOutcomeCfg()
+        cfg.struct_size = C.sizeof(_abi.SdempcOutcomeCfg)
+        cfg.r2_pos, cfg.cos_min, cfg.w2_max = (float(t) for t in score.thresholds())
+        rows = None
+        if target is not None:
+            rows = np.asarray(target, np.float32)
+            if rows.ndim == 1:
+                rows = rows[None, None]
+            elif rows.ndim == 2:
+                rows = rows[None]
+            if rows.ndim != 3 or rows.shape[2] != 13:
+                raise ValueError("target: rows [Bt][Ht][13], [Ht][13] or [13]")
+            rows = np.ascontiguousarray(rows)
+            cfg.target_mode, cfg.tgt_batch, cfg.tgt_steps = 1, rows.shape[0], rows.shape[1]
+        if ranks is None and quantiles is not None:
+            quantiles = tuple(float(q) for q in quantiles)
+            ranks = quantile_ranks(quantiles, self.P)
+        elif ranks is not None:
+            quantiles, ranks = None, [int(r) for r in ranks]
+        if ranks is not None:
+            if not 1 <= len(ranks) <= _abi.OUTCOME_MAX_RANKS:
+                raise ValueError(f"quantiles / ranks: 1 to {_abi.OUTCOME_MAX_RANKS} values")
+            cfg.n_ranks = len(ranks)
+            for k, r in enumerate(ranks):
+                cfg.ranks[k] = r
+        return cfg, rows, ranks, quantiles
+
+    def _outcome_call(self, fn, x0, u, xref, draw, score, target, ranks, quantiles, want_particles):
+        B = x0.shape[0]
+        H, P = self.H, self.P
+        x0, u, xref = _f32(x0, (B, 13)), _f32(u, (B, H, self.m)), _f32(xref, (B, H + 1, 13))
+        cfg, rows, ranks, quantiles = self._outcome_cfg(score, target, ranks, quantiles, B)
+        K = cfg.n_ranks
+        u32p = C.POINTER(C.c_uint32)
+        cost = np.zeros(B, np.float32)
+        words = np.zeros((B, P, _abi.OUTCOME_WORDS), np.uint32) if want_particles else None
+        fail_step = np.zeros((B, H, 5), np.uint32)
+        first_fail = np.zeros((B, H + 1), np.uint32)
+        cause_ever = np.zeros((B, 4), np.uint32)
+        chan_stat = np.zeros((B, H, 4, 3), np.float32)
+        chan_q = np.zeros((B, H, 4, K), np.float32) if K else None
+        agg_stat = np.zeros((B, 4, 3), np.float32)
+        agg_q = np.zeros((B, 4, K), np.float32) if K else None
+        f = lambda a: _fp(a) if a is not None else None
+        w = lambda a: a.ctypes.data_as(u32p) if a is not None else None
+        self._check(fn(self._h, C.byref(cfg), B, _fp(x0), _fp(u), _fp(xref), draw, f(rows), _fp(cost), w(words), w(fail_step), w(first_fail), w(cause_ever),
+                       _fp(chan_stat), f(chan_q), _fp(agg_stat), f(agg_q)))
+        return Outcome.of(P, ranks, quantiles, cost, words, fail_step, first_fail, cause_ever, chan_stat, chan_q, agg_stat, agg_q)
+
+    def outcome(self, x0, u, xref, noise, score=None, target=None, ranks=None, quantiles=(0.5, 0.95), want_particles=False) -> Outcome:
+        """One rollout of u per instance with every particle of its particle x horizon tensor scored on the device as closed_loop(score=...) scores an episode
+        (SPEC.md §12c): Outcome(cost, words, fail_step, first_fail, cause_ever, chan_stat, chan_q, agg_stat, agg_q). score: a Score — the SAME object a
+        campaign is scored with, so predicted and flown failure rates share one definition (default Score(): every criterion off, only non-finite states
+        fail). target: None scores row t against row t of xref; rows [Bt][Ht][13], [Ht][13] or [13] (Ht in {1, H+1}, Bt in {1, B}) against those. quantiles:
+        up to 8 values in [0, 1] (rank ceil(q P) - 1, quantile_ranks) or ranks: the 0-based ranks themselves; both None: no order statistics (they are
+        refused above P = 128). want_particles: also the per-particle score words."""
+        x0 = _f32(x0)
+        noise = _f32(noise, (x0.shape[0], self.P, self.H, 6))
+        return self._outcome_call(_abi.outcome_entries(self.lib)[0], x0, u, xref, _fp(noise), score, target, ranks, quantiles, want_particles)
+
+    def outcome_keys(self, x0, u, xref, keys, score=None, target=None, ranks=None, quantiles=(0.5, 0.95), want_particles=False) -> Outcome:
+        """outcome() with the noise of instance b drawn on the device as normal(keys[b], (P, H, 6)), as solve_keys draws it."""
+        x0 = _f32(x0)
+        keys = self._keys(keys, x0.shape[0])
+        return self._outcome_call(_abi.outcome_entries(self.lib)[1], x0, u, xref, keys.ctypes.data_as(C.POINTER(C.c_uint32)), score, target, ranks, quantiles,
+                                  want_particles)
+
+    def outcome_dev(self, B, score=None, target=None, tgt_steps=None, tgt_batch=None, xref=None, ranks=None, quantiles=None, words=None, fail_step=None,
+                    first_fail=None, cause_ever=None, chan_stat=None, chan_q=None, agg_stat=None, agg_q=None, stream=0):
+        """Device pointers (each may be None): reduces the tensor the last rollout_dev(store_traj=True) of at least B instances left in the handle. target: None
+        (then xref, a pointer to f32[B][H+1][13], gives the target rows) or a pointer to f32[tgt_batch][tgt_steps][13]. Outputs: words u32[B][P][11],
+        fail_step u32[B][H][5], first_fail u32[B][H+1], cause_ever u32[B][4], chan_stat f32[B][H][4][3], chan_q f32[B][H][4][K], agg_stat f32[B][4][3], agg_q
+        f32[B][4][K] (K = len(quantiles) or len(ranks)). Refused after a grad_dev, a solve_dev or a smaller rollout, as tube_dev is."""
+        cfg, _, _, _ = self._outcome_cfg(score, None, ranks, quantiles, B)
+        if target is not None:
+            cfg.target_mode = 1
+            cfg.tgt_steps = self.H + 1 if tgt_steps is None else int(tgt_steps)
+            cfg.tgt_batch = B if tgt_batch is None else int(tgt_batch)
+        self._check(_abi.outcome_entries(self.lib)[2](self._h, C.byref(cfg), B, target, xref, words, fail_step, first_fail, cause_ever, chan_stat, chan_q,
+                                                      agg_stat, agg_q, C.c_void_p(stream)))
 
     def closed_loop(self, x0, xref, keys, T, u_init=None, stepsize_in=None, plant=None, plant_of=None, plant_substeps=1, plant_dt=None,
                     plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, u_act_in=None, disturbance=None,
