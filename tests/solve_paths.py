@@ -17,6 +17,7 @@ import numpy as np
 if __name__ == "__main__":      # (run as a script to rewrite tests/SOLVE_PATHS.md: the package lies one directory up)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import kernel_census as kc
 import orc
 from cases import asymmetric_cfg, asymmetric_model, asymmetric_problem
 
@@ -225,10 +226,55 @@ CASES = {
 GUARD_CASES = ("guard_k0_p20", "guard_kgt0_p80", "guard_kgt0_maxls0_p20")
 
 
+# ---- twins for the duo kernels --------------------------------------------------------------------------------------------------------------
+# The duo layout needs two particle groups at least (P >= 33): two-wave teams up to four groups (TeamPairT<2>, TeamBlock2), the four-wave team
+# beyond (TeamBlock). The cases above with P = 20 or P = 1 get a twin at P = 40 (two groups, the second of eight particles) with the same settings
+# and seed; the four-wave team and the horizon at which the dispatcher drops the noise staging rows (MODE 4) get twins of six cases that together
+# reach the paths listed in DUO_REQUIRED. Found with the oracle's census, as the table above was; `declares` is what each twin is there for.
+def h_mode4(m=4):
+    """The shortest horizon at which launch_duo_m takes the two-wave team without staging rows: the dispatcher's arithmetic, tests/kernel_census.py."""
+    return kc.shortest_h(lambda H: not kc.pair_fits(H, m) and kc.duo_pick(H, m, 2) == 2)
+
+
+def _twin(name, declares=None, P=None, H=None, it=None):
+    c = CASES[name]
+    d = dict(c.cfg)
+    if P is not None:
+        d["num_particles"] = P
+    if H is not None:
+        d.update(horizon=H, num_short_dt=(H + 1) // 2)
+        if H > 20:
+            d.update(short_step_dt=0.01, long_step_dt=0.02)          # (a long horizon spans seconds, as the short ones do: kernel_census.Row.cfg_kw)
+    if it is not None:
+        if d["max_no_improvement_iter"] == d["max_iter"]:
+            d["max_no_improvement_iter"] = it
+        d["max_iter"] = it
+    return dataclasses.replace(c, cfg=d, declares=c.declares if declares is None else declares, spec_ng=(), fast_ng=())
+
+
+P40_TWINS = ("maxls2_p20", "maxls6_p20", "conservative_p20", "noimp2_p20", "band_p20", "mscale_p1", "tiny_step_p20", "max_iter_0_p20", "guard_k0_p20",
+             "guard_kgt0_maxls0_p20")          # (tri_p20, m = 3: the default build has no duo instantiation of the generic motor count)
+_SIX = {  # base case -> what its twin declares at (P = 130, H as the base) and at (P = 70, H = h_mode4(), max_iter = 6)
+    "mix_p80": (("momentum", "rejected_from_momentum", "rejected_from_plain", "ls_exhausted_rejected", "end_max_iter", "end_tolerance"),
+                ("momentum", "rejected_from_momentum", "end_max_iter")),
+    "restart_p80": (("restart", "momentum"), ("restart", "momentum")),
+    "maxls1_p80": (("maxls_1", "end_no_improvement", "rejected_from_plain"), ("maxls_1", "end_no_improvement", "ls_exhausted_rejected", "rejected_from_plain")),
+    "tiny_step_p20": (("end_tolerance", "ls_armijo_held_rejected"), ("end_tolerance", "rejected_from_plain")),
+    "guard_k0_p20": (("end_nonfinite_guard", "guard_at_k0"), ("end_nonfinite_guard", "guard_at_k0")),
+    "guard_kgt0_p80": (("end_nonfinite_guard", "guard_at_k_gt0"), ("end_nonfinite_guard", "guard_at_k_gt0")),
+}
+_stem = lambda n: n.rsplit("_p", 1)[0]
+DUO_CASES = {f"{_stem(n)}_p40": _twin(n, P=40) for n in P40_TWINS}
+DUO_CASES.update({f"{_stem(n)}_p130": _twin(n, d[0], P=130) for n, d in _SIX.items()})
+DUO_CASES.update({f"{_stem(n)}_h4": _twin(n, d[1], P=70, H=h_mode4(), it=6) for n, d in _SIX.items()})
+ALL_CASES = {**CASES, **DUO_CASES}
+DUO_GUARD_CASES = tuple(n for n in DUO_CASES if n.startswith("guard_"))
+
+
 @functools.lru_cache(maxsize=None)
 def problem(name):
     """(cfg, model, x0, xref, noise, u_init, stepsize_in) of the POOL instances of case `name`."""
-    c = CASES[name]
+    c = ALL_CASES[name]
     cfg, model = c.config(), asymmetric_model(c.m)
     x0, xref, noise, u = asymmetric_problem(cfg, POOL, c.seed)
     lo = np.asarray(cfg.input_bound, np.float32)[:, 0]
@@ -279,6 +325,32 @@ SEQUENTIAL = {
 }
 MATRIX_PIPE = (("mix_p80", "f16"), ("maxls3_p80", "f32x3"))          # one case each in the matrix-pipe contraction modes (tile kernels)
 
+# the sequential loop in the persistent duo kernels (sdempc_solve_kernel<Team, M, F16, false, MODE, USTG>), one entry per team shape:
+# name -> (handle options, Team, MODE, USTG, cases). Which shape a launch takes follows from the groups per instance, the horizon and the options
+# (launch_duo, launch_duo_small, launch_duo_m); tests/test_solve_paths_cpu.py checks every (entry, case) against the dispatcher's arithmetic in
+# tests/kernel_census.py, tests/test_gpu_solve_paths.py against the kernel name the launch reports.
+_SIX_OF = lambda tag: tuple(f"{_stem(n)}_{tag}" for n in _SIX)
+DUO = {
+    "pair": (dict(coop=0, pk=0, duo=1), "TeamPairT<2>", 3, False,
+             tuple(n for n, c in CASES.items() if 33 <= c.P <= 128 and c.m in (4, 6)) + tuple(f"{_stem(n)}_p40" for n in P40_TWINS)),
+    "block2_ustg": (dict(coop=0, pk=0, duo=1, ustg=1), "TeamBlock2", 3, True,
+                    ("mix_p80", "restart_p80", "maxls1_p80", "tiny_step_p40", "guard_k0_p40", "guard_kgt0_p80")),
+    "block2_mode4": (dict(coop=0, pk=0, duo=1), "TeamBlock2", 4, True, _SIX_OF("h4")),
+    "block_p130": (dict(coop=0, pk=0), "TeamBlock", 3, False, _SIX_OF("p130")),
+}
+# what each team shape other than the pair reaches at least (the pair's configurations reach every name of PATH_NAMES); a tuple: one of these
+DUO_REQUIRED = ("momentum", ("rejected_from_momentum", "rejected_from_momentum_stop_suppressed"), "rejected_from_plain", "restart", "ls_exhausted_rejected",
+                ("maxls_0", "maxls_1"), "end_tolerance", "end_no_improvement", "guard_at_k0", "guard_at_k_gt0")
+# one guard case and one case of mixed endings per matrix-pipe mode and in math_mode fast, in the pair: (case, mlp_dtype, math_mode)
+DUO_ARITH = tuple((n, mlp, math) for mlp, math in (("f16", "exact"), ("f32x3", "exact"), ("f32x3", "fast"), ("f16", "fast")) for n in ("guard_kgt0_p80", "mix_p100"))
+
+
+def duo_kernel(layout, name, mlp="f32"):
+    """The normalised name of the kernel that entry `layout` of DUO runs case `name` with."""
+    _, team, mode, ustg, _ = DUO[layout]
+    m = ALL_CASES[name].m
+    return f"sdempc_solve_kernel<{team}, {m if m in (4, 6) else 8}, {kc.F16_OF[mlp]}, false, {mode}, {'true' if ustg else 'false'}>"
+
 
 def configurations(cus=256):
     """[(case, kernel, ng or None, B, math_mode, mlp_dtype)] of tests/test_gpu_solve_paths.py on a device of `cus` compute units."""
@@ -289,6 +361,9 @@ def configurations(cus=256):
     for lay, (_, names) in SEQUENTIAL.items():
         out += [(name, lay, None, POOL, "exact", "f32") for name in names]
     out += [(name, "tile", None, POOL, "exact", mlp) for name, mlp in MATRIX_PIPE]
+    for lay, (_, _, _, _, names) in DUO.items():
+        out += [(name, lay, None, POOL, "exact", "f32") for name in names]
+    out += [(name, "pair", None, POOL, math, mlp) for name, mlp, math in DUO_ARITH]
     return out
 
 
@@ -323,7 +398,9 @@ def matrix_markdown(cus=256):
          "Generated by `tests/solve_paths.py` (`python tests/solve_paths.py` rewrites it; `tests/test_solve_paths_cpu.py` fails when it is stale).",
          f"Computed on the CPU from the oracle's event records, for a device of {cus} compute units. A configuration is one launch of",
          "`tests/test_gpu_solve_paths.py`: case, kernel (`spec`: the speculative state machine with `ng` groups per instance; `coop`, `tile`, `duo`,",
-         "`lane`: the sequential loop in that layout), batch, math mode and contraction mode.", "", "## Paths", ""]
+         "`lane`: the sequential loop in that layout; `pair`, `block2_ustg`, `block2_mode4`, `block_p130`: the sequential loop in the persistent duo",
+         "kernels, by team shape: `TeamPairT<2>`, `TeamBlock2` MODE 3 with the control table in global memory, `TeamBlock2` MODE 4, `TeamBlock` MODE 3),",
+         "batch, math mode and contraction mode.", "", "## Paths", ""]
     L += [f"{i + 1}. `{n}`" for i, n in enumerate(PATH_NAMES)]
     L += ["", "## Path x configuration", "", "| case | kernel | ng | B | math | mlp | paths reached (numbers above) |", "|---|---|---|---|---|---|---|"]
     for conf in configurations(cus):

@@ -6,6 +6,7 @@ import functools
 import numpy as np
 import pytest
 
+import kernel_census as kc
 import solve_paths as sp
 from cases import bits_differ
 from sde4mbrl_px4_amd.solver import SdeMpcSolver
@@ -105,6 +106,27 @@ def test_sequential_loop(layout, name):
     else:
         assert (f"TeamBlock, {mk}, 0, " if c.P > 32 else f"TeamWave, {mk}, 0, ") in kname and ", 2, false>" not in kname and ", false, 1," not in kname, kname
     assert wc == _expected_work(name, idx), (wc, _expected_work(name, idx))
+
+
+DUO = [(lay, n) for lay, e in sp.DUO.items() for n in e[4]]
+
+
+@pytest.mark.parametrize("layout,name", DUO, ids=[f"{lay}-{n}" for lay, n in DUO])
+def test_sequential_loop_in_the_duo_kernels(layout, name):
+    """solve_instance in the persistent duo kernels, one instantiation per team shape (two-wave teams in pairs; 128-thread workgroups with the
+    control table in global memory, and without staging rows at the horizon that selects MODE 4; the four-wave team), pinned by options and
+    checked by the reported kernel name; every output word against the oracle, the work counters against the census."""
+    kname, fb, wc, idx = _solve(name, sp.POOL, "exact", "f32", sp.DUO[layout][0])
+    assert fb == 0 and kc.normalise(kname) == (sp.duo_kernel(layout, name), "exact"), kname
+    assert wc == _expected_work(name, idx), (wc, _expected_work(name, idx))
+
+
+@pytest.mark.parametrize("name,mlp,math", sp.DUO_ARITH, ids=[f"{n}-{mlp}-{math}" for n, mlp, math in sp.DUO_ARITH])
+def test_sequential_loop_in_the_pair_kernel_matrix_pipe_modes_and_fast_math(name, mlp, math):
+    """A guard case and a case of mixed endings in TeamPairT<2> with the layer-2 contractions on the matrix pipe, and in math_mode fast."""
+    kname, fb, wc, idx = _solve(name, sp.POOL, math, mlp, sp.DUO["pair"][0])
+    assert fb == 0 and kc.normalise(kname) == (sp.duo_kernel("pair", name, mlp), "exact" if math == "exact" else "fast"), kname
+    assert wc == _expected_work(name, idx, math, mlp), (wc, _expected_work(name, idx, math, mlp))
 
 
 @pytest.mark.parametrize("name,mlp", sp.MATRIX_PIPE)

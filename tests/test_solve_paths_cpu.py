@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import kernel_census as kc
 import orc
 import solve_paths as sp
 from cases import bits_differ
@@ -105,6 +106,113 @@ def test_every_wrong_optimiser_changes_a_compared_bit(mutant):
     b = shown[0][1]
     un = orc.Oracle(cfg, model).solve(x0[b], xref[b], noise[b], u[b], float(s))[0]
     assert bits_differ(un, sp.reference(name)[b][0]) == 0
+
+
+# ---- the duo kernels: twins, team shapes, path coverage and the wrong optimisers on the duo case set alone ----------------------------------
+@pytest.mark.parametrize("name", list(sp.DUO_CASES))
+def test_duo_twin_reaches_the_paths_it_declares(name):
+    c = sp.DUO_CASES[name]
+    ref = sp.reference(name)
+    seen = sp.census([r[3] for r in ref])
+    assert c.declares and set(c.declares) <= set(sp.PATH_NAMES)
+    assert set(c.declares) <= seen, sorted(set(c.declares) - seen)
+    if name.endswith("_h4"):
+        assert c.cfg["horizon"] == sp.h_mode4(c.m) and c.cfg["max_iter"] <= 6
+    else:
+        assert c.cfg["horizon"] <= 12 and c.cfg["max_iter"] <= 12
+    assert 33 <= c.P <= 128 or c.P == 130
+    assert c.m in (4, 6) and not c.spec_ng and not c.fast_ng
+    if name not in sp.DUO_GUARD_CASES:
+        assert all(np.isfinite(a).all() for r in ref for a in r[:3]), name
+
+
+def test_existing_cases_are_untouched_by_the_twins():
+    assert not set(sp.CASES) & set(sp.DUO_CASES) and sp.ALL_CASES["mix_p80"] is sp.CASES["mix_p80"]
+    assert sp.SEQUENTIAL["duo"] == (dict(coop=0, pk=0, duo=1), ("mix_p80",)) and sp.SEQUENTIAL["tile"][1] == tuple(sp.CASES)
+    for n in sp.P40_TWINS:
+        base, twin = sp.CASES[n], sp.DUO_CASES[f"{sp._stem(n)}_p40"]
+        assert {k: v for k, v in twin.cfg.items() if k != "num_particles"} == {k: v for k, v in base.cfg.items() if k != "num_particles"}
+        assert (twin.seed, twin.s_in, twin.warm, twin.x0_scale, twin.declares, twin.m) == (base.seed, base.s_in, base.warm, base.x0_scale, base.declares, base.m)
+    # every case that can take the duo layout in the default build does, in the pair
+    pair = set(sp.DUO["pair"][4])
+    assert {n for n, c in sp.CASES.items() if c.P >= 33} <= pair and len(pair) == len(sp.DUO["pair"][4])
+    assert {n for n, c in sp.CASES.items() if c.P < 33} - {"tri_p20"} == set(sp.P40_TWINS) and sp.CASES["tri_p20"].m == 3
+
+
+def test_dispatcher_takes_each_duo_team_shape_for_its_cases():
+    """The dispatcher's own arithmetic (tests/kernel_census.py: pair_fits, duo_pick, shortest_h) at every (entry, case) of sp.DUO."""
+    assert set(sp.DUO) == {"pair", "block2_ustg", "block2_mode4", "block_p130"}
+    for lay, (opts, team, mode, ustg, names) in sp.DUO.items():
+        assert names
+        for n in names:
+            c = sp.ALL_CASES[n]
+            H, G = c.cfg["horizon"], (c.P + 31) // 32
+            assert opts["coop"] == 0 and (opts.get("duo") == 1 or G > 4)
+            if team == "TeamBlock":
+                assert G >= 5 and c.P == 130 and kc.duo_pick(H, c.m, 4, opts.get("ustg", -1)) == 0 and (mode, ustg) == (3, False)
+                continue
+            assert 2 <= G <= 4 and sp.POOL < 6 * 16          # (no six-team workgroups at this batch on any device)
+            if team == "TeamPairT<2>":
+                assert kc.pair_fits(H, c.m) and opts.get("ustg", -1) != 1 and (mode, ustg) == (3, False)
+            elif mode == 3:
+                assert opts["ustg"] == 1 and ustg and kc.duo_pick(H, c.m, 2, 1) == 1 and H <= 12
+            else:
+                assert ustg and H == kc.shortest_h(lambda h: not kc.pair_fits(h, c.m) and kc.duo_pick(h, c.m, 2) == 2)
+                assert not kc.pair_fits(H, c.m) and kc.duo_pick(H, c.m, 2, opts.get("ustg", -1)) == 2
+            assert sp.duo_kernel(lay, n) == f"sdempc_solve_kernel<{team}, {c.m}, 0, false, {mode}, {'true' if ustg else 'false'}>"
+    built = kc.built_kernels()
+    if built is not None:
+        want = {(sp.duo_kernel(lay, n), "exact") for lay, e in sp.DUO.items() for n in e[4]}
+        want |= {(sp.duo_kernel("pair", n, mlp), "exact" if math == "exact" else "fast") for n, mlp, math in sp.DUO_ARITH}
+        assert want <= built, sorted(want - built)
+
+
+def _duo_records(layouts, arith=False):
+    return [rec for conf in sp.configurations() if conf[1] in layouts and ((conf[4], conf[5]) == ("exact", "f32") or arith) for rec in sp.records_of(conf)]
+
+
+def test_pair_configurations_reach_every_path():
+    seen = sp.census(_duo_records(("pair",)))
+    assert seen == set(sp.PATH_NAMES), sorted(set(sp.PATH_NAMES) - seen)
+
+
+@pytest.mark.parametrize("layout", ["block2_ustg", "block2_mode4", "block_p130"])
+def test_each_other_duo_team_shape_reaches_the_required_paths(layout):
+    seen = sp.census(_duo_records((layout,)))
+    missing = [r for r in sp.DUO_REQUIRED if not ({r} if isinstance(r, str) else set(r)) & seen]
+    assert not missing, (layout, missing)
+    flat = {n for r in sp.DUO_REQUIRED for n in ((r,) if isinstance(r, str) else r)}
+    assert flat <= set(sp.PATH_NAMES) and len(sp.DUO_REQUIRED) == 10
+
+
+def test_duo_arithmetic_cases_are_a_guard_case_and_a_case_of_mixed_endings():
+    assert {(mlp, math) for _, mlp, math in sp.DUO_ARITH} == {("f16", "exact"), ("f32x3", "exact"), ("f32x3", "fast"), ("f16", "fast")}
+    for name, mlp, math in sp.DUO_ARITH:
+        assert name in sp.DUO["pair"][4]
+        causes = {int(r[3].col("cause")[-1]) for r in sp.reference(name, math, mlp)}
+        assert causes == {4} if name.startswith("guard_") else len(causes) >= 2, (name, mlp, math, causes)
+
+
+@pytest.mark.parametrize("mutant", orc.MUTANTS)
+def test_every_wrong_optimiser_changes_a_compared_bit_on_the_duo_case_set(mutant):
+    """As above, on the cases that the duo kernels run and on nothing else."""
+    names = list(dict.fromkeys(n for e in sp.DUO.values() for n in e[4]))
+    shown = None
+    for name in names:
+        cfg, model, x0, xref, noise, u, s = sp.problem(name)
+        O = orc.Oracle(cfg, model)
+        for b, (uo, xe, io, _) in enumerate(sp.reference(name)):
+            with orc.mutant(mutant):
+                um, xm, im, _ = O.solve(x0[b], xref[b], noise[b], u[b], float(s))
+            if bits_differ(um, uo) + bits_differ(xm, xe) + bits_differ(im, io):
+                shown = (name, b)
+                break
+        if shown:
+            break
+    assert shown, f"{mutant} changes no compared bit on any duo case"
+    name, b = shown
+    cfg, model, x0, xref, noise, u, s = sp.problem(name)
+    assert bits_differ(orc.Oracle(cfg, model).solve(x0[b], xref[b], noise[b], u[b], float(s))[0], sp.reference(name)[b][0]) == 0          # the hook is off again
 
 
 def test_committed_matrix_is_current():
