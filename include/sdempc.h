@@ -909,6 +909,79 @@ int sdempc_closed_loop_batch_tracked(sdempc_handle* h, const sdempc_track_cfg* t
  * of this section. `track` is required and checked as above (score_targets is not read). */
 int sdempc_reference_windows(sdempc_handle* h, const sdempc_track_cfg* track, int32_t B, int32_t n, const int32_t* ticks /*[n]*/, float* out /*[n][B][H+1][13]*/);
 
+/* ---- batched closed loop with motor faults and estimator dropouts drawn on the device (SPEC.md §11k) -------------------
+ * sdempc_closed_loop_batch_tracked plus two optional finite Markov chains per episode, stepped on the device from key chains of their own, so that WHEN a motor fails
+ * and WHEN the position source drops out are keys and O(B) thresholds instead of a [T][B][m][2] fault array and an [Ns][B] flag array. With both cfgs NULL the call IS
+ * sdempc_closed_loop_batch_tracked bit for bit, with the same launches; the six new outputs must then be NULL.
+ * A chain has K modes besides state 0 (1 <= K <= 4) and per episode b a key chain c_b; per lane a state s in 0 .. K, cumulative nondecreasing thresholds
+ * onset u32[K] and thresholds clear u32[K]. One step, in integers alone:
+ *   (c, e) = split(c)                  the first half continues the chain, the second is the draw key
+ *   w      = random_bits(e, lanes)     SPEC.md §7.1; an odd count's last block has a zero second counter
+ *   s == 0: s' = j + 1 for the smallest j < K with w_l < onset[l][j], else 0
+ *   s  > 0: s' = 0 if w_l < clear[l][s-1], else s
+ * One transition per step: a lane that fails in a step is not tested for clearing in that step. A threshold of 0 never fires (clear = 0: a permanent failure; onset
+ * all zero: never fails); 0xFFFFFFFF fires on all but one word in 2^32, so "always" is not expressible. The state AFTER the step of tick k (solve j) is the state
+ * DURING it: a lane can be failed at tick 0 from state 0.
+ * fault_proc: lanes = m, one step per control tick k = 0 .. T-1, ticks inside a solve period included. The row (k, b, l) the plant reads (as a row of
+ * sdempc_fault_cfg::fault) is, in state 0, the scheduled row if fault_cfg gives a schedule as well, else (1, 0); in state s' > 0 it is modes[l][s'-1] = (kappa, beta).
+ * No arithmetic is done on the rows. It makes the run a faulted one. The state is two int32 per motor, (s, first): first = tick0 + k of the first step that left
+ * state 0, or -1. drop_proc: one lane, K = 1, one step per solve j, valid or not, before the measurement is formed; the solve's valid flag is (s' == 0), ANDed with
+ * the scheduled flag if sdempc_obs_cfg::valid is given as well. The state is (s, n_dropped), n_dropped the solves with s' = 1. It makes the run an observed one: it
+ * needs an obs cfg, whose pointers may all be NULL, and obs_keys, whose chain it does not touch. Neither chain touches any other chain of the run.
+ * fault_rows / valid_rows are per-row outputs (the rows as the plant / the measurement read them): NULL means neither copied back nor scattered. The *_next outputs
+ * continue a chain bit for bit when carried back in as keys / state_in: the fault chain for any T (pass tick0 + T as the next tick0), the dropout chain when T is a
+ * multiple of solve_period. Checked before the first HIP call and before everything else, in this order: SDEMPC_EINVAL for a new output without its cfg; then for
+ * fault_proc a wrong struct_size, n_modes outside 1 .. 4, batch not 1 or B, a NULL onset, clear, modes or keys, an onset row that decreases, a non-finite mode entry,
+ * a state_in with s outside 0 .. n_modes or first < -1, tick0 < 0 or tick0 + T >= 2^24; then for drop_proc a wrong struct_size, batch not 1 or B, a NULL drop, recover
+ * or keys, a state_in with s outside 0 .. 1 or n_dropped < 0; then drop_proc without obs_keys; then everything sdempc_closed_loop_batch_tracked refuses. No ABI version
+ * change: detect the entry point by its symbol. */
+typedef struct sdempc_fault_process_cfg {
+    int32_t struct_size;      /* sizeof(sdempc_fault_process_cfg) */
+    int32_t n_modes;          /* K, 1 .. 4 */
+    int32_t batch;            /* rows of onset / clear / modes: 1 or B */
+    const uint32_t* onset;    /* [batch][m][K] cumulative, nondecreasing along K */
+    const uint32_t* clear;    /* [batch][m][K] */
+    const float* modes;       /* [batch][m][K][2] (kappa, beta), finite */
+    const uint32_t* keys;     /* [B][2] the fault chain */
+    const int32_t* state_in;  /* [B][m][2] (s, first) or NULL: (0, -1) */
+    int32_t tick0;            /* global tick of the call's first tick, >= 0 */
+} sdempc_fault_process_cfg;
+typedef struct sdempc_dropout_process_cfg {
+    int32_t struct_size;      /* sizeof(sdempc_dropout_process_cfg) */
+    int32_t batch;            /* rows of drop / recover: 1 or B */
+    const uint32_t* drop;     /* [batch] threshold of dropping out */
+    const uint32_t* recover;  /* [batch] threshold of recovering */
+    const uint32_t* keys;     /* [B][2] the dropout chain */
+    const int32_t* state_in;  /* [B][2] (s, n_dropped) or NULL: (0, 0) */
+} sdempc_dropout_process_cfg;
+int sdempc_closed_loop_batch_events(sdempc_handle* h, const sdempc_fault_process_cfg* fault_proc /*or NULL*/, const sdempc_dropout_process_cfg* drop_proc /*or NULL*/,
+                                    const sdempc_track_cfg* track /*or NULL*/,
+                                    const sdempc_process_cfg* dist_proc /*or NULL, W = 6*/, const sdempc_process_cfg* bias_proc /*or NULL, W = 12*/,
+                                    const sdempc_score_cfg* score /*or NULL*/, const uint32_t* score_in /*[B][16] or NULL*/,
+                                    const sdempc_age_cfg* age_cfg /*or NULL*/, const float* xhist_in /*[B][age_max][13] or NULL*/,
+                                    const sdempc_obs_cfg* obs /*or NULL*/, const uint32_t* obs_keys /*[B][2]; NULL without obs*/, const float* xmeas_in /*[B][13] or NULL*/,
+                                    const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*or NULL*/,
+                                    const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                    const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                    const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                    const float* xref /*NULL with track*/, int32_t xref_solves /*0 with track*/, int32_t xref_batch,
+                                    const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                    const float* u_act_in /*[B][m] or NULL*/,
+                                    float* xs /*[B][T+1][13]; may be NULL with score*/, float* us /*[B][T][m]; may be NULL with score*/,
+                                    sdempc_info* info /*[B][Ns]; may be NULL with score*/,
+                                    float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                    uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                    const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                    float* ws /*[B][T][4]; NULL without rate; may be NULL with score*/, float* rate_integ_next /*[B][3] or NULL*/,
+                                    float* rate_tail_next /*[B][H][3] or NULL*/,
+                                    float* xsub /*[B][T * substeps][13] or NULL*/,
+                                    float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
+                                    float* xhist_next /*[B][age_max][13] or NULL*/, uint32_t* score_out /*[B][16]; NULL without score*/,
+                                    float* dist_rows /*[B][T][6] or NULL*/, uint32_t* dist_keys_next /*[B][2] or NULL*/, float* dist_state_next /*[B][6] or NULL*/,
+                                    float* bias_rows /*[B][Ns][12] or NULL*/, uint32_t* bias_keys_next /*[B][2] or NULL*/, float* bias_state_next /*[B][12] or NULL*/,
+                                    float* fault_rows /*[B][T][m][2] or NULL*/, uint32_t* fault_keys_next /*[B][2] or NULL*/, int32_t* fault_state_next /*[B][m][2] or NULL*/,
+                                    int32_t* valid_rows /*[B][Ns] or NULL*/, uint32_t* valid_keys_next /*[B][2] or NULL*/, int32_t* valid_state_next /*[B][2] or NULL*/);
+
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so
  * repeating the call runs in the one-workgroup-per-instance layout. Also SDEMPC_EDEVICE when a large throughput launch that hands its

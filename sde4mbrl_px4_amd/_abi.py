@@ -382,6 +382,34 @@ def tracked_entry(lib):
     return fn
 
 
+class SdempcFaultProcessCfg(C.Structure):
+    """sdempc_fault_process_cfg (SPEC.md §11k): thresholds, modes, key chain, start state and global tick of the motor-fault chain of
+    sdempc_closed_loop_batch_events."""
+    _fields_ = [("struct_size", C.c_int32), ("n_modes", C.c_int32), ("batch", C.c_int32), ("onset", C.POINTER(C.c_uint32)), ("clear", C.POINTER(C.c_uint32)),
+                ("modes", C.POINTER(C.c_float)), ("keys", C.POINTER(C.c_uint32)), ("state_in", C.POINTER(C.c_int32)), ("tick0", C.c_int32)]
+
+
+class SdempcDropoutProcessCfg(C.Structure):
+    """sdempc_dropout_process_cfg (SPEC.md §11k): thresholds, key chain and start state of the estimator-dropout chain of sdempc_closed_loop_batch_events."""
+    _fields_ = [("struct_size", C.c_int32), ("batch", C.c_int32), ("drop", C.POINTER(C.c_uint32)), ("recover", C.POINTER(C.c_uint32)),
+                ("keys", C.POINTER(C.c_uint32)), ("state_in", C.POINTER(C.c_int32))]
+
+
+def events_entry(lib):
+    """sdempc_closed_loop_batch_events (SPEC.md §11k) with its prototype set: the two event cfgs (each may be NULL) in front of the tracked entry point's arguments,
+    then rows, keys_next and state_next of the fault chain and of the dropout chain. Detected by symbol and only when a call needs it, as tracked_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_events
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_events (SPEC.md §11k): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(tracked_entry(lib).argtypes)
+        fp, u32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+        fn.argtypes = [a[0], C.POINTER(SdempcFaultProcessCfg), C.POINTER(SdempcDropoutProcessCfg)] + a[1:] + [fp, u32p, i32p, i32p, u32p, i32p]
+        fn.restype = C.c_int
+    return fn
+
+
 def reference_windows_entry(lib):
     """sdempc_reference_windows (SPEC.md §11j) with its prototype set. Detected by symbol and only when a call needs it, as tracked_entry is."""
     try:
@@ -474,7 +502,7 @@ EXPORTED_SYMBOLS = [
     "sdempc_closed_loop_batch_plant", "sdempc_closed_loop_batch_timed", "sdempc_closed_loop_batch_scenario",
     "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault", "sdempc_closed_loop_batch_observed",
     "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored", "sdempc_closed_loop_batch_drawn",
-    "sdempc_closed_loop_batch_tracked", "sdempc_reference_windows",
+    "sdempc_closed_loop_batch_tracked", "sdempc_reference_windows", "sdempc_closed_loop_batch_events",
     "sdempc_tube_batch", "sdempc_tube_batch_keys", "sdempc_tube_batch_dev",
     "sdempc_risk_batch", "sdempc_risk_batch_keys", "sdempc_risk_batch_dev",
     "sdempc_bands_batch", "sdempc_bands_batch_keys", "sdempc_bands_batch_dev",

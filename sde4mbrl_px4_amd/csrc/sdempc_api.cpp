@@ -199,6 +199,10 @@ struct sdempc_handle {
     // closed loop with processes drawn on the device (sdempc_closed_loop_batch_drawn with a process cfg, allocated on its first use), per row of max_batch: the
     // disturbance chain u32[2] and state f32[6], the bias chain u32[2] and state f32[12], then rho and scale of each (f32[6], f32[6], f32[12], f32[12])
     DevBuf d_proc;
+    // closed loop with events drawn on the device (sdempc_closed_loop_batch_events with an event cfg, allocated on its first use), per row of max_batch: the fault
+    // chain's row (EVENT_EP_WORDS: key u32[2], then (s, first) i32 per motor), the dropout chain u32[2] and state i32[2], then the row of fault parameters
+    // (EVENT_PAR_WORDS: onset u32[8][4], clear u32[8][4], modes f32[8][4][2]) and the dropout thresholds (u32 drop, u32 recover)
+    DevBuf d_evt;
     // closed loop tracking a trajectory (sdempc_closed_loop_batch_tracked with a track cfg, sdempc_reference_windows; allocated on first use, grown, never shrunk): the set of
     // the current call — first / knots i32[n_tables], period / inv_period f32[n_tables], t / w f32[sum L], x f32[sum L][13], c f32[H+1], table_of i32[B], phase / rate f32[B],
     // offset f32[B][3] — in one allocation; track_stage: its host image, alive until the call returns
@@ -637,7 +641,22 @@ struct TrackRun {
     LoopTrack K;                // device pointers of the staged set, dt, renorm; tick0 = the cfg's; B / rows / groups are set per launch
     bool score_targets;
 };
+// SPEC.md §11k: the event chains of one sdempc_closed_loop_batch_events call (host pointers). Given only when the call has an event cfg: without one the call is the
+// tracked call, launch for launch.
+struct EventRun {
+    const sdempc_fault_process_cfg* fault;      // or null (m lanes, one step per control tick)
+    const sdempc_dropout_process_cfg* drop;     // or null (one lane, one step per solve)
+    float* fault_rows;                          // [B][T][m][2] or null
+    uint32_t* fault_keys_next;                  // [B][2] or null
+    int32_t* fault_state_next;                  // [B][m][2] or null
+    int32_t* valid_rows;                        // [B][Ns] or null
+    uint32_t* valid_keys_next;                  // [B][2] or null
+    int32_t* valid_state_next;                  // [B][2] or null
+};
 constexpr size_t PROC_WORDS = 2 + 6 + 2 + 12 + 2 * 6 + 2 * 12;      // words of d_proc per row of max_batch
+constexpr size_t EVT_MODES = 4;
+constexpr size_t EVT_WORDS = EVENT_EP_WORDS + 2 + 2 + EVENT_PAR_WORDS + 2;      // words of d_evt per row of max_batch
+static_assert(SDEMPC_MAX_MOTORS == 8, "EVENT_EP_WORDS / EVENT_PAR_WORDS (sdempc_kernels.h) hold eight motors");
 inline int loop_solves(int T, int S) { return (int)(((long long)T + S - 1) / S); }       // Ns = ceil(T / S)
 // One closed-loop call as its entry point describes it. The five entry points are five nested layers (SPEC.md §11, §11a .. §11d): each takes everything the one
 // below it takes, so `layer` says which parts are present; the arguments of an absent part stay null.
@@ -677,6 +696,8 @@ struct LoopCall {
     bool drawn;                                 // sdempc_closed_loop_batch_drawn (SPEC.md §11i): the scored call with the two process cfgs and their six outputs
     ProcRun pr;                                 // (a NULL cfg: its three outputs must be NULL)
     const sdempc_track_cfg* track;              // sdempc_closed_loop_batch_tracked (SPEC.md §11j): the drawn call with a trajectory set in place of xref; or NULL
+    bool events;                                // sdempc_closed_loop_batch_events (SPEC.md §11k): the tracked call with the two event cfgs and their six outputs
+    EventRun er;                                // (a NULL cfg: its three outputs must be NULL)
 };
 int closed_loop_call(sdempc_handle* h, const LoopCall& c);
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves, bool rows_optional = false, bool tracked = false);
@@ -684,9 +705,10 @@ int check_track(sdempc_handle* h, const sdempc_track_cfg* tk, int B, long long t
 int stage_track(sdempc_handle* h, const sdempc_track_cfg& tk, int B, TrackRun* out);
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr,
-                         const ObsRun* obs = nullptr, const ScoreRun* score = nullptr, const ProcRun* proc = nullptr, const TrackRun* track = nullptr);
+                         const ObsRun* obs = nullptr, const ScoreRun* score = nullptr, const ProcRun* proc = nullptr, const TrackRun* track = nullptr,
+                         const EventRun* evt = nullptr);
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, bool* again);
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -786,7 +808,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_outcome, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_outcome, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_evt, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1829,6 +1851,36 @@ int sdempc_closed_loop_batch_tracked(sdempc_handle* h, const sdempc_track_cfg* t
     });
 }
 
+int sdempc_closed_loop_batch_events(sdempc_handle* h, const sdempc_fault_process_cfg* fault_proc, const sdempc_dropout_process_cfg* drop_proc, const sdempc_track_cfg* track,
+                                    const sdempc_process_cfg* dist_proc, const sdempc_process_cfg* bias_proc, const sdempc_score_cfg* zc, const uint32_t* score_in,
+                                    const sdempc_age_cfg* ac, const float* xhist_in, const sdempc_obs_cfg* oc, const uint32_t* obs_keys, const float* xmeas_in,
+                                    const sdempc_fault_cfg* fc, const sdempc_rate_cfg* rc_, const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc,
+                                    const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T, const float* x0, const float* xref,
+                                    int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in, const float* u_act_in, float* xs,
+                                    float* us, sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next, float* u_act_next, const float* rate_integ_in,
+                                    const float* rate_tail_in, float* ws, float* rate_integ_next, float* rate_tail_next, float* xsub, float* xmeas, uint32_t* obs_keys_next,
+                                    float* xmeas_next, float* xhist_next, uint32_t* score_out, float* dist_rows, uint32_t* dist_keys_next, float* dist_state_next, float* bias_rows,
+                                    uint32_t* bias_keys_next, float* bias_state_next, float* fault_rows, uint32_t* fault_keys_next, int32_t* fault_state_next, int32_t* valid_rows,
+                                    uint32_t* valid_keys_next, int32_t* valid_state_next) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    c.observed = true; c.oc = oc; c.obs_keys = obs_keys; c.xmeas_in = xmeas_in; c.xmeas = xmeas; c.obs_keys_next = obs_keys_next; c.xmeas_next = xmeas_next;
+    c.aged = true; c.ac = ac; c.xhist_in = xhist_in; c.xhist_next = xhist_next;
+    c.scored = true; c.zc = zc; c.score_in = score_in; c.score_out = score_out;
+    c.drawn = true; c.pr = {dist_proc, bias_proc, dist_rows, dist_keys_next, dist_state_next, bias_rows, bias_keys_next, bias_state_next};
+    c.track = track;
+    c.events = true; c.er = {fault_proc, drop_proc, fault_rows, fault_keys_next, fault_state_next, valid_rows, valid_keys_next, valid_state_next};
+    return closed_loop_call(h, c);
+    });
+}
+
 int sdempc_reference_windows(sdempc_handle* h, const sdempc_track_cfg* track, int32_t B, int32_t n, const int32_t* ticks, float* out) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1907,7 +1959,7 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
 }
-// The one path behind the ten closed-loop entry points: every check of the call's parts, in one fixed order (process structs and their arrays, score struct, age struct, observation struct, fault struct, rate, scenario struct,
+// The one path behind the closed-loop entry points: every check of the call's parts, in one fixed order (event structs and their arrays, track struct, process structs and their arrays, score struct, age struct, observation struct, fault struct, rate, scenario struct,
 // timing, loop arguments, plant_ticks, plant set, solve_delay, disturbance, fault schedule, observation rows, age rows, score target rows; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
 int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     if (!h) return SDEMPC_EINVAL;
@@ -1919,6 +1971,42 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    if (c.events) {            // SPEC.md §11k: an output needs its cfg; then the fault cfg, the dropout cfg, and the observation chain the dropouts need
+        const EventRun& er = c.er;
+        const int m = h->m;
+        if (!er.fault && (er.fault_rows || er.fault_keys_next || er.fault_state_next))
+            return fail(h, SDEMPC_EINVAL, "events: fault_rows / fault_keys_next / fault_state_next must be NULL without fault_proc%s");
+        if (!er.drop && (er.valid_rows || er.valid_keys_next || er.valid_state_next))
+            return fail(h, SDEMPC_EINVAL, "events: valid_rows / valid_keys_next / valid_state_next must be NULL without drop_proc%s");
+        if (const sdempc_fault_process_cfg* p = er.fault) {
+            if (p->struct_size != (int32_t)sizeof(sdempc_fault_process_cfg)) return fail(h, SDEMPC_EINVAL, "events: fault_proc struct_size mismatch%s");
+            if (p->n_modes < 1 || p->n_modes > (int)EVT_MODES) return fail(h, SDEMPC_EINVAL, "events: n_modes must be between 1 and 4%s");
+            if (p->batch != 1 && p->batch != B) return fail(h, SDEMPC_EINVAL, "events: fault_proc batch must be 1 or B%s");
+            if (!p->onset || !p->clear || !p->modes || !p->keys) return fail(h, SDEMPC_EINVAL, "events: onset, clear, modes or keys of fault_proc is NULL%s");
+            const int K = p->n_modes;
+            if (B >= 1) {          // (B < 1 is refused below, with the loop arguments)
+                for (size_t r = 0; r < (size_t)p->batch * m; ++r)
+                    for (int j = 1; j < K; ++j)
+                        if (p->onset[r * K + j] < p->onset[r * K + j - 1]) return fail(h, SDEMPC_EINVAL, "events: an onset row decreases (the thresholds are cumulative)%s");
+                for (size_t e = 0; e < (size_t)p->batch * m * K * 2; ++e)
+                    if (!finite(p->modes[e])) return fail(h, SDEMPC_EINVAL, "events: modes holds a non-finite entry%s");
+                for (size_t e = 0; p->state_in && e < (size_t)B * m; ++e)
+                    if (p->state_in[2 * e] < 0 || p->state_in[2 * e] > K || p->state_in[2 * e + 1] < -1)
+                        return fail(h, SDEMPC_EINVAL, "events: fault_proc state_in holds a state outside 0 .. n_modes or a first tick below -1%s");
+            }
+            if (p->tick0 < 0 || (long long)p->tick0 + T >= (1ll << 24)) return fail(h, SDEMPC_EINVAL, "events: tick0 must be >= 0 and tick0 + T below 2^24%s");
+        }
+        if (const sdempc_dropout_process_cfg* p = er.drop) {
+            if (p->struct_size != (int32_t)sizeof(sdempc_dropout_process_cfg)) return fail(h, SDEMPC_EINVAL, "events: drop_proc struct_size mismatch%s");
+            if (p->batch != 1 && p->batch != B) return fail(h, SDEMPC_EINVAL, "events: drop_proc batch must be 1 or B%s");
+            if (!p->drop || !p->recover || !p->keys) return fail(h, SDEMPC_EINVAL, "events: drop, recover or keys of drop_proc is NULL%s");
+            for (size_t e = 0; p->state_in && B >= 1 && e < (size_t)B; ++e)
+                if (p->state_in[2 * e] < 0 || p->state_in[2 * e] > 1 || p->state_in[2 * e + 1] < 0)
+                    return fail(h, SDEMPC_EINVAL, "events: drop_proc state_in holds a state outside 0 .. 1 or a negative count%s");
+        }
+        if (er.drop && !c.obs_keys) return fail(h, SDEMPC_EINVAL, "events: drop_proc needs an obs cfg and obs_keys%s");
+    }
+    const EventRun* evt = c.events && (c.er.fault || c.er.drop) ? &c.er : nullptr;
     const sdempc_track_cfg* tk = c.track;
     if (tk) {                  // SPEC.md §11j: the trajectory set, then what may not be given beside it
         if (int rc = check_track(h, tk, B, T)) return rc;
@@ -2080,8 +2168,8 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const ScoreRun run_z{zc, c.score_in, c.score_out};
     TrackRun run_k;
     if (tk && (rc = stage_track(h, *tk, B, &run_k))) return rc;
-    return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr, run_f.fault || run_f.xsub ? &run_f : nullptr,
-                                oc ? &run_o : nullptr, zc ? &run_z : nullptr, proc, tk ? &run_k : nullptr);
+    return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr,
+                                run_f.fault || run_f.xsub || (evt && evt->fault) ? &run_f : nullptr, oc ? &run_o : nullptr, zc ? &run_z : nullptr, proc, tk ? &run_k : nullptr, evt);
 }
 // every check of a trajectory set (SPEC.md §11j), shared by the two entry points that take one; no HIP call. ticks: control ticks of the call (tick0 + ticks < 2^24)
 int check_track(sdempc_handle* h, const sdempc_track_cfg* tk, int B, long long ticks) {
@@ -2212,10 +2300,10 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt,
-                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc, const TrackRun* track) {
+                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, track, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, track, evt, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -2307,8 +2395,13 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // SPEC.md §11j (track, with timed and plant): the trajectory set lives in d_track (staged once per call by stage_track). In front of every solve ONE launch of the row-filling
 // kernel in its tracking form writes the B windows of the period's first tick into d_xref, where a shared window was broadcast to before; the chunk has no xref region and
 // takes no xref copy. With score targets, one more launch per chunk writes the chunk's [Tc][B][13] target rows in front of the scoring launch, in place of their copy.
+// SPEC.md §11k (evt, with scen, timed and plant): the event chains, states, thresholds and modes live in d_evt (staged from the cfgs with the other inputs, so that a re-run
+// starts from them again). The period's key-schedule launch takes a LoopEvents: with a fault chain it writes the period's rows of a [Tc][B][m][2] region of the chunk, which
+// the plant launch then reads as its fault rows (a scheduled fault given as well is staged beside it, as before, and read by the key schedule); with a dropout chain it
+// writes the solve's flags into a [Pc][B] region, which the measurement reads as its valid flags (scheduled flags likewise). Both regions count in the chunk's bytes and are
+// copied back and scattered only when the caller asked for the rows.
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, bool* again) {
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, bool* again) {
     *again = false;
     const bool tracked = track && timed && plant;                          // (SPEC.md §11j)
     const int B = io.B, T = io.T, Bx = tracked ? 0 : io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
@@ -2337,7 +2430,10 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     const size_t ZR = scoring ? (size_t)(targets ? B : score->cfg->ref_batch) * NX : 0;                                // floats per tick row of the score targets (SPEC.md §11h)
     const bool gproc = proc && proc->dist && scen && timed && plant, bproc = proc && proc->bias && seen;      // (SPEC.md §11i)
     const int NG = SDEMPC_NNOISE, NB = 12;                                                              // widths of the two processes
-    const size_t per_period = (gproc ? (size_t)S * B * NG : 0) + (bproc ? (size_t)B * NB : 0) + (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0) +
+    const bool fproc = evt && evt->fault && flt && scen && timed && plant, dproc = evt && evt->drop && seen;   // (SPEC.md §11k)
+    const int KF = fproc ? evt->fault->n_modes : 0;
+    const size_t EF = (size_t)B * m * 2;                                                                // floats per tick row of the drawn fault rows
+    const size_t per_period = (fproc ? (size_t)S * EF : 0) + (dproc ? (size_t)B : 0) + (gproc ? (size_t)S * B * NG : 0) + (bproc ? (size_t)B * NB : 0) + (size_t)B * OUT + (xref_moves ? (size_t)Bx * XR : 0) + (dist_moves ? (size_t)S * DR : 0) + (sched_moves ? (size_t)S * SR : 0) +
                               (fault_moves ? (size_t)S * FR : 0) + (obs_moves ? ORS : 0) + (valid_moves ? VR : 0) + (age_moves ? AR : 0) + (sref_moves ? (size_t)S * ZR : 0);
     const size_t fixed = (xref_moves ? 0 : (size_t)Bx * XR) + (dist_moves ? 0 : DR) + (sched_moves ? 0 : SR) + (fault_moves ? 0 : FR) + (obs_moves ? 0 : ORS) + (valid_moves ? 0 : VR) + (age_moves ? 0 : AR) + (sref_moves ? 0 : ZR);
     const size_t cap = (h->loop_chunk_bytes < 0 ? LOOP_CHUNK_BYTES : (size_t)h->loop_chunk_bytes) / sizeof(float);
@@ -2371,6 +2467,12 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* p_bstate = p_dchain ? (float*)(p_bchain + 2 * MB) : nullptr;                  // [B][12]
     float* p_drho = p_dchain ? p_bstate + NB * MB : nullptr, *p_dscale = p_dchain ? p_drho + NG * MB : nullptr;
     float* p_brho = p_dchain ? p_dscale + NG * MB : nullptr, *p_bscale = p_dchain ? p_brho + NB * MB : nullptr;
+    if ((fproc || dproc) && !h->d_evt.p && (rc = dev_alloc(h, h->d_evt, sizeof(uint32_t) * EVT_WORDS * (size_t)h->max_batch, true))) return rc;
+    uint32_t* e_fep = (uint32_t*)h->d_evt.p;                         // [B][EVENT_EP_WORDS] (SPEC.md §11k; the layout is the one stated at d_evt, each part sized for max_batch rows)
+    uint32_t* e_dchain = e_fep ? e_fep + EVENT_EP_WORDS * MB : nullptr;                  // [B][2]
+    int32_t* e_dstate = e_fep ? (int32_t*)(e_dchain + 2 * MB) : nullptr;                 // [B][2]
+    uint32_t* e_par = e_fep ? (uint32_t*)(e_dstate + 2 * MB) : nullptr;                  // [batch][EVENT_PAR_WORDS]
+    uint32_t* e_drop = e_fep ? e_par + EVENT_PAR_WORDS * MB : nullptr, *e_recover = e_fep ? e_drop + MB : nullptr;     // [batch]
     uint32_t* d_q = (uint32_t*)h->d_obs.p;                           // q [B][2] (SPEC.md §11f)
     float* d_xm = d_q ? (float*)(d_q + 2 * (size_t)h->max_batch) : nullptr;   // xm [B][13]
     float* d_integ = (float*)h->d_rate.p;                            // g [B][3] (SPEC.md §11d)
@@ -2398,6 +2500,8 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* c_sref = (float*)(c_age + (old ? (age_moves ? (size_t)Pc : 1) * AR : 0));             // [Tc or 1][Br][13] (SPEC.md §11h)
     float* c_pdist = c_sref + (scoring ? (sref_moves ? Tc : 1) * ZR : 0);                        // [Tc][B][6] (SPEC.md §11i)
     float* c_pbeta = c_pdist + (gproc ? Tc * B * NG : 0);                                        // [Pc][B][12]
+    float* c_efault = c_pbeta + (bproc ? (size_t)Pc * B * NB : 0);                               // [Tc][B][m][2] (SPEC.md §11k)
+    int32_t* c_evalid = (int32_t*)(c_efault + (fproc ? Tc * EF : 0));                            // [Pc][B]
     float* d_x = (float*)h->d_x0.p;                                  // x_k: the solve's initial states, advanced in place (SPEC.md §11f: the plant's; the solve reads d_xm)
     hipStream_t st = h->stream;
     // inputs (host vectors live until the synchronisation at the end of the first chunk)
@@ -2474,6 +2578,39 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         HIPCHK(h, hipMemcpyAsync(w ? p_brho : p_drho, pc.rho, sizeof(float) * pc.batch * W, hipMemcpyHostToDevice, st));
         HIPCHK(h, hipMemcpyAsync(w ? p_bscale : p_dscale, pc.scale, sizeof(float) * pc.batch * W, hipMemcpyHostToDevice, st));
     }
+    std::vector<uint32_t> e0, e1;
+    if (fproc) {               // the fault chain's rows (key, then (s, first) per motor; state_in NULL: (0, -1)) and the parameter rows start as given (SPEC.md §11k)
+        const sdempc_fault_process_cfg& pc = *evt->fault;
+        e0.assign((size_t)B * EVENT_EP_WORDS, 0u);
+        for (int b = 0; b < B; ++b) {
+            uint32_t* row = &e0[(size_t)b * EVENT_EP_WORDS];
+            row[0] = pc.keys[2 * b]; row[1] = pc.keys[2 * b + 1];
+            for (int l = 0; l < m; ++l) {
+                row[2 + 2 * l] = pc.state_in ? (uint32_t)pc.state_in[((size_t)b * m + l) * 2] : 0u;
+                row[3 + 2 * l] = pc.state_in ? (uint32_t)pc.state_in[((size_t)b * m + l) * 2 + 1] : 0xffffffffu;
+            }
+        }
+        e1.assign((size_t)pc.batch * EVENT_PAR_WORDS, 0u);
+        for (int r = 0; r < pc.batch; ++r)
+            for (int l = 0; l < m; ++l)
+                for (int j = 0; j < KF; ++j) {
+                    uint32_t* row = &e1[(size_t)r * EVENT_PAR_WORDS];
+                    const size_t e = ((size_t)r * m + l) * KF + j;
+                    row[l * 4 + j] = pc.onset[e];
+                    row[32 + l * 4 + j] = pc.clear[e];
+                    memcpy(&row[64 + (l * 4 + j) * 2], pc.modes + 2 * e, 2 * sizeof(float));
+                }
+        HIPCHK(h, hipMemcpyAsync(e_fep, e0.data(), sizeof(uint32_t) * e0.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(e_par, e1.data(), sizeof(uint32_t) * e1.size(), hipMemcpyHostToDevice, st));
+    }
+    if (dproc) {
+        const sdempc_dropout_process_cfg& pc = *evt->drop;
+        HIPCHK(h, hipMemcpyAsync(e_dchain, pc.keys, sizeof(uint32_t) * 2 * B, hipMemcpyHostToDevice, st));
+        if (pc.state_in) HIPCHK(h, hipMemcpyAsync(e_dstate, pc.state_in, sizeof(int32_t) * 2 * B, hipMemcpyHostToDevice, st));
+        else HIPCHK(h, hipMemsetAsync(e_dstate, 0, sizeof(int32_t) * 2 * B, st));
+        HIPCHK(h, hipMemcpyAsync(e_drop, pc.drop, sizeof(uint32_t) * pc.batch, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(e_recover, pc.recover, sizeof(uint32_t) * pc.batch, hipMemcpyHostToDevice, st));
+    }
     if (!tracked && !xref_moves) {
         HIPCHK(h, hipMemcpyAsync(c_xref, io.xref, sizeof(float) * Bx * XR, hipMemcpyHostToDevice, st));
         if (Bx != B) HIPCHK(h, launch_broadcast_rows(c_xref, (float*)h->d_xref.p, (int)XR, B, st));
@@ -2522,12 +2659,22 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         G.bias.chain = p_bchain; G.bias.state = p_bstate; G.bias.rho = p_brho; G.bias.scale = p_bscale; G.bias.par_ep_stride = proc->bias->batch > 1 ? NB : 0;
         G.bias.sched_ep_stride = biased && obs->Bo > 1 ? NB : 0;
     }
+    LoopEvents E{};            // (chains null: absent)
+    if (fproc) {
+        E.fault.chain = e_fep; E.fault.par = e_par; E.fault.par_ep_stride = evt->fault->batch > 1 ? EVENT_PAR_WORDS : 0; E.fault.K = KF; E.fault.m = m;
+        E.fault.sched_tick_stride = fault_moves ? (int)FR : 0; E.fault.sched_ep_stride = faulty && flt->Bf > 1 ? 2 * m : 0;
+    }
+    if (dproc) {
+        E.drop.chain = e_dchain; E.drop.state = e_dstate; E.drop.drop = e_drop; E.drop.recover = e_recover; E.drop.par_ep_stride = evt->drop->batch > 1 ? 1 : 0;
+        E.drop.sched_ep_stride = gated && obs->Bv > 1 ? 1 : 0;
+    }
     if (seen) {
         O.q = d_q; O.x = d_x; O.xm = d_xm; O.ep_stride = obs->Bo > 1 ? 12 : 0; O.valid_ep_stride = obs->Bv > 1 ? 1 : 0;
         O.renorm = obs->renorm ? 1 : 0;
         if (old && AM > 0) { O.hist = d_hist; O.hist_row_stride = (int)HR; O.age_ep_stride = obs->Ba > 1 ? 1 : 0; O.age_max = AM; }      // (age_max 0: every age is 0)
     }
     if (flt) { V.fault_tick_stride = fault_moves ? (int)FR : 0; V.fault_ep_stride = faulty && flt->Bf > 1 ? 2 * m : 0; }
+    if (fproc) { V.fault_tick_stride = (int)EF; V.fault_ep_stride = 2 * m; }       // (the plant reads the rows the key schedule wrote)
     if (timed) { R.act = d_mot; R.alpha = timed->alpha; R.xi_ticks = S; R.shift = timed->S < H ? timed->S : H; }
     if (scen) {
         C.dist_tick_stride = dist_moves ? (int)DR : 0; C.dist_ep_stride = gust && scen->Bd > 1 ? SDEMPC_NNOISE : 0;
@@ -2545,7 +2692,9 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         W.inv_m = rate->inv_m; W.w = rc_.motor_weight;
         W.xevol = (const float*)h->d_xmean.p; W.wt = d_tail; W.g = d_integ;
     }
-    std::vector<float> hx, hu, hi, hw, hs, hm, hn, hg, hb;
+    std::vector<float> hx, hu, hi, hw, hs, hm, hn, hg, hb, hf;
+    std::vector<int32_t> hv;
+    std::vector<uint32_t> he;
     for (int j0 = 0; j0 < Ns; j0 += Pc) {
         const int np = Ns - j0 < Pc ? Ns - j0 : Pc;                                  // periods of this chunk
         const size_t k0 = (size_t)j0 * S;
@@ -2577,7 +2726,17 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 G.bias.dst = c_pbeta + (size_t)jc * B * NB;
                 O.beta = nullptr;
             }
-            if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st, O, LoopScore{}, G));
+            if (fproc) {               // (the scheduled rows and the written rows of this period's first tick, and its global tick)
+                E.fault.sched = faulty ? (const uint32_t*)(c_fault + (fault_moves ? (size_t)jc * S * FR : 0)) : nullptr;
+                E.fault.dst = (uint32_t*)(c_efault + (size_t)jc * S * EF);
+                E.fault.tick0 = evt->fault->tick0 + (int)(k0 + (size_t)jc * S);
+            }
+            if (dproc) {               // (the scheduled flags go through the chain, which writes the flags the measurement reads)
+                E.drop.sched = O.valid;
+                E.drop.dst = c_evalid + (size_t)jc * B;
+                O.valid = E.drop.dst; O.valid_ep_stride = 1;
+            }
+            if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st, O, LoopScore{}, G, E));
             else if (plant) HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st, plant->Q.substeps));
             else HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st));
             HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));
@@ -2605,7 +2764,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 }
                 if (rate) W.ws = c_ws + t0 * B * 4;
                 if (flt || subs) {
-                    V.fault = faulty ? c_fault + (fault_moves ? t0 * FR : 0) : nullptr;
+                    V.fault = fproc ? c_efault + t0 * EF : faulty ? c_fault + (fault_moves ? t0 * FR : 0) : nullptr;
                     V.xsub = subs ? c_xsub + t0 * nsub * B * NX : nullptr;
                 }
             }
@@ -2668,7 +2827,21 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             hb.resize((size_t)np * B * NB);
             HIPCHK(h, hipMemcpyAsync(hb.data(), c_pbeta, sizeof(float) * hb.size(), hipMemcpyDeviceToHost, st));
         }
+        if (fproc && evt->fault_rows) {
+            hf.resize((size_t)nk * EF);
+            HIPCHK(h, hipMemcpyAsync(hf.data(), c_efault, sizeof(float) * hf.size(), hipMemcpyDeviceToHost, st));
+        }
+        if (dproc && evt->valid_rows) {
+            hv.resize((size_t)np * B);
+            HIPCHK(h, hipMemcpyAsync(hv.data(), c_evalid, sizeof(int32_t) * hv.size(), hipMemcpyDeviceToHost, st));
+        }
         if (j0 + np == Ns) {
+            if (fproc && (evt->fault_keys_next || evt->fault_state_next)) {
+                he.resize((size_t)B * EVENT_EP_WORDS);
+                HIPCHK(h, hipMemcpyAsync(he.data(), e_fep, sizeof(uint32_t) * he.size(), hipMemcpyDeviceToHost, st));
+            }
+            if (dproc && evt->valid_keys_next) HIPCHK(h, hipMemcpyAsync(evt->valid_keys_next, e_dchain, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
+            if (dproc && evt->valid_state_next) HIPCHK(h, hipMemcpyAsync(evt->valid_state_next, e_dstate, sizeof(int32_t) * 2 * B, hipMemcpyDeviceToHost, st));
             if (gproc && proc->dist_keys_next) HIPCHK(h, hipMemcpyAsync(proc->dist_keys_next, p_dchain, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
             if (gproc && proc->dist_state_next) HIPCHK(h, hipMemcpyAsync(proc->dist_state_next, p_dstate, sizeof(float) * B * NG, hipMemcpyDeviceToHost, st));
             if (bproc && proc->bias_keys_next) HIPCHK(h, hipMemcpyAsync(proc->bias_keys_next, p_bchain, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
@@ -2712,6 +2885,19 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             for (int jc = 0; jc < np; ++jc)
                 for (int b = 0; b < B; ++b)
                     memcpy(proc->bias_rows + ((size_t)b * Ns + j0 + jc) * NB, &hb[((size_t)jc * B + b) * NB], sizeof(float) * NB);
+        if (fproc && evt->fault_rows)
+            for (int kc = 0; kc < nk; ++kc)
+                for (int b = 0; b < B; ++b)
+                    memcpy(evt->fault_rows + ((size_t)b * T + k0 + kc) * m * 2, &hf[((size_t)kc * B + b) * m * 2], sizeof(float) * m * 2);
+        for (int b = 0; !he.empty() && b < B; ++b) {
+            const uint32_t* row = &he[(size_t)b * EVENT_EP_WORDS];
+            if (evt->fault_keys_next) memcpy(evt->fault_keys_next + 2 * (size_t)b, row, 2 * sizeof(uint32_t));
+            if (evt->fault_state_next) memcpy(evt->fault_state_next + (size_t)b * m * 2, row + 2, sizeof(int32_t) * m * 2);
+        }
+        if (dproc && evt->valid_rows)
+            for (int jc = 0; jc < np; ++jc)
+                for (int b = 0; b < B; ++b)
+                    evt->valid_rows[(size_t)b * Ns + j0 + jc] = hv[(size_t)jc * B + b];
         if (subs_out)
             for (size_t rr = 0; rr < (size_t)nk * nsub; ++rr)
                 for (int b = 0; b < B; ++b)

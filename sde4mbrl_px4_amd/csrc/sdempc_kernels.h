@@ -289,8 +289,46 @@ struct LoopProcess {
     LoopProcessHalf dist;       // W = 6, one step per control tick
     LoopProcessHalf bias;       // W = 12, one step per solve; needs LoopObserve::q
 };
+// SPEC.md §11k, motor faults and estimator dropouts drawn on the device: a finite Markov chain per lane, stepped by the period's key-schedule thread of episode b
+// beside its schedule. A chain has K modes besides state 0. One step: (c, e) = split(c), w = random_bits(e, lanes) (counter k pairs with k + ceil(lanes / 2), a zero
+// counter in an odd count's last block), and per lane with state s and word w_l: from s = 0 to j + 1 for the smallest j < K with w_l < onset[l][j] (else 0), from
+// s > 0 to 0 if w_l < clear[l][s - 1] (else s). Integer compares only; a threshold of 0 never fires. One transition per step.
+// The fault half (lanes = m <= 8) takes one step per control tick of the period and writes row (i, b) of dst, f32[ticks][B][m][2], which the plant launch then reads
+// as its LoopFault::fault (tick stride B * m * 2, episode stride 2 m): in state 0 the scheduled row, or (1, 0) without a schedule; in state s > 0 the words of
+// modes[l][s - 1], untouched. The episode's row of `chain` holds the key and (s, first) per motor: first = tick0 + i of the first step that left state 0, or -1. sched addresses the PERIOD's first
+// tick. The dropout half (one lane, K = 1) takes one step per launch, before the measurement is formed, and writes dst[b] = (s == 0) & scheduled flag: the valid flag
+// of this solve, which LoopObserve::valid must then address (episode stride 1; the scheduled flags go to sched, of SOLVE j). state holds (s, n_dropped). chain null
+// means absent: the kernel then makes no memory access it did not make before.
+constexpr int EVENT_EP_WORDS = 2 + 2 * 8;            // words of one episode's row of the fault chain: the key u32[2], then (s, first) i32 of motor l at 2 + 2 l
+constexpr int EVENT_PAR_WORDS = 32 + 32 + 64;        // words of one row of fault parameters: onset u32[8][4], clear u32[8][4], modes f32[8][4][2] (motor l < m, mode j < K used)
+struct LoopEventFault {
+    uint32_t* chain;            // [B][EVENT_EP_WORDS] key and per-motor (s, first) of every episode, advanced in place; null: no chain
+    const uint32_t* par;        // the parameters of episode b at par[b * par_ep_stride + ..]: onset cumulative and nondecreasing, clear, modes (kappa, beta) as words
+    int par_ep_stride;          // EVENT_PAR_WORDS, or 0 (one row for every episode: every lane of a wave loads one address)
+    int K, m;                   // modes 1..4, motors 1..8
+    int tick0;                  // the global tick of the period's first tick (>= 0)
+    const uint32_t* sched;      // the scheduled row of tick i, episode b at sched[i * sched_tick_stride + b * sched_ep_stride + 2 * l + 0..1] (words of floats), or null: (1, 0)
+    int sched_tick_stride;      // words between two ticks' rows: Bf * m * 2, or 0
+    int sched_ep_stride;        // words between two episodes' rows: m * 2, or 0
+    uint32_t* dst;              // [ticks][B][m][2] the rows written (words of floats)
+};
+struct LoopEventDrop {
+    uint32_t* chain;            // [B][2]; null: no chain
+    int32_t* state;             // [B][2] (s, n_dropped): in, and out
+    const uint32_t* drop;       // threshold of dropping of episode b at drop[b * par_ep_stride]
+    const uint32_t* recover;    // threshold of recovering, same layout
+    int par_ep_stride;          // 1, or 0 (one pair for every episode)
+    const int32_t* sched;       // the scheduled flag of episode b at sched[b * sched_ep_stride], or null: 1
+    int sched_ep_stride;        // 1, or 0
+    int32_t* dst;               // [B] the flags written
+};
+struct LoopEvents {
+    LoopEventFault fault;       // one step per control tick
+    LoopEventDrop drop;         // one step per solve; needs LoopObserve::q, and LoopObserve::valid == dst
+};
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st,
-                                   const LoopObserve& O = LoopObserve{}, const LoopScore& Z = LoopScore{}, const LoopProcess& G = LoopProcess{});
+                                   const LoopObserve& O = LoopObserve{}, const LoopScore& Z = LoopScore{}, const LoopProcess& G = LoopProcess{},
+                                   const LoopEvents& E = LoopEvents{});
 // SPEC.md §11j, reference windows and score targets cut from a trajectory on the device: the row-filling launch below in its TRACKING form. The tables of a set lie
 // end to end: table j owns knots first[j] .. first[j] + knots[j] - 1 of t / w / x (w[i] = float32(1 / (t[i+1] - t[i])) formed by the library in float64; the last w of
 // a table is not read). Thread i of the launch writes one whole row of 13 floats, row i of out f32[groups][B][rows][13]: group g is tick tick0 + g, its clock value

@@ -319,8 +319,12 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
 // whose beta is then the row this thread has just written (dropout or not); the disturbance process once per tick, beside the schedule's tick loop, into row (i, b) of
 // the period's disturbance rows. One step is one split, W / 2 blocks, and per component one multiply and one fma (kept apart: -ffp-contract=off). Both null: not one
 // access more.
+// SPEC.md §11k (E.drop.chain / E.fault.chain given): the same thread steps the episode's event chains, in integers alone — the dropout chain once, in front of the bias
+// step and the measurement, whose valid flag is then the word this thread has just written (O.valid addresses it); the fault chain once per tick, beside the
+// disturbance step, into row (i, b) of the period's fault rows. One step is one split, ceil(lanes / 2) blocks and per lane at most K + 1 compares; chain and
+// per-motor states stay in registers at constant indices (motor loops unrolled to 8, as the scoring form's). Both null: not one access more.
 __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int ticks,
-                                                                      int xi_ticks, int n, LoopObserve O, LoopScore Z, LoopProcess G) {
+                                                                      int xi_ticks, int n, LoopObserve O, LoopScore Z, LoopProcess G, LoopEvents E) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     if (Z.words) {                                       // (wave-uniform)
@@ -383,6 +387,19 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
         }
         w[13] = nit; w[14] = nls; w[15] = flat;
         return;
+    }
+    if (E.drop.chain) {                                  // (wave-uniform)
+        const LoopEventDrop& Ed = E.drop;
+        uint32_t c2[2], ek[2];
+        split2(Ed.chain[2 * b], Ed.chain[2 * b + 1], c2, ek);
+        Ed.chain[2 * b] = c2[0]; Ed.chain[2 * b + 1] = c2[1];
+        uint32_t w = 0u, pad = 0u;                       // random_bits(e, 1): the first word of block (0, 0)
+        threefry2x32(ek[0], ek[1], w, pad);
+        const int s = Ed.state[2 * b];
+        const int sn = s == 0 ? (w < Ed.drop[(size_t)b * Ed.par_ep_stride] ? 1 : 0) : (w < Ed.recover[(size_t)b * Ed.par_ep_stride] ? 0 : 1);
+        Ed.state[2 * b] = sn; Ed.state[2 * b + 1] += sn;
+        const int scheduled = Ed.sched ? Ed.sched[(size_t)b * Ed.sched_ep_stride] : 1;
+        Ed.dst[b] = sn == 0 && scheduled != 0 ? 1 : 0;
     }
     const float* pbeta = nullptr;                    // this solve's beta where the bias process wrote it
     if (G.bias.chain) {                                  // (wave-uniform)
@@ -460,7 +477,58 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
 #pragma unroll
         for (int e = 0; e < 6; ++e) dg[e] = Pd.state[(size_t)b * 6 + e];
     }
+    const LoopEventFault& Ef = E.fault;
+    uint32_t fc[2] = {0u, 0u};
+    // the states of the m <= 8 motors, three bits each (s <= 4), in ONE register; `first` stays in memory, written by the step that leaves state 0 for the first time
+    uint32_t fp = 0u;
+    // (one row per episode, chain and states, and one row of parameters: every access below is one of two pointers plus a constant, so no address is formed per motor
+    // and mode and none can be kept in registers across the tick loop)
+    uint32_t* fe = Ef.chain ? Ef.chain + (size_t)b * EVENT_EP_WORDS : nullptr;
+    if (Ef.chain) {                                      // (wave-uniform)
+        fc[0] = fe[0]; fc[1] = fe[1];
+#pragma unroll
+        for (int l = 0; l < 8; ++l)
+            if (l < Ef.m) fp |= fe[2 + 2 * l] << (3 * l);
+    }
     for (int i = 0; i < ticks; ++i) {
+        if (Ef.chain) {
+            uint32_t c2[2], ek[2];
+            split2(fc[0], fc[1], c2, ek);
+            fc[0] = c2[0]; fc[1] = c2[1];
+            const int K = Ef.K, m = Ef.m, hf = (m + 1) >> 1;
+            const uint32_t* on = Ef.par + (size_t)b * Ef.par_ep_stride;      // onset u32[8][4], clear u32[8][4], modes f32[8][4][2]
+            const uint32_t* cr = on + 32;
+            const uint32_t* md = on + 64;                        // (the rows are copied as words: no arithmetic is done on them)
+            const uint32_t sch = (uint32_t)i * (uint32_t)Ef.sched_tick_stride + (uint32_t)b * (uint32_t)Ef.sched_ep_stride;
+            const uint32_t out = ((uint32_t)i * (uint32_t)B + (uint32_t)b) * (uint32_t)m * 2u;
+#pragma unroll
+            for (int l = 0; l < 8; ++l)
+                if (l < m) {
+                    // word l of random_bits(e, m): the first word of block l where l < hf, else the second of block l - hf (whose first counter is l - hf; an odd
+                    // m's last block pairs with a zero counter). Each lane runs its own block: a second pass over a block costs less than holding m words.
+                    const int k = l < hf ? l : l - hf;
+                    uint32_t x0 = (uint32_t)k, x1 = k + hf < m ? (uint32_t)(k + hf) : 0u;
+                    threefry2x32(ek[0], ek[1], x0, x1);
+                    const uint32_t w = l < hf ? x0 : x1;
+                    const uint32_t s = (fp >> (3 * l)) & 7u;
+                    uint32_t sn;
+                    if (s == 0u) {
+                        uint32_t cnt = 0u;                   // thresholds at or below the word: the smallest j with w < onset[j], the row being nondecreasing
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (j < K && w >= on[l * 4 + j]) cnt += 1u;
+                        sn = cnt < (uint32_t)K ? cnt + 1u : 0u;
+                        if (sn > 0u && (int32_t)fe[3 + 2 * l] < 0) fe[3 + 2 * l] = (uint32_t)(Ef.tick0 + i);
+                    } else sn = w < cr[l * 4 + (int)s - 1] ? 0u : s;
+                    fp = (fp & ~(7u << (3 * l))) | sn << (3 * l);
+                    uint32_t r0 = 0x3f800000u, r1 = 0u;          // the neutral row (1, 0)
+                    if (sn > 0u) {
+                        const uint32_t* mode = md + (l * 4 + (int)sn - 1) * 2;
+                        r0 = mode[0]; r1 = mode[1];
+                    } else if (Ef.sched) { r0 = Ef.sched[sch + 2u * l]; r1 = Ef.sched[sch + 2u * l + 1u]; }
+                    Ef.dst[out + 2u * l] = r0; Ef.dst[out + 2u * l + 1u] = r1;
+                }
+        }
         if (Pd.chain) {
             uint32_t c2[2], ek[2];
             split2(dc[0], dc[1], c2, ek);
@@ -502,15 +570,21 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
 #pragma unroll
         for (int e = 0; e < 6; ++e) Pd.state[(size_t)b * 6 + e] = dg[e];
     }
+    if (Ef.chain) {
+        fe[0] = fc[0]; fe[1] = fc[1];
+#pragma unroll
+        for (int l = 0; l < 8; ++l)
+            if (l < Ef.m) fe[2 + 2 * l] = (fp >> (3 * l)) & 7u;
+    }
 }
 
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st, const LoopObserve& O,
-                                   const LoopScore& Z, const LoopProcess& G) {
+                                   const LoopScore& Z, const LoopProcess& G, const LoopEvents& E) {
     if (B < 1 || substeps < 1 || ticks < 0 || xi_ticks < ticks) return hipErrorInvalidValue;
     // ticks = 0 is the scoring form and nothing else: score words, no observation, no key buffers
     if ((ticks == 0) != (Z.words != nullptr)) return hipErrorInvalidValue;
     if (Z.words) {
-        if (O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev || G.dist.chain || G.bias.chain) return hipErrorInvalidValue;
+        if (O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev || G.dist.chain || G.bias.chain || E.fault.chain || E.drop.chain) return hipErrorInvalidValue;
         if (!Z.rows || !Z.us || !Z.info || !Z.ref || Z.ticks < 1 || Z.solves < 1 || Z.solves > Z.ticks || Z.rows_per_tick < 1 || Z.m < 1 || Z.m > 8) return hipErrorInvalidValue;
         if ((Z.ref_tick_stride != 0 && Z.ref_tick_stride < 13) || (Z.ref_ep_stride != 0 && Z.ref_ep_stride != 13)) return hipErrorInvalidValue;
         if (Z.r2_pos != Z.r2_pos || Z.cos_min != Z.cos_min || Z.w2_max != Z.w2_max) return hipErrorInvalidValue;
@@ -527,7 +601,20 @@ hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float*
         if (P.sched && ((P.sched_ep_stride != 0 && P.sched_ep_stride != W) || (P.sched_tick_stride != 0 && P.sched_tick_stride < W))) return hipErrorInvalidValue;
     }
     if (G.bias.chain && (!O.q || O.beta)) return hipErrorInvalidValue;
-    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z, G);
+    // SPEC.md §11k: a present half is complete; the fault half's counts and clock are in range, the dropout half writes the flags the observation reads
+    if (E.fault.chain) {
+        const LoopEventFault& F = E.fault;
+        if (!F.par || !F.dst || F.K < 1 || F.K > 4 || F.m < 1 || F.m > 8) return hipErrorInvalidValue;
+        if ((F.par_ep_stride != 0 && F.par_ep_stride != EVENT_PAR_WORDS) || F.tick0 < 0 || (long long)F.tick0 + ticks > (1ll << 24)) return hipErrorInvalidValue;
+        if (F.sched && ((F.sched_ep_stride != 0 && F.sched_ep_stride != 2 * F.m) || (F.sched_tick_stride != 0 && F.sched_tick_stride < 2 * F.m))) return hipErrorInvalidValue;
+    }
+    if (E.drop.chain) {
+        const LoopEventDrop& D = E.drop;
+        if (!D.state || !D.drop || !D.recover || !D.dst || (D.par_ep_stride != 0 && D.par_ep_stride != 1)) return hipErrorInvalidValue;
+        if (D.sched && D.sched_ep_stride != 0 && D.sched_ep_stride != 1) return hipErrorInvalidValue;
+        if (!O.q || O.valid != D.dst || O.valid_ep_stride != 1) return hipErrorInvalidValue;
+    }
+    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z, G, E);
     return hipGetLastError();
 }
 

@@ -214,7 +214,8 @@ class MpcProblem:
                  plant_mlp_dtype=None, plant_math_mode=None, solve_period=1, solve_delay=0, motor_lag=0.0, disturbance=None, plant_of=None, rate_loop=None,
                  fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None, meas_age=None, meas_renorm=False,
                  score=None, score_ref=None, dist_process=None, dist_rng=None, dist_state=None, bias_process=None, bias_rng=None, bias_state=None,
-                 track=None, track_phase=None, track_rate=None):
+                 track=None, track_phase=None, track_rate=None, fault_process=None, fault_rng=None, fault_state=None, drop_process=None, drop_rng=None,
+                 drop_state=None):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -263,7 +264,14 @@ class MpcProblem:
         track_phase and flown at track_rate times its speed; the global tick of the run's first tick is round(curr_t / dt_0). This is a DIFFERENT arithmetic
         from the state_from_traj route above, which stays as it is, float64 and all: float32 interpolation between the knots, the same trajectory to a few
         ulps of a linear interpolant and no further. xdes is then not read; the returned values are the same. track_phase / track_rate without track raise
-        ValueError."""
+        ValueError.
+        fault_process / fault_rng / fault_state and drop_process / drop_rng / drop_state (SPEC.md §11k): a solver.FaultProcess (motor failures at random ticks; the
+        call is then a faulted one) and a solver.Dropouts (bursty loss of the estimate, stepped per solve; the call is then an observed one and needs meas_rng),
+        each drawn on the device from its own key uint32[2] (required), passed through for this one episode. fault_state int32[m][2] is (state, first onset tick)
+        per motor (None: healthy), drop_state int32[2] (state, solves dropped) (None: zeros); the global tick of the run's first tick is round(curr_t / dt_0), as
+        for track. Motor rows and flags have no frame, so nothing is converted. Behind the Gauss-Markov values and before xsub come, per chain given (faults first),
+        its rows f32[T][m][2] / int32[Ns] as the plant / the measurement read them, its key after the run and its state after the run. A key or a state without
+        its process raises ValueError."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -308,10 +316,11 @@ class MpcProblem:
             more["fault"] = f[None, None] if f.ndim == 2 else f[:, None]
         if substep_states:
             more["substep_states"] = True
-        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None or bias_process is not None
+        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None or bias_process is not None or drop_process is not None
         if observed:
             if meas_rng is None:
-                raise ValueError("MpcProblem.simulate: meas_rng (uint32[2], the observation key) is required with meas_noise / meas_bias / meas_valid / bias_process")
+                raise ValueError("MpcProblem.simulate: meas_rng (uint32[2], the observation key) is required with meas_noise / meas_bias / meas_valid / bias_process / "
+                                 "drop_process")
             Ns = -(-T // max(int(solve_period), 1))
             for name, v, signed in (("meas_noise", meas_noise, False), ("meas_bias", meas_bias, True)):
                 if v is None:
@@ -363,6 +372,19 @@ class MpcProblem:
                 g0 = None if g0 is None else np.ascontiguousarray(g0[:, idx] * sgn)
             more.update({f"{name}_process": GaussMarkov.from_coeffs(rho, scale), f"{name}_keys": np.asarray(pk, dtype=np.uint32).reshape(1, 2), f"{name}_state_in": g0})
             drawn.append((idx, sgn))
+        n_evt = 0
+        for name, proc, pk, ps, shape in (("fault", fault_process, fault_rng, fault_state, (1, self.cfg.num_motors, 2)), ("drop", drop_process, drop_rng, drop_state, (1, 2))):
+            if proc is None:
+                if pk is not None or ps is not None:
+                    raise ValueError(f"MpcProblem.simulate: {name}_rng / {name}_state need {name}_process=...")
+                continue
+            if pk is None:
+                raise ValueError(f"MpcProblem.simulate: {name}_rng (uint32[2], the chain's key) is required with {name}_process")
+            more.update({f"{name}_process": proc, f"{name}_keys": np.asarray(pk, dtype=np.uint32).reshape(1, 2),
+                         f"{name}_state_in": None if ps is None else np.asarray(ps, np.int32).reshape(shape)})
+            if name == "fault":
+                more["fault_tick0"] = int(round(float(curr_t) / float(self.cfg.time_steps[0])))
+            n_evt += 1
         if score is None and score_ref is not None:
             raise ValueError("MpcProblem.simulate: score_ref needs score=Score(...)")
         if score is not None:
@@ -396,6 +418,12 @@ class MpcProblem:
         st = OptState(_arr(u_next[0]), np.float32(i[0]), np.float32(s_next[0]), np.float32(i[2]), np.float32(i[3]), np.float32(i[4]),
                       np.float32(i[5]), np.float32(i[6]), np.float32(i[7]))
         ret = (_arr(xs), _arr(us[0]), _arr(info[0]), st, k_next[0].copy())
+        erows = ()
+        if n_evt:                       # the event chains' values sit behind the Gauss-Markov values, in front of xsub: rows, key and state of each, frameless
+            tail = out[-1:] if substep_states else ()
+            body = out[:-1] if substep_states else out
+            erows = tuple(v[0].copy() for v in body[len(body) - 3 * n_evt:])
+            out = body[:len(body) - 3 * n_evt] + tail
         prows = ()
         if drawn:                       # the processes' values sit behind the score, in front of xsub: rows, key and state of each, back in the frame of x
             tail = out[-1:] if substep_states else ()
@@ -421,7 +449,7 @@ class MpcProblem:
                 ret += (_arr(enu2ned(xhist, np) if self.convert_to_enu else xhist),)
         if zrow is not None:
             ret += (zrow,)
-        ret += prows
+        ret += prows + erows
         if substep_states:
             xsub = out[-1][0]
             ret += (_arr(enu2ned(xsub, np) if self.convert_to_enu else xsub),)

@@ -172,6 +172,158 @@ class GaussMarkov:
         return f"GaussMarkov.from_coeffs(rho={self.rho.tolist()}, scale={self.scale.tolist()})"
 
 
+def _threshold_words(p, what):
+    """min(2^32 - 1, floor(p * 2^32)) of probabilities in [0, 1], formed once in float64 (SPEC.md §11k): a word w drawn uniformly fires when w < threshold, so 0 never
+    fires and 2^32 - 1 fires on all but one word."""
+    p = np.asarray(p, np.float64)
+    if not (np.isfinite(p).all() and (p >= 0).all() and (p <= 1).all()):
+        raise ValueError(f"{what}: probabilities must lie in [0, 1]")
+    return np.minimum(np.floor(p * 4294967296.0), 4294967295.0).astype(np.uint32)
+
+
+def _rate_probability(rate_per_s, dt):
+    return -np.expm1(-np.asarray(rate_per_s, np.float64) * float(dt))
+
+
+def _duration_probability(mean_duration_s, dt):
+    d = np.asarray(mean_duration_s, np.float64)
+    if not (d > 0).all():
+        raise ValueError("from_rates: mean_duration_s must be > 0 (inf: never clears)")
+    with np.errstate(divide="ignore"):
+        return np.where(np.isinf(d), 0.0, -np.expm1(-float(dt) / d))
+
+
+class FaultProcess:
+    """Motor faults at RANDOM times, drawn ON THE DEVICE from a key chain (SPEC.md §11k): closed_loop(fault_process=...) steps, per episode and motor, a Markov chain
+    with K <= 4 failure modes once per control tick. FaultProcess(p_onset, p_clear, modes): p_onset f64[m][K] or [B][m][K] is the probability PER TICK that a healthy
+    motor enters mode j (not cumulative; a row's sum may not exceed 1), p_clear, same shape, the probability per tick that a motor in mode j recovers (0: the failure
+    is permanent), modes f32[m][K][2] or [B][m][K][2] the fault row (kappa, beta) of each mode, as a row of closed_loop(fault=...) — see fault_schedule() for the
+    recipes. The device compares threefry words with uint32 thresholds min(2^32 - 1, floor(p * 2^32)), the onset ones cumulated in float64 first, so a probability of
+    0 is exactly never and 1 is all but one word in 2^32 ("always" is not expressible). from_rates(rate_per_s, mean_duration_s, dt, modes) takes failure rates
+    [1/s] and mean durations [s] (inf: permanent) with dt the control tick: p = 1 - exp(-rate dt), p_clear = 1 - exp(-dt / duration). from_thresholds(onset, clear,
+    modes) takes the words as they are (onset cumulative, nondecreasing along K)."""
+
+    def __init__(self, p_onset, p_clear, modes):
+        p_onset = np.asarray(p_onset, np.float64)
+        if p_onset.ndim not in (2, 3):
+            raise ValueError(f"FaultProcess: p_onset must be [m][K] or [B][m][K], got {p_onset.shape}")
+        if not (np.isfinite(p_onset).all() and (p_onset >= 0).all()):
+            raise ValueError("FaultProcess: probabilities must lie in [0, 1]")
+        cum = np.cumsum(p_onset, axis=-1)
+        if (cum[..., -1] > 1.0).any():
+            raise ValueError("FaultProcess: the onset probabilities of a motor sum to more than 1")
+        self._set(_threshold_words(cum, "FaultProcess"), _threshold_words(np.broadcast_to(np.asarray(p_clear, np.float64), p_onset.shape), "FaultProcess"), modes)
+
+    def _set(self, onset, clear, modes):
+        onset, clear = np.asarray(onset), np.asarray(clear)
+        if onset.ndim not in (2, 3) or clear.shape != onset.shape or not 1 <= onset.shape[-1] <= 4:
+            raise ValueError(f"FaultProcess: onset and clear must both be [m][K] or [B][m][K] with 1 <= K <= 4, got {onset.shape} and {clear.shape}")
+        for a in (onset, clear):
+            if a.dtype.kind not in "iu" or (a < 0).any() or (a > 0xFFFFFFFF).any():
+                raise ValueError("FaultProcess: thresholds must be integers in [0, 2^32)")
+        if (np.diff(onset.astype(np.int64), axis=-1) < 0).any():
+            raise ValueError("FaultProcess: an onset row decreases (the thresholds are cumulative)")
+        self.onset = (onset if onset.ndim == 3 else onset[None]).astype(np.uint32)
+        self.clear = (clear if clear.ndim == 3 else clear[None]).astype(np.uint32)
+        md = np.asarray(modes, np.float32)
+        if md.ndim not in (3, 4) or md.shape[-3:] != self.onset.shape[1:] + (2,):
+            raise ValueError(f"FaultProcess: modes must be [m][K][2] or [B][m][K][2] for thresholds {self.onset.shape[1:]}, got {md.shape}")
+        if not np.isfinite(md).all():
+            raise ValueError("FaultProcess: modes holds a non-finite entry")
+        self.modes = md if md.ndim == 4 else md[None]
+        self.n_modes = int(self.onset.shape[-1])
+
+    @classmethod
+    def from_rates(cls, rate_per_s, mean_duration_s, dt, modes):
+        if not float(dt) > 0:
+            raise ValueError("FaultProcess.from_rates: dt > 0 is required")
+        rate = np.asarray(rate_per_s, np.float64)
+        if not (np.isfinite(rate).all() and (rate >= 0).all()):
+            raise ValueError("FaultProcess.from_rates: rates must be finite and >= 0")
+        return cls(_rate_probability(rate, dt), _duration_probability(np.broadcast_to(np.asarray(mean_duration_s, np.float64), rate.shape), dt), modes)
+
+    @classmethod
+    def from_thresholds(cls, onset, clear, modes):
+        self = cls.__new__(cls)
+        self._set(onset, clear, modes)
+        return self
+
+    def arrays(self, B, m):
+        """(onset, clear) as contiguous u32[Bp][m][K] and modes as f32[Bp][m][K][2], Bp = 1 (one set for all episodes) or B."""
+        Bp = max(self.onset.shape[0], self.modes.shape[0])
+        if self.onset.shape[1] != m or Bp not in (1, B) or self.onset.shape[0] not in (1, Bp) or self.modes.shape[0] not in (1, Bp):
+            raise ValueError(f"FaultProcess: thresholds {self.onset.shape} and modes {self.modes.shape} do not fit {B} episodes of {m} motors")
+        K = self.n_modes
+        return (np.ascontiguousarray(np.broadcast_to(self.onset, (Bp, m, K))), np.ascontiguousarray(np.broadcast_to(self.clear, (Bp, m, K))),
+                np.ascontiguousarray(np.broadcast_to(self.modes, (Bp, m, K, 2))))
+
+    def __repr__(self):
+        return f"FaultProcess.from_thresholds(onset={self.onset.tolist()}, clear={self.clear.tolist()}, modes={self.modes.tolist()})"
+
+
+class Dropouts:
+    """Bursty loss of the state estimate, drawn ON THE DEVICE from a key chain (SPEC.md §11k): closed_loop(drop_process=...) steps a two-state chain per episode once
+    per SOLVE, valid or not; while it is in the dropped state the solve's measurement is held, as under meas_valid = 0. Dropouts(p_drop, p_recover): the
+    probability per solve of dropping out and of recovering, scalars or f64[B]. Thresholds as in FaultProcess. from_rates(rate_per_s, mean_duration_s, dt) with dt
+    the time between two solves; from_thresholds(drop, recover) takes the words as they are."""
+
+    def __init__(self, p_drop, p_recover):
+        self._set(_threshold_words(p_drop, "Dropouts"), _threshold_words(p_recover, "Dropouts"))
+
+    def _set(self, drop, recover):
+        drop, recover = np.broadcast_arrays(np.atleast_1d(drop), np.atleast_1d(recover))
+        for a in (drop, recover):
+            if a.ndim != 1 or a.dtype.kind not in "iu" or (a < 0).any() or (a > 0xFFFFFFFF).any():
+                raise ValueError("Dropouts: thresholds must be integers in [0, 2^32), scalars or [B]")
+        self.drop, self.recover = drop.astype(np.uint32), recover.astype(np.uint32)
+
+    @classmethod
+    def from_rates(cls, rate_per_s, mean_duration_s, dt):
+        if not float(dt) > 0:
+            raise ValueError("Dropouts.from_rates: dt > 0 is required")
+        rate = np.asarray(rate_per_s, np.float64)
+        if not (np.isfinite(rate).all() and (rate >= 0).all()):
+            raise ValueError("Dropouts.from_rates: rates must be finite and >= 0")
+        return cls(_rate_probability(rate, dt), _duration_probability(mean_duration_s, dt))
+
+    @classmethod
+    def from_thresholds(cls, drop, recover):
+        self = cls.__new__(cls)
+        self._set(np.asarray(drop), np.asarray(recover))
+        return self
+
+    def arrays(self, B):
+        """(drop, recover) as contiguous u32[Bp], Bp = 1 or B."""
+        if self.drop.shape[0] not in (1, B):
+            raise ValueError(f"Dropouts: thresholds {self.drop.shape} do not fit {B} episodes")
+        return np.ascontiguousarray(self.drop), np.ascontiguousarray(self.recover)
+
+    def __repr__(self):
+        return f"Dropouts.from_thresholds(drop={self.drop.tolist()}, recover={self.recover.tolist()})"
+
+
+def event_summary(fault_state, score=None):
+    """Host reduction of fault_state_next int32[B][m][2] (SPEC.md §11k): episodes with any onset, onsets per motor (episodes whose motor l left state 0 at least
+    once), the first onset tick per episode (-1: none) and, with the score words of the same run, the failure rate among faulted and among unfaulted episodes (NaN
+    for an empty group). An episode failed when its score has a first failing row."""
+    st = np.asarray(fault_state)
+    if st.ndim != 3 or st.shape[2] != 2:
+        raise ValueError(f"event_summary: fault_state must be int[B][m][2], got {st.shape}")
+    first = st[:, :, 1]
+    hit = first >= 0
+    faulted = hit.any(axis=1)
+    out = {"episodes": int(st.shape[0]), "faulted": int(faulted.sum()), "onsets_per_motor": hit.sum(axis=0).astype(np.int64),
+           "first_onset_tick": np.where(faulted, np.where(hit, first, np.iinfo(np.int32).max).min(axis=1), -1).astype(np.int64)}
+    if score is not None:
+        score = np.asarray(score)
+        if score.dtype != SCORE_DTYPE or score.shape != (st.shape[0],):
+            raise ValueError("event_summary: score must be the structured score array [B] of the same run")
+        failed = score["first_fail_row"] != 0xFFFFFFFF
+        out["fail_rate_faulted"] = float(failed[faulted].mean()) if faulted.any() else float("nan")
+        out["fail_rate_unfaulted"] = float(failed[~faulted].mean()) if (~faulted).any() else float("nan")
+    return out
+
+
 class Score:
     """What closed_loop(score=...) scores an episode against (SPEC.md §11h): pos_radius [m] around the tick's target, tilt_max [rad] from the vertical, rate_max
     [rad/s] on the body-rate vector; substeps=True scores the plant's substep states instead of the tick states. The device compares squares and a cosine, so
@@ -1038,7 +1190,8 @@ class SdeMpcSolver:
                     rate_loop=None, rate_integ_in=None, rate_tail_in=None, fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None,
                     meas_keys=None, xmeas_in=None, meas_age=None, meas_age_max=None, meas_renorm=False, xhist_in=None, score=None, score_ref=None, score_in=None,
                     outputs=True, dist_process=None, dist_keys=None, dist_state_in=None, bias_process=None, bias_keys=None, bias_state_in=None,
-                    track=None, track_of=None, track_phase=None, track_rate=None, track_offset=None, track_tick0=None, track_renorm=None):
+                    track=None, track_of=None, track_phase=None, track_rate=None, track_offset=None, track_tick0=None, track_renorm=None,
+                    fault_process=None, fault_keys=None, fault_state_in=None, fault_tick0=0, drop_process=None, drop_keys=None, drop_state_in=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -1149,7 +1302,23 @@ class SdeMpcSolver:
         own model; every keyword above still applies) and the returned tuple is unchanged: nothing new comes back. Windows and targets depend on the global tick
         alone, so passing track_tick0 + T as the next call's track_tick0 with the other continuation values continues the run bit for bit, under the conditions
         stated above for them. xref together with track, a track_* keyword or score_ref="track" without track, raise ValueError; with none of the seven given
-        nothing of this paragraph is touched."""
+        nothing of this paragraph is touched.
+
+        fault_process / fault_keys / fault_state_in / fault_tick0 and drop_process / drop_keys / drop_state_in (SPEC.md §11k, sdempc_closed_loop_batch_events): motor
+        faults and estimator dropouts at RANDOM TIMES, drawn on the device in integers alone, so that a reliability campaign is described by keys and O(B) thresholds
+        instead of a [T][B][m][2] fault array and an [Ns][B] flag array. fault_process is a FaultProcess with its own key chain fault_keys uint32[B][2] (required):
+        per episode and motor a Markov chain with up to four failure modes takes one step per control TICK, ticks inside a solve period included, and the row the
+        plant reads at tick k is the mode's (kappa, beta) while the motor is failed and otherwise the row of `fault` (when given as well) or the neutral (1, 0). The
+        state after the step of tick k is the state during it, so a motor can be failed at tick 0. fault_state_in int32[B][m][2] (None: healthy) holds per motor
+        (state, first): first is the GLOBAL tick fault_tick0 + k of the first onset, or -1. It makes the call a faulted one. drop_process is a Dropouts with its own
+        chain drop_keys: one step per SOLVE, valid or not, before the measurement is formed; the solve is a dropout while the chain is in its dropped state, or where
+        meas_valid (when given as well) says so. drop_state_in int32[B][2] (None: zeros) is (state, solves dropped). It makes the call an observed one and needs
+        meas_keys, whose chain it does not touch. Behind the bias process's values and before xsub (which stays LAST) come, with fault_process, fault_rows
+        f32[B][T][m][2] (the rows the plant read), fault_keys_next and fault_state_next, and with drop_process valid_rows int32[B][Ns] (the flags the measurement
+        read), valid_keys_next and valid_state_next; the rows are None under outputs=False. Carrying the *_next values back in continues a chain bit for bit: the
+        fault chain for any T (with fault_tick0 + T as the next fault_tick0), the dropout chain when T is a multiple of solve_period. event_summary reduces
+        fault_state_next. A process without its keys, or keys / a state / a tick without the process, raises ValueError; with none of the seven given nothing of
+        this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -1226,8 +1395,43 @@ class SdeMpcSolver:
                 raise ValueError(f"closed_loop: {name}_state_in holds a non-finite entry")
             procs[name] = (W_, rho_, scale_, self._keys(pk, B), ps)
         drawn = bool(procs)
+        evts = {}
+        if fault_process is None:
+            if fault_keys is not None or fault_state_in is not None or fault_tick0 != 0:
+                raise ValueError("closed_loop: fault_keys / fault_state_in / fault_tick0 need fault_process=FaultProcess(...)")
+        else:
+            if not isinstance(fault_process, FaultProcess):
+                raise ValueError("closed_loop: fault_process must be a FaultProcess")
+            if fault_keys is None:
+                raise ValueError("closed_loop: fault_keys (uint32[B][2], the fault chain) is required with fault_process")
+            f_tick0 = int(fault_tick0)
+            if f_tick0 < 0 or f_tick0 + max(T, 0) >= 1 << 24:
+                raise ValueError("closed_loop: fault_tick0 must be >= 0 and fault_tick0 + T below 2^24")
+            f_on, f_cl, f_md = fault_process.arrays(B, self.m)
+            f_st = None
+            if fault_state_in is not None:
+                f_st = np.ascontiguousarray(fault_state_in, dtype=np.int32)
+                if f_st.shape != (B, self.m, 2) or (f_st[..., 0] < 0).any() or (f_st[..., 0] > fault_process.n_modes).any() or (f_st[..., 1] < -1).any():
+                    raise ValueError(f"closed_loop: fault_state_in must be int32[{B}][{self.m}][2] of (state in 0 .. n_modes, first tick >= -1)")
+            evts["fault"] = (f_on, f_cl, f_md, self._keys(fault_keys, B), f_st, f_tick0)
+        if drop_process is None:
+            if drop_keys is not None or drop_state_in is not None:
+                raise ValueError("closed_loop: drop_keys / drop_state_in need drop_process=Dropouts(...)")
+        else:
+            if not isinstance(drop_process, Dropouts):
+                raise ValueError("closed_loop: drop_process must be a Dropouts")
+            if drop_keys is None:
+                raise ValueError("closed_loop: drop_keys (uint32[B][2], the dropout chain) is required with drop_process")
+            d_dr, d_re = drop_process.arrays(B)
+            d_st = None
+            if drop_state_in is not None:
+                d_st = np.ascontiguousarray(drop_state_in, dtype=np.int32)
+                if d_st.shape != (B, 2) or (d_st[:, 0] < 0).any() or (d_st[:, 0] > 1).any() or (d_st[:, 1] < 0).any():
+                    raise ValueError(f"closed_loop: drop_state_in must be int32[{B}][2] of (state in 0 .. 1, solves dropped >= 0)")
+            evts["drop"] = (d_dr, d_re, self._keys(drop_keys, B), d_st)
+        events = bool(evts)
         scenario = scenario or "dist" in procs
-        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None or "bias" in procs
+        observed = meas_noise is not None or meas_bias is not None or meas_valid is not None or "bias" in procs or "drop" in evts
         if not observed and (meas_keys is not None or xmeas_in is not None):
             raise ValueError("closed_loop: meas_keys / xmeas_in need one of meas_noise / meas_bias / meas_valid / bias_process")
         if observed:
@@ -1310,8 +1514,8 @@ class SdeMpcSolver:
                     raise ValueError(f"closed_loop: score_in must be the structured score array [{B}] a previous call returned, got dtype {score_in.dtype} and shape {score_in.shape}")
         if score_track and not scored:
             raise ValueError('closed_loop: score_ref="track" needs score=Score(...)')
-        faulted = flt is not None or bool(substep_states) or observed or scored or drawn or tracked
-        full = scored or drawn or tracked          # the entry points from the scored one on take every layer's arguments, NULL where a layer is absent
+        faulted = flt is not None or bool(substep_states) or observed or scored or drawn or tracked or events
+        full = scored or drawn or tracked or events          # the entry points from the scored one on take every layer's arguments, NULL where a layer is absent
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
             raise ValueError("closed_loop: rate_integ_in / rate_tail_in need rate_loop=...")
         if rate_loop is not None and not isinstance(rate_loop, RateLoop):
@@ -1439,9 +1643,9 @@ class SdeMpcSolver:
                 z_out = np.zeros(B, SCORE_DTYPE)
                 lead = [C.byref(zc), None if score_in is None else score_in.ctypes.data_as(u32p)] + lead
                 more, ret = more + (z_out.ctypes.data_as(u32p),), ret + (z_out,)
-            elif drawn or tracked:  # (no score: a NULL score cfg and NULL score pointers)
+            elif drawn or tracked or events:  # (no score: a NULL score cfg and NULL score pointers)
                 lead, more = [None, None] + lead, more + (None,)
-            if drawn or tracked:               # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
+            if drawn or tracked or events:               # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
                 cfgs, keep_p = [], []
                 for name, Nrows in (("dist", max(T, 0)), ("bias", max(Ns, 0))):
                     if name not in procs:
@@ -1459,10 +1663,42 @@ class SdeMpcSolver:
                 lead = cfgs + lead
             if tracked:             # the drawn entry point's arguments behind the track cfg; nothing new comes back
                 lead = [C.byref(tkc)] + lead
+            elif events:            # (no track: a NULL track cfg)
+                lead = [None] + lead
+            if events:              # the tracked entry point's arguments behind (fault_proc, drop_proc), then rows, keys_next and state_next of each chain
+                i32p = C.POINTER(C.c_int32)
+                ecfgs, keep_e = [None, None], []
+                if "fault" in evts:
+                    f_on, f_cl, f_md, fk, f_st, f_tick0 = evts["fault"]
+                    fpc = _abi.SdempcFaultProcessCfg(C.sizeof(_abi.SdempcFaultProcessCfg), f_on.shape[2], f_on.shape[0], f_on.ctypes.data_as(u32p), f_cl.ctypes.data_as(u32p),
+                                                     _fp(f_md), fk.ctypes.data_as(u32p), None if f_st is None else f_st.ctypes.data_as(i32p), f_tick0)
+                    keep_e.append(fpc)
+                    ecfgs[0] = C.byref(fpc)
+                    f_rows = np.zeros((B, max(T, 0), self.m, 2), np.float32) if outputs else None
+                    fk_next, fs_next = np.zeros((B, 2), np.uint32), np.zeros((B, self.m, 2), np.int32)
+                    more = more + (None if f_rows is None else _fp(f_rows), fk_next.ctypes.data_as(u32p), fs_next.ctypes.data_as(i32p))
+                    ret = ret + (f_rows, fk_next, fs_next)
+                else:
+                    more = more + (None, None, None)
+                if "drop" in evts:
+                    d_dr, d_re, dk, d_st = evts["drop"]
+                    dpc = _abi.SdempcDropoutProcessCfg(C.sizeof(_abi.SdempcDropoutProcessCfg), d_dr.shape[0], d_dr.ctypes.data_as(u32p), d_re.ctypes.data_as(u32p),
+                                                       dk.ctypes.data_as(u32p), None if d_st is None else d_st.ctypes.data_as(i32p))
+                    keep_e.append(dpc)
+                    ecfgs[1] = C.byref(dpc)
+                    v_rows = np.zeros((B, max(Ns, 0)), np.int32) if outputs else None
+                    vk_next, vs_next = np.zeros((B, 2), np.uint32), np.zeros((B, 2), np.int32)
+                    more = more + (None if v_rows is None else v_rows.ctypes.data_as(i32p), vk_next.ctypes.data_as(u32p), vs_next.ctypes.data_as(i32p))
+                    ret = ret + (v_rows, vk_next, vs_next)
+                else:
+                    more = more + (None, None, None)
+                lead = ecfgs + lead
             if substep_states:
                 ret = ret + (xsub,)
         # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
-        if tracked:
+        if events:
+            entry = _abi.events_entry(self.lib)
+        elif tracked:
             entry = _abi.tracked_entry(self.lib)
         elif drawn:
             entry = _abi.drawn_entry(self.lib)

@@ -41,10 +41,17 @@
      lemniscate as a periodic table of 161 knots, every episode entering it at its own phase and flying it at its own rate (0.8 .. 1.2); with --score the targets are cut
      from the table as well. It makes the call the timed one. --per-episode-xref gives --small-batch the route it replaces: a host array with a window per solve and
      episode on the same lemniscate (the C2 loop always stages one). So `--timed --per-episode-xref` against `--track` is the array route against the table.
+ 13. --fault-process / --drop-process: motor faults and estimator dropouts drawn on the device from key chains (SPEC.md §11k, sdempc_closed_loop_batch_events) instead of
+     host rows — --fault-process a Markov chain per episode and motor with two modes (dead, and weakened to 60 %), around one failure per 4 s of flight and motor,
+     lasting 1 s on average, thresholds per episode (with --fault as well the host rows are the schedule a healthy motor reads); --drop-process, with --observe, a
+     two-state chain per episode stepped per solve (one solve in four dropped, bursts of two solves), whose flags REPLACE the meas_valid rows (noise and bias stay host
+     rows). Apply to --small-batch and to the C2 loop; either makes the call the timed one. So `--fault --observe` against `--fault-process --observe --drop-process`
+     is host rows against keys for the same two ingredients.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
                                         [--fault] [--substep-states] [--observe] [--age A] [--renorm]
                                         [--score] [--no-outputs] [--score-substeps] [--dist-process] [--bias-process] [--track] [--per-episode-xref]
+                                        [--fault-process] [--drop-process]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -90,7 +97,11 @@ ap.add_argument("--dist-process", action="store_true", help="gusts drawn on the 
 ap.add_argument("--bias-process", action="store_true", help="with --observe: the estimator bias drawn on the device, one Gauss-Markov step per solve, instead of meas_bias rows (SPEC.md §11i)")
 ap.add_argument("--track", action="store_true", help="reference windows (and score targets) cut on the device from a trajectory table, per-episode phase and rate (SPEC.md §11j)")
 ap.add_argument("--per-episode-xref", action="store_true", help="--small-batch: a host xref array with a lemniscate window per solve and episode instead of one hold window")
+ap.add_argument("--fault-process", action="store_true", help="motor faults drawn on the device, one step of a Markov chain per motor and control tick (SPEC.md §11k)")
+ap.add_argument("--drop-process", action="store_true", help="with --observe: estimator dropouts drawn on the device, one step per solve, instead of meas_valid rows (SPEC.md §11k)")
 a = ap.parse_args()
+if a.drop_process and not a.observe:
+    ap.error("--drop-process needs --observe")
 if a.track and a.per_episode_xref:
     ap.error("--track replaces the xref array: not with --per-episode-xref")
 if a.bias_process and not a.observe:
@@ -156,6 +167,18 @@ def scenario_kw(kw, B, T):
             gm = GaussMarkov(0.3 * scale * rng.uniform(0.5, 1.5, (B, 12)), rng.uniform(0.3, 2.0, (B, 12)), DT_TICK * max(a.period, 1))
             kw.pop("meas_bias")
             kw.update(bias_process=gm, bias_keys=np.stack([prng.PRNGKey(30000 + b) for b in range(B)]), bias_state_in=gm.stationary_state(rng, B))
+    if a.fault_process or a.drop_process:
+        from sde4mbrl_px4_amd.solver import Dropouts, FaultProcess
+        rng = np.random.default_rng(12)
+        m = model.num_motors
+        if a.fault_process:
+            modes = np.zeros((B, m, 2, 2), np.float32)
+            modes[:, :, 1, 0] = rng.uniform(0.5, 0.7, (B, m))
+            fp = FaultProcess.from_rates(rng.uniform(0.08, 0.17, (B, m, 2)), rng.uniform(0.5, 1.5, (B, m, 2)), DT_TICK, modes)
+            kw.update(fault_process=fp, fault_keys=np.stack([prng.PRNGKey(40000 + b) for b in range(B)]))
+        if a.drop_process:
+            kw.pop("meas_valid")
+            kw.update(drop_process=Dropouts(rng.uniform(0.12, 0.22, B), rng.uniform(0.4, 0.6, B)), drop_keys=np.stack([prng.PRNGKey(50000 + b) for b in range(B)]))
     if a.score:
         from sde4mbrl_px4_amd.solver import Score
         kw["score"] = Score(pos_radius=1.0, tilt_max=0.6, rate_max=6.0, substeps=a.score_substeps)
@@ -220,6 +243,10 @@ if a.dist_process:
     tag += " dist-process"
 if a.bias_process:
     tag += " bias-process"
+if a.fault_process:
+    tag += " fault-process"
+if a.drop_process:
+    tag += " drop-process"
 if a.track:
     tag += " track"
 if a.per_episode_xref:
@@ -233,7 +260,7 @@ def report_score(out, T):
     if not a.score:
         return
     from sde4mbrl_px4_amd.solver import score_summary
-    at = -1 - (1 if a.substep_states else 0) - 3 * (int(a.dist_process) + int(a.bias_process))      # the score sits in front of the process values and of xsub
+    at = -1 - (1 if a.substep_states else 0) - 3 * (int(a.dist_process) + int(a.bias_process) + int(a.fault_process) + int(a.drop_process))      # the score sits in front of the process values and of xsub
     s = score_summary(out[at], solves=-(-T // max(a.period, 1)))
     print(f"  score: success {s['success_rate']:.3f}, median RMS position error {float(np.median(s['rms_pos_err'])):.3f} m, worst tilt {s['worst_tilt_deg']:.1f} deg, "
           f"{s['mean_steps']:.2f} iterations and {s['mean_ls_trials']:.2f} trials per solve", flush=True)
