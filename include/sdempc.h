@@ -982,6 +982,79 @@ int sdempc_closed_loop_batch_events(sdempc_handle* h, const sdempc_fault_process
                                     float* fault_rows /*[B][T][m][2] or NULL*/, uint32_t* fault_keys_next /*[B][2] or NULL*/, int32_t* fault_state_next /*[B][m][2] or NULL*/,
                                     int32_t* valid_rows /*[B][Ns] or NULL*/, uint32_t* valid_keys_next /*[B][2] or NULL*/, int32_t* valid_state_next /*[B][2] or NULL*/);
 
+/* ---- batched closed loop flown by the geometric baseline controller (SPEC.md §11l) -------------------
+ * sdempc_closed_loop_batch_events with the solve of every solve period, and nothing else, replaced by a geometric tracking controller evaluated on the device: PD
+ * position feedback with a clip on the norm of the acceleration, a desired attitude from the desired acceleration and the reference heading, the SO(3) attitude
+ * error as body-rate commands and a collective thrust. It publishes what the rate loop of sdempc_closed_loop_batch_rate consumes, so `rate` is required and its
+ * motor_weight must be 0. Key schedule (the split that feeds the solve's noise still happens; the noise is not drawn), measured / aged state, reference window (xref
+ * or track), plant, rate loop, lag, delay, period, scenario, faults, processes, events, score, chunking and continuation are that entry point's, untouched: the same
+ * keys and processes fly the MPC through it and the baseline through this one, and the two score arrays are a paired comparison.
+ * Per episode and solve, all in float32, every product and fma as written (SPEC.md §11l fixes the order; rsqrt is the software form of SPEC.md §3.2 whatever the
+ * handle's math_mode; R(q) is SPEC.md §5.2's): x = (p, v, q, w) the state the solve would have started from (the plant's, or the estimate xm), w0 / w1 rows ref_row
+ * and ref_row + 1 of the episode's window.
+ *   e_p = p - p(w0), e_v = v - v(w0);  a_i = -fma(kv_i, e_v_i, kp_i e_p_i);  n2 = fma(a2, a2, fma(a1, a1, a0 a0));  if n2 > amax amax: a = a (amax rsqrt(n2))
+ *   ff_i = accel_ff ? (v_i(w1) - v_i(w0)) inv_dt : 0;  d = (a0 + ff0, a1 + ff1, (a2 + ff2) + g)
+ *   nd = |d|^2 (same chain);  zb = d rsqrt(nd);  xc = (R00, R10, 0) of R(q(w0));  y = zb x xc;  ny = |y|^2;  yb = y rsqrt(ny);  xb = yb x zb;  Rd = [xb yb zb]
+ *   M = Rd^T R(q);  w* = inv_tau (M12 - M21, M20 - M02, M01 - M10)
+ *   c = clamp(fma(kT, d . zb_cur, k0), c_lo, c_hi), zb_cur the third column of R(q), the CURRENT attitude
+ *   unless nd > 0 and ny > 0 (zero or NaN): w* = 0 and c = clamp(k0, c_lo, c_hi)
+ * The period then flies the table uopt[t][l] = c (t < H, l < m), xevol[0] = x, xevol[t][10..12] = w* (t = 1 .. H, every other word 0); info of the solve is
+ * (0, stepsize, 0, 0, 0, 0, 0, 0) and the step size is handed through. u_next holds thrust rows.
+ * The parameter arrays hold `batch` sets, 1 or B (a campaign can sweep them). inv_dt 0 lets the library form float32(1) / float32(time_steps[ref_row]).
+ * Checked before the first HIP call, SDEMPC_EINVAL for: geo NULL or a wrong struct_size, batch not 1 or B, a NULL parameter array, accel_ff other than 0 / 1, ref_row
+ * outside [0, H - 1], inv_dt neither 0 nor the value above, a non-finite or negative kp, kv, amax, inv_tau or g, a non-finite kT or k0, c_lo > c_hi or either outside
+ * some motor's input_bound, no rate cfg, motor_weight != 0; then everything sdempc_closed_loop_batch_events refuses. Not built (SPEC.md §11l): the quaternion-error
+ * mode, rotor drag, feed-through, a controller per plant substep, a baseline that is told of a fault. No ABI version change: detect the entry point by its symbol. */
+typedef struct sdempc_geo_cfg {
+    int32_t struct_size;   /* sizeof(sdempc_geo_cfg) */
+    int32_t batch;         /* parameter sets: 1 or B */
+    const float* kp;       /* [batch][3] position gains, finite and >= 0 */
+    const float* kv;       /* [batch][3] velocity gains, finite and >= 0 */
+    const float* amax;     /* [batch] clip of |a_fb|, finite and >= 0 */
+    const float* inv_tau;  /* [batch] 1 / attitude time constant, finite and >= 0 */
+    const float* g;        /* [batch] gravity, finite and >= 0 */
+    const float* kT;       /* [batch] thrust per acceleration, finite */
+    const float* k0;       /* [batch] thrust offset, finite */
+    const float* c_lo;     /* [batch] thrust clamp, inside every motor's input_bound */
+    const float* c_hi;     /* [batch] */
+    int32_t accel_ff;      /* 1: feed-forward acceleration from the window's velocities */
+    int32_t ref_row;       /* 0 .. H - 1 */
+    float inv_dt;          /* 0, or float32(1) / float32(time_steps[ref_row]) */
+} sdempc_geo_cfg;
+int sdempc_closed_loop_batch_baseline(sdempc_handle* h, const sdempc_geo_cfg* geo,
+                                        const sdempc_fault_process_cfg* fault_proc /*or NULL*/, const sdempc_dropout_process_cfg* drop_proc /*or NULL*/,
+                                      const sdempc_track_cfg* track /*or NULL*/,
+                                      const sdempc_process_cfg* dist_proc /*or NULL, W = 6*/, const sdempc_process_cfg* bias_proc /*or NULL, W = 12*/,
+                                      const sdempc_score_cfg* score /*or NULL*/, const uint32_t* score_in /*[B][16] or NULL*/,
+                                      const sdempc_age_cfg* age_cfg /*or NULL*/, const float* xhist_in /*[B][age_max][13] or NULL*/,
+                                      const sdempc_obs_cfg* obs /*or NULL*/, const uint32_t* obs_keys /*[B][2]; NULL without obs*/, const float* xmeas_in /*[B][13] or NULL*/,
+                                      const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*required*/,
+                                      const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                      const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                      const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                      const float* xref /*NULL with track*/, int32_t xref_solves /*0 with track*/, int32_t xref_batch,
+                                      const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                      const float* u_act_in /*[B][m] or NULL*/,
+                                      float* xs /*[B][T+1][13]; may be NULL with score*/, float* us /*[B][T][m]; may be NULL with score*/,
+                                      sdempc_info* info /*[B][Ns]; may be NULL with score*/,
+                                      float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                      uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                      const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                      float* ws /*[B][T][4]; NULL without rate; may be NULL with score*/, float* rate_integ_next /*[B][3] or NULL*/,
+                                      float* rate_tail_next /*[B][H][3] or NULL*/,
+                                      float* xsub /*[B][T * substeps][13] or NULL*/,
+                                      float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
+                                      float* xhist_next /*[B][age_max][13] or NULL*/, uint32_t* score_out /*[B][16]; NULL without score*/,
+                                      float* dist_rows /*[B][T][6] or NULL*/, uint32_t* dist_keys_next /*[B][2] or NULL*/, float* dist_state_next /*[B][6] or NULL*/,
+                                      float* bias_rows /*[B][Ns][12] or NULL*/, uint32_t* bias_keys_next /*[B][2] or NULL*/, float* bias_state_next /*[B][12] or NULL*/,
+                                      float* fault_rows /*[B][T][m][2] or NULL*/, uint32_t* fault_keys_next /*[B][2] or NULL*/, int32_t* fault_state_next /*[B][m][2] or NULL*/,
+                                      int32_t* valid_rows /*[B][Ns] or NULL*/, uint32_t* valid_keys_next /*[B][2] or NULL*/, int32_t* valid_state_next /*[B][2] or NULL*/);
+/* The controller alone: out[b] = (c, w*[3]) for state x[b] and window xref[b or 0] (Bx 1 or B), with the parameter sets of `geo` (batch 1 or B). For users, and the
+ * direct handle on the device code of this section. Checked as above where it applies (no rate cfg is involved: the clamp bounds are still checked). */
+int sdempc_geo_command_batch(sdempc_handle* h, const sdempc_geo_cfg* geo, int32_t B, const float* x /*[B][13]*/, const float* xref /*[Bx][H+1][13]*/, int32_t Bx,
+                             float* out /*[B][4]*/);
+
+
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so
  * repeating the call runs in the one-workgroup-per-instance layout. Also SDEMPC_EDEVICE when a large throughput launch that hands its

@@ -410,6 +410,40 @@ def events_entry(lib):
     return fn
 
 
+class SdempcGeoCfg(C.Structure):
+    """sdempc_geo_cfg (SPEC.md §11l): the parameter sets of the geometric baseline controller of sdempc_closed_loop_batch_baseline / sdempc_geo_command_batch."""
+    _fields_ = [("struct_size", C.c_int32), ("batch", C.c_int32)] + \
+               [(n, C.POINTER(C.c_float)) for n in ("kp", "kv", "amax", "inv_tau", "g", "kT", "k0", "c_lo", "c_hi")] + \
+               [("accel_ff", C.c_int32), ("ref_row", C.c_int32), ("inv_dt", C.c_float)]
+
+
+def baseline_entry(lib):
+    """sdempc_closed_loop_batch_baseline (SPEC.md §11l) with its prototype set: a geo cfg in front of the events entry point's arguments; nothing new comes back.
+    Detected by symbol and only when a call needs it, as events_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_baseline
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_baseline (SPEC.md §11l): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(events_entry(lib).argtypes)
+        fn.argtypes = [a[0], C.POINTER(SdempcGeoCfg)] + a[1:]
+        fn.restype = C.c_int
+    return fn
+
+
+def geo_command_entry(lib):
+    """sdempc_geo_command_batch (SPEC.md §11l) with its prototype set. Detected by symbol and only when a call needs it, as baseline_entry is."""
+    try:
+        fn = lib.sdempc_geo_command_batch
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_geo_command_batch (SPEC.md §11l): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        fp = C.POINTER(C.c_float)
+        fn.argtypes = [C.c_void_p, C.POINTER(SdempcGeoCfg), C.c_int32, fp, fp, C.c_int32, fp]
+        fn.restype = C.c_int
+    return fn
+
+
 def reference_windows_entry(lib):
     """sdempc_reference_windows (SPEC.md §11j) with its prototype set. Detected by symbol and only when a call needs it, as tracked_entry is."""
     try:
@@ -503,6 +537,7 @@ EXPORTED_SYMBOLS = [
     "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault", "sdempc_closed_loop_batch_observed",
     "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored", "sdempc_closed_loop_batch_drawn",
     "sdempc_closed_loop_batch_tracked", "sdempc_reference_windows", "sdempc_closed_loop_batch_events",
+    "sdempc_closed_loop_batch_baseline", "sdempc_geo_command_batch",
     "sdempc_tube_batch", "sdempc_tube_batch_keys", "sdempc_tube_batch_dev",
     "sdempc_risk_batch", "sdempc_risk_batch_keys", "sdempc_risk_batch_dev",
     "sdempc_bands_batch", "sdempc_bands_batch_keys", "sdempc_bands_batch_dev",

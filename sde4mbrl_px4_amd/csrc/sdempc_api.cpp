@@ -203,6 +203,9 @@ struct sdempc_handle {
     // chain's row (EVENT_EP_WORDS: key u32[2], then (s, first) i32 per motor), the dropout chain u32[2] and state i32[2], then the row of fault parameters
     // (EVENT_PAR_WORDS: onset u32[8][4], clear u32[8][4], modes f32[8][4][2]) and the dropout thresholds (u32 drop, u32 recover)
     DevBuf d_evt;
+    // the geometric baseline controller (sdempc_closed_loop_batch_baseline, sdempc_geo_command_batch; allocated on first use): the parameter rows f32[max_batch][GEO_PAR_WORDS],
+    // then the commands f32[max_batch][4] of sdempc_geo_command_batch
+    DevBuf d_geo;
     // closed loop tracking a trajectory (sdempc_closed_loop_batch_tracked with a track cfg, sdempc_reference_windows; allocated on first use, grown, never shrunk): the set of
     // the current call — first / knots i32[n_tables], period / inv_period f32[n_tables], t / w f32[sum L], x f32[sum L][13], c f32[H+1], table_of i32[B], phase / rate f32[B],
     // offset f32[B][3] — in one allocation; track_stage: its host image, alive until the call returns
@@ -653,6 +656,12 @@ struct EventRun {
     uint32_t* valid_keys_next;                  // [B][2] or null
     int32_t* valid_state_next;                  // [B][2] or null
 };
+// SPEC.md §11l: the baseline controller of one sdempc_closed_loop_batch_baseline call (host pointers, checked by check_geo). Given only by that entry point: without it
+// the call is the events call, launch for launch.
+struct GeoRun {
+    const sdempc_geo_cfg* cfg;
+    float inv_dt;                               // float32(1) / float32(time_steps[ref_row])
+};
 constexpr size_t PROC_WORDS = 2 + 6 + 2 + 12 + 2 * 6 + 2 * 12;      // words of d_proc per row of max_batch
 constexpr size_t EVT_MODES = 4;
 constexpr size_t EVT_WORDS = EVENT_EP_WORDS + 2 + 2 + EVENT_PAR_WORDS + 2;      // words of d_evt per row of max_batch
@@ -698,7 +707,11 @@ struct LoopCall {
     const sdempc_track_cfg* track;              // sdempc_closed_loop_batch_tracked (SPEC.md §11j): the drawn call with a trajectory set in place of xref; or NULL
     bool events;                                // sdempc_closed_loop_batch_events (SPEC.md §11k): the tracked call with the two event cfgs and their six outputs
     EventRun er;                                // (a NULL cfg: its three outputs must be NULL)
+    bool baseline;                              // sdempc_closed_loop_batch_baseline (SPEC.md §11l): the events call with the geometric controller in place of the solve
+    const sdempc_geo_cfg* geo;
 };
+int check_geo(sdempc_handle* h, const sdempc_geo_cfg* g, int B, float* inv_dt);
+int stage_geo(sdempc_handle* h, const sdempc_geo_cfg& g, hipStream_t st);
 int closed_loop_call(sdempc_handle* h, const LoopCall& c);
 int check_loop_args(sdempc_handle* h, const LoopIo& io, int solves, bool rows_optional = false, bool tracked = false);
 int check_track(sdempc_handle* h, const sdempc_track_cfg* tk, int B, long long ticks);
@@ -706,9 +719,9 @@ int stage_track(sdempc_handle* h, const sdempc_track_cfg& tk, int B, TrackRun* o
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr,
                          const ObsRun* obs = nullptr, const ScoreRun* score = nullptr, const ProcRun* proc = nullptr, const TrackRun* track = nullptr,
-                         const EventRun* evt = nullptr);
+                         const EventRun* evt = nullptr, const GeoRun* geo = nullptr);
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, bool* again);
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -808,7 +821,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_outcome, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_evt, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_outcome, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_evt, &h->d_geo, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1881,6 +1894,64 @@ int sdempc_closed_loop_batch_events(sdempc_handle* h, const sdempc_fault_process
     });
 }
 
+int sdempc_closed_loop_batch_baseline(sdempc_handle* h, const sdempc_geo_cfg* geo, const sdempc_fault_process_cfg* fault_proc, const sdempc_dropout_process_cfg* drop_proc,
+                                      const sdempc_track_cfg* track, const sdempc_process_cfg* dist_proc, const sdempc_process_cfg* bias_proc, const sdempc_score_cfg* zc,
+                                      const uint32_t* score_in, const sdempc_age_cfg* ac, const float* xhist_in, const sdempc_obs_cfg* oc, const uint32_t* obs_keys, const float* xmeas_in,
+                                      const sdempc_fault_cfg* fc, const sdempc_rate_cfg* rc_, const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc,
+                                      const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T, const float* x0, const float* xref,
+                                      int32_t xref_solves, int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in, const float* u_act_in, float* xs,
+                                      float* us, sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next, float* u_act_next, const float* rate_integ_in,
+                                      const float* rate_tail_in, float* ws, float* rate_integ_next, float* rate_tail_next, float* xsub, float* xmeas, uint32_t* obs_keys_next,
+                                      float* xmeas_next, float* xhist_next, uint32_t* score_out, float* dist_rows, uint32_t* dist_keys_next, float* dist_state_next, float* bias_rows,
+                                      uint32_t* bias_keys_next, float* bias_state_next, float* fault_rows, uint32_t* fault_keys_next, int32_t* fault_state_next, int32_t* valid_rows,
+                                      uint32_t* valid_keys_next, int32_t* valid_state_next) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    c.observed = true; c.oc = oc; c.obs_keys = obs_keys; c.xmeas_in = xmeas_in; c.xmeas = xmeas; c.obs_keys_next = obs_keys_next; c.xmeas_next = xmeas_next;
+    c.aged = true; c.ac = ac; c.xhist_in = xhist_in; c.xhist_next = xhist_next;
+    c.scored = true; c.zc = zc; c.score_in = score_in; c.score_out = score_out;
+    c.drawn = true; c.pr = {dist_proc, bias_proc, dist_rows, dist_keys_next, dist_state_next, bias_rows, bias_keys_next, bias_state_next};
+    c.track = track;
+    c.events = true; c.er = {fault_proc, drop_proc, fault_rows, fault_keys_next, fault_state_next, valid_rows, valid_keys_next, valid_state_next};
+    c.baseline = true; c.geo = geo;
+    return closed_loop_call(h, c);
+    });
+}
+
+int sdempc_geo_command_batch(sdempc_handle* h, const sdempc_geo_cfg* geo, int32_t B, const float* x, const float* xref, int32_t Bx, float* out) {
+    return guarded(h, [&]() -> int {
+    if (!h) return SDEMPC_EINVAL;
+    float inv_dt = 0.0f;
+    int rc = check_geo(h, geo, B, &inv_dt);
+    if (rc) return rc;
+    if ((rc = check_batch(h, B))) return rc;
+    if (Bx != 1 && Bx != B) return fail(h, SDEMPC_EINVAL, "baseline: Bx must be 1 or B%s");
+    if (!x || !xref || !out) return fail(h, SDEMPC_EINVAL, "NULL host pointer%s");
+    if ((rc = ensure_device(h))) return rc;
+    hipStream_t st = h->stream;
+    if ((rc = stage_geo(h, *geo, st))) return rc;
+    const size_t XR = (size_t)(h->H + 1) * SDEMPC_NX;
+    HIPCHK(h, hipMemcpyAsync(h->d_x0.p, x, sizeof(float) * (size_t)B * SDEMPC_NX, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->d_xref.p, xref, sizeof(float) * (size_t)Bx * XR, hipMemcpyHostToDevice, st));
+    LoopBaseline A{};
+    A.x = (const float*)h->d_x0.p; A.xref = (const float*)h->d_xref.p; A.xref_ep_stride = Bx > 1 ? (int)XR : 0;
+    A.par = (const float*)h->d_geo.p; A.par_ep_stride = geo->batch > 1 ? GEO_PAR_WORDS : 0;
+    A.accel_ff = geo->accel_ff; A.ref_row = geo->ref_row; A.inv_dt = inv_dt; A.H = h->H; A.m = h->m;
+    A.out = (float*)h->d_geo.p + (size_t)GEO_PAR_WORDS * h->max_batch;
+    HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, 1, st, LoopObserve{}, LoopScore{}, LoopProcess{}, LoopEvents{}, A));
+    HIPCHK(h, hipMemcpyAsync(out, A.out, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return SDEMPC_OK;
+    });
+}
+
 int sdempc_reference_windows(sdempc_handle* h, const sdempc_track_cfg* track, int32_t B, int32_t n, const int32_t* ticks, float* out) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -1971,6 +2042,12 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    GeoRun run_g{c.geo, 0.0f};
+    if (c.baseline) {          // SPEC.md §11l: the controller's cfg, then the interface it publishes to
+        if (int rc = check_geo(h, c.geo, B, &run_g.inv_dt)) return rc;
+        if (!rc_) return fail(h, SDEMPC_EINVAL, "baseline: the controller publishes thrust and body rates and needs a rate cfg%s");
+        if (rc_->struct_size == (int32_t)sizeof(sdempc_rate_cfg) && rc_->motor_weight != 0.0f) return fail(h, SDEMPC_EINVAL, "baseline: motor_weight must be 0 (the table holds no motor values)%s");
+    }
     if (c.events) {            // SPEC.md §11k: an output needs its cfg; then the fault cfg, the dropout cfg, and the observation chain the dropouts need
         const EventRun& er = c.er;
         const int m = h->m;
@@ -2169,7 +2246,45 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     TrackRun run_k;
     if (tk && (rc = stage_track(h, *tk, B, &run_k))) return rc;
     return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr,
-                                run_f.fault || run_f.xsub || (evt && evt->fault) ? &run_f : nullptr, oc ? &run_o : nullptr, zc ? &run_z : nullptr, proc, tk ? &run_k : nullptr, evt);
+                                run_f.fault || run_f.xsub || (evt && evt->fault) ? &run_f : nullptr, oc ? &run_o : nullptr, zc ? &run_z : nullptr, proc, tk ? &run_k : nullptr, evt,
+                                c.baseline ? &run_g : nullptr);
+}
+// every check of a geometric-controller cfg (SPEC.md §11l), shared by the two entry points that take one; no HIP call. inv_dt: what the launch is given
+int check_geo(sdempc_handle* h, const sdempc_geo_cfg* g, int B, float* inv_dt) {
+    auto ok = [](float v) { return fabsf(v) < INFINITY && v >= 0.0f; };
+    auto finite = [](float v) { return fabsf(v) < INFINITY; };
+    if (!g || g->struct_size != (int32_t)sizeof(sdempc_geo_cfg)) return fail(h, SDEMPC_EINVAL, "baseline: cfg NULL or struct_size mismatch%s");
+    if (g->batch != 1 && g->batch != B) return fail(h, SDEMPC_EINVAL, "baseline: batch must be 1 or B%s");
+    if (!g->kp || !g->kv || !g->amax || !g->inv_tau || !g->g || !g->kT || !g->k0 || !g->c_lo || !g->c_hi) return fail(h, SDEMPC_EINVAL, "baseline: a parameter array is NULL%s");
+    if (g->accel_ff != 0 && g->accel_ff != 1) return fail(h, SDEMPC_EINVAL, "baseline: accel_ff must be 0 or 1%s");
+    if (g->ref_row < 0 || g->ref_row > h->H - 1) return fail(h, SDEMPC_EINVAL, "baseline: ref_row must be between 0 and H - 1%s");
+    const float want = 1.0f / h->time_steps[g->ref_row];
+    if (g->inv_dt != 0.0f && !(g->inv_dt == want)) return fail(h, SDEMPC_EINVAL, "baseline: inv_dt must be 0 or (float)1 / time_steps[ref_row]%s");
+    *inv_dt = want;
+    for (int r = 0; B >= 1 && r < g->batch; ++r) {     // (B < 1 is refused with the loop arguments)
+        for (int a = 0; a < 3; ++a)
+            if (!ok(g->kp[3 * r + a]) || !ok(g->kv[3 * r + a])) return fail(h, SDEMPC_EINVAL, "baseline: kp / kv hold a non-finite or negative gain%s");
+        if (!ok(g->amax[r]) || !ok(g->inv_tau[r]) || !ok(g->g[r])) return fail(h, SDEMPC_EINVAL, "baseline: amax, inv_tau or g is non-finite or negative%s");
+        if (!finite(g->kT[r]) || !finite(g->k0[r])) return fail(h, SDEMPC_EINVAL, "baseline: kT or k0 is non-finite%s");
+        if (!(g->c_lo[r] <= g->c_hi[r])) return fail(h, SDEMPC_EINVAL, "baseline: c_lo must not exceed c_hi%s");
+        for (int l = 0; l < h->m; ++l)
+            if (!(g->c_lo[r] >= h->cfg.u_lo[l]) || !(g->c_hi[r] <= h->cfg.u_hi[l])) return fail(h, SDEMPC_EINVAL, "baseline: c_lo / c_hi must lie inside every motor's input_bound%s");
+    }
+    return 0;
+}
+// the parameter rows of a checked cfg onto the device (d_geo: GEO_PAR_WORDS floats per set), on st; the host image is copied before the call returns
+int stage_geo(sdempc_handle* h, const sdempc_geo_cfg& g, hipStream_t st) {
+    int rc;
+    if (!h->d_geo.p && (rc = dev_alloc(h, h->d_geo, sizeof(float) * (GEO_PAR_WORDS + 4) * (size_t)h->max_batch, true))) return rc;
+    std::vector<float> rows((size_t)g.batch * GEO_PAR_WORDS, 0.0f);
+    for (int r = 0; r < g.batch; ++r) {
+        float* row = &rows[(size_t)r * GEO_PAR_WORDS];
+        for (int a = 0; a < 3; ++a) { row[a] = g.kp[3 * r + a]; row[3 + a] = g.kv[3 * r + a]; }
+        row[6] = g.amax[r]; row[7] = g.inv_tau[r]; row[8] = g.g[r]; row[9] = g.kT[r]; row[10] = g.k0[r]; row[11] = g.c_lo[r]; row[12] = g.c_hi[r];
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_geo.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));       // (rows dies with this frame)
+    return 0;
 }
 // every check of a trajectory set (SPEC.md §11j), shared by the two entry points that take one; no HIP call. ticks: control ticks of the call (tick0 + ticks < 2^24)
 int check_track(sdempc_handle* h, const sdempc_track_cfg* tk, int B, long long ticks) {
@@ -2300,10 +2415,10 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt,
-                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt) {
+                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, track, evt, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, track, evt, geo, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -2401,8 +2516,9 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // writes the solve's flags into a [Pc][B] region, which the measurement reads as its valid flags (scheduled flags likewise). Both regions count in the chunk's bytes and are
 // copied back and scattered only when the caller asked for the rows.
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, bool* again) {
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, bool* again) {
     *again = false;
+    const bool flown = geo && rate && timed && plant;                      // (SPEC.md §11l: the geometric controller in place of the solve)
     const bool tracked = track && timed && plant;                          // (SPEC.md §11j)
     const int B = io.B, T = io.T, Bx = tracked ? 0 : io.xref_batch, H = h->H, m = h->m, NX = SDEMPC_NX;
     const int S = timed ? (timed->S < T ? timed->S : T) : 1;               // (a period longer than the run is one period of T ticks)
@@ -2659,6 +2775,14 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         G.bias.chain = p_bchain; G.bias.state = p_bstate; G.bias.rho = p_brho; G.bias.scale = p_bscale; G.bias.par_ep_stride = proc->bias->batch > 1 ? NB : 0;
         G.bias.sched_ep_stride = biased && obs->Bo > 1 ? NB : 0;
     }
+    LoopBaseline A{};          // (x null: absent)
+    if (flown) {
+        if ((rc = stage_geo(h, *geo->cfg, st))) return rc;
+        A.par = (const float*)h->d_geo.p; A.par_ep_stride = geo->cfg->batch > 1 ? GEO_PAR_WORDS : 0;
+        A.accel_ff = geo->cfg->accel_ff; A.ref_row = geo->cfg->ref_row; A.inv_dt = geo->inv_dt; A.H = H; A.m = m;
+        A.uopt = (float*)h->d_uopt.p; A.xevol = (float*)h->d_xmean.p; A.step = (const float*)h->d_step.p;
+        h->last_coop_B = 0;    // (no solve of this run can leave a barrier word to read)
+    }
     LoopEvents E{};            // (chains null: absent)
     if (fproc) {
         E.fault.chain = e_fep; E.fault.par = e_par; E.fault.par_ep_stride = evt->fault->batch > 1 ? EVENT_PAR_WORDS : 0; E.fault.K = KF; E.fault.m = m;
@@ -2739,7 +2863,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st, O, LoopScore{}, G, E));
             else if (plant) HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st, plant->Q.substeps));
             else HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st));
-            HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));
+            if (!flown) HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));      // (SPEC.md §11l: the split happened, its draw is not used)
             const float* win = c_xref + (xref_moves ? (size_t)jc * Bx * XR : 0);
             const float* xr = win;
             if (tracked) {             // the windows of this solve's tick, cut where the solve reads them
@@ -2751,7 +2875,11 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 xr = (const float*)h->d_xref.p;
             }
             float* info_j = c_info + (size_t)jc * B * 8;
-            if ((rc = sdempc_solve_batch_dev(h, B, seen ? d_xm : d_x, xr, h->d_noise.p, h->d_u.p, h->d_step.p, h->d_uopt.p, h->d_xmean.p, info_j, st))) return rc;
+            if (flown) {               // the controller's tables where the solve would have left its own, from the B windows the solve would have read
+                A.x = seen ? d_xm : d_x; A.info = info_j;
+                A.xref = xr; A.xref_ep_stride = (int)XR;
+                HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, LoopScore{}, LoopProcess{}, LoopEvents{}, A));
+            } else if ((rc = sdempc_solve_batch_dev(h, B, seen ? d_xm : d_x, xr, h->d_noise.p, h->d_u.p, h->d_step.p, h->d_uopt.p, h->d_xmean.p, info_j, st))) return rc;
             L.info = info_j; L.coop_bar = h->last_coop_B > 0 ? (const unsigned*)h->d_coop_bar.p : nullptr;
             L.xs = c_xs + (size_t)jc * S * B * NX; L.us = c_us + (size_t)jc * S * B * m;
             if (timed) {

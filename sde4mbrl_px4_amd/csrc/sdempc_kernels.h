@@ -326,9 +326,32 @@ struct LoopEvents {
     LoopEventFault fault;       // one step per control tick
     LoopEventDrop drop;         // one step per solve; needs LoopObserve::q, and LoopObserve::valid == dst
 };
+// SPEC.md §11l, the geometric baseline controller: ONE further launch of the period's key-schedule kernel per solve period, in its BASELINE form (ticks = 0, empty
+// LoopObserve / LoopScore / LoopProcess / LoopEvents, null key buffers: the key words are neither read nor written), where the solve is launched otherwise. Thread b
+// forms (c, omega*) of episode b from the state the solve would have started from and rows ref_row, ref_row + 1 of its reference window (sdempc_geo.inc.h) and
+// fills what the rate-loop plant launch reads: uopt[b][t][l] = c, xevol[b][0] = x, xevol[b][t >= 1] = (0 .. 0, omega*), info[b] = (0, step[b], 0 ..). With `out`
+// given it stores (c, omega*) there and nothing else (sdempc_geo_command_batch). x null means absent: every other launch passes that, and the kernel then makes no
+// memory access it did not make before.
+constexpr int GEO_PAR_WORDS = 16;                    // floats of one parameter row: kp[3], kv[3], amax, inv_tau, g, kT, k0, c_lo, c_hi, 3 unused
+struct LoopBaseline {
+    const float* x;             // [B][13] the state each command is formed from; null: not the baseline form
+    const float* xref;          // the window of episode b at xref + b * xref_ep_stride, rows of 13 floats
+    int xref_ep_stride;         // (H + 1) * 13, or 0 (one window for every episode)
+    const float* par;           // the parameter row of episode b at par + b * par_ep_stride
+    int par_ep_stride;          // GEO_PAR_WORDS, or 0 (one row for every episode: every lane of a wave loads one address)
+    int accel_ff;               // 1: feed-forward acceleration from the velocities of rows ref_row, ref_row + 1 (wave-uniform)
+    int ref_row;                // 0 .. H - 1
+    float inv_dt;               // float32(1) / float32(time_steps[ref_row])
+    int H, m;
+    float* uopt;                // [B][H][m]
+    float* xevol;               // [B][H+1][13]
+    float* info;                // [B][8]
+    const float* step;          // [B] the step size handed through
+    float* out;                 // [B][4] (c, omega*), or null: the tables above
+};
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st,
                                    const LoopObserve& O = LoopObserve{}, const LoopScore& Z = LoopScore{}, const LoopProcess& G = LoopProcess{},
-                                   const LoopEvents& E = LoopEvents{});
+                                   const LoopEvents& E = LoopEvents{}, const LoopBaseline& A = LoopBaseline{});
 // SPEC.md §11j, reference windows and score targets cut from a trajectory on the device: the row-filling launch below in its TRACKING form. The tables of a set lie
 // end to end: table j owns knots first[j] .. first[j] + knots[j] - 1 of t / w / x (w[i] = float32(1 / (t[i+1] - t[i])) formed by the library in float64; the last w of
 // a table is not read). Thread i of the launch writes one whole row of 13 floats, row i of out f32[groups][B][rows][13]: group g is tick tick0 + g, its clock value

@@ -121,6 +121,7 @@ DI float bits_to_normal(uint32_t bits) {
 #include "sdempc_risk.inc.h"
 #include "sdempc_band.inc.h"
 #include "sdempc_outcome.inc.h"
+#include "sdempc_geo.inc.h"
 namespace sdempc {
 
 // grid: x = chunks of 256 threads over [pg][r][lane] (pg < ceil(ceil(P/2)/32), r < H*6), y = instance
@@ -323,10 +324,18 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
 // step and the measurement, whose valid flag is then the word this thread has just written (O.valid addresses it); the fault chain once per tick, beside the
 // disturbance step, into row (i, b) of the period's fault rows. One step is one split, ceil(lanes / 2) blocks and per lane at most K + 1 compares; chain and
 // per-motor states stay in registers at constant indices (motor loops unrolled to 8, as the scoring form's). Both null: not one access more.
+// SPEC.md §11l (A.x given; ticks = 0, O / Z / G / E empty, keys / sub / xi null and untouched): the BASELINE form of the launch, one per solve period where the solve
+// is launched otherwise. Thread b forms the geometric controller's command of episode b and fills the tables the plant launch reads (sdempc_geo.inc.h). A.x null
+// (every period and scoring launch): not one access more.
 __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int ticks,
-                                                                      int xi_ticks, int n, LoopObserve O, LoopScore Z, LoopProcess G, LoopEvents E) {
+                                                                      int xi_ticks, int n, LoopObserve O, LoopScore Z, LoopProcess G, LoopEvents E,
+                                                                      LoopBaseline A) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
+    if (A.x) {                                           // (wave-uniform)
+        geo_fill(A, b);
+        return;
+    }
     if (Z.words) {                                       // (wave-uniform)
         uint32_t* w = Z.words + (size_t)b * 16;
         uint32_t cnt = w[0], imax = w[3], first = w[8], causes = w[9], nbad = w[10];
@@ -579,16 +588,23 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
 }
 
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st, const LoopObserve& O,
-                                   const LoopScore& Z, const LoopProcess& G, const LoopEvents& E) {
+                                   const LoopScore& Z, const LoopProcess& G, const LoopEvents& E, const LoopBaseline& A) {
     if (B < 1 || substeps < 1 || ticks < 0 || xi_ticks < ticks) return hipErrorInvalidValue;
-    // ticks = 0 is the scoring form and nothing else: score words, no observation, no key buffers
-    if ((ticks == 0) != (Z.words != nullptr)) return hipErrorInvalidValue;
+    // ticks = 0 is the scoring form or the baseline form and nothing else: score words or a state, no observation, no key buffers
+    if ((ticks == 0) != (Z.words != nullptr || A.x != nullptr) || (Z.words && A.x)) return hipErrorInvalidValue;
+    if (A.x) {      // SPEC.md §11l: a present block is complete and addresses rows inside the window
+        if (O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev || G.dist.chain || G.bias.chain || E.fault.chain || E.drop.chain) return hipErrorInvalidValue;
+        if (!A.xref || !A.par || A.H < 1 || A.m < 1 || A.m > 8 || A.ref_row < 0 || A.ref_row > A.H - 1) return hipErrorInvalidValue;
+        if ((A.xref_ep_stride != 0 && A.xref_ep_stride != (A.H + 1) * 13) || (A.par_ep_stride != 0 && A.par_ep_stride != GEO_PAR_WORDS)) return hipErrorInvalidValue;
+        if ((A.accel_ff != 0 && A.accel_ff != 1) || A.inv_dt != A.inv_dt) return hipErrorInvalidValue;
+        if (!A.out && (!A.uopt || !A.xevol || !A.info || !A.step)) return hipErrorInvalidValue;
+    }
     if (Z.words) {
         if (O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev || G.dist.chain || G.bias.chain || E.fault.chain || E.drop.chain) return hipErrorInvalidValue;
         if (!Z.rows || !Z.us || !Z.info || !Z.ref || Z.ticks < 1 || Z.solves < 1 || Z.solves > Z.ticks || Z.rows_per_tick < 1 || Z.m < 1 || Z.m > 8) return hipErrorInvalidValue;
         if ((Z.ref_tick_stride != 0 && Z.ref_tick_stride < 13) || (Z.ref_ep_stride != 0 && Z.ref_ep_stride != 13)) return hipErrorInvalidValue;
         if (Z.r2_pos != Z.r2_pos || Z.cos_min != Z.cos_min || Z.w2_max != Z.w2_max) return hipErrorInvalidValue;
-    } else if (!keys_dev || !sub_dev || !xi_dev) return hipErrorInvalidValue;
+    } else if (!A.x && (!keys_dev || !sub_dev || !xi_dev)) return hipErrorInvalidValue;
     if (O.q && (!O.x || !O.xm || !O.xmeas || (O.ep_stride != 0 && O.ep_stride != 12) || (O.valid_ep_stride != 0 && O.valid_ep_stride != 1))) return hipErrorInvalidValue;
     if ((O.age || O.renorm) && !O.q) return hipErrorInvalidValue;
     if (O.age && (!O.hist || O.age_max < 1 || O.hist_row_stride < B * 13 || (O.age_ep_stride != 0 && O.age_ep_stride != 1))) return hipErrorInvalidValue;
@@ -614,7 +630,7 @@ hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float*
         if (D.sched && D.sched_ep_stride != 0 && D.sched_ep_stride != 1) return hipErrorInvalidValue;
         if (!O.q || O.valid != D.dst || O.valid_ep_stride != 1) return hipErrorInvalidValue;
     }
-    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z, G, E);
+    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z, G, E, A);
     return hipGetLastError();
 }
 

@@ -215,7 +215,7 @@ class MpcProblem:
                  fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None, meas_age=None, meas_renorm=False,
                  score=None, score_ref=None, dist_process=None, dist_rng=None, dist_state=None, bias_process=None, bias_rng=None, bias_state=None,
                  track=None, track_phase=None, track_rate=None, fault_process=None, fault_rng=None, fault_state=None, drop_process=None, drop_rng=None,
-                 drop_state=None):
+                 drop_state=None, controller=None):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -271,7 +271,10 @@ class MpcProblem:
         per motor (None: healthy), drop_state int32[2] (state, solves dropped) (None: zeros); the global tick of the run's first tick is round(curr_t / dt_0), as
         for track. Motor rows and flags have no frame, so nothing is converted. Behind the Gauss-Markov values and before xsub come, per chain given (faults first),
         its rows f32[T][m][2] / int32[Ns] as the plant / the measurement read them, its key after the run and its state after the run. A key or a state without
-        its process raises ValueError."""
+        its process raises ValueError.
+        controller (SPEC.md §11l): a solver.GeometricController flies the episode in place of the MPC's solves — the baseline — through rate_loop (required), passed
+        through for this one episode; its gains act on quantities of the solver's frame. Everything above still applies and the returned values are the same: the
+        OptState then holds thrust rows and zero telemetry."""
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -409,7 +412,7 @@ class MpcProblem:
         out = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
             plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag,
-            disturbance=disturbance, plant_of=plant_of, **more)
+            disturbance=disturbance, plant_of=plant_of, **more, **({} if controller is None else {"controller": controller}))
         xs, us, info, u_next, s_next, k_next = out[:6]
         xs = xs[0]
         if self.convert_to_enu:

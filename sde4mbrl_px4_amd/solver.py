@@ -80,6 +80,112 @@ class RateLoop:
         return f"RateLoop(kp={self.kp.tolist()}, ki={self.ki.tolist()}, integ_limit={self.integ_limit.tolist()}, mixer={self.mixer!r}, motor_weight={self.motor_weight})"
 
 
+class GeometricController:
+    """The geometric baseline controller (SPEC.md §11l): PD position feedback with a clip on the norm of the acceleration, a desired attitude from the desired
+    acceleration and the reference heading, the SO(3) attitude error as body-rate commands and a collective thrust along the current body z axis. It publishes the
+    interface a RateLoop consumes, so closed_loop(controller=..., rate_loop=...) flies it in place of the MPC's solves, everything else untouched. kp / kv: a
+    scalar, three values (x, y, z) or f32[B][3] (one set per episode); max_acc, attctrl_tau, gravity, thrust_const, thrust_offset, thrust_min, thrust_max: a
+    scalar or f32[B]. The thrust command is clamp(thrust_const * (a_des . z_body) + thrust_offset, thrust_min, thrust_max) in the model's motor units (None: the
+    tightest input bound of the handle's motors); accel_ff adds the window's velocity difference of rows ref_row, ref_row + 1 over its time step as a feed-forward
+    acceleration. Not built: the quaternion-error mode, rotor drag, feed-through."""
+
+    def __init__(self, kp, kv, max_acc, attctrl_tau, gravity, thrust_const, thrust_offset, thrust_min=None, thrust_max=None, accel_ff=False, ref_row=0):
+        def rows(v, what, width, nonneg=True):
+            a = np.asarray(v, np.float32)
+            if width == 3 and a.ndim == 0:
+                a = np.full(3, a, np.float32)
+            a = a.reshape((1,) + a.shape) if a.ndim == (1 if width == 3 else 0) else a
+            if a.ndim != (2 if width == 3 else 1) or (width == 3 and a.shape[1] != 3) or a.shape[0] < 1:
+                raise ValueError(f"GeometricController: {what} must be a scalar" + (", three values or f32[B][3]" if width == 3 else " or f32[B]") + f", got shape {np.shape(v)}")
+            if not np.isfinite(a).all() or (nonneg and (a < 0).any()):
+                raise ValueError(f"GeometricController: {what} holds a non-finite" + (" or negative" if nonneg else "") + " value")
+            return np.ascontiguousarray(a)
+
+        self.kp, self.kv = rows(kp, "kp", 3), rows(kv, "kv", 3)
+        self.max_acc, self.gravity = rows(max_acc, "max_acc", 1), rows(gravity, "gravity", 1)
+        tau = rows(attctrl_tau, "attctrl_tau", 1)
+        if (tau <= 0).any():
+            raise ValueError("GeometricController: attctrl_tau must be > 0")
+        self.attctrl_tau = tau
+        self.inv_tau = (np.float32(1.0) / tau).astype(np.float32)
+        self.thrust_const, self.thrust_offset = rows(thrust_const, "thrust_const", 1, False), rows(thrust_offset, "thrust_offset", 1, False)
+        self.thrust_min = None if thrust_min is None else rows(thrust_min, "thrust_min", 1, False)
+        self.thrust_max = None if thrust_max is None else rows(thrust_max, "thrust_max", 1, False)
+        self.accel_ff, self.ref_row = bool(accel_ff), int(ref_row)
+        if self.ref_row < 0:
+            raise ValueError("GeometricController: ref_row must be >= 0")
+        sizes = {a.shape[0] for a in self._params() if a is not None and a.shape[0] > 1}
+        if len(sizes) > 1:
+            raise ValueError(f"GeometricController: per-episode parameters disagree on B: {sorted(sizes)}")
+        self.batch = sizes.pop() if sizes else 1
+
+    def _params(self):
+        return (self.kp, self.kv, self.max_acc, self.inv_tau, self.gravity, self.thrust_const, self.thrust_offset, self.thrust_min, self.thrust_max)
+
+    @classmethod
+    def from_yaml(cls, path, **kw):
+        """The reference's controller settings file, keys verbatim: attctrl_tau, norm_thrust_const, norm_thrust_offset, max_acc, gravity, Kp_*, Kv_*. Its thrust
+        constants belong to PX4's normalised thrust: for_model calibrates them for a model of this package. trajectory_path is ignored."""
+        import yaml
+        with open(path) as f:
+            d = yaml.safe_load(f)
+        if int(d.get("ctrl_mode", 2)) != 2:
+            raise NotImplementedError("GeometricController: ctrl_mode 1 (quaternion error) needs a division, which SPEC.md §3 does not have; only ctrl_mode 2 is built")
+        if any(float(d.get(k, 0.0)) != 0.0 for k in ("drag_dx", "drag_dy", "drag_dz")):
+            raise NotImplementedError("GeometricController: rotor drag is not built (drag_d* must be 0)")
+        if bool(d.get("feedthrough_enable", False)):
+            raise NotImplementedError("GeometricController: feedthrough_enable is not built")
+        args = dict(kp=[d["Kp_x"], d["Kp_y"], d["Kp_z"]], kv=[d["Kv_x"], d["Kv_y"], d["Kv_z"]], max_acc=d["max_acc"], attctrl_tau=d["attctrl_tau"], gravity=d["gravity"],
+                    thrust_const=d["norm_thrust_const"], thrust_offset=d["norm_thrust_offset"])
+        args.update(kw)
+        return cls(**args)
+
+    @staticmethod
+    def hover_calibration(model):
+        """(u_h, kT, k0) in float64 for a RotorSDEModel: the hover command u_h solves m (ct2 u^2 + ct1 u + ct0) = mass grav; kT = mass / (m (2 ct2 u_h + ct1)) is
+        the command per acceleration along the body axis there, k0 = u_h - kT grav."""
+        m, mass, grav = int(model.num_motors), float(model.mass), float(model.grav)
+        ct2, ct1, ct0 = (float(v) for v in np.asarray(model.thrust_poly, np.float64))
+        c = ct0 - mass * grav / m
+        if ct2 == 0.0:
+            u_h = -c / ct1
+        else:
+            disc = ct1 * ct1 - 4.0 * ct2 * c
+            if disc < 0:
+                raise ValueError("GeometricController.for_model: the model cannot hover (no real hover command)")
+            u_h = (-ct1 + np.sqrt(disc)) / (2.0 * ct2)
+        kT = mass / (m * (2.0 * ct2 * u_h + ct1))
+        return u_h, kT, u_h - kT * grav
+
+    @classmethod
+    def for_model(cls, model, **gains):
+        """A controller whose thrust map is calibrated for `model` (hover_calibration, rounded to float32) and whose gravity is the model's; the gains (kp, kv,
+        max_acc, attctrl_tau, and optionally thrust_min, thrust_max, accel_ff, ref_row) are the caller's."""
+        _, kT, k0 = cls.hover_calibration(model)
+        gains.setdefault("gravity", float(model.grav))
+        return cls(thrust_const=float(np.float32(kT)), thrust_offset=float(np.float32(k0)), **gains)
+
+    def arrays(self, B, u_lo, u_hi):
+        """The parameter sets as the C ABI takes them: (batch, dict of contiguous f32 arrays with `batch` rows), batch 1 or B. thrust_min / thrust_max None: the
+        tightest of the motors' input bounds u_lo / u_hi."""
+        if self.batch not in (1, B):
+            raise ValueError(f"GeometricController: per-episode parameters are for B = {self.batch}, the call has B = {B}")
+        lo = np.full(1, np.max(np.asarray(u_lo, np.float32)), np.float32) if self.thrust_min is None else self.thrust_min
+        hi = np.full(1, np.min(np.asarray(u_hi, np.float32)), np.float32) if self.thrust_max is None else self.thrust_max
+        if lo.shape[0] not in (1, self.batch) or hi.shape[0] not in (1, self.batch):
+            raise ValueError("GeometricController: thrust_min / thrust_max disagree with the other parameters on B")
+        if (np.broadcast_to(lo, (self.batch,)) > np.broadcast_to(hi, (self.batch,))).any():
+            raise ValueError("GeometricController: thrust_min must not exceed thrust_max")
+        names = ("kp", "kv", "amax", "inv_tau", "g", "kT", "k0", "c_lo", "c_hi")
+        vals = (self.kp, self.kv, self.max_acc, self.inv_tau, self.gravity, self.thrust_const, self.thrust_offset, lo, hi)
+        return self.batch, {n: np.ascontiguousarray(np.broadcast_to(v, (self.batch,) + v.shape[1:]), dtype=np.float32) for n, v in zip(names, vals)}
+
+    def __repr__(self):
+        return (f"GeometricController(kp={self.kp.tolist()}, kv={self.kv.tolist()}, max_acc={self.max_acc.tolist()}, attctrl_tau={self.attctrl_tau.tolist()}, "
+                f"gravity={self.gravity.tolist()}, thrust_const={self.thrust_const.tolist()}, thrust_offset={self.thrust_offset.tolist()}, accel_ff={self.accel_ff}, "
+                f"ref_row={self.ref_row})")
+
+
 def fault_schedule(T, B, m):
     """The neutral per-motor fault schedule f32[T][B][m][2] of closed_loop(fault=...) (SPEC.md §11e): every row (kappa, beta) = (1, 0), to be edited in place.
     Row (k, b, l) acts on every plant substep of control tick k of episode b: what reaches rotor l is fma(kappa, a_l, beta), a_l the motor state (which
@@ -1191,7 +1297,7 @@ class SdeMpcSolver:
                     meas_keys=None, xmeas_in=None, meas_age=None, meas_age_max=None, meas_renorm=False, xhist_in=None, score=None, score_ref=None, score_in=None,
                     outputs=True, dist_process=None, dist_keys=None, dist_state_in=None, bias_process=None, bias_keys=None, bias_state_in=None,
                     track=None, track_of=None, track_phase=None, track_rate=None, track_offset=None, track_tick0=None, track_renorm=None,
-                    fault_process=None, fault_keys=None, fault_state_in=None, fault_tick0=0, drop_process=None, drop_keys=None, drop_state_in=None):
+                    fault_process=None, fault_keys=None, fault_state_in=None, fault_tick0=0, drop_process=None, drop_keys=None, drop_state_in=None, controller=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -1318,7 +1424,15 @@ class SdeMpcSolver:
         read), valid_keys_next and valid_state_next; the rows are None under outputs=False. Carrying the *_next values back in continues a chain bit for bit: the
         fault chain for any T (with fault_tick0 + T as the next fault_tick0), the dropout chain when T is a multiple of solve_period. event_summary reduces
         fault_state_next. A process without its keys, or keys / a state / a tick without the process, raises ValueError; with none of the seven given nothing of
-        this paragraph is touched."""
+        this paragraph is touched.
+
+        controller (SPEC.md §11l, sdempc_closed_loop_batch_baseline): the BASELINE. A GeometricController replaces the solve of every solve period, and nothing else:
+        from the state the solve would have started from (the plant's, or the estimate) and rows ref_row, ref_row + 1 of the episode's reference window it forms a
+        collective thrust and three body rates on the device, and the period flies them through rate_loop (required, with motor_weight 0; ValueError otherwise)
+        exactly as it flies a solution's table. Keys, gusts, faults, estimator, windows, score, chunking and continuation are untouched, so a second call with the
+        same arguments and controller=None flies the MPC under the same conditions and the two scores are a paired comparison. The returned tuple is the rate
+        route's: u_next holds thrust rows (every motor the thrust command), info rows are (0, stepsize, 0, ...) and the step size is handed through. Parameters may
+        be one set or one per episode. With controller=None nothing of this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -1514,8 +1628,17 @@ class SdeMpcSolver:
                     raise ValueError(f"closed_loop: score_in must be the structured score array [{B}] a previous call returned, got dtype {score_in.dtype} and shape {score_in.shape}")
         if score_track and not scored:
             raise ValueError('closed_loop: score_ref="track" needs score=Score(...)')
-        faulted = flt is not None or bool(substep_states) or observed or scored or drawn or tracked or events
-        full = scored or drawn or tracked or events          # the entry points from the scored one on take every layer's arguments, NULL where a layer is absent
+        baseline = controller is not None
+        if baseline:
+            if not isinstance(controller, GeometricController):
+                raise ValueError("closed_loop: controller must be a GeometricController")
+            if rate_loop is None:
+                raise ValueError("closed_loop: controller= publishes thrust and body rates and needs rate_loop=RateLoop(...)")
+            if not isinstance(rate_loop, RateLoop) or rate_loop.motor_weight != 0.0:
+                raise ValueError("closed_loop: controller= needs a RateLoop with motor_weight 0 (its table holds no motor values)")
+            gc, keep_g = self._geo_cfg(controller, B)
+        faulted = flt is not None or bool(substep_states) or observed or scored or drawn or tracked or events or baseline
+        full = scored or drawn or tracked or events or baseline          # the entry points from the scored one on take every layer's arguments, NULL where a layer is absent
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
             raise ValueError("closed_loop: rate_integ_in / rate_tail_in need rate_loop=...")
         if rate_loop is not None and not isinstance(rate_loop, RateLoop):
@@ -1643,9 +1766,9 @@ class SdeMpcSolver:
                 z_out = np.zeros(B, SCORE_DTYPE)
                 lead = [C.byref(zc), None if score_in is None else score_in.ctypes.data_as(u32p)] + lead
                 more, ret = more + (z_out.ctypes.data_as(u32p),), ret + (z_out,)
-            elif drawn or tracked or events:  # (no score: a NULL score cfg and NULL score pointers)
+            elif drawn or tracked or events or baseline:  # (no score: a NULL score cfg and NULL score pointers)
                 lead, more = [None, None] + lead, more + (None,)
-            if drawn or tracked or events:               # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
+            if drawn or tracked or events or baseline:   # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
                 cfgs, keep_p = [], []
                 for name, Nrows in (("dist", max(T, 0)), ("bias", max(Ns, 0))):
                     if name not in procs:
@@ -1663,9 +1786,9 @@ class SdeMpcSolver:
                 lead = cfgs + lead
             if tracked:             # the drawn entry point's arguments behind the track cfg; nothing new comes back
                 lead = [C.byref(tkc)] + lead
-            elif events:            # (no track: a NULL track cfg)
+            elif events or baseline:    # (no track: a NULL track cfg)
                 lead = [None] + lead
-            if events:              # the tracked entry point's arguments behind (fault_proc, drop_proc), then rows, keys_next and state_next of each chain
+            if events or baseline:  # the tracked entry point's arguments behind (fault_proc, drop_proc), then rows, keys_next and state_next of each chain
                 i32p = C.POINTER(C.c_int32)
                 ecfgs, keep_e = [None, None], []
                 if "fault" in evts:
@@ -1693,10 +1816,14 @@ class SdeMpcSolver:
                 else:
                     more = more + (None, None, None)
                 lead = ecfgs + lead
+            if baseline:            # the events entry point's arguments behind the geo cfg; nothing new comes back
+                lead = [C.byref(gc)] + lead
             if substep_states:
                 ret = ret + (xsub,)
         # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
-        if events:
+        if baseline:
+            entry = _abi.baseline_entry(self.lib)
+        elif events:
             entry = _abi.events_entry(self.lib)
         elif tracked:
             entry = _abi.tracked_entry(self.lib)
@@ -1776,6 +1903,36 @@ class SdeMpcSolver:
         out = np.zeros((k.shape[0], B, self.H + 1, 13), np.float32)
         self._check(_abi.reference_windows_entry(self.lib)(self._h, C.byref(cfg), B, k.shape[0], k.ctypes.data_as(C.POINTER(C.c_int32)), _fp(out)))
         del keep
+        return out
+
+    def _geo_cfg(self, controller, B):
+        """sdempc_geo_cfg of a GeometricController for B episodes on this handle, and what must stay alive while it is in use."""
+        if controller.ref_row > self.H - 1:
+            raise ValueError(f"controller.ref_row must be between 0 and H - 1 = {self.H - 1}, got {controller.ref_row}")
+        bounds = np.asarray(self.cfg_py.input_bound, np.float32)
+        batch, arr = controller.arrays(B, bounds[:, 0], bounds[:, 1])
+        inv_dt = np.float32(1.0) / np.float32(self.cfg_py.time_steps[controller.ref_row])
+        gc = _abi.SdempcGeoCfg(C.sizeof(_abi.SdempcGeoCfg), batch, *[_fp(arr[n]) for n in ("kp", "kv", "amax", "inv_tau", "g", "kT", "k0", "c_lo", "c_hi")],
+                               int(controller.accel_ff), controller.ref_row, float(inv_dt))
+        return gc, arr
+
+    def geo_command(self, x, xref, controller):
+        """The geometric controller alone (SPEC.md §11l, sdempc_geo_command_batch): (c, omega*) f32[B][4] for states x f32[B][13] and windows xref f32[Bx][H+1][13]
+        (Bx in {1, B}, or one window f32[H+1][13]), formed by the device code the closed loop runs."""
+        if not isinstance(controller, GeometricController):
+            raise ValueError("geo_command: controller must be a GeometricController")
+        x = _f32(x)
+        B = x.shape[0]
+        x = _f32(x, (B, 13))
+        xref = _f32(xref)
+        if xref.ndim == 2:
+            xref = xref[None]
+        if xref.ndim != 3 or xref.shape[1:] != (self.H + 1, 13) or xref.shape[0] not in (1, B):
+            raise ValueError(f"geo_command: xref must be f32[Bx][{self.H + 1}][13] with Bx in (1, {B}) or f32[{self.H + 1}][13], got {xref.shape}")
+        xref = np.ascontiguousarray(xref)
+        gc, keep = self._geo_cfg(controller, B)
+        out = np.zeros((B, 4), np.float32)
+        self._check(_abi.geo_command_entry(self.lib)(self._h, C.byref(gc), B, _fp(x), _fp(xref), xref.shape[0], _fp(out)))
         return out
 
     def _rate_cfg(self, rate_loop, plant_substeps, plant_dt):

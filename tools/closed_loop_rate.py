@@ -47,11 +47,15 @@
      two-state chain per episode stepped per solve (one solve in four dropped, bursts of two solves), whose flags REPLACE the meas_valid rows (noise and bias stay host
      rows). Apply to --small-batch and to the C2 loop; either makes the call the timed one. So `--fault --observe` against `--fault-process --observe --drop-process`
      is host rows against keys for the same two ingredients.
+ 14. --controller geo: the same loops flown by the geometric baseline controller (SPEC.md §11l, sdempc_closed_loop_batch_baseline) in place of the MPC's solves — gains
+     calibrated for the model (GeometricController.for_model), one set for every episode, through the rate loop of --rate-loop (implied). Applies to --small-batch and
+     to the C2 loop; everything above still applies, so the same command with and without it is the paired comparison of SPEC.md §11l. The "one batch solve" figure
+     beside the C2 loop is then the MPC's solve, for scale: the baseline's period has no solve in it.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
                                         [--fault] [--substep-states] [--observe] [--age A] [--renorm]
                                         [--score] [--no-outputs] [--score-substeps] [--dist-process] [--bias-process] [--track] [--per-episode-xref]
-                                        [--fault-process] [--drop-process]
+                                        [--fault-process] [--drop-process] [--controller geo]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -99,7 +103,10 @@ ap.add_argument("--track", action="store_true", help="reference windows (and sco
 ap.add_argument("--per-episode-xref", action="store_true", help="--small-batch: a host xref array with a lemniscate window per solve and episode instead of one hold window")
 ap.add_argument("--fault-process", action="store_true", help="motor faults drawn on the device, one step of a Markov chain per motor and control tick (SPEC.md §11k)")
 ap.add_argument("--drop-process", action="store_true", help="with --observe: estimator dropouts drawn on the device, one step per solve, instead of meas_valid rows (SPEC.md §11k)")
+ap.add_argument("--controller", choices=("mpc", "geo"), default="mpc", help="geo: the geometric baseline controller in place of the solves, through the rate loop (SPEC.md §11l)")
 a = ap.parse_args()
+if a.controller == "geo":
+    a.rate_loop = True
 if a.drop_process and not a.observe:
     ap.error("--drop-process needs --observe")
 if a.track and a.per_episode_xref:
@@ -134,6 +141,9 @@ def scenario_kw(kw, B, T):
     if a.rate_loop:
         from sde4mbrl_px4_amd.solver import RateLoop
         kw["rate_loop"] = RateLoop(kp=[0.03, 0.03, 0.08], ki=[0.3, 0.3, 0.5], integ_limit=0.05)
+    if a.controller == "geo":
+        from sde4mbrl_px4_amd.solver import GeometricController
+        kw["controller"] = GeometricController.for_model(model, kp=[4.0, 4.0, 6.0], kv=[2.5, 2.5, 3.25], max_acc=7.0, attctrl_tau=0.2)
     if a.fault:
         from sde4mbrl_px4_amd.solver import fault_schedule
         rng = np.random.default_rng(6)
@@ -227,6 +237,8 @@ if a.disturbance:
     tag += " disturbance"
 if a.plant_switch >= 0:
     tag += f" plant-switch at {a.plant_switch}"
+if a.controller == "geo":
+    tag += " controller=geo"
 if a.rate_loop:
     tag += " rate-loop"
 if a.fault:
