@@ -1054,6 +1054,69 @@ int sdempc_closed_loop_batch_baseline(sdempc_handle* h, const sdempc_geo_cfg* ge
 int sdempc_geo_command_batch(sdempc_handle* h, const sdempc_geo_cfg* geo, int32_t B, const float* x /*[B][13]*/, const float* xref /*[Bx][H+1][13]*/, int32_t Bx,
                              float* out /*[B][4]*/);
 
+/* ---- batched closed loop with per-row ensemble histories over the episodes, by cohort (SPEC.md §11m) -------------------
+ * sdempc_closed_loop_batch_baseline plus a reducer over the EPISODES: for every scored row i = 0 .. R-1 of the call (R = T, or T * substeps with a substep score)
+ * and every cohort g < n_cohorts one row of W = SDEMPC_ENSEMBLE_BASE_WORDS + 4 * n_edges 32-bit words, formed on the device from the rows, targets and thresholds
+ * the score reads — the survival curve, the failures by cause, and sum / min / max / cumulative edge counts of the score's channels dp, dv, c, w2 — so that the
+ * time-resolved curves of a campaign cost R * G * W words of output whatever B is. With `ens` NULL the call IS sdempc_closed_loop_batch_baseline bit for bit, with
+ * the same launches (ens_out must then be NULL). `geo` may be NULL here: the episodes are then flown by the MPC's own solves, exactly as
+ * sdempc_closed_loop_batch_events flies them (`rate` is then optional again), and the same ensemble cfg reduces both sides of a paired comparison.
+ * Per episode b and scored row, with (dp, dv, c, w2, nf, cause) of that row exactly as the score forms them (above, at sdempc_score_cfg): r_b is the row's index — the
+ * value score word 0 had before the row was counted, so a run continued through score_in keeps counting — and f_b the episode's score word 8 after the chunk was
+ * scored (0xffffffff: never). "Failed before the row" is f_b < r_b, "failed by now" f_b <= r_b, both unsigned. The episode is INCLUDED in the statistics of its cohort when
+ * nf = 0 and, with over = 1, it has not failed before the row; over = 0 includes every finite row. The words of (i, g):
+ *    0 u32 episodes of the cohort                          3 u32 episodes of the cohort whose row has cause != 0
+ *    1 u32 episodes included                               4 .. 7 u32 episodes of the cohort whose row has cause bit 1, 2, 4, 8
+ *    2 u32 episodes of the cohort failed by now            8 + 3k + {0, 1, 2} f32 sum, min, max of channel k in (dp, dv, c, w2) over the included episodes
+ *   20 + k * n_edges + j u32 included episodes with v_k < edges[k][j]
+ * min starts at +inf and v < min replaces it, max starts at -inf and v > max replaces it; no channel can be -0 and finite rows and targets give no NaN, so both are
+ * independent of order. A float sum has ONE association: episodes in blocks of 256 consecutive b; in a block, lane l holds v if its episode is included and +0
+ * otherwise; per wave of 64 lanes, for d = 1, 2, 4, 8, 16, 32 every lane forms x_l + x_(l xor d); the block sum is (s0 + s1) + (s2 + s3) of its four waves; the
+ * total starts at +0 and adds the block sums in ascending order. An empty cohort reads (0, .., +0, +inf, -inf, .., 0). The words do not depend on chunking, on
+ * which outputs were requested or on the layout of the solves; they DO depend on B and on the order of the episodes (the sums' association).
+ * Checked before the first HIP call, in this order and in front of everything else, SDEMPC_EINVAL for: ens without ens_out or ens_out without ens, a wrong
+ * struct_size, n_cohorts outside 1 .. 16, n_edges outside 0 .. 16, over other than 0 / 1, edges NULL with n_edges > 0, a NaN edge, edges of a channel that
+ * descend (equal neighbours pass), a cohort entry outside [0, n_cohorts), ens without a score cfg; then everything sdempc_closed_loop_batch_baseline (geo NULL:
+ * sdempc_closed_loop_batch_events) refuses. No ABI version change: detect the entry point by its symbol. */
+#define SDEMPC_ENSEMBLE_BASE_WORDS 20
+typedef struct sdempc_ensemble_cfg {
+    int32_t struct_size;     /* sizeof(sdempc_ensemble_cfg) */
+    int32_t n_cohorts;       /* G, 1 .. 16 */
+    int32_t n_edges;         /* E, 0 .. 16 edges per channel */
+    int32_t over;            /* 1: episodes that have not failed before the row ("alive"); 0: every finite row */
+    const int32_t* cohort;   /* [B] cohort of each episode, in [0, G); NULL: all 0 */
+    const float* edges;      /* [4][E] ascending edges of dp, dv, c, w2; may be NULL with E = 0 */
+} sdempc_ensemble_cfg;
+int sdempc_closed_loop_batch_ensemble(sdempc_handle* h, const sdempc_ensemble_cfg* ens /*or NULL*/, uint32_t* ens_out /*[R][G][W]; NULL without ens*/,
+                                      const sdempc_geo_cfg* geo /*or NULL: the MPC*/,
+                                        const sdempc_fault_process_cfg* fault_proc /*or NULL*/, const sdempc_dropout_process_cfg* drop_proc /*or NULL*/,
+                                      const sdempc_track_cfg* track /*or NULL*/,
+                                      const sdempc_process_cfg* dist_proc /*or NULL, W = 6*/, const sdempc_process_cfg* bias_proc /*or NULL, W = 12*/,
+                                      const sdempc_score_cfg* score /*or NULL*/, const uint32_t* score_in /*[B][16] or NULL*/,
+                                      const sdempc_age_cfg* age_cfg /*or NULL*/, const float* xhist_in /*[B][age_max][13] or NULL*/,
+                                      const sdempc_obs_cfg* obs /*or NULL*/, const uint32_t* obs_keys /*[B][2]; NULL without obs*/, const float* xmeas_in /*[B][13] or NULL*/,
+                                      const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*required with geo*/,
+                                      const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                      const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                      const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                      const float* xref /*NULL with track*/, int32_t xref_solves /*0 with track*/, int32_t xref_batch,
+                                      const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                      const float* u_act_in /*[B][m] or NULL*/,
+                                      float* xs /*[B][T+1][13]; may be NULL with score*/, float* us /*[B][T][m]; may be NULL with score*/,
+                                      sdempc_info* info /*[B][Ns]; may be NULL with score*/,
+                                      float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                      uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                      const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                      float* ws /*[B][T][4]; NULL without rate; may be NULL with score*/, float* rate_integ_next /*[B][3] or NULL*/,
+                                      float* rate_tail_next /*[B][H][3] or NULL*/,
+                                      float* xsub /*[B][T * substeps][13] or NULL*/,
+                                      float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
+                                      float* xhist_next /*[B][age_max][13] or NULL*/, uint32_t* score_out /*[B][16]; NULL without score*/,
+                                      float* dist_rows /*[B][T][6] or NULL*/, uint32_t* dist_keys_next /*[B][2] or NULL*/, float* dist_state_next /*[B][6] or NULL*/,
+                                      float* bias_rows /*[B][Ns][12] or NULL*/, uint32_t* bias_keys_next /*[B][2] or NULL*/, float* bias_state_next /*[B][12] or NULL*/,
+                                      float* fault_rows /*[B][T][m][2] or NULL*/, uint32_t* fault_keys_next /*[B][2] or NULL*/, int32_t* fault_state_next /*[B][m][2] or NULL*/,
+                                      int32_t* valid_rows /*[B][Ns] or NULL*/, uint32_t* valid_keys_next /*[B][2] or NULL*/, int32_t* valid_state_next /*[B][2] or NULL*/);
+
 
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so

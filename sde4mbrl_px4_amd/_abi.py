@@ -431,6 +431,29 @@ def baseline_entry(lib):
     return fn
 
 
+class SdempcEnsembleCfg(C.Structure):
+    """sdempc_ensemble_cfg (SPEC.md §11m): cohorts, edges and the inclusion rule of the per-row ensemble reducer of sdempc_closed_loop_batch_ensemble."""
+    _fields_ = [("struct_size", C.c_int32), ("n_cohorts", C.c_int32), ("n_edges", C.c_int32), ("over", C.c_int32), ("cohort", C.POINTER(C.c_int32)),
+                ("edges", C.POINTER(C.c_float))]
+
+
+ENSEMBLE_BASE_WORDS = 20         # SDEMPC_ENSEMBLE_BASE_WORDS: a row of (scored row, cohort) holds 20 + 4 * n_edges words
+
+
+def ensemble_entry(lib):
+    """sdempc_closed_loop_batch_ensemble (SPEC.md §11m) with its prototype set: an ensemble cfg (may be NULL) and ens_out in front of the baseline entry point's
+    arguments (whose geo cfg may be NULL here: the MPC). Detected by symbol and only when a call needs it, as baseline_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_ensemble
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_ensemble (SPEC.md §11m): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(baseline_entry(lib).argtypes)
+        fn.argtypes = [a[0], C.POINTER(SdempcEnsembleCfg), C.POINTER(C.c_uint32)] + a[1:]
+        fn.restype = C.c_int
+    return fn
+
+
 def geo_command_entry(lib):
     """sdempc_geo_command_batch (SPEC.md §11l) with its prototype set. Detected by symbol and only when a call needs it, as baseline_entry is."""
     try:
@@ -537,7 +560,7 @@ EXPORTED_SYMBOLS = [
     "sdempc_closed_loop_batch_rate", "sdempc_closed_loop_batch_fault", "sdempc_closed_loop_batch_observed",
     "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored", "sdempc_closed_loop_batch_drawn",
     "sdempc_closed_loop_batch_tracked", "sdempc_reference_windows", "sdempc_closed_loop_batch_events",
-    "sdempc_closed_loop_batch_baseline", "sdempc_geo_command_batch",
+    "sdempc_closed_loop_batch_baseline", "sdempc_geo_command_batch", "sdempc_closed_loop_batch_ensemble",
     "sdempc_tube_batch", "sdempc_tube_batch_keys", "sdempc_tube_batch_dev",
     "sdempc_risk_batch", "sdempc_risk_batch_keys", "sdempc_risk_batch_dev",
     "sdempc_bands_batch", "sdempc_bands_batch_keys", "sdempc_bands_batch_dev",

@@ -196,6 +196,9 @@ struct sdempc_handle {
     DevBuf d_hist;
     // closed loop scored on the device (sdempc_closed_loop_batch_scored with a score cfg, allocated on its first use): the score words u32[max_batch][16]
     DevBuf d_score;
+    // per-row ensemble histories (sdempc_closed_loop_batch_ensemble with an ensemble cfg; allocated on first use, grown, never shrunk): the cohorts i32[max_batch], the
+    // edges f32[4][ENS_MAX_EDGES], then for one slab of rows the combined words u32[rows][G][W] and the per-block partial words u32[rows][nblk][G][W]
+    DevBuf d_ens;
     // closed loop with processes drawn on the device (sdempc_closed_loop_batch_drawn with a process cfg, allocated on its first use), per row of max_batch: the
     // disturbance chain u32[2] and state f32[6], the bias chain u32[2] and state f32[12], then rho and scale of each (f32[6], f32[6], f32[12], f32[12])
     DevBuf d_proc;
@@ -662,7 +665,14 @@ struct GeoRun {
     const sdempc_geo_cfg* cfg;
     float inv_dt;                               // float32(1) / float32(time_steps[ref_row])
 };
-constexpr size_t PROC_WORDS = 2 + 6 + 2 + 12 + 2 * 6 + 2 * 12;      // words of d_proc per row of max_batch
+// SPEC.md §11m: the ensemble reducer of one sdempc_closed_loop_batch_ensemble call (host pointers, checked at the front of closed_loop_call). Given only when the
+// call has an ensemble cfg: without one the call is the baseline (or, without a geo cfg, the events) call, launch for launch.
+struct EnsRun {
+    const sdempc_ensemble_cfg* cfg;
+    uint32_t* out;                              // [R][G][W], R = T (tick score) or T * substeps (substep score)
+};
+constexpr size_t ENS_SLAB_BYTES = 32u << 20;    // device bytes of partial words one pair of ensemble launches may fill: a chunk with more rows is reduced in slabs
+constexpr size_t PROC_WORDS = 2 + 6 + 2 + 12 + 2 * 6 + 2 * 12;     // words of d_proc per row of max_batch
 constexpr size_t EVT_MODES = 4;
 constexpr size_t EVT_WORDS = EVENT_EP_WORDS + 2 + 2 + EVENT_PAR_WORDS + 2;      // words of d_evt per row of max_batch
 static_assert(SDEMPC_MAX_MOTORS == 8, "EVENT_EP_WORDS / EVENT_PAR_WORDS (sdempc_kernels.h) hold eight motors");
@@ -709,6 +719,9 @@ struct LoopCall {
     EventRun er;                                // (a NULL cfg: its three outputs must be NULL)
     bool baseline;                              // sdempc_closed_loop_batch_baseline (SPEC.md §11l): the events call with the geometric controller in place of the solve
     const sdempc_geo_cfg* geo;
+    bool ensembled;                             // sdempc_closed_loop_batch_ensemble (SPEC.md §11m): the baseline call (geo NULL: the events call) with ens / ens_out
+    const sdempc_ensemble_cfg* ens;             // or NULL: no ensemble (ens_out must then be NULL)
+    uint32_t* ens_out;
 };
 int check_geo(sdempc_handle* h, const sdempc_geo_cfg* g, int B, float* inv_dt);
 int stage_geo(sdempc_handle* h, const sdempc_geo_cfg& g, hipStream_t st);
@@ -719,9 +732,9 @@ int stage_track(sdempc_handle* h, const sdempc_track_cfg& tk, int B, TrackRun* o
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr,
                          const ObsRun* obs = nullptr, const ScoreRun* score = nullptr, const ProcRun* proc = nullptr, const TrackRun* track = nullptr,
-                         const EventRun* evt = nullptr, const GeoRun* geo = nullptr);
+                         const EventRun* evt = nullptr, const GeoRun* geo = nullptr, const EnsRun* ens = nullptr);
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, bool* again);
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, const EnsRun* ens, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -821,7 +834,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_outcome, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_proc, &h->d_evt, &h->d_geo, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_outcome, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_ens, &h->d_proc, &h->d_evt, &h->d_geo, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1925,6 +1938,39 @@ int sdempc_closed_loop_batch_baseline(sdempc_handle* h, const sdempc_geo_cfg* ge
     });
 }
 
+int sdempc_closed_loop_batch_ensemble(sdempc_handle* h, const sdempc_ensemble_cfg* ens, uint32_t* ens_out, const sdempc_geo_cfg* geo, const sdempc_fault_process_cfg* fault_proc,
+                                      const sdempc_dropout_process_cfg* drop_proc, const sdempc_track_cfg* track, const sdempc_process_cfg* dist_proc,
+                                      const sdempc_process_cfg* bias_proc, const sdempc_score_cfg* zc, const uint32_t* score_in, const sdempc_age_cfg* ac, const float* xhist_in,
+                                      const sdempc_obs_cfg* oc, const uint32_t* obs_keys, const float* xmeas_in, const sdempc_fault_cfg* fc, const sdempc_rate_cfg* rc_,
+                                      const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc, const void* const* plant_blobs,
+                                      const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T, const float* x0, const float* xref, int32_t xref_solves,
+                                      int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in, const float* u_act_in, float* xs, float* us,
+                                      sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next, float* u_act_next, const float* rate_integ_in,
+                                      const float* rate_tail_in, float* ws, float* rate_integ_next, float* rate_tail_next, float* xsub, float* xmeas, uint32_t* obs_keys_next,
+                                      float* xmeas_next, float* xhist_next, uint32_t* score_out, float* dist_rows, uint32_t* dist_keys_next, float* dist_state_next, float* bias_rows,
+                                      uint32_t* bias_keys_next, float* bias_state_next, float* fault_rows, uint32_t* fault_keys_next, int32_t* fault_state_next, int32_t* valid_rows,
+                                      uint32_t* valid_keys_next, int32_t* valid_state_next) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    c.observed = true; c.oc = oc; c.obs_keys = obs_keys; c.xmeas_in = xmeas_in; c.xmeas = xmeas; c.obs_keys_next = obs_keys_next; c.xmeas_next = xmeas_next;
+    c.aged = true; c.ac = ac; c.xhist_in = xhist_in; c.xhist_next = xhist_next;
+    c.scored = true; c.zc = zc; c.score_in = score_in; c.score_out = score_out;
+    c.drawn = true; c.pr = {dist_proc, bias_proc, dist_rows, dist_keys_next, dist_state_next, bias_rows, bias_keys_next, bias_state_next};
+    c.track = track;
+    c.events = true; c.er = {fault_proc, drop_proc, fault_rows, fault_keys_next, fault_state_next, valid_rows, valid_keys_next, valid_state_next};
+    c.baseline = geo != nullptr; c.geo = geo;      // (geo NULL: the MPC's own solves, i.e. the events call)
+    c.ensembled = true; c.ens = ens; c.ens_out = ens_out;
+    return closed_loop_call(h, c);
+    });
+}
+
 int sdempc_geo_command_batch(sdempc_handle* h, const sdempc_geo_cfg* geo, int32_t B, const float* x, const float* xref, int32_t Bx, float* out) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -2030,7 +2076,7 @@ int solve_staged(sdempc_handle* h, int32_t B, float* uopt, float* xevol, sdempc_
         if (attempt) return fail(h, SDEMPC_EDEVICE, "cooperative solve: a grid barrier timed out twice%s");
     }
 }
-// The one path behind the closed-loop entry points: every check of the call's parts, in one fixed order (event structs and their arrays, track struct, process structs and their arrays, score struct, age struct, observation struct, fault struct, rate, scenario struct,
+// The one path behind the closed-loop entry points: every check of the call's parts, in one fixed order (ensemble cfg with its edges and cohorts, baseline cfg, event structs and their arrays, track struct, process structs and their arrays, score struct, age struct, observation struct, fault struct, rate, scenario struct,
 // timing, loop arguments, plant_ticks, plant set, solve_delay, disturbance, fault schedule, observation rows, age rows, score target rows; a part the layer lacks is skipped) and before the first HIP call, then the plant set onto the device and the loop.
 int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     if (!h) return SDEMPC_EINVAL;
@@ -2042,8 +2088,28 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    if (c.ensembled) {         // SPEC.md §11m: output and cfg come together; the cfg's own fields, edges and cohorts; then the score it reduces
+        const sdempc_ensemble_cfg* en = c.ens;
+        if ((en == nullptr) != (c.ens_out == nullptr)) return fail(h, SDEMPC_EINVAL, "ensemble: ens and ens_out must be given together%s");
+        if (en) {
+            if (en->struct_size != (int32_t)sizeof(sdempc_ensemble_cfg)) return fail(h, SDEMPC_EINVAL, "ensemble: struct_size mismatch%s");
+            if (en->n_cohorts < 1 || en->n_cohorts > ENS_MAX_COHORTS) return fail(h, SDEMPC_EINVAL, "ensemble: n_cohorts must be between 1 and 16%s");
+            if (en->n_edges < 0 || en->n_edges > ENS_MAX_EDGES) return fail(h, SDEMPC_EINVAL, "ensemble: n_edges must be between 0 and 16%s");
+            if (en->over != 0 && en->over != 1) return fail(h, SDEMPC_EINVAL, "ensemble: over must be 0 (every finite row) or 1 (alive)%s");
+            const int E = en->n_edges;
+            if (E > 0 && !en->edges) return fail(h, SDEMPC_EINVAL, "ensemble: edges is NULL with n_edges > 0%s");
+            for (int e = 0; e < 4 * E; ++e)
+                if (en->edges[e] != en->edges[e]) return fail(h, SDEMPC_EINVAL, "ensemble: an edge is NaN%s");
+            for (int k = 0; k < 4; ++k)
+                for (int j = 1; j < E; ++j)
+                    if (en->edges[k * E + j] < en->edges[k * E + j - 1]) return fail(h, SDEMPC_EINVAL, "ensemble: the edges of a channel must ascend%s");
+            for (int b = 0; en->cohort && b < B; ++b)
+                if (en->cohort[b] < 0 || en->cohort[b] >= en->n_cohorts) return fail(h, SDEMPC_EINVAL, "ensemble: a cohort entry lies outside [0, n_cohorts)%s");
+            if (!c.zc) return fail(h, SDEMPC_EINVAL, "ensemble: an ensemble cfg needs a score cfg%s");
+        }
+    }
     GeoRun run_g{c.geo, 0.0f};
-    if (c.baseline) {          // SPEC.md §11l: the controller's cfg, then the interface it publishes to
+    if (c.baseline) {        // SPEC.md §11l: the controller's cfg, then the interface it publishes to
         if (int rc = check_geo(h, c.geo, B, &run_g.inv_dt)) return rc;
         if (!rc_) return fail(h, SDEMPC_EINVAL, "baseline: the controller publishes thrust and body rates and needs a rate cfg%s");
         if (rc_->struct_size == (int32_t)sizeof(sdempc_rate_cfg) && rc_->motor_weight != 0.0f) return fail(h, SDEMPC_EINVAL, "baseline: motor_weight must be 0 (the table holds no motor values)%s");
@@ -2245,9 +2311,10 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const ScoreRun run_z{zc, c.score_in, c.score_out};
     TrackRun run_k;
     if (tk && (rc = stage_track(h, *tk, B, &run_k))) return rc;
+    const EnsRun run_e{c.ens, c.ens_out};
     return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr,
                                 run_f.fault || run_f.xsub || (evt && evt->fault) ? &run_f : nullptr, oc ? &run_o : nullptr, zc ? &run_z : nullptr, proc, tk ? &run_k : nullptr, evt,
-                                c.baseline ? &run_g : nullptr);
+                                c.baseline ? &run_g : nullptr, c.ens ? &run_e : nullptr);
 }
 // every check of a geometric-controller cfg (SPEC.md §11l), shared by the two entry points that take one; no HIP call. inv_dt: what the launch is given
 int check_geo(sdempc_handle* h, const sdempc_geo_cfg* g, int B, float* inv_dt) {
@@ -2415,10 +2482,10 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt,
-                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo) {
+                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, const EnsRun* ens) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, track, evt, geo, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, track, evt, geo, ens, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -2516,7 +2583,7 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // writes the solve's flags into a [Pc][B] region, which the measurement reads as its valid flags (scheduled flags likewise). Both regions count in the chunk's bytes and are
 // copied back and scattered only when the caller asked for the rows.
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, bool* again) {
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, const EnsRun* ens, bool* again) {
     *again = false;
     const bool flown = geo && rate && timed && plant;                      // (SPEC.md §11l: the geometric controller in place of the solve)
     const bool tracked = track && timed && plant;                          // (SPEC.md §11j)
@@ -2589,6 +2656,24 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     int32_t* e_dstate = e_fep ? (int32_t*)(e_dchain + 2 * MB) : nullptr;                 // [B][2]
     uint32_t* e_par = e_fep ? (uint32_t*)(e_dstate + 2 * MB) : nullptr;                  // [batch][EVENT_PAR_WORDS]
     uint32_t* e_drop = e_fep ? e_par + EVENT_PAR_WORDS * MB : nullptr, *e_recover = e_fep ? e_drop + MB : nullptr;     // [batch]
+    // SPEC.md §11m: the ensemble words of a chunk are formed after its scoring launch, in slabs of rows no larger than ENS_SLAB_BYTES of partial words
+    const bool ensemble = ens && scoring;
+    const int EG = ensemble ? ens->cfg->n_cohorts : 0, EE = ensemble ? ens->cfg->n_edges : 0, EW = ENS_BASE_WORDS + 4 * EE, nblk = (B + 255) / 256;
+    const size_t ens_rows_max = Tc * (score_sub ? (size_t)nsub : 1), ens_row_words = (size_t)(nblk + 1) * EG * EW;     // (per row: the combined words and nblk blocks of partial words)
+    size_t ens_slab = ensemble ? ENS_SLAB_BYTES / (sizeof(uint32_t) * ens_row_words) : 0;
+    ens_slab = ens_slab < 1 ? 1 : ens_slab;
+    ens_slab = ens_slab > 65535 ? 65535 : ens_slab;                  // (the partial form's rows are the grid's y extent)
+    ens_slab = ens_slab > ens_rows_max ? ens_rows_max : ens_slab;
+    const size_t ens_head = MB + 4 * ENS_MAX_EDGES;                  // words in front of the slab: cohorts, edges
+    if (ensemble && h->d_ens.bytes < sizeof(uint32_t) * (ens_head + ens_slab * ens_row_words)) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        dev_free(h->d_ens);
+        if ((rc = dev_alloc(h, h->d_ens, sizeof(uint32_t) * (ens_head + ens_slab * ens_row_words), true))) return rc;
+    }
+    int32_t* n_cohort = ensemble ? (int32_t*)h->d_ens.p : nullptr;   // [B]
+    float* n_edges = ensemble ? (float*)(n_cohort + MB) : nullptr;   // [4][E]
+    uint32_t* n_out = ensemble ? (uint32_t*)(n_edges + 4 * ENS_MAX_EDGES) : nullptr;         // [slab][G][W]
+    uint32_t* n_part = ensemble ? n_out + ens_slab * EG * EW : nullptr;                      // [slab][nblk][G][W]
     uint32_t* d_q = (uint32_t*)h->d_obs.p;                           // q [B][2] (SPEC.md §11f)
     float* d_xm = d_q ? (float*)(d_q + 2 * (size_t)h->max_batch) : nullptr;   // xm [B][13]
     float* d_integ = (float*)h->d_rate.p;                            // g [B][3] (SPEC.md §11d)
@@ -2683,6 +2768,11 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         HIPCHK(h, hipMemcpyAsync(d_score, z_in, sizeof(uint32_t) * 16 * (size_t)B, hipMemcpyHostToDevice, st));
         if (!sref_moves) HIPCHK(h, hipMemcpyAsync(c_sref, score->cfg->score_ref, sizeof(float) * ZR, hipMemcpyHostToDevice, st));      // (targets: they move)
     }
+    if (ensemble) {            // the cohorts (NULL: all 0) and the edges as given (SPEC.md §11m)
+        if (ens->cfg->cohort) HIPCHK(h, hipMemcpyAsync(n_cohort, ens->cfg->cohort, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, st));
+        else HIPCHK(h, hipMemsetAsync(n_cohort, 0, sizeof(int32_t) * (size_t)B, st));
+        if (EE > 0) HIPCHK(h, hipMemcpyAsync(n_edges, ens->cfg->edges, sizeof(float) * 4 * (size_t)EE, hipMemcpyHostToDevice, st));
+    }
     for (int w = 0; w < 2; ++w) {      // the process chains, states (NULL: zeros) and coefficients start as given (SPEC.md §11i)
         if (!(w ? bproc : gproc)) continue;
         const sdempc_process_cfg& pc = w ? *proc->bias : *proc->dist;
@@ -2763,6 +2853,13 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         Z.rows_per_tick = score_sub ? nsub : 1; Z.m = m;
         Z.r2_pos = zc.r2_pos; Z.cos_min = zc.cos_min; Z.w2_max = zc.w2_max;
         for (int l = 0; l < 8; ++l) { Z.u_lo[l] = l < m ? h->cfg.u_lo[l] : 0.0f; Z.u_hi[l] = l < m ? h->cfg.u_hi[l] : 0.0f; Z.uref[l] = l < m ? h->cfg.uref[l] : 0.0f; }
+    }
+    LoopEnsemble N{};          // (part null: absent; only the launches after a chunk's scoring launch take it)
+    if (ensemble) {            // rows, targets and thresholds are the scoring launch's own
+        N.part = n_part; N.out = n_out; N.words = d_score; N.cohort = n_cohort; N.edges = n_edges;
+        N.rows = Z.rows; N.ref = Z.ref; N.ref_tick_stride = Z.ref_tick_stride; N.ref_ep_stride = Z.ref_ep_stride; N.rows_per_tick = Z.rows_per_tick;
+        N.nblk = nblk; N.G = EG; N.E = EE; N.over = ens->cfg->over;
+        N.r2_pos = Z.r2_pos; N.cos_min = Z.cos_min; N.w2_max = Z.w2_max;
     }
     LoopTrack K{};             // (t null: absent)
     if (tracked) K = track->K;
@@ -2920,6 +3017,17 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 HIPCHK(h, launch_broadcast_rows(nullptr, c_sref, 0, 0, st, K));
             }
             HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, Z));
+        }
+        if (ensemble) {            // SPEC.md §11m: the chunk's rows over the episodes, slab by slab — partial words per block, then the blocks in ascending order
+            N.chunk_rows = nk * Z.rows_per_tick;
+            for (int r0 = 0; r0 < N.chunk_rows; r0 += (int)ens_slab) {
+                N.row0 = r0; N.nrows = N.chunk_rows - r0 < (int)ens_slab ? N.chunk_rows - r0 : (int)ens_slab;
+                N.combine = 0;
+                HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, LoopScore{}, LoopProcess{}, LoopEvents{}, LoopBaseline{}, N));
+                N.combine = 1;
+                HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, LoopScore{}, LoopProcess{}, LoopEvents{}, LoopBaseline{}, N));
+                HIPCHK(h, hipMemcpyAsync(ens->out + (k0 * Z.rows_per_tick + (size_t)r0) * EG * EW, n_out, sizeof(uint32_t) * (size_t)N.nrows * EG * EW, hipMemcpyDeviceToHost, st));
+            }
         }
         unsigned gave_up = 0;
         if (io.xs) {

@@ -349,9 +349,32 @@ struct LoopBaseline {
     const float* step;          // [B] the step size handed through
     float* out;                 // [B][4] (c, omega*), or null: the tables above
 };
+// SPEC.md §11m, per-row ensemble histories over the episodes, by cohort: TWO further forms of the period's key-schedule kernel (ticks = 0, every other struct empty,
+// null key buffers), launched after a chunk's scoring launch on rows, targets and thresholds that launch read (sdempc_ensemble.inc.h). The PARTIAL form (combine 0)
+// runs on a grid of (blocks of 256 consecutive episodes) x nrows and writes part[i][k][g][W]; the COMBINE form (combine 1) runs one thread per (row, cohort, word),
+// walks the blocks in ascending order and writes out[i][g][W]. W = ENS_BASE_WORDS + 4 E words (the table at sdempc_ensemble_cfg, include/sdempc.h). Both forms
+// branch off before the kernel's `b >= B` return: the partial form has workgroup barriers and masks instead. part null means absent: every other launch passes
+// that, and the kernel then makes no memory access it did not make before.
+constexpr int ENS_MAX_COHORTS = 16, ENS_MAX_EDGES = 16, ENS_BASE_WORDS = 20, ENS_MAX_WORDS = ENS_BASE_WORDS + 4 * ENS_MAX_EDGES;
+struct LoopEnsemble {
+    uint32_t* part;             // [nrows][nblk][G][W] per-block partial words; null: neither form
+    uint32_t* out;              // [nrows][G][W] the combined words (combine form)
+    const uint32_t* words;      // [B][16] the score words AFTER the chunk's scoring launch (words 0 and 8 are read)
+    const int32_t* cohort;      // [B] cohort of each episode, in [0, G)
+    const float* edges;         // [4][E] ascending edges of the channels dp, dv, c, w2 (not read with E = 0)
+    const float* rows;          // LoopScore::rows of the chunk
+    const float* ref;           // LoopScore::ref, with its two strides
+    int ref_tick_stride, ref_ep_stride, rows_per_tick;
+    int chunk_rows;             // rows the chunk's scoring launch counted: chunk row j has the global index words[b][0] - chunk_rows + j
+    int row0, nrows;            // this launch reduces chunk rows row0 .. row0 + nrows - 1
+    int nblk;                   // ceil(B / 256)
+    int G, E, over;             // cohorts 1 .. 16, edges per channel 0 .. 16, 1: only episodes that have not failed before the row are included
+    int combine;                // 0: the partial form, 1: the combine form (wave-uniform)
+    float r2_pos, cos_min, w2_max;      // LoopScore's
+};
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st,
                                    const LoopObserve& O = LoopObserve{}, const LoopScore& Z = LoopScore{}, const LoopProcess& G = LoopProcess{},
-                                   const LoopEvents& E = LoopEvents{}, const LoopBaseline& A = LoopBaseline{});
+                                   const LoopEvents& E = LoopEvents{}, const LoopBaseline& A = LoopBaseline{}, const LoopEnsemble& N = LoopEnsemble{});
 // SPEC.md §11j, reference windows and score targets cut from a trajectory on the device: the row-filling launch below in its TRACKING form. The tables of a set lie
 // end to end: table j owns knots first[j] .. first[j] + knots[j] - 1 of t / w / x (w[i] = float32(1 / (t[i+1] - t[i])) formed by the library in float64; the last w of
 // a table is not read). Thread i of the launch writes one whole row of 13 floats, row i of out f32[groups][B][rows][13]: group g is tick tick0 + g, its clock value

@@ -122,6 +122,7 @@ DI float bits_to_normal(uint32_t bits) {
 #include "sdempc_band.inc.h"
 #include "sdempc_outcome.inc.h"
 #include "sdempc_geo.inc.h"
+#include "sdempc_ensemble.inc.h"
 namespace sdempc {
 
 // grid: x = chunks of 256 threads over [pg][r][lane] (pg < ceil(ceil(P/2)/32), r < H*6), y = instance
@@ -327,9 +328,17 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
 // SPEC.md §11l (A.x given; ticks = 0, O / Z / G / E empty, keys / sub / xi null and untouched): the BASELINE form of the launch, one per solve period where the solve
 // is launched otherwise. Thread b forms the geometric controller's command of episode b and fills the tables the plant launch reads (sdempc_geo.inc.h). A.x null
 // (every period and scoring launch): not one access more.
+// SPEC.md §11m (N.part given; ticks = 0, O / Z / G / E / A empty, keys / sub / xi null and untouched): the two ENSEMBLE forms of the launch, after a chunk's scoring
+// launch (sdempc_ensemble.inc.h) — the partial form on a grid of (blocks of episodes) x (rows), whose threads past B stay for its workgroup barriers and are masked,
+// and the combine form, one thread per (row, cohort, word): both leave before the `b >= B` return. N.part null (every launch before §11m): not one access more.
 __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int ticks,
                                                                       int xi_ticks, int n, LoopObserve O, LoopScore Z, LoopProcess G, LoopEvents E,
-                                                                      LoopBaseline A) {
+                                                                      LoopBaseline A, LoopEnsemble N) {
+    if (N.part) {                                        // (wave-uniform)
+        if (N.combine) ens_combine(N);
+        else ens_partial(N, B);
+        return;
+    }
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     if (A.x) {                                           // (wave-uniform)
@@ -346,16 +355,9 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
             const float g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3], g4 = g[4], g5 = g[5];
             for (int jj = 0; jj < Z.rows_per_tick; ++jj) {
                 const float* x = Z.rows + ((size_t)(i * Z.rows_per_tick + jj) * B + b) * 13;
-                bool nf = false;
-#pragma unroll
-                for (int c = 0; c < 13; ++c) nf = nf || !(__builtin_fabsf(x[c]) < __builtin_inff());
-                const float e0 = x[0] - g0, e1 = x[1] - g1, e2 = x[2] - g2;
-                const float dp = FMA(e2, e2, FMA(e1, e1, e0 * e0));
-                const float f0 = x[3] - g3, f1 = x[4] - g4, f2 = x[5] - g5;
-                const float dv = FMA(f2, f2, FMA(f1, f1, f0 * f0));
-                const float c = FMA(-2.0f, x[7] * x[7] + x[8] * x[8], 1.0f);
-                const float w2 = FMA(x[12], x[12], FMA(x[11], x[11], x[10] * x[10]));
-                const uint32_t cause = (!(dp <= Z.r2_pos) ? 1u : 0u) | (!(c >= Z.cos_min) ? 2u : 0u) | (!(w2 <= Z.w2_max) ? 4u : 0u) | (nf ? 8u : 0u);
+                bool nf;
+                float dp, dv, c, w2;                     // (the row's quantities, stated once for this form and the ensemble forms: sdempc_ensemble.inc.h)
+                const uint32_t cause = score_row(x, g0, g1, g2, g3, g4, g5, Z.r2_pos, Z.cos_min, Z.w2_max, dp, dv, c, w2, nf);
                 sdp = sdp + dp;
                 if (dp > mdp) { mdp = dp; imax = cnt; }
                 ldp = dp;
@@ -588,8 +590,21 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
 }
 
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st, const LoopObserve& O,
-                                   const LoopScore& Z, const LoopProcess& G, const LoopEvents& E, const LoopBaseline& A) {
+                                   const LoopScore& Z, const LoopProcess& G, const LoopEvents& E, const LoopBaseline& A, const LoopEnsemble& N) {
     if (B < 1 || substeps < 1 || ticks < 0 || xi_ticks < ticks) return hipErrorInvalidValue;
+    if (N.part) {   // SPEC.md §11m: a present block is complete, stands alone, and addresses rows the chunk's scoring launch counted
+        if (ticks != 0 || Z.words || A.x || O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev || G.dist.chain || G.bias.chain || E.fault.chain || E.drop.chain) return hipErrorInvalidValue;
+        if (!N.out || !N.words || !N.cohort || !N.rows || !N.ref || (N.E > 0 && !N.edges)) return hipErrorInvalidValue;
+        if (N.G < 1 || N.G > ENS_MAX_COHORTS || N.E < 0 || N.E > ENS_MAX_EDGES || (N.over != 0 && N.over != 1) || (N.combine != 0 && N.combine != 1)) return hipErrorInvalidValue;
+        if (N.rows_per_tick < 1 || N.row0 < 0 || N.nrows < 1 || N.nrows > 65535 || N.row0 + N.nrows > N.chunk_rows || N.nblk != (B + 255) / 256) return hipErrorInvalidValue;
+        if ((N.ref_tick_stride != 0 && N.ref_tick_stride < 13) || (N.ref_ep_stride != 0 && N.ref_ep_stride != 13)) return hipErrorInvalidValue;
+        if (N.r2_pos != N.r2_pos || N.cos_min != N.cos_min || N.w2_max != N.w2_max) return hipErrorInvalidValue;
+        if (N.combine) {
+            const long long threads = (long long)N.nrows * N.G * (ENS_BASE_WORDS + 4 * N.E);
+            sdempc_loop_keys_period_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(nullptr, nullptr, nullptr, B, 0, 0, substeps, O, Z, G, E, A, N);
+        } else sdempc_loop_keys_period_kernel<<<dim3((unsigned)N.nblk, (unsigned)N.nrows), 256, 0, st>>>(nullptr, nullptr, nullptr, B, 0, 0, substeps, O, Z, G, E, A, N);
+        return hipGetLastError();
+    }
     // ticks = 0 is the scoring form or the baseline form and nothing else: score words or a state, no observation, no key buffers
     if ((ticks == 0) != (Z.words != nullptr || A.x != nullptr) || (Z.words && A.x)) return hipErrorInvalidValue;
     if (A.x) {      // SPEC.md §11l: a present block is complete and addresses rows inside the window
@@ -630,7 +645,7 @@ hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float*
         if (D.sched && D.sched_ep_stride != 0 && D.sched_ep_stride != 1) return hipErrorInvalidValue;
         if (!O.q || O.valid != D.dst || O.valid_ep_stride != 1) return hipErrorInvalidValue;
     }
-    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z, G, E, A);
+    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z, G, E, A, LoopEnsemble{});
     return hipGetLastError();
 }
 

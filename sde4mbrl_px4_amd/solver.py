@@ -633,6 +633,123 @@ def score_summary(score, solves=None):
     return out
 
 
+ENSEMBLE_CHANNELS = ("dp", "dv", "c", "w2")        # the device's channel order (SPEC.md §11m): squared position error, squared velocity error, tilt cosine, squared rate
+
+
+class Ensemble:
+    """What closed_loop(ensemble=...) reduces over the EPISODES, per scored row and cohort (SPEC.md §11m): counts, the survival curve, sum / min / max of the score's
+    four channels and, per channel, cumulative counts against edges given here in the user's units — pos_edges [m], vel_edges [m/s], tilt_edges_deg [degrees],
+    rate_edges [rad/s]. The device compares squares and a cosine, as the score does, so the edges are squared (or their cosine taken) in float64, rounded to float32
+    ONCE and sorted ascending in the DEVICE's order; channels with fewer edges than the longest are filled up with +inf (every included finite value is below it).
+    A tilt edge counts the episodes tilted MORE than the edge (c < cos(edge)), and the cosine sorts the tilt edges into DESCENDING degrees: tilt_edges_deg holds
+    them in that device order. over="alive" includes an episode in a row's statistics only while it has not failed before that row; over="all" every finite row.
+    n_cohorts (1 .. 16; None: taken from the cohort array of the call, max + 1) lets a cohort be empty."""
+
+    def __init__(self, pos_edges=(), vel_edges=(), tilt_edges_deg=(), rate_edges=(), over="alive", n_cohorts=None):
+        if over not in ("alive", "all"):
+            raise ValueError('Ensemble: over must be "alive" or "all"')
+        if n_cohorts is not None and not (1 <= int(n_cohorts) <= 16):
+            raise ValueError("Ensemble: n_cohorts must be between 1 and 16")
+        self.over, self.n_cohorts = over, None if n_cohorts is None else int(n_cohorts)
+        user = [np.atleast_1d(np.asarray(e, np.float64)).ravel() for e in (pos_edges, vel_edges, tilt_edges_deg, rate_edges)]
+        for name, e in zip(("pos_edges", "vel_edges", "tilt_edges_deg", "rate_edges"), user):
+            if np.isnan(e).any() or (e < 0).any():
+                raise ValueError(f"Ensemble: {name} must hold values >= 0 (and no NaN)")
+        if (user[2] > 180.0).any():
+            raise ValueError("Ensemble: tilt_edges_deg must lie in [0, 180]")
+        self.pos_edges, self.vel_edges, self.rate_edges = (np.sort(e) for e in (user[0], user[1], user[3]))
+        self.tilt_edges_deg = np.sort(user[2])[::-1].copy()
+        with np.errstate(over="ignore"):
+            dev = [np.float32(self.pos_edges * self.pos_edges), np.float32(self.vel_edges * self.vel_edges), np.float32(np.cos(np.radians(self.tilt_edges_deg))),
+                   np.float32(self.rate_edges * self.rate_edges)]
+        self.counts = tuple(int(d.size) for d in dev)            # edges per channel that the caller gave
+        self.n_edges = max(self.counts)
+        if self.n_edges > 16:
+            raise ValueError("Ensemble: at most 16 edges per channel")
+        self.edges = np.full((4, self.n_edges), np.inf, np.float32)
+        for k, d in enumerate(dev):
+            self.edges[k, :d.size] = np.sort(d)                   # (rounding keeps the order; equal neighbours are allowed)
+        self.words = _abi.ENSEMBLE_BASE_WORDS + 4 * self.n_edges
+
+    @classmethod
+    def from_device_edges(cls, edges, over="alive", n_cohorts=None):
+        """An Ensemble whose edges are given as the device compares them: f32[4][E] for (dp, dv, c, w2) — squared metres, squared m/s, a cosine, squared rad/s —
+        each row ascending, no NaN. For edges derived from a Score's own thresholds (Score.thresholds()) or from recorded channel values; the user-unit edges are
+        their square roots and arc cosines."""
+        e = np.ascontiguousarray(edges, np.float32)
+        if e.ndim != 2 or e.shape[0] != 4 or e.shape[1] > 16 or np.isnan(e).any() or (e[:, 1:] < e[:, :-1]).any():
+            raise ValueError("Ensemble.from_device_edges: edges must be f32[4][E], E <= 16, every row ascending, no NaN")
+        self = cls(over=over, n_cohorts=n_cohorts)
+        with np.errstate(invalid="ignore"):
+            self.pos_edges, self.vel_edges, self.rate_edges = (np.sqrt(e[k].astype(np.float64)) for k in (0, 1, 3))
+            self.tilt_edges_deg = np.degrees(np.arccos(np.clip(e[2].astype(np.float64), -1.0, 1.0)))
+        self.counts, self.n_edges, self.edges = (e.shape[1],) * 4, e.shape[1], e
+        self.words = _abi.ENSEMBLE_BASE_WORDS + 4 * self.n_edges
+        return self
+
+    def __repr__(self):
+        return (f"Ensemble(pos_edges={self.pos_edges.tolist()}, vel_edges={self.vel_edges.tolist()}, tilt_edges_deg={self.tilt_edges_deg.tolist()}, "
+                f"rate_edges={self.rate_edges.tolist()}, over={self.over!r}, n_cohorts={self.n_cohorts})")
+
+
+def ensemble_summary(words, ensemble, quantiles=(0.5, 0.9)):
+    """Host arithmetic on the word array u32[R][G][W] that closed_loop(ensemble=...) returns (SPEC.md §11m), per scored row and cohort, float64[R][G] unless said
+    otherwise (NaN where a ratio has an empty denominator):
+        n, n_in           episodes of the cohort, episodes included in the statistics (int64)
+        survival          1 - (episodes failed by this row) / n
+        fail_now          (episodes whose row violates a criterion) / n;  fail_now_by_cause: the same per SCORE_CAUSES name
+        rms_pos, rms_vel  sqrt(sum / n_in) of the squared position / velocity error over the included episodes
+        mean_cos_tilt, rms_rate   sum / n_in of the tilt cosine, sqrt(sum / n_in) of the squared rate
+        min_pos, max_pos, min_vel, max_vel, min_rate, max_rate   square roots of the extrema;  min_tilt_deg, max_tilt_deg from the largest / smallest cosine
+        cdf_pos, cdf_vel, cdf_rate   [R][G][edges given]: fraction of the included episodes BELOW each edge;  frac_tilt_above: fraction tilted MORE than each
+                          tilt edge (in the order of ensemble.tilt_edges_deg)
+        q_pos, q_vel, q_tilt_deg, q_rate   [R][G][len(quantiles)]: the smallest edge below which (for tilt: at or below which) at least that fraction of the
+                          included episodes lies — an upper estimate no finer than the edges; NaN where no edge reaches the level."""
+    w = np.ascontiguousarray(words)
+    if not isinstance(ensemble, Ensemble):
+        raise ValueError("ensemble_summary: ensemble must be the Ensemble the words were formed with")
+    if w.dtype != np.uint32 or w.ndim != 3 or w.shape[2] != ensemble.words:
+        raise ValueError(f"ensemble_summary: words must be uint32[R][G][{ensemble.words}], got dtype {w.dtype} and shape {w.shape}")
+    E = ensemble.n_edges
+    n, n_in = w[..., 0].astype(np.int64), w[..., 1].astype(np.int64)
+    fl = w[..., 8:20].view(np.float32).astype(np.float64).reshape(w.shape[0], w.shape[1], 4, 3)
+    out = {"n": n, "n_in": n_in}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        nf, ni = n.astype(np.float64), n_in.astype(np.float64)
+        out["survival"] = 1.0 - w[..., 2] / nf
+        out["fail_now"] = w[..., 3] / nf
+        out["fail_now_by_cause"] = {name: w[..., 4 + i] / nf for i, name in enumerate(SCORE_CAUSES)}
+        mean = fl[..., 0] / ni[..., None]
+        out["rms_pos"], out["rms_vel"], out["mean_cos_tilt"], out["rms_rate"] = np.sqrt(mean[..., 0]), np.sqrt(mean[..., 1]), mean[..., 2], np.sqrt(mean[..., 3])
+        empty = n_in == 0
+        for k, name in ((0, "pos"), (1, "vel"), (3, "rate")):
+            out["min_" + name] = np.where(empty, np.nan, np.sqrt(fl[..., k, 1]))
+            out["max_" + name] = np.where(empty, np.nan, np.sqrt(fl[..., k, 2]))
+        out["min_tilt_deg"] = np.where(empty, np.nan, np.degrees(np.arccos(np.clip(fl[..., 2, 2], -1.0, 1.0))))
+        out["max_tilt_deg"] = np.where(empty, np.nan, np.degrees(np.arccos(np.clip(fl[..., 2, 1], -1.0, 1.0))))
+        cnt = w[..., 20:].reshape(w.shape[0], w.shape[1], 4, E).astype(np.float64) / ni[..., None, None]
+        levels = np.atleast_1d(np.asarray(quantiles, np.float64))
+        for k, name, edges in ((0, "pos", ensemble.pos_edges), (1, "vel", ensemble.vel_edges), (3, "rate", ensemble.rate_edges)):
+            cdf = cnt[..., k, :edges.size]
+            out["cdf_" + name] = cdf
+            out["q_" + name] = _edge_quantiles(cdf, edges, levels)
+        above = cnt[..., 2, :ensemble.tilt_edges_deg.size]
+        out["frac_tilt_above"] = above
+        out["q_tilt_deg"] = _edge_quantiles((1.0 - above)[..., ::-1], ensemble.tilt_edges_deg[::-1], levels)
+    return out
+
+
+def _edge_quantiles(cdf, edges, levels):
+    """[..][len(levels)]: the smallest of the ascending edges whose cumulative fraction cdf[.., j] reaches each level; NaN where none does (or the cdf is NaN)."""
+    out = np.full(cdf.shape[:-1] + (levels.size,), np.nan)
+    for i, q in enumerate(levels):
+        hit = cdf >= q
+        first = np.argmax(hit, axis=-1) if edges.size else np.zeros(cdf.shape[:-1], np.int64)
+        if edges.size:
+            out[..., i] = np.where(hit.any(axis=-1), edges[first], np.nan)
+    return out
+
+
 class _TubeFields(NamedTuple):
     cost: np.ndarray
     mean: np.ndarray
@@ -1297,7 +1414,7 @@ class SdeMpcSolver:
                     meas_keys=None, xmeas_in=None, meas_age=None, meas_age_max=None, meas_renorm=False, xhist_in=None, score=None, score_ref=None, score_in=None,
                     outputs=True, dist_process=None, dist_keys=None, dist_state_in=None, bias_process=None, bias_keys=None, bias_state_in=None,
                     track=None, track_of=None, track_phase=None, track_rate=None, track_offset=None, track_tick0=None, track_renorm=None,
-                    fault_process=None, fault_keys=None, fault_state_in=None, fault_tick0=0, drop_process=None, drop_keys=None, drop_state_in=None, controller=None):
+                    fault_process=None, fault_keys=None, fault_state_in=None, fault_tick0=0, drop_process=None, drop_keys=None, drop_state_in=None, controller=None, ensemble=None, cohort=None):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -1432,7 +1549,19 @@ class SdeMpcSolver:
         exactly as it flies a solution's table. Keys, gusts, faults, estimator, windows, score, chunking and continuation are untouched, so a second call with the
         same arguments and controller=None flies the MPC under the same conditions and the two scores are a paired comparison. The returned tuple is the rate
         route's: u_next holds thrust rows (every motor the thrust command), info rows are (0, stepsize, 0, ...) and the step size is handed through. Parameters may
-        be one set or one per episode. With controller=None nothing of this paragraph is touched."""
+        be one set or one per episode. With controller=None nothing of this paragraph is touched.
+
+        ensemble / cohort (SPEC.md §11m, sdempc_closed_loop_batch_ensemble): TIME-RESOLVED histories of the batch, reduced over the EPISODES on the device. ensemble
+        is an Ensemble (edges per channel, over="alive" or "all") and needs score (ValueError otherwise); cohort int[B] (None: all 0) puts every episode into one of
+        up to 16 groups — faulted / unfaulted, a parameter cell, a controller arm. For every scored row of the call (T of them, or T * plant_substeps with a substep
+        score) and every cohort the device forms 20 + 4 * n_edges words from the rows, targets and thresholds the score reads: the cohort's size, the episodes
+        included, failed by now (the survival curve) and violating each criterion in this row, sum / min / max of the squared position and velocity errors, the
+        tilt cosine and the squared rate over the included episodes, and how many of them lie below each edge. They come back as ONE more value, uint32[R][G][W],
+        right behind the score (ensemble_summary reduces it); nothing else in the returned tuple moves or changes, and the words are the same under outputs=False
+        and any chunking. A float sum has one fixed association over blocks of 256 consecutive episodes, so the words depend on B and on the order of the episodes.
+        A run continued through score_in keeps counting rows, so its words are the later rows of the joined run. With controller=None the MPC is flown, with a
+        controller the baseline: one Ensemble and one cohort array give the two arms of a paired comparison. cohort without ensemble raises ValueError; with neither
+        given nothing of this paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -1637,6 +1766,24 @@ class SdeMpcSolver:
             if not isinstance(rate_loop, RateLoop) or rate_loop.motor_weight != 0.0:
                 raise ValueError("closed_loop: controller= needs a RateLoop with motor_weight 0 (its table holds no motor values)")
             gc, keep_g = self._geo_cfg(controller, B)
+        ensembled = ensemble is not None
+        if cohort is not None and not ensembled:
+            raise ValueError("closed_loop: cohort needs ensemble=Ensemble(...)")
+        if ensembled:
+            if not isinstance(ensemble, Ensemble):
+                raise ValueError("closed_loop: ensemble must be an Ensemble")
+            if not scored:
+                raise ValueError("closed_loop: ensemble needs score=Score(...) (it reduces the score's own quantities)")
+            coh = None
+            if cohort is not None:
+                coh = np.asarray(cohort)
+                if coh.dtype.kind not in "iu" or coh.shape != (B,):
+                    raise ValueError(f"closed_loop: cohort must be int[{B}], got dtype {coh.dtype} and shape {coh.shape}")
+                coh = np.ascontiguousarray(coh, dtype=np.int32)
+            n_coh = ensemble.n_cohorts if ensemble.n_cohorts is not None else (1 if coh is None or B == 0 else int(coh.max()) + 1)
+            if not (1 <= n_coh <= 16) or (coh is not None and B > 0 and (coh.min() < 0 or coh.max() >= n_coh)):
+                raise ValueError(f"closed_loop: cohort must hold entries in [0, {n_coh}) and at most 16 cohorts")
+        baseline_args = baseline or ensembled     # (the ensemble entry point takes the baseline one's arguments, its geo cfg NULL without a controller)
         faulted = flt is not None or bool(substep_states) or observed or scored or drawn or tracked or events or baseline
         full = scored or drawn or tracked or events or baseline          # the entry points from the scored one on take every layer's arguments, NULL where a layer is absent
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
@@ -1766,9 +1913,12 @@ class SdeMpcSolver:
                 z_out = np.zeros(B, SCORE_DTYPE)
                 lead = [C.byref(zc), None if score_in is None else score_in.ctypes.data_as(u32p)] + lead
                 more, ret = more + (z_out.ctypes.data_as(u32p),), ret + (z_out,)
+                if ensembled:       # (the word array sits right behind the score; its pointer leads the C call, below)
+                    ens_words = np.zeros((max(T, 0) * (int(plant_substeps) if score.substeps else 1), n_coh, ensemble.words), np.uint32)
+                    ret = ret + (ens_words,)
             elif drawn or tracked or events or baseline:  # (no score: a NULL score cfg and NULL score pointers)
                 lead, more = [None, None] + lead, more + (None,)
-            if drawn or tracked or events or baseline:   # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
+            if drawn or tracked or events or baseline_args:   # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
                 cfgs, keep_p = [], []
                 for name, Nrows in (("dist", max(T, 0)), ("bias", max(Ns, 0))):
                     if name not in procs:
@@ -1786,9 +1936,9 @@ class SdeMpcSolver:
                 lead = cfgs + lead
             if tracked:             # the drawn entry point's arguments behind the track cfg; nothing new comes back
                 lead = [C.byref(tkc)] + lead
-            elif events or baseline:    # (no track: a NULL track cfg)
+            elif events or baseline_args:    # (no track: a NULL track cfg)
                 lead = [None] + lead
-            if events or baseline:  # the tracked entry point's arguments behind (fault_proc, drop_proc), then rows, keys_next and state_next of each chain
+            if events or baseline_args:  # the tracked entry point's arguments behind (fault_proc, drop_proc), then rows, keys_next and state_next of each chain
                 i32p = C.POINTER(C.c_int32)
                 ecfgs, keep_e = [None, None], []
                 if "fault" in evts:
@@ -1818,10 +1968,18 @@ class SdeMpcSolver:
                 lead = ecfgs + lead
             if baseline:            # the events entry point's arguments behind the geo cfg; nothing new comes back
                 lead = [C.byref(gc)] + lead
+            elif ensembled:         # (no controller: a NULL geo cfg)
+                lead = [None] + lead
+            if ensembled:           # the baseline entry point's arguments behind (ensemble cfg, ens_out)
+                ec = _abi.SdempcEnsembleCfg(C.sizeof(_abi.SdempcEnsembleCfg), n_coh, ensemble.n_edges, 1 if ensemble.over == "alive" else 0,
+                                            None if coh is None else coh.ctypes.data_as(C.POINTER(C.c_int32)), _fp(ensemble.edges) if ensemble.n_edges else None)
+                lead = [C.byref(ec), ens_words.ctypes.data_as(u32p)] + lead
             if substep_states:
                 ret = ret + (xsub,)
         # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
-        if baseline:
+        if ensembled:
+            entry = _abi.ensemble_entry(self.lib)
+        elif baseline:
             entry = _abi.baseline_entry(self.lib)
         elif events:
             entry = _abi.events_entry(self.lib)

@@ -51,11 +51,16 @@
      calibrated for the model (GeometricController.for_model), one set for every episode, through the rate loop of --rate-loop (implied). Applies to --small-batch and
      to the C2 loop; everything above still applies, so the same command with and without it is the paired comparison of SPEC.md §11l. The "one batch solve" figure
      beside the C2 loop is then the MPC's solve, for scale: the baseline's period has no solve in it.
+ 15. --ensemble G E: with --score, the per-row ensemble histories over the episodes (SPEC.md §11m, sdempc_closed_loop_batch_ensemble) — G cohorts dealt out round robin,
+     E edges per channel (position error up to 2 m, velocity error up to 4 m/s, tilt up to 60 degrees, rate up to 8 rad/s), over = alive. After every chunk's scoring
+     launch the key kernel runs twice more (partial words per block of 256 episodes, then the blocks in order) and R x G x (20 + 4 E) words come back. Applies to
+     --small-batch and to the C2 loop; the same command without it takes the entry point it took before. The last run's survival and RMS position error per row of
+     cohort 0 are printed.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
                                         [--fault] [--substep-states] [--observe] [--age A] [--renorm]
                                         [--score] [--no-outputs] [--score-substeps] [--dist-process] [--bias-process] [--track] [--per-episode-xref]
-                                        [--fault-process] [--drop-process] [--controller geo]
+                                        [--fault-process] [--drop-process] [--controller geo] [--ensemble G E]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -104,7 +109,12 @@ ap.add_argument("--per-episode-xref", action="store_true", help="--small-batch: 
 ap.add_argument("--fault-process", action="store_true", help="motor faults drawn on the device, one step of a Markov chain per motor and control tick (SPEC.md §11k)")
 ap.add_argument("--drop-process", action="store_true", help="with --observe: estimator dropouts drawn on the device, one step per solve, instead of meas_valid rows (SPEC.md §11k)")
 ap.add_argument("--controller", choices=("mpc", "geo"), default="mpc", help="geo: the geometric baseline controller in place of the solves, through the rate loop (SPEC.md §11l)")
+ap.add_argument("--ensemble", type=int, nargs=2, metavar=("G", "E"), help="with --score: per-row ensemble words over the episodes, G cohorts and E edges per channel (SPEC.md §11m)")
 a = ap.parse_args()
+if a.ensemble and not a.score:
+    ap.error("--ensemble needs --score")
+if a.ensemble and not (1 <= a.ensemble[0] <= 16 and 0 <= a.ensemble[1] <= 16):
+    ap.error("--ensemble: G in 1 .. 16, E in 0 .. 16")
 if a.controller == "geo":
     a.rate_loop = True
 if a.drop_process and not a.observe:
@@ -195,6 +205,12 @@ def scenario_kw(kw, B, T):
         kw["score_ref"] = "track" if a.track else np.ascontiguousarray(np.broadcast_to(np.asarray(W.HOVER, np.float32), (T, B, 13)))
         if a.no_outputs:
             kw["outputs"] = False
+        if a.ensemble:
+            from sde4mbrl_px4_amd.solver import Ensemble
+            G_, E_ = a.ensemble
+            grid = np.arange(1, E_ + 1) / max(E_, 1)
+            kw["ensemble"] = Ensemble(pos_edges=2.0 * grid, vel_edges=4.0 * grid, tilt_edges_deg=60.0 * grid, rate_edges=8.0 * grid, over="alive", n_cohorts=G_)
+            kw["cohort"] = (np.arange(B) % G_).astype(np.int32)
     if a.track:
         kw.update(track_kw(B))
     if a.disturbance:
@@ -265,14 +281,22 @@ if a.per_episode_xref:
     tag += " per-episode-xref"
 if a.score:
     tag += " score" + ("/substeps" if a.score_substeps else "") + (" no-outputs" if a.no_outputs else "")
+if a.ensemble:
+    tag += f" ensemble G={a.ensemble[0]} E={a.ensemble[1]}"
 
 
-def report_score(out, T):
+def report_score(out, T, pk_ens=None):
     """score_summary of a scored call's result (the score sits behind every other value, in front of xsub)"""
     if not a.score:
         return
     from sde4mbrl_px4_amd.solver import score_summary
     at = -1 - (1 if a.substep_states else 0) - 3 * (int(a.dist_process) + int(a.bias_process) + int(a.fault_process) + int(a.drop_process))      # the score sits in front of the process values and of xsub
+    if a.ensemble:             # (the ensemble words sit right behind the score)
+        from sde4mbrl_px4_amd.solver import ensemble_summary
+        e = ensemble_summary(out[at], pk_ens)
+        print("  ensemble, cohort 0: survival per row " + " ".join(f"{v:.3f}" for v in e["survival"][:, 0]) + "; RMS position error [m] " +
+              " ".join(f"{v:.3f}" for v in e["rms_pos"][:, 0]), flush=True)
+        at -= 1
     s = score_summary(out[at], solves=-(-T // max(a.period, 1)))
     print(f"  score: success {s['success_rate']:.3f}, median RMS position error {float(np.median(s['rms_pos_err'])):.3f} m, worst tilt {s['worst_tilt_deg']:.1f} deg, "
           f"{s['mean_steps']:.2f} iterations and {s['mean_ls_trials']:.2f} trials per solve", flush=True)
@@ -294,7 +318,7 @@ if a.small_batch:
         out = S.closed_loop(x0, xr, keys, T, **kw)
         dt = time.perf_counter() - t
         print(f"C1 B={B} T={T}{tag}: {T / dt:8.1f} ticks/s ({B * T / dt:9.1f} episode-ticks/s, {dt * 1e3 / T:.3f} ms/tick)", flush=True)
-    report_score(out, T)
+    report_score(out, T, kw.get("ensemble"))
     S.close()
     sys.exit(0)
 
@@ -346,5 +370,5 @@ if not a.skip_c2:
         loop = time.perf_counter() - t
         print(f"C2 f32x3/fast B={B}{tag}: closed_loop {B * T / loop:8.1f} episode-ticks/s ({loop / T:.3f} s/tick, T = {T}); one batch solve_keys "
               f"{B / one:8.1f} solves/s ({one:.3f} s); ratio {(B * T / loop) / (B / one):.3f}", flush=True)
-    report_score(out, T)
+    report_score(out, T, pk.get("ensemble"))
     S.close()
