@@ -1117,6 +1117,63 @@ int sdempc_closed_loop_batch_ensemble(sdempc_handle* h, const sdempc_ensemble_cf
                                       float* fault_rows /*[B][T][m][2] or NULL*/, uint32_t* fault_keys_next /*[B][2] or NULL*/, int32_t* fault_state_next /*[B][m][2] or NULL*/,
                                       int32_t* valid_rows /*[B][Ns] or NULL*/, uint32_t* valid_keys_next /*[B][2] or NULL*/, int32_t* valid_state_next /*[B][2] or NULL*/);
 
+/* ---- batched closed loop that retires failed episodes and solves only the live set (SPEC.md §11n) -----------------------
+ * sdempc_closed_loop_batch_ensemble with one more rule: an episode whose score records a failure (word 8 != 0xffffffff, from this call's rows or from score_in) is
+ * RETIRED at the next solve-period boundary. With `retire` NULL the call IS sdempc_closed_loop_batch_ensemble bit for bit, with the same launches (retired_at and
+ * live_per_solve must then be NULL). Per solve j of the call: live_0(b) = word 8 of score_in[b] is all ones (no score_in: every episode); live_{j+1}(b) = live_j(b)
+ * and word 8 is still all ones after period j's rows were scored. It depends on the rows alone — not on chunking, B or the outputs requested.
+ *  - A live episode is solved as ever, in a dense batch of n_live_j instances (results do not depend on an instance's position or the batch size).
+ *  - A retired episode gets no solve: its uopt / xevol tables stay as they are and its info row of that solve is (0, stepsize, 0, 0, 0, 0, 0, 0), so the step size is
+ *    held. The plant launch, the key schedule, the observation, process and event chains, the history and the windows run over all B as ever (the solve's subkey is
+ *    split and not used). At the call's entry every episode's uopt table is the warm start (u_init, or uref tiled) and every row of its xevol table is x0[b]: an
+ *    episode retired at entry flies that, whatever the handle did before.
+ *  - Scoring runs once per PERIOD: period j's rows, us rows and info row are scored for episode b only where live_j(b); a retired episode's 16 words are frozen at
+ *    the end of the period of its first failure. An episode that never fails has every word and every row bit-identical to the call without `retire`.
+ *  - With `geo` the controller skips retired episodes by the same mask (nothing is compacted); their info rows are the held ones.
+ *  - An ensemble cfg must have over = 1: the rows of a retired episode are not a fleet statistic, and over = 1 leaves them out.
+ * retired_at[b]: the first solve index of THIS call at which b was not solved (0: retired at entry), -1: none (an episode failing in the call's last period is
+ * retired by the next call). live_per_solve[j] = n_live_j. A run cut in two through score_in and the *_next outputs composes: the second call's score words, keys
+ * and chains are the single call's, its retired_at counts from its own first solve, and every row of an episode live at the cut is the single call's; an episode
+ * retired before the cut agrees through its failing period and flies the second call's entry tables behind the cut (its held tables are not carried across calls).
+ * Checked before the first HIP call, in this order and in front of everything else, SDEMPC_EINVAL for: retire without retired_at / live_per_solve or either of them
+ * without retire, a wrong struct_size, reserved != 0, retire without a score cfg, retire with an ensemble cfg whose over is 0; then everything
+ * sdempc_closed_loop_batch_ensemble refuses. No ABI version change: detect the entry point by its symbol. */
+typedef struct sdempc_retire_cfg {
+    int32_t struct_size;     /* sizeof(sdempc_retire_cfg) */
+    int32_t reserved;        /* 0 */
+} sdempc_retire_cfg;
+int sdempc_closed_loop_batch_retire(sdempc_handle* h, const sdempc_retire_cfg* retire /*or NULL*/, int32_t* retired_at /*[B]; NULL without retire*/,
+                                    int32_t* live_per_solve /*[Ns]; NULL without retire*/,
+                                    const sdempc_ensemble_cfg* ens /*or NULL*/, uint32_t* ens_out /*[R][G][W]; NULL without ens*/,
+                                    const sdempc_geo_cfg* geo /*or NULL: the MPC*/,
+                                    const sdempc_fault_process_cfg* fault_proc /*or NULL*/, const sdempc_dropout_process_cfg* drop_proc /*or NULL*/,
+                                    const sdempc_track_cfg* track /*or NULL*/,
+                                    const sdempc_process_cfg* dist_proc /*or NULL, W = 6*/, const sdempc_process_cfg* bias_proc /*or NULL, W = 12*/,
+                                    const sdempc_score_cfg* score /*required with retire*/, const uint32_t* score_in /*[B][16] or NULL*/,
+                                    const sdempc_age_cfg* age_cfg /*or NULL*/, const float* xhist_in /*[B][age_max][13] or NULL*/,
+                                    const sdempc_obs_cfg* obs /*or NULL*/, const uint32_t* obs_keys /*[B][2]; NULL without obs*/, const float* xmeas_in /*[B][13] or NULL*/,
+                                    const sdempc_fault_cfg* fault_cfg /*or NULL*/, const sdempc_rate_cfg* rate /*required with geo*/,
+                                    const sdempc_scenario_cfg* scenario /*or NULL*/, const sdempc_timing_cfg* timing, const sdempc_plant_cfg* pc,
+                                    const void* const* plant_blobs /*[num_plants]*/, const size_t* plant_blob_bytes /*[num_plants]*/,
+                                    const int32_t* plant_of /*[plant_ticks][B] or NULL*/, int32_t B, int32_t T, const float* x0,
+                                    const float* xref /*NULL with track*/, int32_t xref_solves /*0 with track*/, int32_t xref_batch,
+                                    const uint32_t* keys, const float* u_init /*or NULL*/, const float* stepsize_in /*or NULL*/,
+                                    const float* u_act_in /*[B][m] or NULL*/,
+                                    float* xs /*[B][T+1][13]; may be NULL with score*/, float* us /*[B][T][m]; may be NULL with score*/,
+                                    sdempc_info* info /*[B][Ns]; may be NULL with score*/,
+                                    float* u_next /*[B][H][m] or NULL*/, float* stepsize_next /*[B] or NULL*/,
+                                    uint32_t* keys_next /*[B][2] or NULL*/, float* u_act_next /*[B][m] or NULL*/,
+                                    const float* rate_integ_in /*[B][3] or NULL*/, const float* rate_tail_in /*[B][H][3] or NULL*/,
+                                    float* ws /*[B][T][4]; NULL without rate; may be NULL with score*/, float* rate_integ_next /*[B][3] or NULL*/,
+                                    float* rate_tail_next /*[B][H][3] or NULL*/,
+                                    float* xsub /*[B][T * substeps][13] or NULL*/,
+                                    float* xmeas /*[B][Ns][13] or NULL*/, uint32_t* obs_keys_next /*[B][2] or NULL*/, float* xmeas_next /*[B][13] or NULL*/,
+                                    float* xhist_next /*[B][age_max][13] or NULL*/, uint32_t* score_out /*[B][16]; NULL without score*/,
+                                    float* dist_rows /*[B][T][6] or NULL*/, uint32_t* dist_keys_next /*[B][2] or NULL*/, float* dist_state_next /*[B][6] or NULL*/,
+                                    float* bias_rows /*[B][Ns][12] or NULL*/, uint32_t* bias_keys_next /*[B][2] or NULL*/, float* bias_state_next /*[B][12] or NULL*/,
+                                    float* fault_rows /*[B][T][m][2] or NULL*/, uint32_t* fault_keys_next /*[B][2] or NULL*/, int32_t* fault_state_next /*[B][m][2] or NULL*/,
+                                    int32_t* valid_rows /*[B][Ns] or NULL*/, uint32_t* valid_keys_next /*[B][2] or NULL*/, int32_t* valid_state_next /*[B][2] or NULL*/);
+
 
 /* After the stream of the last sdempc_solve_batch_dev call has been synchronised: SDEMPC_OK, or SDEMPC_EDEVICE when a grid barrier of
  * a cooperative layout gave up (results of that call invalid, telemetry NaN). The handle then stays off the cooperative layouts, so

@@ -454,6 +454,25 @@ def ensemble_entry(lib):
     return fn
 
 
+class SdempcRetireCfg(C.Structure):
+    """sdempc_retire_cfg (SPEC.md §11n): its presence retires failed episodes at the next solve-period boundary in sdempc_closed_loop_batch_retire."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32)]
+
+
+def retire_entry(lib):
+    """sdempc_closed_loop_batch_retire (SPEC.md §11n) with its prototype set: a retire cfg (may be NULL), retired_at and live_per_solve in front of the ensemble
+    entry point's arguments. Detected by symbol and only when a call needs it, as ensemble_entry is."""
+    try:
+        fn = lib.sdempc_closed_loop_batch_retire
+    except AttributeError:
+        raise RuntimeError(f"{lib_path()} has no sdempc_closed_loop_batch_retire (SPEC.md §11n): rebuild the library (make -C sde4mbrl_px4_amd/csrc)") from None
+    if fn.argtypes is None:
+        a = list(ensemble_entry(lib).argtypes)
+        fn.argtypes = [a[0], C.POINTER(SdempcRetireCfg), C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + a[1:]
+        fn.restype = C.c_int
+    return fn
+
+
 def geo_command_entry(lib):
     """sdempc_geo_command_batch (SPEC.md §11l) with its prototype set. Detected by symbol and only when a call needs it, as baseline_entry is."""
     try:
@@ -561,6 +580,7 @@ EXPORTED_SYMBOLS = [
     "sdempc_closed_loop_batch_aged", "sdempc_closed_loop_batch_scored", "sdempc_closed_loop_batch_drawn",
     "sdempc_closed_loop_batch_tracked", "sdempc_reference_windows", "sdempc_closed_loop_batch_events",
     "sdempc_closed_loop_batch_baseline", "sdempc_geo_command_batch", "sdempc_closed_loop_batch_ensemble",
+    "sdempc_closed_loop_batch_retire",
     "sdempc_tube_batch", "sdempc_tube_batch_keys", "sdempc_tube_batch_dev",
     "sdempc_risk_batch", "sdempc_risk_batch_keys", "sdempc_risk_batch_dev",
     "sdempc_bands_batch", "sdempc_bands_batch_keys", "sdempc_bands_batch_dev",

@@ -199,6 +199,10 @@ struct sdempc_handle {
     // per-row ensemble histories (sdempc_closed_loop_batch_ensemble with an ensemble cfg; allocated on first use, grown, never shrunk): the cohorts i32[max_batch], the
     // edges f32[4][ENS_MAX_EDGES], then for one slab of rows the combined words u32[rows][G][W] and the per-block partial words u32[rows][nblk][G][W]
     DevBuf d_ens;
+    // retiring failed episodes (sdempc_closed_loop_batch_retire with a retire cfg; allocated on first use): per row of max_batch live i32, retired_at i32, list i32 and
+    // the row count u32, then the block counts u32[ceil(max_batch / 256)] and n_live; behind them, each part 16-byte aligned and sized for max_batch rows, the dense
+    // staging of the live set's solve: x0 [13], xref [(H+1) 13], u [H m], step, subkey [2] in, and uopt [H m], xevol [(H+1) 13], info [8] out
+    DevBuf d_retire;
     // closed loop with processes drawn on the device (sdempc_closed_loop_batch_drawn with a process cfg, allocated on its first use), per row of max_batch: the
     // disturbance chain u32[2] and state f32[6], the bias chain u32[2] and state f32[12], then rho and scale of each (f32[6], f32[6], f32[12], f32[12])
     DevBuf d_proc;
@@ -671,6 +675,12 @@ struct EnsRun {
     const sdempc_ensemble_cfg* cfg;
     uint32_t* out;                              // [R][G][W], R = T (tick score) or T * substeps (substep score)
 };
+// SPEC.md §11n: the outputs of one sdempc_closed_loop_batch_retire call (host pointers, checked at the front of closed_loop_call). Given only when the call has a
+// retire cfg: without one the call is the ensemble call, launch for launch.
+struct RetireRun {
+    int32_t* retired_at;                        // [B]
+    int32_t* live;                              // [Ns]
+};
 constexpr size_t ENS_SLAB_BYTES = 32u << 20;    // device bytes of partial words one pair of ensemble launches may fill: a chunk with more rows is reduced in slabs
 constexpr size_t PROC_WORDS = 2 + 6 + 2 + 12 + 2 * 6 + 2 * 12;     // words of d_proc per row of max_batch
 constexpr size_t EVT_MODES = 4;
@@ -722,6 +732,10 @@ struct LoopCall {
     bool ensembled;                             // sdempc_closed_loop_batch_ensemble (SPEC.md §11m): the baseline call (geo NULL: the events call) with ens / ens_out
     const sdempc_ensemble_cfg* ens;             // or NULL: no ensemble (ens_out must then be NULL)
     uint32_t* ens_out;
+    bool retiring;                              // sdempc_closed_loop_batch_retire (SPEC.md §11n): the ensemble call with retire / retired_at / live_per_solve
+    const sdempc_retire_cfg* retire;            // or NULL: nobody is retired (the two outputs must then be NULL)
+    int32_t* retired_at;
+    int32_t* live_per_solve;
 };
 int check_geo(sdempc_handle* h, const sdempc_geo_cfg* g, int B, float* inv_dt);
 int stage_geo(sdempc_handle* h, const sdempc_geo_cfg& g, hipStream_t st);
@@ -732,9 +746,9 @@ int stage_track(sdempc_handle* h, const sdempc_track_cfg& tk, int B, TrackRun* o
 int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* const* plant_blobs, const size_t* plant_blob_bytes, const int32_t* plant_of, int B, int sched_rows);
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt = nullptr,
                          const ObsRun* obs = nullptr, const ScoreRun* score = nullptr, const ProcRun* proc = nullptr, const TrackRun* track = nullptr,
-                         const EventRun* evt = nullptr, const GeoRun* geo = nullptr, const EnsRun* ens = nullptr);
+                         const EventRun* evt = nullptr, const GeoRun* geo = nullptr, const EnsRun* ens = nullptr, const RetireRun* ret = nullptr);
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, const EnsRun* ens, bool* again);
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, const EnsRun* ens, const RetireRun* ret, bool* again);
 int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const* blobs, const int32_t* plant_of, int B, PlantRun* out, int xi_ticks = 1);
 }  // namespace
 
@@ -834,7 +848,7 @@ namespace {
 void release_device(sdempc_handle* h) {
     if (h->dev_ready || h->stream || h->d_dt.p) {
         (void)hipSetDevice(h->device);
-        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_outcome, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_ens, &h->d_proc, &h->d_evt, &h->d_geo, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
+        for (DevBuf* b : {&h->d_sctab, &h->d_ustg, &h->d_part, &h->d_act, &h->d_dt, &h->d_sdt, &h->d_disc, &h->d_beta, &h->d_wts, &h->d_traj, &h->d_x0, &h->d_u, &h->d_xref, &h->d_noise, &h->d_noise_canon, &h->d_traj_canon, &h->d_keys, &h->d_tube, &h->d_band, &h->d_risk, &h->d_outcome, &h->d_loop, &h->d_loop_chunk, &h->d_plant, &h->d_rate, &h->d_obs, &h->d_hist, &h->d_score, &h->d_ens, &h->d_retire, &h->d_proc, &h->d_evt, &h->d_geo, &h->d_track, &h->d_work, &h->d_coop_bar, &h->d_coop_pp, &h->d_coop_ck,
                           &h->d_step, &h->d_cost, &h->d_grad, &h->d_xmean, &h->d_uopt, &h->d_info})
             dev_free(*b);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1971,6 +1985,40 @@ int sdempc_closed_loop_batch_ensemble(sdempc_handle* h, const sdempc_ensemble_cf
     });
 }
 
+int sdempc_closed_loop_batch_retire(sdempc_handle* h, const sdempc_retire_cfg* retire, int32_t* retired_at, int32_t* live_per_solve, const sdempc_ensemble_cfg* ens, uint32_t* ens_out, const sdempc_geo_cfg* geo, const sdempc_fault_process_cfg* fault_proc,
+                                      const sdempc_dropout_process_cfg* drop_proc, const sdempc_track_cfg* track, const sdempc_process_cfg* dist_proc,
+                                      const sdempc_process_cfg* bias_proc, const sdempc_score_cfg* zc, const uint32_t* score_in, const sdempc_age_cfg* ac, const float* xhist_in,
+                                      const sdempc_obs_cfg* oc, const uint32_t* obs_keys, const float* xmeas_in, const sdempc_fault_cfg* fc, const sdempc_rate_cfg* rc_,
+                                      const sdempc_scenario_cfg* sc, const sdempc_timing_cfg* tc, const sdempc_plant_cfg* pc, const void* const* plant_blobs,
+                                      const size_t* plant_blob_bytes, const int32_t* plant_of, int32_t B, int32_t T, const float* x0, const float* xref, int32_t xref_solves,
+                                      int32_t xref_batch, const uint32_t* keys, const float* u_init, const float* stepsize_in, const float* u_act_in, float* xs, float* us,
+                                      sdempc_info* info, float* u_next, float* stepsize_next, uint32_t* keys_next, float* u_act_next, const float* rate_integ_in,
+                                      const float* rate_tail_in, float* ws, float* rate_integ_next, float* rate_tail_next, float* xsub, float* xmeas, uint32_t* obs_keys_next,
+                                      float* xmeas_next, float* xhist_next, uint32_t* score_out, float* dist_rows, uint32_t* dist_keys_next, float* dist_state_next, float* bias_rows,
+                                      uint32_t* bias_keys_next, float* bias_state_next, float* fault_rows, uint32_t* fault_keys_next, int32_t* fault_state_next, int32_t* valid_rows,
+                                      uint32_t* valid_keys_next, int32_t* valid_state_next) {
+    return guarded(h, [&]() -> int {
+    LoopCall c{};
+    c.layer = rc_ ? LOOP_RATE : LOOP_SCENARIO;
+    c.io = {B, T, xref_solves, xref_batch, x0, xref, keys, u_init, stepsize_in, xs, us, info, u_next, stepsize_next, keys_next};
+    c.pc = pc; c.plant_blobs = plant_blobs; c.plant_blob_bytes = plant_blob_bytes; c.plant_of = plant_of;
+    c.tc = tc; c.u_act_in = u_act_in; c.u_act_next = u_act_next;
+    c.sc = sc;
+    c.rc = rc_; c.rate_integ_in = rate_integ_in; c.rate_tail_in = rate_tail_in; c.ws = ws; c.rate_integ_next = rate_integ_next; c.rate_tail_next = rate_tail_next;
+    c.faulted = true; c.fc = fc; c.xsub = xsub;
+    c.observed = true; c.oc = oc; c.obs_keys = obs_keys; c.xmeas_in = xmeas_in; c.xmeas = xmeas; c.obs_keys_next = obs_keys_next; c.xmeas_next = xmeas_next;
+    c.aged = true; c.ac = ac; c.xhist_in = xhist_in; c.xhist_next = xhist_next;
+    c.scored = true; c.zc = zc; c.score_in = score_in; c.score_out = score_out;
+    c.drawn = true; c.pr = {dist_proc, bias_proc, dist_rows, dist_keys_next, dist_state_next, bias_rows, bias_keys_next, bias_state_next};
+    c.track = track;
+    c.events = true; c.er = {fault_proc, drop_proc, fault_rows, fault_keys_next, fault_state_next, valid_rows, valid_keys_next, valid_state_next};
+    c.baseline = geo != nullptr; c.geo = geo;      // (geo NULL: the MPC's own solves, i.e. the events call)
+    c.ensembled = true; c.ens = ens; c.ens_out = ens_out;
+    c.retiring = true; c.retire = retire; c.retired_at = retired_at; c.live_per_solve = live_per_solve;
+    return closed_loop_call(h, c);
+    });
+}
+
 int sdempc_geo_command_batch(sdempc_handle* h, const sdempc_geo_cfg* geo, int32_t B, const float* x, const float* xref, int32_t Bx, float* out) {
     return guarded(h, [&]() -> int {
     if (!h) return SDEMPC_EINVAL;
@@ -2088,6 +2136,18 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     const sdempc_timing_cfg* tc = c.tc;
     auto finite = [](float v) { return fabsf(v) < INFINITY; };
     const float inv_m = 1.0f / (float)h->m;
+    if (c.retiring) {          // SPEC.md §11n: outputs and cfg come together; the cfg's own fields; then the score it reads and the ensemble it may not feed
+        const sdempc_retire_cfg* rt = c.retire;
+        if ((rt == nullptr) != (c.retired_at == nullptr) || (rt == nullptr) != (c.live_per_solve == nullptr))
+            return fail(h, SDEMPC_EINVAL, "retire: retire, retired_at and live_per_solve must be given together%s");
+        if (rt) {
+            if (rt->struct_size != (int32_t)sizeof(sdempc_retire_cfg)) return fail(h, SDEMPC_EINVAL, "retire: struct_size mismatch%s");
+            if (rt->reserved != 0) return fail(h, SDEMPC_EINVAL, "retire: reserved must be 0%s");
+            if (!c.zc) return fail(h, SDEMPC_EINVAL, "retire: a retire cfg needs a score cfg (an episode is retired by its score)%s");
+            if (c.ens && c.ens->struct_size == (int32_t)sizeof(sdempc_ensemble_cfg) && c.ens->over == 0)
+                return fail(h, SDEMPC_EINVAL, "retire: an ensemble over every finite row (over 0) may not be combined with retire (use over 1)%s");
+        }
+    }
     if (c.ensembled) {         // SPEC.md §11m: output and cfg come together; the cfg's own fields, edges and cohorts; then the score it reduces
         const sdempc_ensemble_cfg* en = c.ens;
         if ((en == nullptr) != (c.ens_out == nullptr)) return fail(h, SDEMPC_EINVAL, "ensemble: ens and ens_out must be given together%s");
@@ -2312,9 +2372,10 @@ int closed_loop_call(sdempc_handle* h, const LoopCall& c) {
     TrackRun run_k;
     if (tk && (rc = stage_track(h, *tk, B, &run_k))) return rc;
     const EnsRun run_e{c.ens, c.ens_out};
+    const RetireRun run_y{c.retired_at, c.live_per_solve};
     return closed_loop_attempts(h, io, &run, timed ? &run_t : nullptr, scenario ? &run_s : nullptr, rated ? &run_r : nullptr,
                                 run_f.fault || run_f.xsub || (evt && evt->fault) ? &run_f : nullptr, oc ? &run_o : nullptr, zc ? &run_z : nullptr, proc, tk ? &run_k : nullptr, evt,
-                                c.baseline ? &run_g : nullptr, c.ens ? &run_e : nullptr);
+                                c.baseline ? &run_g : nullptr, c.ens ? &run_e : nullptr, c.retiring && c.retire ? &run_y : nullptr);
 }
 // every check of a geometric-controller cfg (SPEC.md §11l), shared by the two entry points that take one; no HIP call. inv_dt: what the launch is given
 int check_geo(sdempc_handle* h, const sdempc_geo_cfg* g, int B, float* inv_dt) {
@@ -2482,10 +2543,11 @@ int check_plant_args(sdempc_handle* h, const sdempc_plant_cfg* pc, const void* c
 }
 // the loop, and once more from the host inputs if a cooperative-layout barrier gave up or the ticket count was off (closed_loop_run)
 int closed_loop_attempts(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt,
-                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, const EnsRun* ens) {
+                         const ObsRun* obs, const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, const EnsRun* ens,
+                         const RetireRun* ret) {
     for (int attempt = 0;; ++attempt) {
         bool again = false;
-        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, track, evt, geo, ens, &again);
+        int rc = closed_loop_run(h, io, plant, timed, scen, rate, flt, obs, score, proc, track, evt, geo, ens, ret, &again);
         if (rc) return rc;
         if (!again) return SDEMPC_OK;
         if (attempt) return fail(h, SDEMPC_EDEVICE, "closed loop: a cooperative-layout grid barrier gave up or the ticket count was off twice%s");
@@ -2582,8 +2644,12 @@ constexpr size_t LOOP_CHUNK_BYTES = (size_t)256 << 20;
 // the plant launch then reads as its fault rows (a scheduled fault given as well is staged beside it, as before, and read by the key schedule); with a dropout chain it
 // writes the solve's flags into a [Pc][B] region, which the measurement reads as its valid flags (scheduled flags likewise). Both regions count in the chunk's bytes and are
 // copied back and scattered only when the caller asked for the rows.
+// SPEC.md §11n (ret, with score): the live flags, the list, n_live and the dense staging live in d_retire. The scoring launch runs once per PERIOD, masked by the live
+// flags, followed by the two live-list launches; n_live is read back in front of every solve (one synchronisation per period). With n_live == B the period's launches are
+// the ones they were; below B the solve runs on the gathered live set and its results are scattered back (coop_bar then stays out of the plant launch: the scatter folds
+// the give-up words); with the controller the baseline launch takes the mask. The ensemble launches stay per chunk and count rows by the loop's own counter.
 int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, const TimedRun* timed, const ScenarioRun* scen, const RateRun* rate, const FaultRun* flt, const ObsRun* obs,
-                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, const EnsRun* ens, bool* again) {
+                    const ScoreRun* score, const ProcRun* proc, const TrackRun* track, const EventRun* evt, const GeoRun* geo, const EnsRun* ens, const RetireRun* ret, bool* again) {
     *again = false;
     const bool flown = geo && rate && timed && plant;                      // (SPEC.md §11l: the geometric controller in place of the solve)
     const bool tracked = track && timed && plant;                          // (SPEC.md §11j)
@@ -2674,6 +2740,18 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
     float* n_edges = ensemble ? (float*)(n_cohort + MB) : nullptr;   // [4][E]
     uint32_t* n_out = ensemble ? (uint32_t*)(n_edges + 4 * ENS_MAX_EDGES) : nullptr;         // [slab][G][W]
     uint32_t* n_part = ensemble ? n_out + ens_slab * EG * EW : nullptr;                      // [slab][nblk][G][W]
+    // SPEC.md §11n: the live flags, the list and the dense staging of the live set's solve (the layout is the one stated at d_retire, each part sized for max_batch rows)
+    const bool retire = ret && scoring;
+    const size_t HM = (size_t)H * m;
+    auto up4 = [](size_t words) { return (words + 3) & ~(size_t)3; };
+    const size_t nblk_max = (MB + 255) / 256;
+    const size_t o_live = 0, o_rat = o_live + up4(MB), o_list = o_rat + up4(MB), o_cnt = o_list + up4(MB), o_blk = o_cnt + up4(MB), o_nl = o_blk + up4(nblk_max);
+    const size_t o_sx = o_nl + 4, o_sxr = o_sx + up4(MB * NX), o_su = o_sxr + up4(MB * XR), o_sstep = o_su + up4(MB * HM), o_ssub = o_sstep + up4(MB);
+    const size_t o_suo = o_ssub + up4(2 * MB), o_sxe = o_suo + up4(MB * HM), o_sinf = o_sxe + up4(MB * XR), retire_words = o_sinf + up4(MB * 8);
+    if (retire && !h->d_retire.p && (rc = dev_alloc(h, h->d_retire, sizeof(uint32_t) * retire_words, true))) return rc;
+    uint32_t* y_base = retire ? (uint32_t*)h->d_retire.p : nullptr;
+    int32_t* y_live = retire ? (int32_t*)(y_base + o_live) : nullptr;       // [B]
+    int32_t* y_nlive = retire ? (int32_t*)(y_base + o_nl) : nullptr;        // [1]
     uint32_t* d_q = (uint32_t*)h->d_obs.p;                           // q [B][2] (SPEC.md §11f)
     float* d_xm = d_q ? (float*)(d_q + 2 * (size_t)h->max_batch) : nullptr;   // xm [B][13]
     float* d_integ = (float*)h->d_rate.p;                            // g [B][3] (SPEC.md §11d)
@@ -2768,6 +2846,14 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         HIPCHK(h, hipMemcpyAsync(d_score, z_in, sizeof(uint32_t) * 16 * (size_t)B, hipMemcpyHostToDevice, st));
         if (!sref_moves) HIPCHK(h, hipMemcpyAsync(c_sref, score->cfg->score_ref, sizeof(float) * ZR, hipMemcpyHostToDevice, st));      // (targets: they move)
     }
+    std::vector<float> xe0;
+    if (retire) {              // SPEC.md §11n: the tables a retired episode flies are defined by the call — the warm start, and x0 in every row of xevol
+        xe0.resize((size_t)B * XR);
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t <= H; ++t) memcpy(&xe0[(size_t)b * XR + (size_t)t * NX], io.x0 + (size_t)b * NX, sizeof(float) * NX);
+        HIPCHK(h, hipMemcpyAsync(h->d_uopt.p, u_in, sizeof(float) * (size_t)B * HM, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(h->d_xmean.p, xe0.data(), sizeof(float) * xe0.size(), hipMemcpyHostToDevice, st));
+    }
     if (ensemble) {            // the cohorts (NULL: all 0) and the edges as given (SPEC.md §11m)
         if (ens->cfg->cohort) HIPCHK(h, hipMemcpyAsync(n_cohort, ens->cfg->cohort, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, st));
         else HIPCHK(h, hipMemsetAsync(n_cohort, 0, sizeof(int32_t) * (size_t)B, st));
@@ -2860,6 +2946,29 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
         N.rows = Z.rows; N.ref = Z.ref; N.ref_tick_stride = Z.ref_tick_stride; N.ref_ep_stride = Z.ref_ep_stride; N.rows_per_tick = Z.rows_per_tick;
         N.nblk = nblk; N.G = EG; N.E = EE; N.over = ens->cfg->over;
         N.r2_pos = Z.r2_pos; N.cos_min = Z.cos_min; N.w2_max = Z.w2_max;
+    }
+    LoopRetire Y{};            // (live null: absent; only the launches after a period's scoring launch take it)
+    LoopCompact Qg{}, Qs{};    // (list null: absent; the gather and the scatter around a dense solve)
+    if (retire) {              // live_0 from the staged score words; the list and n_live of the first solve
+        Y.live = y_live; Y.words = d_score; Y.retired_at = (int32_t*)(y_base + o_rat); Y.blk = y_base + o_blk; Y.list = (int32_t*)(y_base + o_list); Y.n_live = y_nlive;
+        Y.count = ensemble ? y_base + o_cnt : nullptr; Y.nblk = nblk;
+        N.count = Y.count;
+        Y.init = 1; Y.solve = 0;
+        HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, LoopScore{}, LoopProcess{}, LoopEvents{}, LoopBaseline{}, LoopEnsemble{}, Y));
+        Y.init = 0; Y.place = 1;
+        HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, LoopScore{}, LoopProcess{}, LoopEvents{}, LoopBaseline{}, LoopEnsemble{}, Y));
+        Qg.list = Qs.list = Y.list; Qg.B = Qs.B = B; Qs.scatter = 1;
+        Qg.nseg = 5;           // the solve's state, window, warm start, step size and subkey (the state and the window are set per period)
+        Qg.seg[0].dst = y_base + o_sx; Qg.seg[0].words = NX;
+        Qg.seg[1].dst = y_base + o_sxr; Qg.seg[1].words = (int)XR;
+        Qg.seg[2].src = (const uint32_t*)h->d_u.p; Qg.seg[2].dst = y_base + o_su; Qg.seg[2].words = (int)HM;
+        Qg.seg[3].src = (const uint32_t*)h->d_step.p; Qg.seg[3].dst = y_base + o_sstep; Qg.seg[3].words = 1;
+        Qg.seg[4].src = d_sub; Qg.seg[4].dst = y_base + o_ssub; Qg.seg[4].words = 2;
+        Qs.nseg = 3;           // the solve's tables and its info rows (set per period)
+        Qs.seg[0].src = y_base + o_suo; Qs.seg[0].dst = (uint32_t*)h->d_uopt.p; Qs.seg[0].words = (int)HM;
+        Qs.seg[1].src = y_base + o_sxe; Qs.seg[1].dst = (uint32_t*)h->d_xmean.p; Qs.seg[1].words = (int)XR;
+        Qs.seg[2].src = y_base + o_sinf; Qs.seg[2].words = 8;
+        Qs.live = y_live; Qs.held_step = (const float*)h->d_step.p; Qs.gave_up = d_gave_up;
     }
     LoopTrack K{};             // (t null: absent)
     if (tracked) K = track->K;
@@ -2960,7 +3069,15 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             if (timed) HIPCHK(h, launch_loop_keys_period(d_keys, d_sub, d_xi, B, ticks, S, plant->Q.substeps, st, O, LoopScore{}, G, E));
             else if (plant) HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st, plant->Q.substeps));
             else HIPCHK(h, launch_loop_keys(d_keys, d_sub, d_xi, B, st));
-            if (!flown) HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));      // (SPEC.md §11l: the split happened, its draw is not used)
+            int n_live = B;
+            if (retire) {              // SPEC.md §11n: four bytes and one synchronisation per period — the size of this period's solve
+                HIPCHK(h, hipMemcpyAsync(&n_live, y_nlive, sizeof n_live, hipMemcpyDeviceToHost, st));
+                HIPCHK(h, hipStreamSynchronize(st));
+                if (n_live < 0 || n_live > B) return fail(h, SDEMPC_EDEVICE, "closed loop: the live count read back lies outside [0, B]%s");
+                ret->live[j0 + jc] = n_live;
+            }
+            const bool dense = retire && !flown && n_live < B;         // (n_live == B: exactly the launches of a call without retire)
+            if (!flown && !dense) HIPCHK(h, launch_noise_from_keys(d_sub, (float*)h->d_noise.p, B, h->P, h->G, H, st));      // (SPEC.md §11l: the split happened, its draw is not used)
             const float* win = c_xref + (xref_moves ? (size_t)jc * Bx * XR : 0);
             const float* xr = win;
             if (tracked) {             // the windows of this solve's tick, cut where the solve reads them
@@ -2975,9 +3092,23 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             if (flown) {               // the controller's tables where the solve would have left its own, from the B windows the solve would have read
                 A.x = seen ? d_xm : d_x; A.info = info_j;
                 A.xref = xr; A.xref_ep_stride = (int)XR;
+                A.live = retire ? y_live : nullptr;
                 HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, LoopScore{}, LoopProcess{}, LoopEvents{}, A));
+            } else if (dense) {        // SPEC.md §11n: the live set alone, in a dense batch — gather, noise from the dense subkeys, solve on the staging, scatter
+                h->last_coop_B = 0;
+                if (n_live > 0) {
+                    Qg.n = n_live;
+                    Qg.seg[0].src = (const uint32_t*)(seen ? d_xm : d_x); Qg.seg[1].src = (const uint32_t*)xr;
+                    HIPCHK(h, launch_broadcast_rows(nullptr, nullptr, 0, 0, st, LoopTrack{}, Qg));
+                    HIPCHK(h, launch_noise_from_keys(y_base + o_ssub, (float*)h->d_noise.p, n_live, h->P, h->G, H, st));
+                    if ((rc = sdempc_solve_batch_dev(h, n_live, y_base + o_sx, y_base + o_sxr, h->d_noise.p, y_base + o_su, y_base + o_sstep, y_base + o_suo, y_base + o_sxe,
+                                                     y_base + o_sinf, st))) return rc;
+                }
+                Qs.n = n_live; Qs.seg[2].dst = (uint32_t*)info_j; Qs.held_info = info_j;
+                Qs.coop_bar = h->last_coop_B > 0 ? (const unsigned*)h->d_coop_bar.p : nullptr;      // (indexed by dense position: folded into the sticky flag here)
+                HIPCHK(h, launch_broadcast_rows(nullptr, nullptr, 0, 0, st, LoopTrack{}, Qs));
             } else if ((rc = sdempc_solve_batch_dev(h, B, seen ? d_xm : d_x, xr, h->d_noise.p, h->d_u.p, h->d_step.p, h->d_uopt.p, h->d_xmean.p, info_j, st))) return rc;
-            L.info = info_j; L.coop_bar = h->last_coop_B > 0 ? (const unsigned*)h->d_coop_bar.p : nullptr;
+            L.info = info_j; L.coop_bar = !dense && h->last_coop_B > 0 ? (const unsigned*)h->d_coop_bar.p : nullptr;
             L.xs = c_xs + (size_t)jc * S * B * NX; L.us = c_us + (size_t)jc * S * B * m;
             if (timed) {
                 const size_t t0 = (size_t)jc * S;                                    // first tick row of this period inside the chunk
@@ -3009,8 +3140,24 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
                 const int i0 = AM - d + 1 > 0 ? AM - d + 1 : 0;
                 if (i0 < AM) HIPCHK(h, hipMemcpyAsync(d_hist + (size_t)i0 * HR, V.xsub + (size_t)(d - AM + i0 - 1) * HR, sizeof(float) * (AM - i0) * HR, hipMemcpyDeviceToDevice, st));
             }
+            if (retire) {              // SPEC.md §11n: this period's rows into the words of the live episodes, then the live set of the next solve
+                const size_t t0 = (size_t)jc * S;
+                if (targets) {
+                    K.tick0 = track->K.tick0 + (int)(k0 + t0) + 1; K.B = B; K.rows = 1; K.groups = ticks;
+                    HIPCHK(h, launch_broadcast_rows(nullptr, c_sref + t0 * ZR, 0, 0, st, K));
+                }
+                LoopScore Zp = Z;
+                Zp.rows = Z.rows + t0 * Z.rows_per_tick * B * NX; Zp.us = c_us + t0 * B * m; Zp.info = info_j; Zp.ref = c_sref + (sref_moves ? t0 * ZR : 0);
+                Zp.ticks = ticks; Zp.solves = 1; Zp.live = y_live;
+                HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, Zp));
+                Y.solve = j0 + jc + 1 < Ns ? j0 + jc + 1 : -1; Y.rows = ticks * Z.rows_per_tick;
+                Y.place = 0;
+                HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, LoopScore{}, LoopProcess{}, LoopEvents{}, LoopBaseline{}, LoopEnsemble{}, Y));
+                Y.place = 1;
+                HIPCHK(h, launch_loop_keys_period(nullptr, nullptr, nullptr, B, 0, 0, nsub, st, LoopObserve{}, LoopScore{}, LoopProcess{}, LoopEvents{}, LoopBaseline{}, LoopEnsemble{}, Y));
+            }
         }
-        if (scoring) {             // SPEC.md §11h: the chunk's rows into the score words, one thread per episode
+        if (scoring && !retire) {  // SPEC.md §11h: the chunk's rows into the score words, one thread per episode
             Z.ticks = nk; Z.solves = np;
             if (targets) {         // SPEC.md §11j: the target of chunk tick i is the row at theta(k0 + i + 1)
                 K.tick0 = track->K.tick0 + (int)k0 + 1; K.B = B; K.rows = 1; K.groups = nk;
@@ -3082,6 +3229,7 @@ int closed_loop_run(sdempc_handle* h, const LoopIo& io, const PlantRun* plant, c
             if (gproc && proc->dist_state_next) HIPCHK(h, hipMemcpyAsync(proc->dist_state_next, p_dstate, sizeof(float) * B * NG, hipMemcpyDeviceToHost, st));
             if (bproc && proc->bias_keys_next) HIPCHK(h, hipMemcpyAsync(proc->bias_keys_next, p_bchain, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, st));
             if (bproc && proc->bias_state_next) HIPCHK(h, hipMemcpyAsync(proc->bias_state_next, p_bstate, sizeof(float) * B * NB, hipMemcpyDeviceToHost, st));
+            if (retire) HIPCHK(h, hipMemcpyAsync(ret->retired_at, Y.retired_at, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
             if (scoring) HIPCHK(h, hipMemcpyAsync(score->score_out, d_score, sizeof(uint32_t) * 16 * (size_t)B, hipMemcpyDeviceToHost, st));
             if (AM > 0 && obs->xhist_next) {
                 hn.resize((size_t)AM * HR);

@@ -48,7 +48,8 @@ DI void ens_partial(const LoopEnsemble& N, int B) {
         const float* x = N.rows + ((size_t)row * B + b) * 13;
         cause = score_row(x, g[0], g[1], g[2], g[3], g[4], g[5], N.r2_pos, N.cos_min, N.w2_max, v[0], v[1], v[2], v[3], nf);
         // the global index of this row: word 0 after the chunk's scoring launch counts every row of the chunk
-        const uint32_t r = N.words[(size_t)b * 16] - (uint32_t)N.chunk_rows + (uint32_t)row;
+        // (SPEC.md §11n: a retired episode's word 0 is frozen, and the loop's own count of its rows stands in)
+        const uint32_t r = (N.count ? N.count[b] : N.words[(size_t)b * 16]) - (uint32_t)N.chunk_rows + (uint32_t)row;
         const uint32_t f = N.words[(size_t)b * 16 + 8];
         before = f < r; by_now = f <= r;
         coh = N.cohort[b];

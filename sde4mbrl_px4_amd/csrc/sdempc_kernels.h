@@ -266,6 +266,7 @@ struct LoopScore {
     int m;
     float r2_pos, cos_min, w2_max;      // thresholds: squared radius, cosine of the tilt, squared rate (+inf, -inf, +inf: off); never NaN
     float u_lo[8], u_hi[8], uref[8];    // of motor j < m (wave-uniform kernel arguments, read at constant indices)
+    const int32_t* live;        // SPEC.md §11n: [B], episode b is scored only where live[b] != 0; null: every episode (not one access more)
 };
 // SPEC.md §11i, gusts and estimator bias drawn on the device: a first-order Gauss-Markov process per component and episode, stepped by the period's key-schedule
 // thread of episode b beside its schedule. One step: (c, e) = split(c), xi = normal(e, (W,)) (counter i pairs with i + W / 2), t_i = scale_i * xi_i (rounded),
@@ -348,6 +349,7 @@ struct LoopBaseline {
     float* info;                // [B][8]
     const float* step;          // [B] the step size handed through
     float* out;                 // [B][4] (c, omega*), or null: the tables above
+    const int32_t* live;        // SPEC.md §11n: [B], where live[b] == 0 only the info row is written and the tables stay; null: every episode (not one access more)
 };
 // SPEC.md §11m, per-row ensemble histories over the episodes, by cohort: TWO further forms of the period's key-schedule kernel (ticks = 0, every other struct empty,
 // null key buffers), launched after a chunk's scoring launch on rows, targets and thresholds that launch read (sdempc_ensemble.inc.h). The PARTIAL form (combine 0)
@@ -371,10 +373,31 @@ struct LoopEnsemble {
     int G, E, over;             // cohorts 1 .. 16, edges per channel 0 .. 16, 1: only episodes that have not failed before the row are included
     int combine;                // 0: the partial form, 1: the combine form (wave-uniform)
     float r2_pos, cos_min, w2_max;      // LoopScore's
+    const uint32_t* count;      // SPEC.md §11n: [B] rows of episode b up to the end of the chunk, read in place of word 0 (which a retired episode froze); null: word 0
+};
+// SPEC.md §11n, retiring failed episodes: TWO further forms of the period's key-schedule kernel (ticks = 0, every other struct empty, null key buffers), launched
+// after a period's scoring launch, one thread per episode on a grid of ceil(B / 256) blocks (sdempc_retire.inc.h). The COUNT form (place 0) updates live[b] from
+// word 8 of the episode's score words, stamps retired_at where an episode leaves the live set, and writes the block's live count to blk[k]; the PLACE form (place 1)
+// writes the ascending list of live episodes and n_live. Both branch off before the kernel's `b >= B` return (a workgroup barrier; threads past B are masked).
+// live null means absent: every other launch passes that, and the kernel then makes no memory access it did not make before.
+struct LoopRetire {
+    int32_t* live;              // [B] 1: still solved and scored; null: neither form
+    const uint32_t* words;      // [B][16] the score words after the period's scoring launch (word 8 is read; word 0 with init and count)
+    int32_t* retired_at;        // [B] the call's first solve the episode is left out of, -1: none
+    uint32_t* blk;              // [nblk] live episodes of each block of 256
+    int32_t* list;              // [B] the live episodes, ascending; entries past n_live are not written
+    int32_t* n_live;            // [1]
+    uint32_t* count;            // [B] scored-or-not rows of each episode so far (LoopEnsemble::count), or null
+    int solve;                  // what retired_at takes: the index of the call's next solve, or -1 when this was its last period
+    int rows;                   // rows of the period just scored, added to count
+    int nblk;                   // ceil(B / 256)
+    int place;                  // 0: the count form, 1: the place form (wave-uniform)
+    int init;                   // 1 (count form): the call's entry — live from word 8 alone, retired_at = -1 or 0, count = word 0
 };
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st,
                                    const LoopObserve& O = LoopObserve{}, const LoopScore& Z = LoopScore{}, const LoopProcess& G = LoopProcess{},
-                                   const LoopEvents& E = LoopEvents{}, const LoopBaseline& A = LoopBaseline{}, const LoopEnsemble& N = LoopEnsemble{});
+                                   const LoopEvents& E = LoopEvents{}, const LoopBaseline& A = LoopBaseline{}, const LoopEnsemble& N = LoopEnsemble{},
+                                   const LoopRetire& Y = LoopRetire{});
 // SPEC.md §11j, reference windows and score targets cut from a trajectory on the device: the row-filling launch below in its TRACKING form. The tables of a set lie
 // end to end: table j owns knots first[j] .. first[j] + knots[j] - 1 of t / w / x (w[i] = float32(1 / (t[i+1] - t[i])) formed by the library in float64; the last w of
 // a table is not read). Thread i of the launch writes one whole row of 13 floats, row i of out f32[groups][B][rows][13]: group g is tick tick0 + g, its clock value
@@ -399,8 +422,25 @@ struct LoopTrack {
     int B, rows, groups;
     int renorm;                 // 1: scale the attitude of every row to unit length, software rsqrt (wave-uniform)
 };
-// rows_dev[b][0..n) = row_dev[0..n) for b < B; or, with K.t given (row_dev, n and B are then not read): rows_dev[g][b][r][0..13) from the trajectory set K
-hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st, const LoopTrack& K = LoopTrack{});
+// SPEC.md §11n, the dense solve of the live set: the row-filling launch in its GATHER form (scatter 0: row list[i] of every segment's src to row i of its dst) and
+// its SCATTER form (scatter 1: row i to row list[i]), bit copies of `words` 4-byte words per row (sdempc_retire.inc.h). The scatter form also writes the held info
+// row (0, held_step[b], 0 ..) of every episode with live[b] == 0 and sets *gave_up where word 1 of a dense instance's cooperative barrier is set (coop_bar null:
+// the solve took no cooperative layout). list null means absent: every other launch passes that, and the kernel then makes no memory access it did not make before.
+constexpr int COMPACT_SEGS = 5;
+struct LoopCompact {
+    const int32_t* list;        // [n] live episodes, ascending; null: neither form
+    int n, B, i0;               // dense rows, episodes, first dense row of this launch (set by the launcher)
+    int scatter, nseg;
+    struct Seg { const uint32_t* src; uint32_t* dst; int words; int vec; } seg[COMPACT_SEGS];    // vec is set by the launcher: 16-byte copies
+    const int32_t* live;        // [B] (scatter form)
+    float* held_info;           // [B][8] the solve's info rows (scatter form)
+    const float* held_step;     // [B] the current step sizes (scatter form)
+    const unsigned* coop_bar;   // [n][COOP_BAR_WORDS] of the dense solve, or null
+    unsigned* gave_up;          // the loop's sticky flag
+};
+// rows_dev[b][0..n) = row_dev[0..n) for b < B; or, with K.t given (row_dev, n and B are then not read): rows_dev[g][b][r][0..13) from the trajectory set K;
+// or, with Q.list given (nothing else is read): the gather or scatter form
+hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st, const LoopTrack& K = LoopTrack{}, const LoopCompact& Q = LoopCompact{});
 // canonical [B][P][C] <-> device [B][G][C][32] (to_dev: zero-pads particles >= P)
 hipError_t launch_relayout(bool to_dev, const float* in, float* out, int B, int P, int G, int C, hipStream_t st);
 // SPEC.md §7: noise of B instances from their threefry keys (device u32[B][2]) straight into the device layout [B][G][H][6][32]

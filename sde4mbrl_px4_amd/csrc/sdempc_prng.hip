@@ -123,6 +123,7 @@ DI float bits_to_normal(uint32_t bits) {
 #include "sdempc_outcome.inc.h"
 #include "sdempc_geo.inc.h"
 #include "sdempc_ensemble.inc.h"
+#include "sdempc_retire.inc.h"
 namespace sdempc {
 
 // grid: x = chunks of 256 threads over [pg][r][lane] (pg < ceil(ceil(P/2)/32), r < H*6), y = instance
@@ -331,21 +332,36 @@ hipError_t launch_loop_keys(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev
 // SPEC.md §11m (N.part given; ticks = 0, O / Z / G / E / A empty, keys / sub / xi null and untouched): the two ENSEMBLE forms of the launch, after a chunk's scoring
 // launch (sdempc_ensemble.inc.h) — the partial form on a grid of (blocks of episodes) x (rows), whose threads past B stay for its workgroup barriers and are masked,
 // and the combine form, one thread per (row, cohort, word): both leave before the `b >= B` return. N.part null (every launch before §11m): not one access more.
+// SPEC.md §11n (Y.live given; ticks = 0, O / Z / G / E / A / N empty, keys / sub / xi null and untouched): the two LIVE-LIST forms of the launch, after a period's scoring
+// launch (sdempc_retire.inc.h) — one thread per episode, threads past B stay for the workgroup barrier and are masked: both leave before the `b >= B` return. The
+// scoring and baseline forms take a mask of the same flags (Z.live, A.live). Y.live, Z.live and A.live null (every launch before §11n): not one access more.
 __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* __restrict__ keys, uint32_t* __restrict__ sub, float* __restrict__ xi, int B, int ticks,
                                                                       int xi_ticks, int n, LoopObserve O, LoopScore Z, LoopProcess G, LoopEvents E,
-                                                                      LoopBaseline A, LoopEnsemble N) {
+                                                                      LoopBaseline A, LoopEnsemble N, LoopRetire Y) {
     if (N.part) {                                        // (wave-uniform)
         if (N.combine) ens_combine(N);
         else ens_partial(N, B);
         return;
     }
+    if (Y.live) {                                        // (wave-uniform)
+        retire_live_list(Y, B);
+        return;
+    }
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     if (A.x) {                                           // (wave-uniform)
+        if (A.live && A.live[b] == 0) {                  // SPEC.md §11n: a retired episode keeps its tables; its info row is the held one
+            float* inf = A.info + (size_t)b * 8;
+            inf[0] = 0.0f; inf[1] = A.step[b];
+#pragma unroll
+            for (int c = 2; c < 8; ++c) inf[c] = 0.0f;
+            return;
+        }
         geo_fill(A, b);
         return;
     }
     if (Z.words) {                                       // (wave-uniform)
+        if (Z.live && Z.live[b] == 0) return;            // SPEC.md §11n: a retired episode's words are frozen
         uint32_t* w = Z.words + (size_t)b * 16;
         uint32_t cnt = w[0], imax = w[3], first = w[8], causes = w[9], nbad = w[10];
         float sdp = __uint_as_float(w[1]), mdp = __uint_as_float(w[2]), ldp = __uint_as_float(w[4]), sdv = __uint_as_float(w[5]);
@@ -590,8 +606,15 @@ __global__ void __launch_bounds__(256) sdempc_loop_keys_period_kernel(uint32_t* 
 }
 
 hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float* xi_dev, int B, int ticks, int xi_ticks, int substeps, hipStream_t st, const LoopObserve& O,
-                                   const LoopScore& Z, const LoopProcess& G, const LoopEvents& E, const LoopBaseline& A, const LoopEnsemble& N) {
+                                   const LoopScore& Z, const LoopProcess& G, const LoopEvents& E, const LoopBaseline& A, const LoopEnsemble& N, const LoopRetire& Y) {
     if (B < 1 || substeps < 1 || ticks < 0 || xi_ticks < ticks) return hipErrorInvalidValue;
+    if (Y.live) {   // SPEC.md §11n: a present block is complete and stands alone
+        if (ticks != 0 || N.part || Z.words || A.x || O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev || G.dist.chain || G.bias.chain || E.fault.chain || E.drop.chain) return hipErrorInvalidValue;
+        if (!Y.blk || Y.nblk != (B + 255) / 256 || (Y.place != 0 && Y.place != 1) || (Y.init != 0 && Y.init != 1)) return hipErrorInvalidValue;
+        if (Y.place ? (!Y.list || !Y.n_live || Y.init) : (!Y.words || !Y.retired_at || Y.rows < 0 || Y.solve < -1)) return hipErrorInvalidValue;
+        sdempc_loop_keys_period_kernel<<<(unsigned)Y.nblk, 256, 0, st>>>(nullptr, nullptr, nullptr, B, 0, 0, substeps, O, Z, G, E, A, N, Y);
+        return hipGetLastError();
+    }
     if (N.part) {   // SPEC.md §11m: a present block is complete, stands alone, and addresses rows the chunk's scoring launch counted
         if (ticks != 0 || Z.words || A.x || O.q || O.age || O.renorm || keys_dev || sub_dev || xi_dev || G.dist.chain || G.bias.chain || E.fault.chain || E.drop.chain) return hipErrorInvalidValue;
         if (!N.out || !N.words || !N.cohort || !N.rows || !N.ref || (N.E > 0 && !N.edges)) return hipErrorInvalidValue;
@@ -601,8 +624,8 @@ hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float*
         if (N.r2_pos != N.r2_pos || N.cos_min != N.cos_min || N.w2_max != N.w2_max) return hipErrorInvalidValue;
         if (N.combine) {
             const long long threads = (long long)N.nrows * N.G * (ENS_BASE_WORDS + 4 * N.E);
-            sdempc_loop_keys_period_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(nullptr, nullptr, nullptr, B, 0, 0, substeps, O, Z, G, E, A, N);
-        } else sdempc_loop_keys_period_kernel<<<dim3((unsigned)N.nblk, (unsigned)N.nrows), 256, 0, st>>>(nullptr, nullptr, nullptr, B, 0, 0, substeps, O, Z, G, E, A, N);
+            sdempc_loop_keys_period_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(nullptr, nullptr, nullptr, B, 0, 0, substeps, O, Z, G, E, A, N, LoopRetire{});
+        } else sdempc_loop_keys_period_kernel<<<dim3((unsigned)N.nblk, (unsigned)N.nrows), 256, 0, st>>>(nullptr, nullptr, nullptr, B, 0, 0, substeps, O, Z, G, E, A, N, LoopRetire{});
         return hipGetLastError();
     }
     // ticks = 0 is the scoring form or the baseline form and nothing else: score words or a state, no observation, no key buffers
@@ -645,7 +668,7 @@ hipError_t launch_loop_keys_period(uint32_t* keys_dev, uint32_t* sub_dev, float*
         if (D.sched && D.sched_ep_stride != 0 && D.sched_ep_stride != 1) return hipErrorInvalidValue;
         if (!O.q || O.valid != D.dst || O.valid_ep_stride != 1) return hipErrorInvalidValue;
     }
-    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z, G, E, A, LoopEnsemble{});
+    sdempc_loop_keys_period_kernel<<<(B + 255) / 256, 256, 0, st>>>(keys_dev, sub_dev, xi_dev, B, ticks, xi_ticks, substeps, O, Z, G, E, A, LoopEnsemble{}, LoopRetire{});
     return hipGetLastError();
 }
 
@@ -698,7 +721,14 @@ DI void track_row(const LoopTrack& K, int b, float u, float* y) {
 // rows[b] = row for b < B (one reference window shared by every episode of a closed-loop batch), n floats per row
 // SPEC.md §11j (K.t given; row, n and total are then not read): the TRACKING form of the launch. Thread i forms row i of rows f32[groups][B][K.rows][13] from the
 // trajectory set and stores its 13 floats, so neighbouring threads write neighbouring rows. K.t null (every launch before §11j): not one access more.
-__global__ void __launch_bounds__(256) sdempc_broadcast_rows_kernel(const float* __restrict__ row, float* __restrict__ rows, int n, long long total, LoopTrack K) {
+// SPEC.md §11n (Q.list given; row, rows, n, total and K are then not read): the GATHER and SCATTER forms of the launch, x = chunks of 256 copy units of one row,
+// y = dense row (sdempc_retire.inc.h). Q.list null (every launch before §11n): not one access more.
+__global__ void __launch_bounds__(256) sdempc_broadcast_rows_kernel(const float* __restrict__ row, float* __restrict__ rows, int n, long long total, LoopTrack K,
+                                                                    LoopCompact Q) {
+    if (Q.list) {                                        // (wave-uniform)
+        compact_rows(Q);
+        return;
+    }
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (K.t) {                                           // (wave-uniform)
         const long long per_group = (long long)K.B * K.rows;
@@ -717,18 +747,38 @@ __global__ void __launch_bounds__(256) sdempc_broadcast_rows_kernel(const float*
     if (i < total) rows[i] = row[i % n];
 }
 
-hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st, const LoopTrack& K) {
+hipError_t launch_broadcast_rows(const float* row_dev, float* rows_dev, int n, int B, hipStream_t st, const LoopTrack& K, const LoopCompact& Q0) {
+    if (Q0.list) {  // SPEC.md §11n: a present block is complete; a segment is copied 16 bytes at a time where its row length and both bases allow
+        LoopCompact Q = Q0;
+        if (K.t || row_dev || rows_dev || Q.n < 0 || Q.B < 1 || Q.n > Q.B || Q.nseg < 1 || Q.nseg > COMPACT_SEGS || (Q.scatter != 0 && Q.scatter != 1)) return hipErrorInvalidValue;
+        if (Q.scatter ? (!Q.live || !Q.held_info || !Q.held_step || (Q.coop_bar && !Q.gave_up)) : Q.n < 1) return hipErrorInvalidValue;
+        unsigned units = 0;
+        for (int s = 0; s < Q.nseg; ++s) {
+            LoopCompact::Seg& g = Q.seg[s];
+            if (!g.src || !g.dst || g.words < 1) return hipErrorInvalidValue;
+            g.vec = (g.words & 3) == 0 && ((reinterpret_cast<uintptr_t>(g.src) | reinterpret_cast<uintptr_t>(g.dst)) & 15u) == 0 ? 1 : 0;
+            units += (unsigned)(g.vec ? g.words >> 2 : g.words);
+        }
+        const unsigned gx = (units + 255u) / 256u;
+        const int rows_y = Q.n + (Q.scatter ? 1 : 0);   // (the scatter form's held-row pass is grid row n)
+        for (int i0 = 0; i0 < rows_y; i0 += 65535) {
+            Q.i0 = i0;
+            const int ny = rows_y - i0 < 65535 ? rows_y - i0 : 65535;
+            sdempc_broadcast_rows_kernel<<<dim3(gx, (unsigned)ny), 256, 0, st>>>(nullptr, nullptr, 0, 0, K, Q);
+        }
+        return hipGetLastError();
+    }
     if (K.t) {      // SPEC.md §11j: a present set is complete, and its clock stays exact in float32
         if (!rows_dev || !K.w || !K.x || !K.first || !K.knots || !K.period || !K.inv_period || !K.c || !K.table_of || !K.phase || !K.rate || !K.offset) return hipErrorInvalidValue;
         if (K.B < 1 || K.rows < 1 || K.groups < 1 || K.tick0 < 0 || (long long)K.tick0 + K.groups > (1ll << 24) || (K.renorm != 0 && K.renorm != 1)) return hipErrorInvalidValue;
         const long long threads = (long long)K.B * K.rows * K.groups;
         if (threads > (1ll << 31) - 256) return hipErrorInvalidValue;
-        sdempc_broadcast_rows_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(nullptr, rows_dev, 0, 0, K);
+        sdempc_broadcast_rows_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(nullptr, rows_dev, 0, 0, K, LoopCompact{});
         return hipGetLastError();
     }
     if (B < 1 || n < 1) return hipErrorInvalidValue;
     const long long total = (long long)n * B;
-    sdempc_broadcast_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(row_dev, rows_dev, n, total, K);
+    sdempc_broadcast_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(row_dev, rows_dev, n, total, K, LoopCompact{});
     return hipGetLastError();
 }
 

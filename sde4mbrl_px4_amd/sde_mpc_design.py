@@ -215,7 +215,7 @@ class MpcProblem:
                  fault=None, substep_states=False, meas_noise=None, meas_bias=None, meas_valid=None, meas_rng=None, meas_age=None, meas_renorm=False,
                  score=None, score_ref=None, dist_process=None, dist_rng=None, dist_state=None, bias_process=None, bias_rng=None, bias_state=None,
                  track=None, track_phase=None, track_rate=None, fault_process=None, fault_rng=None, fault_state=None, drop_process=None, drop_rng=None,
-                 drop_state=None, controller=None):
+                 drop_state=None, controller=None, retire=False):
         """T ticks of m_mpc in closed loop with the model itself as the plant, on the device (SPEC.md §11): solve, apply uopt[0], one
         Euler–Maruyama step of the controller's own model under a fresh noise draw, warm-start from the shifted solution. Equivalent to
         T calls of m_mpc, each followed by that step, but with no host round trip per tick. `x` is converted into the solver's frame once
@@ -274,7 +274,12 @@ class MpcProblem:
         its process raises ValueError.
         controller (SPEC.md §11l): a solver.GeometricController flies the episode in place of the MPC's solves — the baseline — through rate_loop (required), passed
         through for this one episode; its gains act on quantities of the solver's frame. Everything above still applies and the returned values are the same: the
-        OptState then holds thrust rows and zero telemetry."""
+        OptState then holds thrust rows and zero telemetry.
+        retire (SPEC.md §11n; needs score): with retire=True the episode is neither solved nor scored from the solve-period boundary after its first failing row
+        on — it flies its held table to the end — passed through for this one episode. Behind the score come retired_at, the first solve index at which it was not
+        solved (-1: never), and live int32[Ns], 1 for every solve that ran."""
+        if retire and score is None:
+            raise ValueError("MpcProblem.simulate: retire needs score=Score(...)")
         if not self.shift_warm_start:
             raise ValueError("MpcProblem.simulate: the closed loop always warm-starts from the shifted solution (shift_warm_start=True)")
         T = int(T)
@@ -412,7 +417,7 @@ class MpcProblem:
         out = self.solver().closed_loop(
             xs0[None], xref, rng, T, u_init=u0, stepsize_in=s0, plant=plant, plant_substeps=plant_substeps, plant_dt=plant_dt,
             plant_mlp_dtype=plant_mlp_dtype, plant_math_mode=plant_math_mode, solve_period=solve_period, solve_delay=solve_delay, motor_lag=motor_lag,
-            disturbance=disturbance, plant_of=plant_of, **more, **({} if controller is None else {"controller": controller}))
+            disturbance=disturbance, plant_of=plant_of, **more, **({} if controller is None else {"controller": controller}), **({"retire": True} if retire else {}))
         xs, us, info, u_next, s_next, k_next = out[:6]
         xs = xs[0]
         if self.convert_to_enu:
@@ -439,6 +444,12 @@ class MpcProblem:
                 prows += (_arr(np.ascontiguousarray(rows_, np.float32)), k_.copy(), _arr(np.ascontiguousarray(g_, np.float32)))
             out = body + tail
         zrow = None
+        yvals = ()
+        if retire:                      # retired_at and live sit behind the score, in front of xsub
+            tail = out[-1:] if substep_states else ()
+            body = out[:-1] if substep_states else out
+            yvals = (int(body[-2][0]), body[-1].copy())
+            out = body[:-2] + tail
         if score is not None:           # the score sits behind every other value, in front of xsub
             zrow = out[-2] if substep_states else out[-1]
             out = out[:-2] + out[-1:] if substep_states else out[:-1]
@@ -452,6 +463,7 @@ class MpcProblem:
                 ret += (_arr(enu2ned(xhist, np) if self.convert_to_enu else xhist),)
         if zrow is not None:
             ret += (zrow,)
+        ret += yvals
         ret += prows + erows
         if substep_states:
             xsub = out[-1][0]

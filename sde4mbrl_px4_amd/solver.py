@@ -739,6 +739,20 @@ def ensemble_summary(words, ensemble, quantiles=(0.5, 0.9)):
     return out
 
 
+def retire_summary(retired_at, live, B):
+    """Host arithmetic on the two arrays closed_loop(retire=True) returns (SPEC.md §11n): retired_at int32[B] and live int32[Ns]. Returns a dict: "solves_run"
+    sum(live), "solves_saved" B * Ns - sum(live), "saved_share" their ratio to B * Ns (0 for an empty call), "retired" the episodes with retired_at >= 0 and
+    "retired_at_entry" those with retired_at == 0."""
+    r, l, B = np.asarray(retired_at), np.asarray(live), int(B)
+    if r.dtype.kind not in "iu" or r.shape != (B,):
+        raise ValueError(f"retire_summary: retired_at must be int[{B}], got dtype {r.dtype} and shape {r.shape}")
+    if l.dtype.kind not in "iu" or l.ndim != 1 or (l.size and (l.min() < 0 or l.max() > B)):
+        raise ValueError(f"retire_summary: live must be int[Ns] with entries in [0, {B}]")
+    total, run = B * int(l.size), int(l.astype(np.int64).sum())
+    return {"solves_run": run, "solves_saved": total - run, "saved_share": (total - run) / total if total else 0.0,
+            "retired": int((r >= 0).sum()), "retired_at_entry": int((r == 0).sum())}
+
+
 def _edge_quantiles(cdf, edges, levels):
     """[..][len(levels)]: the smallest of the ascending edges whose cumulative fraction cdf[.., j] reaches each level; NaN where none does (or the cdf is NaN)."""
     out = np.full(cdf.shape[:-1] + (levels.size,), np.nan)
@@ -1414,7 +1428,8 @@ class SdeMpcSolver:
                     meas_keys=None, xmeas_in=None, meas_age=None, meas_age_max=None, meas_renorm=False, xhist_in=None, score=None, score_ref=None, score_in=None,
                     outputs=True, dist_process=None, dist_keys=None, dist_state_in=None, bias_process=None, bias_keys=None, bias_state_in=None,
                     track=None, track_of=None, track_phase=None, track_rate=None, track_offset=None, track_tick0=None, track_renorm=None,
-                    fault_process=None, fault_keys=None, fault_state_in=None, fault_tick0=0, drop_process=None, drop_keys=None, drop_state_in=None, controller=None, ensemble=None, cohort=None):
+                    fault_process=None, fault_keys=None, fault_state_in=None, fault_tick0=0, drop_process=None, drop_keys=None, drop_state_in=None, controller=None, ensemble=None, cohort=None,
+                    retire=False):
         """B episodes of T closed-loop ticks on the device (SPEC.md §11, sdempc_closed_loop_batch): solve, apply uopt[0], one step of the
         model under its own noise draw, warm-start from the shifted solution. x0 f32[B][13]; keys uint32[B][2]; xref f32[Tx][Bx][H+1][13]
         with Tx in {1, T} (one window on every tick, or one per tick) and Bx in {1, B} (shared, or one per episode), or a single window
@@ -1561,7 +1576,19 @@ class SdeMpcSolver:
         and any chunking. A float sum has one fixed association over blocks of 256 consecutive episodes, so the words depend on B and on the order of the episodes.
         A run continued through score_in keeps counting rows, so its words are the later rows of the joined run. With controller=None the MPC is flown, with a
         controller the baseline: one Ensemble and one cohort array give the two arms of a paired comparison. cohort without ensemble raises ValueError; with neither
-        given nothing of this paragraph is touched."""
+        given nothing of this paragraph is touched.
+
+        retire (SPEC.md §11n, sdempc_closed_loop_batch_retire): with retire=True an episode whose score records a failure — a first failing row, from this call's
+        rows or from score_in — is RETIRED at the next solve-period boundary: it is neither solved nor scored from then on, and everything else about it proceeds as
+        before (the plant flies its held table, its chains and keys advance, its info rows are (0, stepsize, 0, ...)). Only the live episodes are solved, in a dense
+        batch, so the device time of a campaign falls with the retired share. Needs score (ValueError otherwise); with ensemble= only over="alive" (ValueError for
+        over="all": the rows of a retired episode are not a fleet statistic). An episode that never fails has every row and every score word bit-identical to the
+        run without retire; one that fails has identical rows through the end of its failing period, where its score words freeze. TWO more values come back right
+        behind the score (and the ensemble words, if any): retired_at int32[B], the first solve index of this call at which the episode was not solved (0: retired
+        at entry, -1: never), and live int32[Ns], the number of episodes solved at each solve (retire_summary reduces them). A run cut in two through score_in and
+        the *_next outputs gives the single call's score, keys and every row of the episodes live at the cut (an episode retired before the cut flies the second
+        call's warm start behind it: its held table is not carried across calls). With controller= the baseline skips retired episodes by the same mask. retire=False: nothing of this
+        paragraph is touched."""
         x0 = _f32(x0)
         B, T = x0.shape[0], int(T)
         x0 = _f32(x0, (B, 13))
@@ -1783,7 +1810,14 @@ class SdeMpcSolver:
             n_coh = ensemble.n_cohorts if ensemble.n_cohorts is not None else (1 if coh is None or B == 0 else int(coh.max()) + 1)
             if not (1 <= n_coh <= 16) or (coh is not None and B > 0 and (coh.min() < 0 or coh.max() >= n_coh)):
                 raise ValueError(f"closed_loop: cohort must hold entries in [0, {n_coh}) and at most 16 cohorts")
-        baseline_args = baseline or ensembled     # (the ensemble entry point takes the baseline one's arguments, its geo cfg NULL without a controller)
+        retiring = bool(retire)
+        if retiring:
+            if not scored:
+                raise ValueError("closed_loop: retire needs score=Score(...) (an episode is retired by its score)")
+            if ensembled and ensemble.over != "alive":
+                raise ValueError('closed_loop: retire may not be combined with Ensemble(over="all") (the rows of a retired episode are not a fleet statistic)')
+        ens_args = ensembled or retiring          # (the retire entry point takes the ensemble one's arguments, its ensemble cfg NULL without an ensemble)
+        baseline_args = baseline or ens_args      # (the ensemble entry point takes the baseline one's arguments, its geo cfg NULL without a controller)
         faulted = flt is not None or bool(substep_states) or observed or scored or drawn or tracked or events or baseline
         full = scored or drawn or tracked or events or baseline          # the entry points from the scored one on take every layer's arguments, NULL where a layer is absent
         if rate_loop is None and (rate_integ_in is not None or rate_tail_in is not None):
@@ -1916,6 +1950,9 @@ class SdeMpcSolver:
                 if ensembled:       # (the word array sits right behind the score; its pointer leads the C call, below)
                     ens_words = np.zeros((max(T, 0) * (int(plant_substeps) if score.substeps else 1), n_coh, ensemble.words), np.uint32)
                     ret = ret + (ens_words,)
+                if retiring:        # (behind the score and the ensemble words; their pointers lead the C call, below)
+                    retired_at, live = np.full(B, -1, np.int32), np.zeros(max(Ns, 0), np.int32)
+                    ret = ret + (retired_at, live)
             elif drawn or tracked or events or baseline:  # (no score: a NULL score cfg and NULL score pointers)
                 lead, more = [None, None] + lead, more + (None,)
             if drawn or tracked or events or baseline_args:   # the scored entry point's arguments behind (dist_proc, bias_proc), then rows, keys_next and state_next of each process
@@ -1968,16 +2005,23 @@ class SdeMpcSolver:
                 lead = ecfgs + lead
             if baseline:            # the events entry point's arguments behind the geo cfg; nothing new comes back
                 lead = [C.byref(gc)] + lead
-            elif ensembled:         # (no controller: a NULL geo cfg)
+            elif ens_args:          # (no controller: a NULL geo cfg)
                 lead = [None] + lead
             if ensembled:           # the baseline entry point's arguments behind (ensemble cfg, ens_out)
                 ec = _abi.SdempcEnsembleCfg(C.sizeof(_abi.SdempcEnsembleCfg), n_coh, ensemble.n_edges, 1 if ensemble.over == "alive" else 0,
                                             None if coh is None else coh.ctypes.data_as(C.POINTER(C.c_int32)), _fp(ensemble.edges) if ensemble.n_edges else None)
                 lead = [C.byref(ec), ens_words.ctypes.data_as(u32p)] + lead
+            elif retiring:          # (no ensemble: a NULL ensemble cfg and no word array)
+                lead = [None, None] + lead
+            if retiring:            # the ensemble entry point's arguments behind (retire cfg, retired_at, live_per_solve)
+                yc = _abi.SdempcRetireCfg(C.sizeof(_abi.SdempcRetireCfg), 0)
+                lead = [C.byref(yc), retired_at.ctypes.data_as(C.POINTER(C.c_int32)), live.ctypes.data_as(C.POINTER(C.c_int32))] + lead
             if substep_states:
                 ret = ret + (xsub,)
         # the entry point, from (timed, scenario, rate_loop, faulted) alone; only the one that is called is looked up
-        if ensembled:
+        if retiring:
+            entry = _abi.retire_entry(self.lib)
+        elif ensembled:
             entry = _abi.ensemble_entry(self.lib)
         elif baseline:
             entry = _abi.baseline_entry(self.lib)

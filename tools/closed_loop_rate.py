@@ -56,11 +56,19 @@
      launch the key kernel runs twice more (partial words per block of 256 episodes, then the blocks in order) and R x G x (20 + 4 E) words come back. Applies to
      --small-batch and to the C2 loop; the same command without it takes the entry point it took before. The last run's survival and RMS position error per row of
      cohort 0 are printed.
+ 16. --retire [--failed-at-entry F]: with --score, failed episodes are retired at the next solve-period boundary and only the live set is solved (SPEC.md §11n,
+     sdempc_closed_loop_batch_retire) — scoring once per period, n_live read back in front of every solve (one synchronisation per period), the solve on the gathered
+     live set. --failed-at-entry F marks the fraction F of the episodes (every episode b with b mod 1000 < 1000 F) as failed in score_in, with or without --retire:
+     without it those episodes are flown and solved like the rest, which is the baseline the gain is measured against. Applies to --small-batch and to the C2
+     loop; the same command without --retire takes the entry point it took before. The last run's retire_summary is printed. --score-wide switches every threshold
+     of --score off, so that no finite episode fails: with --retire that leaves the per-period read-back and scoring as the only difference, and with
+     --failed-at-entry F exactly the marked share is retired.
 usage: python tools/closed_loop_rate.py [--ticks 40] [--c2-ticks 3] [--skip-c2] [--skip-b1] [--plant own|self|one|per-episode] [--substeps N] [--repeats R]
                                         [--small-batch B] [--timed] [--period S] [--delay D] [--lag ALPHA] [--disturbance] [--plant-switch K] [--rate-loop]
                                         [--fault] [--substep-states] [--observe] [--age A] [--renorm]
                                         [--score] [--no-outputs] [--score-substeps] [--dist-process] [--bias-process] [--track] [--per-episode-xref]
                                         [--fault-process] [--drop-process] [--controller geo] [--ensemble G E]
+                                        [--retire] [--failed-at-entry F] [--score-wide]
 Run under `rocprofv3 --kernel-trace --stats -- python tools/closed_loop_rate.py --skip-c2 --loop-only` for the kernel split of a tick
 (solve kernel against key schedule, noise, plant step)."""
 import argparse
@@ -110,7 +118,14 @@ ap.add_argument("--fault-process", action="store_true", help="motor faults drawn
 ap.add_argument("--drop-process", action="store_true", help="with --observe: estimator dropouts drawn on the device, one step per solve, instead of meas_valid rows (SPEC.md §11k)")
 ap.add_argument("--controller", choices=("mpc", "geo"), default="mpc", help="geo: the geometric baseline controller in place of the solves, through the rate loop (SPEC.md §11l)")
 ap.add_argument("--ensemble", type=int, nargs=2, metavar=("G", "E"), help="with --score: per-row ensemble words over the episodes, G cohorts and E edges per channel (SPEC.md §11m)")
+ap.add_argument("--score-wide", action="store_true", help="with --score: every threshold off (infinite radius, tilt and rate), so that no finite episode fails")
+ap.add_argument("--retire", action="store_true", help="with --score: retire failed episodes at the next solve-period boundary and solve only the live set (SPEC.md §11n)")
+ap.add_argument("--failed-at-entry", type=float, default=0.0, metavar="F", help="with --score: mark this fraction of the episodes as failed in score_in")
 a = ap.parse_args()
+if (a.retire or a.failed_at_entry or a.score_wide) and not a.score:
+    ap.error("--retire / --failed-at-entry / --score-wide need --score")
+if not 0.0 <= a.failed_at_entry <= 1.0:
+    ap.error("--failed-at-entry: F in [0, 1]")
 if a.ensemble and not a.score:
     ap.error("--ensemble needs --score")
 if a.ensemble and not (1 <= a.ensemble[0] <= 16 and 0 <= a.ensemble[1] <= 16):
@@ -201,10 +216,17 @@ def scenario_kw(kw, B, T):
             kw.update(drop_process=Dropouts(rng.uniform(0.12, 0.22, B), rng.uniform(0.4, 0.6, B)), drop_keys=np.stack([prng.PRNGKey(50000 + b) for b in range(B)]))
     if a.score:
         from sde4mbrl_px4_amd.solver import Score
-        kw["score"] = Score(pos_radius=1.0, tilt_max=0.6, rate_max=6.0, substeps=a.score_substeps)
+        kw["score"] = Score(substeps=a.score_substeps) if a.score_wide else Score(pos_radius=1.0, tilt_max=0.6, rate_max=6.0, substeps=a.score_substeps)
         kw["score_ref"] = "track" if a.track else np.ascontiguousarray(np.broadcast_to(np.asarray(W.HOVER, np.float32), (T, B, 13)))
         if a.no_outputs:
             kw["outputs"] = False
+        if a.failed_at_entry > 0.0:
+            from sde4mbrl_px4_amd.solver import score_init
+            z = score_init(B)
+            z["first_fail_row"][(np.arange(B) % 1000) < int(round(1000 * a.failed_at_entry))] = 0
+            kw["score_in"] = z
+        if a.retire:
+            kw["retire"] = True
         if a.ensemble:
             from sde4mbrl_px4_amd.solver import Ensemble
             G_, E_ = a.ensemble
@@ -280,9 +302,13 @@ if a.track:
 if a.per_episode_xref:
     tag += " per-episode-xref"
 if a.score:
-    tag += " score" + ("/substeps" if a.score_substeps else "") + (" no-outputs" if a.no_outputs else "")
+    tag += " score" + ("/substeps" if a.score_substeps else "") + ("/wide" if a.score_wide else "") + (" no-outputs" if a.no_outputs else "")
 if a.ensemble:
     tag += f" ensemble G={a.ensemble[0]} E={a.ensemble[1]}"
+if a.failed_at_entry:
+    tag += f" failed-at-entry={a.failed_at_entry:g}"
+if a.retire:
+    tag += " retire"
 
 
 def report_score(out, T, pk_ens=None):
@@ -291,6 +317,12 @@ def report_score(out, T, pk_ens=None):
         return
     from sde4mbrl_px4_amd.solver import score_summary
     at = -1 - (1 if a.substep_states else 0) - 3 * (int(a.dist_process) + int(a.bias_process) + int(a.fault_process) + int(a.drop_process))      # the score sits in front of the process values and of xsub
+    if a.retire:               # (retired_at and live sit behind the score and the ensemble words)
+        from sde4mbrl_px4_amd.solver import retire_summary
+        r = retire_summary(out[at - 1], out[at], out[at - 1].shape[0])
+        print(f"  retire: {r['solves_run']} solves run, {r['solves_saved']} saved ({100 * r['saved_share']:.1f} %), {r['retired']} episodes retired, "
+              f"{r['retired_at_entry']} of them at entry; live per solve " + " ".join(str(int(v)) for v in out[at]), flush=True)
+        at -= 2
     if a.ensemble:             # (the ensemble words sit right behind the score)
         from sde4mbrl_px4_amd.solver import ensemble_summary
         e = ensemble_summary(out[at], pk_ens)
