@@ -99,7 +99,10 @@ typedef struct sdempc_cfg {
      * software forms of SPEC.md §3, results identical to the CPU oracle bit for bit. 1 = fast: the same kernels with the
      * hardware transcendentals (v_exp_f32, v_rcp_f32, v_rsq_f32) and the hidden activation kept as 1 / (1 + 2^a') with its affine maps folded into the
      * weights by sdempc_create (SPEC.md §10, §10b); about 1e-7 relative per operation away from the exact path, and — through the oracle's model of the three
-     * instructions (SPEC.md §10a) — compared with the CPU oracle bit for bit as well. */
+     * instructions (SPEC.md §10a) — compared with the CPU oracle bit for bit as well. With mlp_dtype 1 or 2 the mode rescales the rows of W3 by exact
+     * powers of two (compensated in the residual scales: the same model) when they lie outside [2^-4, 2^2), and REFUSES (SDEMPC_EINVAL from sdempc_create
+     * and from a call that prepares a plant) a model its binary16 limbs cannot carry: a limb operand weight beyond 65504, eoff < 8, 0 < C2 < 2^-6, a row
+     * rescale that would round (SPEC.md §10e, "What the mode accepts"). */
     int32_t math_mode;
     /* state_constr (launch/iris_sitl_traj_mpc.yaml:16-29; commented out in every YAML the reference ships), penalty form
      * (slack_proximal: False): stage cost += sum_k state_w[k] * (max(0, x[id_k] - hi_k)^2 + max(0, lo_k - x[id_k])^2) at x_{t+1},

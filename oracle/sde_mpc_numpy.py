@@ -423,14 +423,53 @@ class Model:
         self.b3n = f[2112]
 
 
+W3_BAND_LO, W3_BAND_HI, W3_BAND_TO, ADJ_EOFF_MIN, ADJ_C2_MIN = -3, 2, -1, 8, 2.0 ** -6
+WRONG_SCALE_VARIANTS = ("no_normalisation", "b3_not_scaled", "no_compensation", "common_exponent_from_force_rows", "eoff_off_by_one")
+
+
+def normalise_output_layer(M, wrong=None):
+    """SPEC.md §10e, "Normalisation of the output layer", on a Model in place: row i of W3 and b3[i] times 2^n_i, sF / sT of that output times 2^-n_i; n_i = 0 when
+    the binary exponent (frexp) of the row's largest entry is in W3_BAND_LO .. W3_BAND_HI, else W3_BAND_TO minus that exponent. -> n (int[6])"""
+    n = np.zeros(6, np.int32)
+    if wrong == "no_normalisation":
+        return n
+    for i in range(6):
+        mx = F(np.abs(M.W3[i]).max())
+        if mx > 0 and np.isfinite(mx):
+            g = int(np.frexp(mx)[1])
+            if not (W3_BAND_LO <= g <= W3_BAND_HI):
+                n[i] = W3_BAND_TO - g
+    if wrong == "common_exponent_from_force_rows":
+        n[:] = n[:3].max() if np.any(n[:3] > 0) else n[:3].min()
+    for i in range(6):
+        if n[i] == 0:
+            continue
+        s = M.sF if i < 3 else M.sT
+        w3, b3, sc = np.ldexp(M.W3[i], int(n[i])).astype(F), F(np.ldexp(M.b3[i], int(n[i]))), F(np.ldexp(s[i % 3], -int(n[i])))
+        if not (np.array_equal(np.ldexp(w3, -int(n[i])).astype(F), M.W3[i]) and F(np.ldexp(b3, -int(n[i]))) == M.b3[i] and F(np.ldexp(sc, int(n[i]))) == s[i % 3]):
+            raise ValueError("model refused: the rescale of a row of W3 (with b3 and its residual scale) is not exact in float32")
+        M.W3[i] = w3
+        if wrong != "b3_not_scaled":
+            M.b3[i] = b3
+        if wrong != "no_compensation":
+            s[i % 3] = sc
+    return n
+
+
 class Restatement:
     """One (config, model): rollout / cost in float32, bit for bit as SPEC.md writes them; APG loop of §8."""
 
-    def __init__(self, cfg, model, hw=None):
+    def __init__(self, cfg, model, hw=None, wrong=None):
+        """wrong: None, or the name of a one-line-wrong variant of §10e's normalisation and scale offset (WRONG_SCALE_VARIANTS): what the tests must tell apart"""
+        assert wrong is None or wrong in WRONG_SCALE_VARIANTS, wrong
         self.cfg = cfg
         self.M = Model(model.to_blob() if hasattr(model, "to_blob") else bytes(model))
         self.H, self.P, self.m = cfg.horizon, cfg.num_particles, cfg.num_motors
         self.mlp = cfg.mlp_dtype                    # "f32", "f16" (SPEC.md §9) or "f32x3" (§9b); the matrix-pipe modes go through mfma16_dot: small cases only
+        self.adj_mx_log = None                      # set to a list to record the largest output adjoint of every particle and step (mlp_vjp_scaled)
+        self.w3_exponents = np.zeros(6, np.int32)
+        if getattr(cfg, "math_mode", "exact") == "fast" and self.mlp in ("f32x3", "f16"):
+            self.w3_exponents = normalise_output_layer(self.M, wrong)
         q = None
         if self.mlp == "f16":                        # layer-1 (state inputs) and layer-2 weights live in fp16
             q = np.vectorize(lambda w: np.asarray(np.uint16(f16_rtz_bits(w))).view(np.float16).astype(F))
@@ -479,6 +518,13 @@ class Restatement:
             if bound > 0 and np.isfinite(bound):
                 self.adj_eoff = min(10, 14 - int(np.frexp(bound)[1]))
             self.adj_eoff = max(self.adj_eoff, -40)
+            # §10e, "What the mode accepts": no binary16 limbs beyond 65504, no scale offset below ADJ_EOFF_MIN, no non-zero C2 below 2^-6
+            wmax = max(float(np.abs(a).max()) for a in (M.W2, self.V["W2"], self.V["W1z"], self.V["W1u"], M.W3[:6]))
+            if wmax > 65504.0 or self.adj_eoff < ADJ_EOFF_MIN or 0 < C2 < ADJ_C2_MIN:
+                raise ValueError(f"model refused by math_mode fast with mlp_dtype {self.mlp}: largest binary16 operand weight {wmax:g} (limit 65504), "
+                                 f"eoff {self.adj_eoff} (at least {ADJ_EOFF_MIN}), C2 {C2:g} (zero or at least {ADJ_C2_MIN})")
+            if wrong == "eoff_off_by_one":
+                self.adj_eoff -= 1
             # A-operand matrices of the two narrow contractions: rows 0..5 W1z^T (density / drift tile), drift rows 6..6+m-1 W1u^T, the rest zero
             self.Zn = np.zeros((32, 32), F); self.Zd = np.zeros((32, 32), F)
             self.Zn[:6, :] = self.V["W1z"][32:, :].T
@@ -675,6 +721,8 @@ class Restatement:
                 if not np.isnan(v_) and (np.isnan(mx) or v_ > mx):
                     mx = v_
             e = int(np.frexp(mx)[1]) if (mx > 0 and np.isfinite(mx)) else 0
+            if self.adj_mx_log is not None:         # (tests: which particles reach the clamp below)
+                self.adj_mx_log.append(float(mx))
             e = max(e, -100)
             sig = F(np.ldexp(F(-2), self.adj_eoff - e))
             inv = F(np.ldexp(F(1), e - self.adj_eoff))

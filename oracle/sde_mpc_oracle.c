@@ -330,6 +330,9 @@ static inline preal act_rsqrt(const model_t* M, preal a) {
     return NAME(rsqrt)(a);
 }
 
+/* SPEC.md §10e: a row of W3 is left as given when the binary exponent (frexp) of its largest entry is in W3_BAND_LO .. W3_BAND_HI, else brought to W3_BAND_TO;
+ * the smallest scale offset the matrix-pipe fast modes accept */
+enum { W3_BAND_LO = -3, W3_BAND_HI = 2, W3_BAND_TO = -1, ADJ_EOFF_MIN = 8 };
 static int parse_blob(const void* blob, model_t* M, int f16, int fast) {
     const int32_t* hd = (const int32_t*)blob;
     if (hd[0] != SDEMPC_BLOB_MAGIC || hd[1] != 1) return -1;
@@ -364,6 +367,31 @@ static int parse_blob(const void* blob, model_t* M, int f16, int fast) {
     f += HID;
     M->b3n = f[0];
     M->f16 = f16;
+#ifdef ORC_MFMA16
+    if (fast && (f16 == 1 || f16 == 2)) {
+        /* SPEC.md §10e, "Normalisation of the output layer" (the same float32 statements as sdempc_create's): row i of W3 and b3[i] times 2^n_i, the residual
+         * scale of output i times 2^-n_i; n_i = 0 when the largest entry of the row is in [2^-4, 2^2), else the power that brings it into [2^-2, 2^-1) */
+        for (int i = 0; i < 6; ++i) {
+            float mx = 0.0f;
+            for (int k = 0; k < HID; ++k) mx = fmaxf(mx, fabsf(M->W3[i][k]));
+            if (!(mx > 0.0f && mx < INFINITY)) continue;
+            int g = 0;
+            (void)frexpf(mx, &g);
+            if (g >= W3_BAND_LO && g <= W3_BAND_HI) continue;
+            const int n = W3_BAND_TO - g;
+            real* s = i < 3 ? &M->sF[i] : &M->sT[i - 3];
+            int exact = 1;
+            for (int k = 0; k <= HID + 1; ++k) {
+                real* v = k < HID ? &M->W3[i][k] : k == HID ? &M->b3[i] : s;
+                const int e = k <= HID ? n : -n;
+                const float w = ldexpf(*v, e);
+                if (ldexpf(w, -e) != *v && *v == *v) exact = 0;
+                *v = w;
+            }
+            if (!exact) return -2;
+        }
+    }
+#endif
     if (f16 == 1) { /* layer-1 (state inputs) and layer-2 weights live in fp16, forward and adjoint alike */
         for (int r = 0; r < 2 * HID; ++r) for (int k = 0; k < NN; ++k) M->W1z[r][k] = f16_rtz(M->W1z[r][k]);
         for (int r = 0; r < HID; ++r) for (int k = 0; k < HID; ++k) M->W2[r][k] = f16_rtz(M->W2[r][k]);
@@ -439,6 +467,13 @@ static int parse_blob(const void* blob, model_t* M, int f16, int fast) {
         int eb = 0;
         if (bound > 0.0f && bound < INFINITY) { (void)frexpf(bound, &eb); if (14 - eb < M->adj_eoff) M->adj_eoff = 14 - eb; }
         if (M->adj_eoff < -40) M->adj_eoff = -40;
+        /* SPEC.md §10e, "What the mode accepts": no binary16 limbs beyond 65504, no scale offset below ADJ_EOFF_MIN, no non-zero C2 below 2^-6 (sdempc_create refuses the same models) */
+        float wmax = 0.0f;
+        for (int j = 0; j < HID; ++j) for (int k = 0; k < HID; ++k) wmax = fmaxf(wmax, fmaxf(fabsf(M->W2[j][k]), fabsf(M->vW2[j][k])));
+        for (int r = 0; r < 2 * HID; ++r) for (int k = 0; k < NN; ++k) wmax = fmaxf(wmax, fabsf(M->vW1z[r][k]));
+        for (int r = 0; r < HID; ++r) for (int j = 0; j < MAXM; ++j) wmax = fmaxf(wmax, fabsf(M->vW1u[r][j]));
+        for (int i = 0; i < 6; ++i) for (int k = 0; k < HID; ++k) wmax = fmaxf(wmax, fabsf(M->W3[i][k]));
+        if (wmax > 65504.0f || M->adj_eoff < ADJ_EOFF_MIN || (C2 > 0.0f && C2 < 0.015625f)) return -2;          /* (C2 below 2^-6: W2's second limbs are sub-normal) */
         for (int img = 0; img < 4; ++img) for (int i = 0; i < HID; ++i) for (int hf = 0; hf < 2; ++hf) for (int k = 0; k < 16; ++k) {
             const int un = slot_unit(hf, k);
             float w = 0.0f;
@@ -900,7 +935,8 @@ static int ctx_init(ctx_t* X, const sdempc_cfg* C, const void* blob) {
 #ifdef ORC_VEC
     if (C->mlp_dtype != 0) return SDEMPC_EINVAL;   /* the timing build has the f32 arithmetic only */
 #endif
-    if (parse_blob(blob, &X->M, C->mlp_dtype, C->math_mode != 0)) return SDEMPC_EBLOB;
+    const int pb = parse_blob(blob, &X->M, C->mlp_dtype, C->math_mode != 0);
+    if (pb) return pb == -2 ? SDEMPC_EINVAL : SDEMPC_EBLOB;          /* -2: a model the matrix-pipe fast modes refuse (SPEC.md §10e) */
     if (C->math_mode) {
 #ifdef ORC_MFMA16
         if (!orc_transc_ready()) return SDEMPC_EINVAL;      /* tests/orc.py maps the instruction tables (orc_transc_open) before a fast-mode oracle is made */

@@ -49,6 +49,11 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// SPEC.md §10e: the rows of W3 are left as given when the binary exponent (frexp) of their largest entry is in W3_BAND_LO .. W3_BAND_HI, else brought to
+// W3_BAND_TO; the smallest scale offset and the smallest non-zero bound C2 the matrix-pipe fast modes accept
+constexpr int W3_BAND_LO = -3, W3_BAND_HI = 2, W3_BAND_TO = -1, ADJ_EOFF_MIN = 8;
+constexpr float ADJ_C2_MIN = 0.015625f;
+
 // What a model blob becomes for one arithmetic and one time grid — the one statement of it, for the handle's own model (sdempc_create) and for the plants of
 // sdempc_closed_loop_batch_plant: the device payload (mlp_dtype f16: the fp16 rounding of SPEC.md §9; math_mode fast: the forward block and the block of
 // the vector-Jacobian products of §10b), the kernels' model constants (ModelK, with the scale offset of §10e) and sigma_i * sqrt(dt_t) (SPEC.md §5: float32).
@@ -58,9 +63,33 @@ struct PreparedModel {
     std::vector<float> sdt;      // [nsteps][6]
     ModelK M;
 };
-void prepare_model(const float* f, int mlp_dtype, int math_mode, const float* time_steps, int nsteps, PreparedModel& out) {
+// -> nullptr, or why the model is refused in this arithmetic (SPEC.md §10e, "What the mode accepts": the caller returns SDEMPC_EINVAL with this text).
+const char* prepare_model(const float* f, int mlp_dtype, int math_mode, const float* time_steps, int nsteps, PreparedModel& out) {
     std::vector<float>& B = out.blob_f;
     B.assign(f, f + SDEMPC_BLOB_FLOATS);
+    const bool mpfast = math_mode == 1 && mlp_dtype != 0;
+    if (mpfast) {
+        // SPEC.md §10e, "Normalisation of the output layer": the binary16 limbs of the adjoint's W3'^T image and of the scaled output adjoints need the rows of
+        // W3 in a fixed range. Row i of W3 and b3[i] times 2^n_i, the residual scale of that output times 2^-n_i: the same function (§5.2 uses o_i only as
+        // sF_i o_i / sT_i o_i), exact in float32. n_i = 0 when the largest entry of the row is in [2^-4, 2^2) (every synthetic vehicle), else the power that
+        // brings it into [2^-2, 2^-1). A row whose rescale would round (an underflow, an overflow) is refused. The oracle states the same (parse_blob).
+        for (int i = 0; i < 6; ++i) {
+            float mx = 0.0f;
+            for (int k = 0; k < 32; ++k) mx = fmaxf(mx, fabsf(B[blob::W3 + i * 32 + k]));
+            if (!(mx > 0.0f && mx < INFINITY)) continue;
+            int g = 0;
+            (void)frexpf(mx, &g);
+            if (g >= W3_BAND_LO && g <= W3_BAND_HI) continue;
+            const int n = W3_BAND_TO - g;
+            float* s = &B[40 + i];                          // sF[0..2], sT[0..2]
+            bool exact = true;
+            auto mul = [&](float& v, int e) { const float w = ldexpf(v, e); if (ldexpf(w, -e) != v && v == v) exact = false; v = w; };
+            for (int k = 0; k < 32; ++k) mul(B[blob::W3 + i * 32 + k], n);
+            mul(B[blob::B3 + i], n);
+            mul(*s, -n);
+            if (!exact) return "math_mode fast with mlp_dtype f32x3 / f16: a row of W3 lies outside [2^-4, 2^2) and its rescale (W3 row, b3, residual scale) is not exact in float32";
+        }
+    }
     if (mlp_dtype == 1) {   // layer-1 state-input weights and layer-2 weights live in fp16 (forward and adjoint alike)
         for (int i = 0; i < 64 * 6; ++i) B[blob::W1Z + i] = f16_rtz_host(B[blob::W1Z + i]);
         for (int i = 0; i < 32 * 32; ++i) B[blob::W2 + i] = f16_rtz_host(B[blob::W2 + i]);
@@ -120,7 +149,7 @@ void prepare_model(const float* f, int mlp_dtype, int math_mode, const float* ti
     for (int i = 0; i < 3; ++i) { M.J[i] = f[2 + i]; M.iJ[i] = f[5 + i]; }
     M.ct2 = f[8]; M.ct1 = f[9]; M.ct0 = f[10]; M.cm2 = f[11]; M.cm1 = f[12];
     for (int j = 0; j < 8; ++j) { M.rx[j] = f[16 + j]; M.ry[j] = f[24 + j]; M.dir[j] = f[32 + j]; }
-    for (int i = 0; i < 3; ++i) { M.sF[i] = f[40 + i]; M.sT[i] = f[43 + i]; }
+    for (int i = 0; i < 3; ++i) { M.sF[i] = B[40 + i]; M.sT[i] = B[43 + i]; }      // (§10e: the normalised ones)
     for (int i = 0; i < 6; ++i) M.b3[i] = B[blob::B3 + i];      // (math_mode fast: the forward block's, SPEC.md §10b)
     M.b3n = B[blob::B3N];
     M.adj_s0 = -2.0f; M.adj_i0 = 1.0f;
@@ -143,7 +172,18 @@ void prepare_model(const float* f, int mlp_dtype, int math_mode, const float* ti
         if (bound > 0.0f && bound < INFINITY) { (void)frexpf(bound, &e); if (14 - e < eoff) eoff = 14 - e; }
         if (eoff < -40) eoff = -40;
         M.adj_s0 = ldexpf(-2.0f, eoff); M.adj_i0 = ldexpf(1.0f, -eoff);
+        // SPEC.md §10e, "What the mode accepts": a weight beyond binary16's largest finite value has no limbs, and below eoff = ADJ_EOFF_MIN the second limbs
+        // of the scaled output adjoints are sub-normal. Neither has an exact host-side cure: the model is refused, not evaluated wrongly.
+        float wmax = 0.0f;
+        for (int i = 0; i < 32 * 32; ++i) wmax = fmaxf(wmax, fmaxf(fabsf(F[blob::W2 + i]), fabsf(V[blob::W2 + i])));
+        for (int i = 0; i < 64 * 6; ++i) wmax = fmaxf(wmax, fabsf(V[blob::W1Z + i]));
+        for (int i = 0; i < 32 * 8; ++i) wmax = fmaxf(wmax, fabsf(V[blob::W1U + i]));
+        for (int i = 0; i < 6 * 32; ++i) wmax = fmaxf(wmax, fabsf(F[blob::W3 + i]));
+        if (wmax > 65504.0f) return "math_mode fast with mlp_dtype f32x3 / f16: a weight of a binary16 operand image (-2 c W2, 4 W2, W1z, W1u, -2 W3) exceeds 65504 in magnitude";
+        if (C2 > 0.0f && C2 < ADJ_C2_MIN) return "math_mode fast with mlp_dtype f32x3 / f16: the largest absolute column sum C2 of 4 W2 is below 2^-6 (the second binary16 limbs of W2 are sub-normal)";
+        if (eoff < ADJ_EOFF_MIN) return "math_mode fast with mlp_dtype f32x3 / f16: the scale offset eoff of the adjoint's binary16 contractions is below 8 (bound = max(B3/4, Bn/4, C2 B3/16) >= 2^7: W2 or w3n too large)";
     }
+    return nullptr;
 }
 }  // namespace
 
@@ -790,7 +830,7 @@ int sdempc_create(const sdempc_cfg* cfg, const void* model_blob, size_t blob_byt
     if (cfg->mlp_dtype < 0 || cfg->mlp_dtype > 2) return fail(nullptr, SDEMPC_EINVAL, "mlp_dtype must be 0 (f32), 1 (f16) or 2 (f32x3)%s");
     if (cfg->math_mode != 0 && cfg->math_mode != 1) return fail(nullptr, SDEMPC_EINVAL, "math_mode must be 0 (exact) or 1 (fast)%s");
     PreparedModel pm;
-    prepare_model(f, cfg->mlp_dtype, cfg->math_mode, h->time_steps.data(), h->H, pm);
+    if (const char* why = prepare_model(f, cfg->mlp_dtype, cfg->math_mode, h->time_steps.data(), h->H, pm)) return fail(nullptr, SDEMPC_EINVAL, "model refused: %s", why);
     h->blob_f = std::move(pm.blob_f);
     // tables (SPEC.md §5: float32 host arithmetic)
     h->h_sdt = std::move(pm.sdt);
@@ -2569,7 +2609,8 @@ int stage_plants(sdempc_handle* h, const sdempc_plant_cfg& pc, const void* const
     stg.assign(o_xi, 0);
     PreparedModel pm;
     for (int p = 0; p < Np; ++p) {
-        prepare_model((const float*)((const int32_t*)blobs[p] + SDEMPC_BLOB_HEADER_INTS), dtype, mode, &dt, 1, pm);
+        if (const char* why = prepare_model((const float*)((const int32_t*)blobs[p] + SDEMPC_BLOB_HEADER_INTS), dtype, mode, &dt, 1, pm))
+            return fail(h, SDEMPC_EINVAL, "plant: model refused: %s", why);
         memcpy(&stg[o_model + sizeof(ModelK) * p], &pm.M, sizeof(ModelK));
         memcpy(&stg[o_wts + sizeof(float) * stride * p], pm.blob_f.data(), sizeof(float) * stride);
         memcpy(&stg[o_sdt + sizeof(float) * SDEMPC_NNOISE * p], pm.sdt.data(), sizeof(float) * SDEMPC_NNOISE);
